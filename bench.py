@@ -25,12 +25,16 @@ batch, so the launch shape does not depend on how K divides by the group size.  
 profiles/r02_g_group_size_sweep.txt: 14 -> 20.2 M frames/s, 16 -> 20.7, 24 -> 21.9, 32 -> 23.2, 48 -> 23.8, 64 -> 24.6;
 32 batches = 1024 tiles = a 68 s clip's worth per launch.)
 
-Timing: a *round* is EXACTLY K steps bracketed by a barrier + torch.cuda.synchronize() on both
-sides (max over ranks).  Rounds are repeated until `--min-time` (0.25 s) has been timed; `value`
-comes from the MEDIAN round, so it does not depend on K being large (`rounds`, `round_ms` in the
-line).  Every 4th round brackets the launches of the dominant kernel with HIP events; such a round
-issues its K steps on stream 0 alone, because
-with kernels of other streams sharing the CUs an event pair measures a time-sliced duration.
+Timing: W warm-up steps, then ONE timed round of EXACTLY K steps bracketed by a barrier +
+torch.cuda.synchronize() on both sides (max over ranks); `ms_per_step` = round time / K.  With
+`--min-time S` rounds of K steps are repeated until S seconds have been timed and `value` comes from
+the median round (`rounds`, `round_ms` in the line).  The launches of the dominant kernel are timed
+with HIP events in a separate pass after the timed rounds, on stream 0 alone, because with kernels
+of other streams sharing the CUs an event pair measures a time-sliced duration.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the float32 PCM
+[4 sources, samples] of the last batch of the last timed round -- as DIR/pcm.npy (rank 0).  The
+inputs depend only on the arguments, so two builds can be compared output for output.
 
 Rank 0 prints ONE compact JSON line (< 4 KB, strict JSON) as the LAST line of stdout: the contract keys, `roofline`
 of the dominant kernel of the headline workload (transposed conv1 + bias + rectify + soft mask + cross-fade),
@@ -162,6 +166,7 @@ def time_cpu(fn, min_seconds, max_reps=1000):
             return el / reps, reps, el
 
 
+DUMP_LIMIT = 64 << 20     # bytes of --dump-outputs in all
 HEADLINE_LIMIT = 4096     # bytes: the driver keeps a bounded tail of stdout and parses the LAST line of it
 DETAIL_FILE = "bench_detail.json"
 
@@ -243,6 +248,20 @@ def headline(line):
     return text
 
 
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """Write each array of `arrays` {name: ndarray} as float32 to dirname/<name>.npy.  When they exceed `limit` bytes in
+    all, every array is cut to the same fixed, seeded sample of its flat elements (the same indices for the same shape)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            n = max(1, int(a.size * (limit / float(total))))
+            idx = np.unique(np.random.RandomState(0).randint(0, a.size, n))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def emit(line, detail_stdout=False, out=None):
     """Write the full result to DETAIL_FILE (next to bench.py; best effort), optionally print it on an EARLIER stdout
     line, then print the compact headline as the last stdout line."""
@@ -303,8 +322,11 @@ def main():
                     help="target number of independent 32-tile batches that share one set of kernel launches "
                          "(dcs_separate_batch); every batch still counts as one step")
     ap.add_argument("--streams", type=int, default=3, help="launch groups in flight per GPU (HIP streams)")
-    ap.add_argument("--min-time", type=float, default=0.25, help="seconds of timed rounds to accumulate")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the round of K steps until this many seconds are timed (default: one round, K steps)")
     ap.add_argument("--max-rounds", type=int, default=4000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the PCM the last timed step computed as DIR/pcm.npy (float32)")
     ap.add_argument("--sat-tiles", type=int, default=4096, help="tiles of the saturating extra run (0 = skip)")
     ap.add_argument("--legs", default="ikala,bach10_f16,bach10_f32,score_informed,transform",
                     help="comma list of extra BASELINE configs to measure on rank 0 at N=1 ('' = none)")
@@ -498,42 +520,47 @@ def main():
             el = float(tt.item())
         return el
 
-    # ---- warm-up: at least W steps, and every (lane, group size) pair of the schedule at least twice (with DCS_GRAPH=1 the
-    # second identical call captures its hipGraph) plus once more
+    # ---- warm-up: W steps in the launch groups of the round, then every (lane, group size) pair of the schedule three more
+    # times (first launches load code objects; with DCS_GRAPH=1 the second identical call captures its hipGraph)
     warm = 0
-    while warm < max(args.warmup, 3 * K):
+    while warm < args.warmup:
         for i, g in enumerate(groups):
+            if warm >= args.warmup:
+                break
             lanes[i % NS].step(g)
-        warm += K
+            warm += g
     for ln in lanes:
-        for _ in range(3):
-            ln.step(1)
+        for g in sorted(set(groups)) + [1]:
+            for _ in range(3):
+                ln.step(g)
     torch.cuda.synchronize()
 
-    # ---- timed rounds
-    round_s, events_tiles, events_rounds = [], 0, 0
-    ctx0.timing_stride(1)
-    ctx0.timing_reset()
+    # ---- timed rounds: exactly K steps each; one round unless --min-time asks for more
+    round_s = []
     total = 0.0
-    while (total < args.min_time or len(round_s) < 3) and len(round_s) < args.max_rounds:
-        instrumented = (len(round_s) % 4 == 3) and not os.environ.get("DCS_BENCH_NOEVENTS")
-        if instrumented:
-            ctx0.timing(["final"])
-            before = lanes[0].launched_tiles
-        # an event round issues its K steps on stream 0 alone: with other streams' kernels sharing the CUs an event pair
-        # would measure the kernel's time-sliced duration, not its own
-        el = timed(groups, lanes[:1] if instrumented else lanes)
-        if instrumented:
-            ctx0.timing(None)
-            events_tiles += lanes[0].launched_tiles - before
-            events_rounds += 1
-        round_s.append(el)
-        total += el
-    final_ms, final_launches = ctx0.timing_query("final")
-    ctx0.timing_reset()
+    while (not round_s or total < args.min_time) and len(round_s) < max(1, args.max_rounds):
+        round_s.append(timed(groups, lanes))
+        total += round_s[-1]
     med = statistics.median(round_s)
     value = world * frames_per_step * K / med
-    clean = [t for i, t in enumerate(round_s) if i % 4 != 3] or round_s
+    if args.dump_outputs and rank == 0:                     # the last step: the last batch of the last launch group
+        dump_outputs(args.dump_outputs, {"pcm": lanes[(len(groups) - 1) % NS].pcm[groups[-1] - 1].cpu().numpy()})
+
+    # ---- HIP events around every launch of the dominant kernel: the round's launch groups (at most 12) issued on stream 0
+    # alone -- with other streams' kernels sharing the CUs an event pair would measure a time-sliced duration
+    events_tiles, events_rounds = 0, 0
+    ctx0.timing_stride(1)
+    ctx0.timing_reset()
+    if not os.environ.get("DCS_BENCH_NOEVENTS"):
+        ctx0.timing(["final"])
+        for _ in range(3):
+            before = lanes[0].launched_tiles
+            timed(groups[:12], lanes[:1])
+            events_tiles += lanes[0].launched_tiles - before
+            events_rounds += 1
+        ctx0.timing(None)
+    final_ms, final_launches = ctx0.timing_query("final")
+    ctx0.timing_reset()
 
     # ---- N > 1: what the collective costs -- the same rounds with the gather switched off, and the collective alone (one
     # launch group's payload per call, back to back on lane 0), so that a scaling curve can be read: compute vs exchange
@@ -682,8 +709,8 @@ def main():
     ev_tiles = events_tiles / float(final_launches) if final_launches else groups[0] * n_tiles
     roofline = roof(ev_tiles, final_ms, final_launches, frames=ev_tiles / n_tiles * frames_per_step,
                     key="final_kernel_%dx%d_tiles" % (groups[0], n_tiles), clips=max(1, int(round(ev_tiles / n_tiles))))
-    roofline["timed"] = ("HIP events around every launch of the kernel in %d of the %d timed rounds; those rounds run "
-                         "their K steps on stream 0 alone" % (events_rounds, len(round_s)))
+    roofline["timed"] = ("HIP events around every launch of the kernel in %d passes over the round's first %d launch groups "
+                         "on stream 0 alone, after the timed rounds" % (events_rounds, len(groups[:12])))
     single = {"ms_per_step": round(el1 * 1e3, 5), "value": round(world * frames_per_step / el1, 1),
               "whole_path_frac_of_f32_peak": round(n_tiles * ARCHS["dsd"].flops_per_tile(TC, F) / el1 / 1e12 / PEAK_F32_TFLOPS, 4),
               "kernels": "one-batch kernels (csrc/dsd_lat.hip), one launch per layer, issued eagerly" if net0.final_kernel(T, 1) == "one_batch"
@@ -926,8 +953,7 @@ def main():
             "single_stream_x_realtime": round(single["value"] * HOP / SR, 1),
             "rounds": len(round_s), "timed_region_s": round(total, 4),
             "round_ms": {"median": round(med * 1e3, 4), "min": round(min(round_s) * 1e3, 4),
-                         "max": round(max(round_s) * 1e3, 4),
-                         "median_without_event_rounds": round(statistics.median(clean) * 1e3, 4)},
+                         "max": round(max(round_s) * 1e3, 4)},
             "config": {"workload": "DSD100 4-source separate_dsd path (BASELINE configs[1]): frameSize=%d hop=512 "
                                    "hann, time_context=30 overlap=25 scale=0.3, one batch of %d tiles = %.2f s of "
                                    "44.1 kHz audio per GPU per step, STFT->net->mask->overlap-add->iSTFT, "

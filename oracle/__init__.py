@@ -30,8 +30,9 @@ Contents
                500-527``).
 ``ref_exec``   executes the reference's OWN pure-NumPy function bodies by line
                range from ``/root/reference`` (build container only -- that
-               tree does not exist on the GPU box).  Used to pin ``stft_np`` /
-               ``tiling_np`` / ``score_np`` and to generate ``tests/golden/*.npz``.
+               tree does not exist on the GPU box).  Used by
+               ``tests/golden/make_golden.py`` to generate ``tests/golden/*.npz``,
+               which pin ``stft_np`` / ``tiling_np`` / ``score_np`` / ``net_ref``.
 
 Parity status
 -------------

@@ -147,3 +147,52 @@ def random_draw(seed):
     bias += rs.uniform(-0.02, 0.02, bias.shape)
     params[-1] = bias.astype(np.float32)
     return arch, F, params, x
+
+
+def stored_elements(shape, seed, frac=0.05, edge=4):
+    """The elements of a reference output [..., frames, bins] that tests/golden/fresh_random_draws.npz keeps at full
+    precision: a seeded sample of `frac` of them plus every element of the first bin and of the last `edge` bins (where
+    strided filters leave columns uncovered).  The same (shape, seed) always selects the same elements."""
+    sel = np.random.RandomState(20_000 + int(seed)).rand(*shape) < frac
+    sel[..., :1] = True
+    sel[..., -edge:] = True
+    return sel
+
+
+def single_branch_draw(seed):
+    """Seeded draws of the single-branch score-informed graph (trainCNNrwc_samp.py): (params, x [B, 4, 30, 129])."""
+    rs = np.random.RandomState(500 + seed)
+    tc, F, B = 30, 129, int(rs.randint(1, 3))
+    params = synth_params("bach10_si1", tc, F, seed=int(rs.randint(1 << 30)), gain=float(rs.uniform(0.6, 2.0)))
+    x = (0.3 * rs.uniform(0, 3, (B, 4, tc, F)) * (rs.uniform(size=(B, 4, tc, F)) < 0.6)).astype(np.float32)
+    y = pre_bias_output("bach10_si1", params, x)
+    params[-1] = np.array([-np.quantile(y[:, c], 0.7) for c in range(4)], dtype=np.float32)
+    return params, x
+
+
+# ---- seeded inputs of the score-informed front-end draws (tests/test_oracle_golden.py; the reference's answers on them are
+# tests/golden/fresh_*.npz, written by make_golden.py)
+def trainer_filterspec_draw(seed):
+    """Seeded rectangles that overlap within and across instruments, a window that does not start at frame 0, an
+    instrument without notes on odd seeds: (mag [T - start, F], notes [ninst, 6, 43], start, T)."""
+    rs = np.random.RandomState(700 + seed)
+    T, F, ninst = int(rs.randint(40, 90)), int(rs.randint(60, 300)), int(rs.randint(2, 6))
+    mag = rs.rand(T, F).astype(np.float32)
+    notes = np.zeros((ninst, 6, 43))
+    for j in range(ninst):
+        for p in range(0 if j == ninst - 1 and seed % 2 else int(rs.randint(1, 6))):
+            b = int(rs.randint(0, T + 20))
+            notes[j, p, :3] = (b, b + int(rs.randint(1, 30)), 40 + p)
+            for k in range(int(rs.randint(1, 12))):
+                f0 = int(rs.randint(0, F - 16))
+                notes[j, p, 3 + 2 * k], notes[j, p, 4 + 2 * k] = f0, f0 + int(rs.randint(1, 16))
+    start = int(rs.randint(0, 10))
+    return mag[start:], notes, start, T
+
+
+def timbre_draw(seed):
+    """Seeded timbre templates [2 instruments, 128 pitches, 20 harmonics] (float32) and magnitudes [520, 1025]."""
+    rs = np.random.RandomState(900 + seed)
+    H = rs.uniform(0.0, 2.0, (2, 128, 20)).astype(np.float32)
+    mag = np.abs(rs.randn(520, 1025)).astype(np.float32)
+    return H, mag

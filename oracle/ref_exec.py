@@ -7,9 +7,9 @@ unchanged under Python 3 / NumPy 2 when sliced out by line range.  This module
 slices them out of ``/root/reference`` AT RUN TIME (nothing is copied into the
 repo) and exposes them as a namespace.
 
-``/root/reference`` exists only in the build container; on the GPU box
-``available()`` is False and everything that depends on this module is skipped
--- the committed ``tests/golden/*.npz`` carry the reference's answers there.
+Only ``tests/golden/make_golden.py`` runs this module: the committed
+``tests/golden/*.npz`` carry the reference's answers to the tests, which
+therefore need no reference tree.
 """
 import os
 

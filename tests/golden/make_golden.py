@@ -10,6 +10,7 @@ The reference's pure-NumPy helpers are executed by line range through
 are written as small compressed fixtures.  The GPU box has no reference tree,
 so the parity tests there read these files.
 """
+import json
 import os
 import sys
 
@@ -243,7 +244,119 @@ def networks(only=None):
         print(name, p.shape, "zeros %.3f" % d["zero_fraction"], "max %.3f" % p.max())
 
 
+def fresh():
+    """The reference's answers on the seeded draws of the "fresh input" tests (oracle/cases.py builds the inputs again in
+    the tests): tests/golden/fresh_*.npz.  Large masks are kept as SHA-256 digests of their bytes."""
+    import hashlib
+    import pickle
+    import tempfile
+    from oracle import cases, score_np
+
+    def digest(a):
+        return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+    # STFT / iSTFT of the script on fresh audio
+    rs = np.random.RandomState(99)
+    audio = rs.uniform(-1, 1, 7001)
+    d = {}
+    for N, hop in [(1024, 512), (2048, 512)]:
+        m0, p0 = ref_exec.script_dsd().compute_file(audio, phase=True, frameSize=N, hopSize=hop)
+        d["mag_%d" % N], d["phase_%d" % N] = m0, p0
+        d["inverse_%d" % N] = ref_exec.script_dsd().compute_inverse(m0, p0, frameSize=N, hopSize=hop)
+    np.savez_compressed(os.path.join(HERE, "fresh_stft.npz"), **d)
+
+    # the trainers' LargeDatasetMask2.filterSpec on seeded note rectangles
+    f = ref_exec.dataset_filterspec_sum()
+    d = {}
+    for seed in range(6):
+        mag, notes, start, T = cases.trainer_filterspec_draw(seed)
+        d["mask_%d" % seed] = f(mag, notes, start, T)
+    np.savez_compressed(os.path.join(HERE, "fresh_trainer_filterspec.npz"), **d)
+
+    sc = ref_exec.score()
+    with tempfile.TemporaryDirectory() as tmp:
+        # the timbre branch of the script's filterSpec on fresh templates
+        d = {}
+        for seed in range(6):
+            score_np.synth_score(os.path.join(tmp, "t_b.txt"), 50 + seed, n_notes=25, total=6.0)
+            tab = sc.expandMidi("t_b", tmp, 0, 40.0, 50, 440, 20, 44100, 512, 2048, 0.2, 0.2, 520, 0.5)
+            melody = np.zeros((2, tab.shape[0], 43))
+            melody[0] = tab
+            melody[1, : tab.shape[0] // 2] = tab[: tab.shape[0] // 2]
+            H, mag = cases.timbre_draw(seed)
+            model = os.path.join(tmp, "m%d.pkl" % seed)
+            with open(model, "wb") as fh:
+                pickle.dump(H, fh, protocol=2)
+            want = sc.filterSpec(mag[30:400], melody, 2, 30, 400, timbre_model_path=model)
+            d["tab_%d" % seed] = tab
+            d["mask_sha256_%d" % seed] = digest(want)
+            d["mask_shape_%d" % seed] = np.array(want.shape)
+            d["mask_dtype_%d" % seed] = str(want.dtype)
+        np.savez_compressed(os.path.join(HERE, "fresh_timbre.npz"), **d)
+
+        # expandMidi / getMidiNum / str2midi on seeded scores
+        d = {}
+        for seed in range(25):
+            score_np.synth_score(os.path.join(tmp, "s_b.txt"), seed, n_notes=30, total=12.0 if seed % 2 else 9.5)
+            for hop, N, nfr in ((512, 4096, 864), (256, 1024, 1725), (441, 2048, 1002)):
+                d["tab_%d_%d" % (seed, hop)] = sc.expandMidi("s_b", tmp, 0, 40.0, 50, 440, 20, 44100, hop, N, 0.2, 0.2, nfr, 0.5)
+            d["tab_%d_window" % seed] = sc.expandMidi("s_b", tmp, 2.0, 8.0, 30, 442, 20, 44100, 512, 4096, 0.1, 0.3, 500, 0.0)
+            d["num_%d" % seed] = sc.getMidiNum("s_b", tmp, 0, 40.0)
+        notes = ["C4", "A4", "Bb3", "F#5", "Cx2", "Db1", "B0", "E10"[:3]]
+        d["notes"] = np.array(notes)
+        d["midi"] = np.array([sc.str2midi(n) for n in notes], dtype=np.float64)
+        np.savez_compressed(os.path.join(HERE, "fresh_score.npz"), **d)
+
+    # networks: parameter order of the reference's graphs at the real sizes, single-branch draws, random draws
+    d = {}
+    for arch, C, F in NET_SHAPE_CASES:
+        shapes = ref_exec.network_param_shapes(arch, 32, C, 30, F)
+        d["shapes_%s_%d_%d" % (arch, C, F)] = np.array(json.dumps([list(s) for s in shapes]))
+    np.savez_compressed(os.path.join(HERE, "fresh_param_shapes.npz"), **d)
+    d = {}
+    for seed in range(4):
+        params, x = cases.single_branch_draw(seed)
+        p_ref = ref_exec.network_output("bach10_si1", params, x)
+        d["p_%d" % seed] = p_ref
+        for which in ("bach10_si1", "bach10_si_trainer", "bach10_si"):
+            d["masked_%s_%d" % (which, seed)] = np.stack(ref_exec.mask_sources(which, p_ref, x))
+    np.savez_compressed(os.path.join(HERE, "fresh_single_branch.npz"), **d)
+    # random draws: 16 MB of float64 in all, so every output is kept as (a) its sums over the bins of every frame and (b) the
+    # elements cases.stored_elements selects; the iKala outputs also keep every element the tie routing changes
+    d = {}
+
+    def keep(key, seed, a):
+        d["%s_%d" % (key, seed)] = a[cases.stored_elements(a.shape, seed)]
+        d["%s_shape_%d" % (key, seed)] = np.array(a.shape)
+        d["%s_binsum_%d" % (key, seed)] = a.sum(axis=-1)
+
+    for seed in range(24):
+        arch, F, params, x = cases.random_draw(seed)
+        p_ref = ref_exec.network_output(arch, params, x)
+        keep("p", seed, p_ref)
+        if arch == "ikala":
+            p1 = ref_exec.network_output(arch, params, x, tie_mode="first")
+            keep("p_tie_first", seed, p1)
+            ties = np.flatnonzero(p1 != p_ref)
+            d["ties_%d" % seed] = ties
+            d["ties_p_%d" % seed], d["ties_p_tie_first_%d" % seed] = p_ref.reshape(-1)[ties], p1.reshape(-1)[ties]
+        keep("masked", seed, np.stack(ref_exec.mask_sources("ikala" if arch == "ikala_nopool" else arch, p_ref, x)))
+    np.savez_compressed(os.path.join(HERE, "fresh_random_draws.npz"), **d)
+    for n in sorted(os.listdir(HERE)):
+        if n.startswith("fresh_"):
+            print(n, os.path.getsize(os.path.join(HERE, n)))
+
+
+# (graph, channels, bins) of the parameter-order check: every graph at the sizes its script runs
+NET_SHAPE_CASES = [("dsd", 1, 513), ("dsd", 1, 1025), ("hiphop", 1, 513), ("ikala", 1, 513), ("ikala", 1, 1025),
+                   ("ikala_nopool", 1, 513), ("bach10", 1, 2049), ("bach10_si", 4, 2049), ("bach10_si1", 4, 2049),
+                   ("dsd_ild", 2, 513)]
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "fresh":
+        fresh()
+        raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "networks":
         networks(only=sys.argv[2:] or None)
         raise SystemExit(0)

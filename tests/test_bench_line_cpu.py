@@ -125,3 +125,24 @@ def test_round_plan_pipelines_the_gather_only_where_it_can():
     assert bench.plan_round(1, 32, 3, True, "root") == ([1], False)
     groups, piped = bench.plan_round(384, 32, 3, True, "root")
     assert sum(groups) == 384 and len(groups) == 12 and not piped
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: arrays within the limit are written whole as float32; beyond it every array is cut to a seeded sample
+    of its elements, the same one on every run, so that two builds can be compared output for output."""
+    import numpy as np
+    rs = np.random.RandomState(1)
+    small = rs.randn(4, 1000)
+    bench.dump_outputs(str(tmp_path / "a"), {"pcm": small})
+    got = np.load(str(tmp_path / "a" / "pcm.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = {"pcm": rs.randn(4, 50000), "other": rs.randn(30000)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, limit=200000)
+    sizes = 0
+    for name, a in big.items():
+        b, c = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("b", "c"))
+        assert b.dtype == np.float32 and np.array_equal(b, c) and 0 < b.size < a.size
+        assert np.isin(b, a.reshape(-1).astype(np.float32)).all()
+        sizes += b.nbytes
+    assert sizes <= 200000

@@ -510,6 +510,29 @@ def test_bench_gather_code_path_with_a_world_of_one_rank():
             assert line["parity_check"]["ok"] is True
 
 
+def test_bench_times_exactly_the_given_steps_and_dumps_the_last_step(tmp_path):
+    """bench.py --gpus 1 --steps 5: one timed round of exactly 5 steps (one launch group of 5 batches on lane 0), and
+    --dump-outputs writes the PCM of its last batch -- the audio of clip 4 of lane 0 -- equal to a separation of that audio."""
+    import bench
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--sat-tiles", "0",
+           "--legs", "", "--no-cpu-baseline", "--no-host-fed", "--no-cli", "--no-parity-check", "--dump-outputs", str(tmp_path)]
+    env = dict(os.environ)
+    for k in ("DCS_BENCH_SAME_DEVICE", "DCS_BENCH_FORCE_GATHER"):
+        env.pop(k, None)
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads(r.stdout.splitlines()[-1])
+    assert line["steps"] == 5 and line["rounds"] == 1 and line["ms_per_step"] > 0
+    assert line["config"]["launch_groups_per_round"] == [5]
+    got = np.load(str(tmp_path / "pcm.npy"))
+    L = bench.samples_for_tiles(32)
+    assert got.dtype == np.float32 and got.shape == (4, L)
+    audio = synth_audio(L, seed=100 + 4)
+    want = dcs.Separator("dsd", synth_params("dsd", 30, 1025, seed=2), 0.3, 30, 25, 32, 1025, 2048, 512,
+                         np.hanning).separate(audio)
+    assert np.max(np.abs(got - want)) < 1e-4
+
+
 @needs_two_gpus
 @pytest.mark.parametrize("impl,mode", [("torch", "allgather"), ("torch", "root"), ("dcs", "allgather"), ("dcs", "root")])
 def test_bench_two_gpus_over_rccl_gather_is_exact(impl, mode):

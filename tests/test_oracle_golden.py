@@ -1,10 +1,12 @@
 """Pin the CPU oracle against outputs of the reference's own code
-(tests/golden/*.npz, produced by tests/golden/make_golden.py) and, when the
-reference tree is present (build container), against the live reference code."""
+(tests/golden/*.npz, produced by tests/golden/make_golden.py; the fresh_*.npz
+hold the reference's answers on the seeded draws of oracle/cases.py)."""
+import hashlib
+
 import numpy as np
 import pytest
 
-from oracle import ref_exec, stft_np, tiling_np
+from oracle import cases, stft_np, tiling_np
 
 STFT_CASES = ["stft_n1024_hann", "stft_n2048_hann", "stft_n4096_bh",
               "stft_n1024_hop256_hann", "stft_n512_hop200_hann"]
@@ -100,41 +102,29 @@ def test_sum_normalised_masks_match_the_trainers_dataset_class(golden, name, tmp
         assert got.dtype == np.float32 and np.array_equal(got, gs["mask_timbre"])
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="reference tree only exists in the build container")
-def test_live_trainer_filterspec_agrees_on_fresh_scores():
-    """The reference's LargeDatasetMask2.filterSpec executed now against the restatement: seeded rectangles that overlap
-    within and across instruments, windows that do not start at frame 0, an instrument without notes."""
+def test_live_trainer_filterspec_agrees_on_fresh_scores(golden):
+    """The reference's LargeDatasetMask2.filterSpec (its answers stored in fresh_trainer_filterspec) against the
+    restatement: seeded rectangles that overlap within and across instruments, windows that do not start at frame 0, an
+    instrument without notes."""
     from oracle import score_np
-    f = ref_exec.dataset_filterspec_sum()
+    g = golden("fresh_trainer_filterspec")
     for seed in range(6):
-        rs = np.random.RandomState(700 + seed)
-        T, F, ninst = int(rs.randint(40, 90)), int(rs.randint(60, 300)), int(rs.randint(2, 6))
-        mag = rs.rand(T, F).astype(np.float32)
-        notes = np.zeros((ninst, 6, 43))
-        for j in range(ninst):
-            for p in range(0 if j == ninst - 1 and seed % 2 else int(rs.randint(1, 6))):
-                b = int(rs.randint(0, T + 20))
-                notes[j, p, :3] = (b, b + int(rs.randint(1, 30)), 40 + p)
-                for k in range(int(rs.randint(1, 12))):
-                    f0 = int(rs.randint(0, F - 16))
-                    notes[j, p, 3 + 2 * k], notes[j, p, 4 + 2 * k] = f0, f0 + int(rs.randint(1, 16))
-        start = int(rs.randint(0, 10))
-        want = f(mag[start:], notes, start, T)
-        got = score_np.filterSpec(mag[start:], notes, ninst, start, T, normalise='sum')
+        mag, notes, start, T = cases.trainer_filterspec_draw(seed)
+        want = g["mask_%d" % seed]
+        got = score_np.filterSpec(mag, notes, notes.shape[0], start, T, normalise='sum')
         assert want.dtype == got.dtype == np.float32 and np.array_equal(want, got)
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="reference tree only exists in the build container")
-def test_live_reference_agrees_on_fresh_input():
+def test_live_reference_agrees_on_fresh_input(golden):
+    """The script's compute_file / compute_inverse on fresh audio (the reference's answers: fresh_stft)."""
+    g = golden("fresh_stft")
     rs = np.random.RandomState(99)
     audio = rs.uniform(-1, 1, 7001)
-    ref = ref_exec.script_dsd()
     for N, hop in [(1024, 512), (2048, 512)]:
-        m0, p0 = ref.compute_file(audio, phase=True, frameSize=N, hopSize=hop)
+        m0, p0 = g["mag_%d" % N], g["phase_%d" % N]
         m1, p1 = stft_np.compute_file(audio, phase=True, frameSize=N, hopSize=hop)
         assert np.array_equal(m0, m1) and np.array_equal(p0, p1)
-        assert np.array_equal(ref.compute_inverse(m0, p0, frameSize=N, hopSize=hop),
-                              stft_np.compute_inverse(m1, p1, frameSize=N, hopSize=hop))
+        assert np.array_equal(g["inverse_%d" % N], stft_np.compute_inverse(m1, p1, frameSize=N, hopSize=hop))
 
 
 # ------------------------------------------------------------------ score-informed front-end (SURVEY 8a-10)
@@ -204,49 +194,51 @@ def test_timbre_model_masks_match_the_reference_filterSpec(golden, tmp_path):
     assert len(np.unique(g["mask"])) > 100 and float(g["mask"].max()) == 1.0      # weighted, not binary; normalised per instrument
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="reference tree only exists in the build container")
-def test_live_reference_timbre_branch_agrees_on_fresh_models(tmp_path):
+def test_live_reference_timbre_branch_agrees_on_fresh_models(golden, tmp_path):
+    """The timbre branch of the script's filterSpec on fresh templates: the reference's note tables (stored) against the
+    restatement's, and its masks (stored as SHA-256 digests of their bytes) against the oracle's restatement and the
+    shipped host code, bit for bit."""
     import pickle
     from oracle import score_np
     from deepconvsep_amd import score
-    sc = ref_exec.score()
+    g = golden("fresh_timbre")
     for seed in range(6):
-        rs = np.random.RandomState(900 + seed)
         p = score_np.synth_score(str(tmp_path / "t_b.txt"), 50 + seed, n_notes=25, total=6.0)
-        tab = sc.expandMidi("t_b", str(tmp_path), 0, 40.0, 50, 440, 20, 44100, 512, 2048, 0.2, 0.2, 520, 0.5)
+        tab = g["tab_%d" % seed]
+        assert np.array_equal(score_np.expandMidi(p, 0, 40.0, 50, 440, 20, 44100, 512, 2048, 0.2, 0.2, 520, 0.5), tab)
         melody = np.zeros((2, tab.shape[0], 43))
         melody[0] = tab
         melody[1, : tab.shape[0] // 2] = tab[: tab.shape[0] // 2]
-        H = rs.uniform(0.0, 2.0, (2, 128, 20)).astype(np.float32)
+        H, mag = cases.timbre_draw(seed)
         model = str(tmp_path / ("m%d.pkl" % seed))
         with open(model, "wb") as fh:
             pickle.dump(H, fh, protocol=2)
-        mag = np.abs(rs.randn(520, 1025)).astype(np.float32)
-        want = sc.filterSpec(mag[30:400], melody, 2, 30, 400, timbre_model_path=model)
-        assert np.array_equal(score_np.filterSpec(mag[30:400], melody, 2, 30, 400, H), want)
-        assert np.array_equal(score.filterSpec(mag[30:400], melody, 2, 30, 400, timbre_model_path=model), want)
+        for got in (score_np.filterSpec(mag[30:400], melody, 2, 30, 400, H),
+                    score.filterSpec(mag[30:400], melody, 2, 30, 400, timbre_model_path=model)):
+            assert str(got.dtype) == str(g["mask_dtype_%d" % seed])
+            assert list(got.shape) == list(g["mask_shape_%d" % seed])
+            assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == str(g["mask_sha256_%d" % seed])
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="reference tree only exists in the build container")
-def test_live_reference_score_code_agrees_on_fresh_scores(tmp_path):
-    """The reference's own expandMidi / getMidiNum / filterSpec (Python-2 bodies executed with the shims of
-    oracle.ref_exec.score) against the restatement, many seeded scores, three (frameSize, hop) pairs and a window
-    that does not start at zero.  For sr = 44100 and these hops Python 2's integer ``samplerate / hop`` and Python 3's
-    true division give the same frame numbers, which is what makes the executed reference a valid pin."""
+def test_live_reference_score_code_agrees_on_fresh_scores(golden, tmp_path):
+    """The reference's own expandMidi / getMidiNum / str2midi (Python-2 bodies executed with the shims of
+    oracle.ref_exec.score; their answers stored in fresh_score) against the restatement, many seeded scores, three
+    (frameSize, hop) pairs and a window that does not start at zero.  For sr = 44100 and these hops Python 2's integer
+    ``samplerate / hop`` and Python 3's true division give the same frame numbers, which is what makes the executed
+    reference a valid pin."""
     from oracle import score_np
-    sc = ref_exec.score()
+    g = golden("fresh_score")
     for hop in (512, 256, 441):
         assert round(float(44100 / hop)) == round(float(44100 // hop))
         assert int(round(0.2 * float(44100 / hop))) == int(round(0.2 * float(44100 // hop)))
     for seed in range(25):
         p = score_np.synth_score(str(tmp_path / "s_b.txt"), seed, n_notes=30, total=12.0 if seed % 2 else 9.5)
         for hop, N, nfr in ((512, 4096, 864), (256, 1024, 1725), (441, 2048, 1002)):
-            a = sc.expandMidi("s_b", str(tmp_path), 0, 40.0, 50, 440, 20, 44100, hop, N, 0.2, 0.2, nfr, 0.5)
             b = score_np.expandMidi(p, 0, 40.0, 50, 440, 20, 44100, hop, N, 0.2, 0.2, nfr, 0.5)
-            assert np.array_equal(a, b)
-            assert sc.getMidiNum("s_b", str(tmp_path), 0, 40.0) == score_np.getMidiNum(p, 0, 40.0)
-        a = sc.expandMidi("s_b", str(tmp_path), 2.0, 8.0, 30, 442, 20, 44100, 512, 4096, 0.1, 0.3, 500, 0.0)
+            assert np.array_equal(g["tab_%d_%d" % (seed, hop)], b)
+        assert int(g["num_%d" % seed]) == score_np.getMidiNum(p, 0, 40.0)
         b = score_np.expandMidi(p, 2.0, 8.0, 30, 442, 20, 44100, 512, 4096, 0.1, 0.3, 500, 0.0)
-        assert np.array_equal(a, b)
-    for note in ("C4", "A4", "Bb3", "F#5", "Cx2", "Db1", "B0", "E10"[:3]):
-        assert sc.str2midi(note) == score_np.str2midi(note)
+        assert np.array_equal(g["tab_%d_window" % seed], b)
+    assert [str(n) for n in g["notes"]] == ["C4", "A4", "Bb3", "F#5", "Cx2", "Db1", "B0", "E10"[:3]]
+    for note, want in zip(g["notes"], g["midi"]):
+        assert score_np.str2midi(str(note)) == want

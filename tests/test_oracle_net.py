@@ -140,9 +140,11 @@ def test_stereo_ild_graph_autograd_equals_explicit_and_masks_per_channel():
 
 
 # ------------------------------------------------------------------------------------------------ reference graphs
-# tests/golden/net_*.npz: the reference's own build_ca source and mask expressions executed on the NumPy Lasagne
-# stand-in (oracle/lasagne_np.py, oracle/ref_exec.py:build_network) -- see make_golden.py:networks().
-from oracle import cases, ref_exec  # noqa: E402
+# tests/golden/net_*.npz and fresh_*.npz: the reference's own build_ca source and mask expressions executed on the NumPy
+# Lasagne stand-in (oracle/lasagne_np.py, oracle/ref_exec.py:build_network) -- see make_golden.py:networks() and fresh().
+import json  # noqa: E402
+
+from oracle import cases  # noqa: E402
 
 NET_NAMES = [c[0] for c in cases.NET_CASES]
 
@@ -185,27 +187,28 @@ def test_net_ref_matches_the_reference_graph_fixtures(golden, name):
         assert np.max(np.abs(g["masked_sum"] - g["masked"])) > 1e-3      # the two semantics are different functions
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("arch,C,F", [("dsd", 1, 513), ("dsd", 1, 1025), ("hiphop", 1, 513), ("ikala", 1, 513),
                                       ("ikala", 1, 1025), ("ikala_nopool", 1, 513), ("bach10", 1, 2049), ("bach10_si", 4, 2049),
                                       ("bach10_si1", 4, 2049), ("dsd_ild", 2, 513)])
-def test_parameter_order_comes_from_the_reference_graph(arch, C, F):
-    """``get_all_params`` of the reference's own build_ca at the real sizes == the shape list the HIP model checks
-    (deepconvsep_amd.arch) and the one the torch oracle uses -- count, order and shapes (13 / 15 / 17 arrays)."""
-    shapes = [tuple(s) for s in ref_exec.network_param_shapes(arch, 32, C, 30, F)]
+def test_parameter_order_comes_from_the_reference_graph(golden, arch, C, F):
+    """``get_all_params`` of the reference's own build_ca at the real sizes (stored in fresh_param_shapes) == the shape
+    list the HIP model checks (deepconvsep_amd.arch) and the one the torch oracle uses -- count, order and shapes
+    (13 / 15 / 17 arrays)."""
+    shapes = [tuple(s) for s in json.loads(str(golden("fresh_param_shapes")["shapes_%s_%d_%d" % (arch, C, F)]))]
     a = "dsd" if arch == "hiphop" else arch
     assert shapes == [tuple(s) for s in ARCHS[a].param_shapes(30, F)]
     assert shapes == [tuple(s) for s in net_ref.SPECS[a].param_shapes(30, F)]
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("name", ["net_dsd_f33_tiny", "net_ikala_f270_sparse", "net_bach10si_f129_sparse"])
 def test_fixtures_regenerate_bit_for_bit(golden, name):
+    """A network fixture comes back from its case definition (oracle/cases.py) bit for bit: tiles and calibrated output
+    bias.  Its outputs are the reference's answers, written by make_golden.py where the reference tree exists; the tests
+    compare the oracle with them (test_net_ref_matches_the_reference_graph_fixtures)."""
     g, arch, params = _case(golden, name)
-    p = ref_exec.network_output(arch, params, g["x"])
-    assert np.array_equal(p, g["p"])
-    assert np.array_equal(np.stack(ref_exec.mask_sources(arch, p, g["x"])), g["masked"])
-    x = g["x"]
+    seed, B = next((c[4], c[3]) for c in cases.NET_CASES if c[0] == name)
+    x = cases.make_input(arch, B, 30, int(g["F"]), seed + 500)
+    assert np.array_equal(x, g["x"])
     fresh = cases.calibrate(arch, 30, int(g["F"]), int(g["seed"]), str(g["kind"]), x)
     assert np.array_equal(fresh[-1], g["out_bias"])
 
@@ -235,22 +238,19 @@ def test_single_branch_score_informed_graph_is_the_live_part_of_the_17_array_gra
     assert ARCHS["bach10_si1"].flops_per_tile(tc, F) == ARCHS["bach10_si"].flops_per_tile(tc, F, live_only=True)
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("seed", range(4))
-def test_single_branch_graph_and_trainer_masks_equal_the_executed_reference(seed):
+def test_single_branch_graph_and_trainer_masks_equal_the_executed_reference(golden, seed):
     """Seeded draws of the single-branch graph: the reference's own build_ca of trainCNNrwc_samp.py and the TRAINERS' mask
-    lines (trainCNNrwc_samp.py:288-305, trainCNNrwc.py:246-263: masks x channel sum) executed, against net_ref."""
-    rs = np.random.RandomState(500 + seed)
-    tc, F, B = 30, 129, int(rs.randint(1, 3))
-    params = synth_params("bach10_si1", tc, F, seed=int(rs.randint(1 << 30)), gain=float(rs.uniform(0.6, 2.0)))
-    x = (0.3 * rs.uniform(0, 3, (B, 4, tc, F)) * (rs.uniform(size=(B, 4, tc, F)) < 0.6)).astype(np.float32)
-    y = cases.pre_bias_output("bach10_si1", params, x)
-    params[-1] = np.array([-np.quantile(y[:, c], 0.7) for c in range(4)], dtype=np.float32)
-    p_ref = ref_exec.network_output("bach10_si1", params, x)
+    lines (trainCNNrwc_samp.py:288-305, trainCNNrwc.py:246-263: masks x channel sum) executed (their answers stored in
+    fresh_single_branch), against net_ref."""
+    g = golden("fresh_single_branch")
+    params, x = cases.single_branch_draw(seed)
+    B, tc, F = x.shape[0], 30, 129
+    p_ref = g["p_%d" % seed]
     p = net_ref.forward("bach10_si1", params, x.astype(np.float64), inverse='explicit').numpy()
     assert p.shape == p_ref.shape == (B, 4, tc, F) and np.max(np.abs(p - p_ref)) < 1e-11
     for which, mixture in (("bach10_si1", "sum"), ("bach10_si_trainer", "sum"), ("bach10_si", "ch0")):
-        m_ref = ref_exec.mask_sources(which, p_ref, x)
+        m_ref = g["masked_%s_%d" % (which, seed)]
         m = net_ref.predict("bach10_si1", params, x.astype(np.float64), inverse='explicit', mixture=mixture)
         for a, b in zip(m, m_ref):
             assert np.max(np.abs(a - b)) < 1e-11
@@ -278,22 +278,30 @@ def test_lasagne_standin_layer_order_and_alias():
     assert L.get_output(out).shape == (2, 2, 6, 8)
 
 
-@pytest.mark.skipif(not ref_exec.available(), reason="needs /root/reference (build container only)")
+def _check_stored(g, key, seed, a):
+    """`a` against the reference output stored as its bin sums and the elements cases.stored_elements selects: those
+    elements within 1e-11, every frame's sum over the bins within (bins x 1e-11)."""
+    assert list(a.shape) == list(g["%s_shape_%d" % (key, seed)])
+    assert np.max(np.abs(a[cases.stored_elements(a.shape, seed)] - g["%s_%d" % (key, seed)])) < 1e-11
+    assert np.max(np.abs(a.sum(axis=-1) - g["%s_binsum_%d" % (key, seed)])) < a.shape[-1] * 1e-11
+
+
 @pytest.mark.parametrize("seed", range(24))
-def test_random_draws_net_ref_equals_the_executed_reference_graph(seed):
+def test_random_draws_net_ref_equals_the_executed_reference_graph(golden, seed):
     """24 seeded draws (graph, weights of either bias sign and gain 0.5 .. 2.2, dense / few-level / sparse inputs,
     10 .. 97 % of the outputs cut to exact zeros): the torch oracle against the reference's own build_ca source executed on
-    the Lasagne stand-in -- network output, both tie routings of the iKala graph, masked sources."""
+    the Lasagne stand-in (its answers stored in fresh_random_draws: the sum over the bins of every frame, a seeded sample
+    of the elements with the edge bins, and every element the tie routing changes) -- network output, both tie routings of
+    the iKala graph, masked sources."""
+    g = golden("fresh_random_draws")
     arch, F, params, x = cases.random_draw(seed)
-    p_ref = ref_exec.network_output(arch, params, x)
     p = net_ref.forward(arch, params, x.astype(np.float64), inverse='explicit').numpy()
-    assert p.shape == p_ref.shape
-    assert np.max(np.abs(p - p_ref)) < 1e-11
+    _check_stored(g, "p", seed, p)
     if arch == "ikala":
         p1 = net_ref.forward(arch, params, x.astype(np.float64), tie_mode='first', inverse='explicit').numpy()
-        assert np.max(np.abs(p1 - ref_exec.network_output(arch, params, x, tie_mode="first"))) < 1e-11
-    m_ref = ref_exec.mask_sources("ikala" if arch == "ikala_nopool" else arch, p_ref, x)   # the separate script's masks
-    m = net_ref.predict(arch, params, x.astype(np.float64), inverse='explicit')
-    assert len(m) == len(m_ref)
-    for a, b in zip(m, m_ref):
-        assert np.max(np.abs(a - b)) < 1e-11
+        _check_stored(g, "p_tie_first", seed, p1)
+        ties = g["ties_%d" % seed]
+        assert np.max(np.abs(p.reshape(-1)[ties] - g["ties_p_%d" % seed]), initial=0.0) < 1e-11
+        assert np.max(np.abs(p1.reshape(-1)[ties] - g["ties_p_tie_first_%d" % seed]), initial=0.0) < 1e-11
+    m = net_ref.predict(arch, params, x.astype(np.float64), inverse='explicit')     # the separate script's masks
+    _check_stored(g, "masked", seed, np.stack(m))
