@@ -26,9 +26,17 @@ extern "C" int dcs_version(void) { return 100; }
 
 // ------------------------------------------------------------------------------- buffers / timing
 namespace {
+// a guarded block of dcs_dev_alloc: [red zone | bytes | padding to 256 | red zone], the padding checked as red zone
+struct GuardedBlock {
+    void* base;
+    char* ptr;
+    size_t bytes, guard_end;   // guard_end: bytes from ptr to the end of the allocation
+    std::string name;
+};
 struct GuardRegistry {
     std::mutex mu;
     std::vector<DcsBuffer*> live;
+    std::vector<GuardedBlock> owned;
 };
 GuardRegistry& guard_registry() {
     static GuardRegistry r;
@@ -72,6 +80,41 @@ int DcsBuffer::ensure(size_t need) {
     return DCS_OK;
 }
 
+hipError_t dcs_dev_alloc(void** p, size_t bytes, const char* name) {
+    *p = nullptr;
+    const size_t g = guard_bytes_env();
+    if (g == 0) return hipMalloc(p, bytes);
+    const size_t payload = (bytes + 255) / 256 * 256;
+    void* base = nullptr;
+    hipError_t e = hipMalloc(&base, payload + 2 * g);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemset(base, guard_poison_env(), payload + 2 * g)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
+        (void)hipFree(base);
+        return e;
+    }
+    char* ptr = (char*)base + g;
+    GuardRegistry& r = guard_registry();
+    std::lock_guard<std::mutex> lk(r.mu);
+    r.owned.push_back(GuardedBlock{base, ptr, bytes, payload + g, name ? name : "?"});
+    *p = ptr;
+    return hipSuccess;
+}
+
+void dcs_dev_free(void* p) {
+    if (!p) return;
+    if (guard_bytes_env() != 0) {
+        GuardRegistry& r = guard_registry();
+        std::lock_guard<std::mutex> lk(r.mu);
+        for (size_t i = 0; i < r.owned.size(); ++i)
+            if (r.owned[i].ptr == p) {
+                (void)hipFree(r.owned[i].base);
+                r.owned.erase(r.owned.begin() + (std::ptrdiff_t)i);
+                return;
+            }
+    }
+    (void)hipFree(p);
+}
+
 void DcsBuffer::release() {
     if (base) (void)hipFree(base);
     else if (ptr) (void)hipFree(ptr);
@@ -92,21 +135,36 @@ long long dcs_buffers_check_guards(char* where, size_t where_len) {
     long long bad = 0;
     const unsigned char poison = (unsigned char)guard_poison_env();
     std::vector<unsigned char> h;
+    // bytes [lo, hi) of the allocation around `ptr` (lo < 0: leading red zone) must still hold the poison
+    auto check = [&](const char* ptr, std::ptrdiff_t lo, std::ptrdiff_t hi, size_t bytes, const char* what, const char* name) -> bool {
+        h.resize((size_t)(hi - lo));
+        if (hipMemcpy(h.data(), ptr + lo, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (size_t i = 0; i < h.size(); ++i)
+            if (h[i] != poison) {
+                if (bad == 0 && where) {
+                    const std::ptrdiff_t at = lo + (std::ptrdiff_t)i;
+                    if (at < 0)
+                        snprintf(where, where_len, "leading red zone of %s%s (%zu bytes), %td bytes before the block", what, name, bytes, -at);
+                    else
+                        snprintf(where, where_len, "trailing red zone of %s%s (%zu bytes), byte %td past the end of the block", what, name,
+                                 bytes, at - (std::ptrdiff_t)bytes);
+                }
+                ++bad;
+            }
+        return true;
+    };
     for (DcsBuffer* b : r.live) {
         if (!b->base || b->guard == 0) continue;
-        h.resize(b->guard);
-        for (int side = 0; side < 2; ++side) {
-            const char* src = side == 0 ? (const char*)b->base : (const char*)b->ptr + b->bytes;
-            if (hipMemcpy(h.data(), src, b->guard, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-            for (size_t i = 0; i < b->guard; ++i)
-                if (h[i] != poison) {
-                    if (bad == 0 && where)
-                        snprintf(where, where_len, "%s red zone of a %zu-byte scratch block, byte %zu (%s the block)",
-                                 side == 0 ? "leading" : "trailing", b->bytes, i, side == 0 ? "counted from the red zone's start, before" : "past the end of");
-                    ++bad;
-                }
-        }
+        const std::ptrdiff_t g = (std::ptrdiff_t)b->guard, n = (std::ptrdiff_t)b->bytes;
+        if (!check((const char*)b->ptr, -g, 0, b->bytes, "a scratch block", "") ||
+            !check((const char*)b->ptr, n, n + g, b->bytes, "a scratch block", ""))
+            return -1;
     }
+    const std::ptrdiff_t g = (std::ptrdiff_t)guard_bytes_env();
+    for (const GuardedBlock& o : r.owned)
+        if (!check(o.ptr, -g, 0, o.bytes, "", o.name.c_str()) ||
+            !check(o.ptr, (std::ptrdiff_t)o.bytes, (std::ptrdiff_t)o.guard_end, o.bytes, "", o.name.c_str()))
+            return -1;
     return bad;
 }
 
@@ -121,12 +179,12 @@ extern "C" int dcs_debug_check_guards(dcs_ctx* ctx, int64_t* n_blocks_out) {
         std::lock_guard<std::mutex> lk(r.mu);
         int64_t n = 0;
         for (DcsBuffer* b : r.live) n += (b->base && b->guard) ? 1 : 0;
-        *n_blocks_out = n;
+        *n_blocks_out = n + (int64_t)r.owned.size();
     }
     char where[200] = "";
     const long long bad = dcs_buffers_check_guards(where, sizeof(where));
     if (bad < 0) DCS_FAIL(DCS_EHIP, "dcs_debug_check_guards: copying a red zone failed");
-    if (bad > 0) DCS_FAIL(DCS_EHIP, "scratch red zones damaged: %lld bytes, first in the %s", bad, where);
+    if (bad > 0) DCS_FAIL(DCS_EHIP, "red zones damaged: %lld bytes, first in the %s", bad, where);
     return DCS_OK;
 }
 
@@ -263,7 +321,7 @@ extern "C" int dcs_destroy(dcs_ctx* ctx) {
     }
     ctx->gemm_ws.release();
     ctx->score_ring.release();
-    if (ctx->ola_rise_d) (void)hipFree(ctx->ola_rise_d);
+    dcs_dev_free(ctx->ola_rise_d);
     delete ctx;
     return DCS_OK;
 }
@@ -336,18 +394,18 @@ extern "C" int dcs_stft_plan(dcs_ctx* ctx, int frame, int hop, const double* win
         twf[k].x = (float)twd[k].x;
         twf[k].y = (float)twd[k].y;
     }
-    auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-        DCS_HIP(hipMalloc(dst, bytes));
+    auto up = [&](void** dst, const void* src, size_t bytes, const char* name) -> int {
+        DCS_HIP(dcs_dev_alloc(dst, bytes, name));
         DCS_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
         return DCS_OK;
     };
     int rc = DCS_OK;
-    if ((rc = up((void**)&p->win_f, wf.data(), frame * sizeof(float))) ||
-        (rc = up((void**)&p->win_d, window_h, frame * sizeof(double))) ||
-        (rc = up((void**)&p->wsq_f, wsqf.data(), frame * sizeof(float))) ||
-        (rc = up((void**)&p->wsq_d, wsqd.data(), frame * sizeof(double))) ||
-        (rc = up((void**)&p->tw_f, twf.data(), (M + 1) * sizeof(float2))) ||
-        (rc = up((void**)&p->tw_d, twd.data(), (M + 1) * sizeof(double2)))) {
+    if ((rc = up((void**)&p->win_f, wf.data(), frame * sizeof(float), "stft.win_f")) ||
+        (rc = up((void**)&p->win_d, window_h, frame * sizeof(double), "stft.win_d")) ||
+        (rc = up((void**)&p->wsq_f, wsqf.data(), frame * sizeof(float), "stft.wsq_f")) ||
+        (rc = up((void**)&p->wsq_d, wsqd.data(), frame * sizeof(double), "stft.wsq_d")) ||
+        (rc = up((void**)&p->tw_f, twf.data(), (M + 1) * sizeof(float2), "stft.tw_f")) ||
+        (rc = up((void**)&p->tw_d, twd.data(), (M + 1) * sizeof(double2), "stft.tw_d"))) {
         dcs_stft_plan_destroy(p);
         return rc;
     }
@@ -358,12 +416,12 @@ extern "C" int dcs_stft_plan(dcs_ctx* ctx, int frame, int hop, const double* win
 extern "C" int dcs_stft_plan_destroy(dcs_stft* p) {
     if (!p) return DCS_OK;
     DCS_ON_DEVICE(p->ctx->device);
-    (void)hipFree(p->win_f);
-    (void)hipFree(p->win_d);
-    (void)hipFree(p->wsq_f);
-    (void)hipFree(p->wsq_d);
-    (void)hipFree(p->tw_f);
-    (void)hipFree(p->tw_d);
+    dcs_dev_free(p->win_f);
+    dcs_dev_free(p->win_d);
+    dcs_dev_free(p->wsq_f);
+    dcs_dev_free(p->wsq_d);
+    dcs_dev_free(p->tw_f);
+    dcs_dev_free(p->tw_d);
     delete p;
     return DCS_OK;
 }
@@ -475,10 +533,10 @@ extern "C" int dcs_overlap_add(dcs_ctx* ctx, const float* out_d, int64_t n, int 
     if (ov > 0 && (rise != ctx->ola_rise_h || !ctx->ola_rise_d)) {
         // a new ramp: earlier launches on the stream may still read the old table
         DCS_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->ola_rise_d) (void)hipFree(ctx->ola_rise_d);
+        dcs_dev_free(ctx->ola_rise_d);
         ctx->ola_rise_d = nullptr;
         ctx->ola_rise_h.clear();
-        DCS_HIP(hipMalloc((void**)&ctx->ola_rise_d, ov * sizeof(float)));
+        DCS_HIP(dcs_dev_alloc((void**)&ctx->ola_rise_d, ov * sizeof(float), "ctx.ola_rise"));
         DCS_HIP(hipMemcpy(ctx->ola_rise_d, rise.data(), ov * sizeof(float), hipMemcpyHostToDevice));
         ctx->ola_rise_h = rise;
     }

@@ -96,8 +96,21 @@ struct DcsBuffer {
     void release();
     ~DcsBuffer();              // leaves the guard registry (the memory itself is freed by release())
 };
-// number of damaged red-zone bytes over every live guarded DcsBuffer (0 = intact), < 0 on a HIP error
+// number of damaged red-zone bytes over every live guarded block (DcsBuffer and dcs_dev_alloc; 0 = intact), < 0 on a HIP error
 long long dcs_buffers_check_guards(char* where, size_t where_len);
+
+// Every device block libdcs owns outside DcsBuffer -- model weights and their packed / fragment-ordered / bf16 and f16
+// copies, STFT plan tables, cross-fade ramps -- comes from here and goes back through dcs_dev_free (which takes the
+// pointer dcs_dev_alloc handed out).  Without DCS_WS_GUARD: hipMalloc / hipFree.  With it: the DcsBuffer treatment --
+// red zones on either side, payload rounded up to 256 bytes, red zones AND payload filled with the poison byte (so padding
+// of a plane packed on the device that no pack kernel wrote shows as NaN), the block registered under `name` for
+// dcs_debug_check_guards.  Returns what the underlying HIP call returned (DCS_HIP(...) works as it did with hipMalloc).
+hipError_t dcs_dev_alloc(void** p, size_t bytes, const char* name);
+void dcs_dev_free(void* p);
+
+// DcsGemm::Bfrag: 16-K chunks per 16-column block.  gemm_rows_splitk_kernel loads four chunks per 64-K step of a wave
+// without a K check, so the block holds whole steps (the chunks past K zero); the packer and the kernel both use this.
+__host__ __device__ inline int dcs_bfrag_chunks(int K) { return ((K + 63) >> 6) * 4; }
 
 // Small host tables (clip lengths, note rectangles) on their way to the device without a stream synchronisation in the
 // call: begin() hands out a pinned host slot of a ring (waiting, if ever, for the upload that used the slot kSlots calls
@@ -228,7 +241,7 @@ struct DcsGemm {
     // Bq holds the weights UNSPLIT, as 32-byte f32 pieces in the planes' piece order (dcs_gemm_pack_b32): the all-rows kernels split
     // them in registers -- 4 bytes per weight from HBM instead of 6.  Only those kernels take it (M 128 .. 176)
     int bq_f32;
-    // optional (gemm_rows_splitk_kernel only): B once more in that kernel's FRAGMENT order, [n_cols / 16][(K + 15) / 16][64 lanes][4]:
+    // optional (gemm_rows_splitk_kernel only): B once more in that kernel's FRAGMENT order, [n_cols / 16][dcs_bfrag_chunks(K)][64 lanes][4]:
     // lane (kq, fi) of column block nt and K chunk c holds B[16 c + 4 kq + e][16 nt + fi], e = 0 .. 3 (rows >= K zero) -- one
     // 16-byte load per lane and 16 K (1 KB per wave, contiguous) instead of four 4-byte loads on four 64-byte segments
     const float* Bfrag;

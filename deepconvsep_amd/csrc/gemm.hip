@@ -219,7 +219,8 @@ __global__ __launch_bounds__(kThreads) void gemm_rows_kernel(const DcsGemm g) {
 // of four consecutive steps are one 16-byte load.  Two accumulators alternate to stay issue-bound
 // (the 16x16x4 f32 MFMA has a 40-cycle dependent latency but a 32-cycle issue interval).
 // ------------------------------------------------------------------------------------------------
-// BF: B from DcsGemm::Bfrag (fragment order: one 16-byte load per lane and 16 K).
+// BF: B from DcsGemm::Bfrag (fragment order: one 16-byte load per lane and 16 K; dcs_bfrag_chunks(K) chunks per column block, so
+// the four chunks of a wave's last step are inside the block whatever K is -- the B loads have no K check).
 template <bool BF>
 __global__ __launch_bounds__(kThreads) void gemm_rows_splitk_kernel(const DcsGemm g) {
     __shared__ float red[3 * 64 * 4];
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void gemm_rows_splitk_kernel(const DcsGem
     const int64_t rr = row_ok ? r : 0;
     const float* a_ptr = g.A + (g.a_rowmap ? (int64_t)g.a_rowmap[rr] : dcs_group_row(rr, g.a_gdiv, g.a_gmul, g.a_gdiv >= g.M)) * g.lda + 4 * kq;
     const float* b_ptr = g.B + (int64_t)(4 * kq) * gldb + n0 + fi;
-    const f32x4* bf_ptr = BF ? reinterpret_cast<const f32x4*>(g.Bfrag) + (int64_t)blockIdx.y * ((gK + 15) >> 4) * 64 + lane : nullptr;
+    const f32x4* bf_ptr = BF ? reinterpret_cast<const f32x4*>(g.Bfrag) + (int64_t)blockIdx.y * dcs_bfrag_chunks(gK) * 64 + lane : nullptr;
 
     f32x4 a_cur[4], a_nxt[4];
     float b_cur[16], b_nxt[16];

@@ -1278,8 +1278,9 @@ __global__ __launch_bounds__(kThreads) void mask_ola_kernel(const float* __restr
 }
 
 template <typename T>
-int upload(T** dst, const std::vector<T>& src) {
-    DCS_HIP(hipMalloc((void**)dst, src.size() * sizeof(T)));
+int upload(T** dst, const std::vector<T>& src, const char* field) {   // field: the UP macro's spelling, "g->W1c"
+    const std::string name = std::string("generic.") + (strncmp(field, "g->", 3) ? field : field + 3);
+    DCS_HIP(dcs_dev_alloc((void**)dst, src.size() * sizeof(T), name.c_str()));
     DCS_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return DCS_OK;
 }
@@ -1523,7 +1524,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
     for (int h = 0; h < d.hidden; ++h) biasfc[h] = P[7][h];
     int rc = DCS_OK;
 #define UP(dst, src)                                \
-    if (rc == DCS_OK) rc = upload(&(dst), (src));
+    if (rc == DCS_OK) rc = upload(&(dst), (src), #dst);
     UP(g->W1c, W1c) UP(g->W1t, W1t) UP(g->bias1, bias1) UP(g->W2m, W2m) UP(g->bias2, bias2) UP(g->k2off, k2off) UP(g->k2uv, k2uv)
     UP(g->W2t, W2t) UP(g->bias0, bias0) UP(g->kt_off, kt_off) UP(g->kt_uv, kt_uv) UP(g->Bfc, Bfc) UP(g->biasfc, biasfc)
     UP(g->W2m_h, W2m_h) UP(g->W2t_h, W2t_h)
@@ -1567,7 +1568,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
             float* Wf2_d = nullptr;
             UP(Wf2_d, Wf2) UP(g->bias2fc, bias2fc)
             const size_t rows = (size_t)dcs_round_up(Kf, 128);
-            if (rc == DCS_OK && hipMalloc((void**)&g->B2fc, rows * g->hid64 * sizeof(float)) != hipSuccess) {
+            if (rc == DCS_OK && dcs_dev_alloc((void**)&g->B2fc, rows * g->hid64 * sizeof(float), "generic.B2fc") != hipSuccess) {
                 (void)hipGetLastError();
                 g->B2fc = nullptr;                       // does not fit: layer by layer
             }
@@ -1578,7 +1579,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
                 if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = DCS_EHIP;
                 g->K2fc = (int)Kf;
             }
-            if (Wf2_d) (void)hipFree(Wf2_d);
+            dcs_dev_free(Wf2_d);
         }
     }
     if (g->use_slabconv) { UP(g->Wslab, Wslab) UP(g->Wslab_t, Wslab_t) UP(g->Wslab_q3, Wslab_q3) UP(g->Wslab_t_q3, Wslab_t_q3) UP(g->Wslab_h, Wslab_h) UP(g->Wslab_t_h, Wslab_t_h) UP(g->Wps_q3, Wps_q3) UP(g->Wps_t_q3, Wps_t_q3) UP(g->Wps_h, Wps_h) UP(g->Wps_t_h, Wps_t_h) }
@@ -1645,8 +1646,7 @@ void dcs_generic_destroy(DcsGenericNet* g) {
                     g->biasd[3], g->bout, g->rise_d, g->Bdq[0], g->Bdq[1], g->Bdq[2], g->Bdq[3], g->biasd_cl[0], g->biasd_cl[1],
                     g->biasd_cl[2], g->biasd_cl[3], g->Wx3, g->Bfcq, g->Wfx3, g->Bdh[0], g->Bdh[1], g->Bdh[2], g->Bdh[3], g->biasd_h[0],
                     g->biasd_h[1], g->biasd_h[2], g->biasd_h[3], g->Bfch, g->Bd32[0], g->Bd32[1], g->Bd32[2], g->Bd32[3], g->B2fc, g->bias2fc};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    for (void* p : ptrs) dcs_dev_free(p);
     g->ws.release();
     delete g;
 }
@@ -1878,13 +1878,13 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
         ks16 = dcs_gemm_f16_longk_slices(ctx, (int)n, pitch16, g->hid64);
         if (ks16 >= 2 && !g->Bfch) {
             void* plane = nullptr;
-            if (hipMalloc(&plane, dcs_gemm_bh_bytes(g->flat_p, g->hid64)) != hipSuccess) {
+            if (dcs_dev_alloc(&plane, dcs_gemm_bh_bytes(g->flat_p, g->hid64), "generic.Bfch") != hipSuccess) {
                 (void)hipGetLastError();
                 g->bfch_failed = true;
             } else {
                 const int rc = dcs_gemm_pack_bh_plain(ctx, g->Bfc, g->flat_p, g->hid64, g->hid64, plane);
                 if (rc != DCS_OK) {
-                    (void)hipFree(plane);
+                    dcs_dev_free(plane);
                     return rc;
                 }
                 g->Bfch = plane;
@@ -1966,13 +1966,13 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
         if (!fold2 && fcq_on && n >= 128 && n <= 176 && g->flat_p >= 16384 && (g->hid64 % 128) == 0 && !g->Bfcq && !g->bfcq_failed &&
             (!g->conv_f16 || g->bfch_failed)) {           // (under the f16 switch the layer takes the f16 plane below instead)
             void* planes = nullptr;                       // (unsplit 32-byte pieces since round 6: the long-K launch is the all-rows kernel)
-            if (hipMalloc(&planes, dcs_gemm_b32_bytes(g->flat_p, g->hid64)) != hipSuccess) {
+            if (dcs_dev_alloc(&planes, dcs_gemm_b32_bytes(g->flat_p, g->hid64), "generic.Bfcq") != hipSuccess) {
                 (void)hipGetLastError();
                 g->bfcq_failed = true;
             } else {
                 const int rc = dcs_gemm_pack_b32(ctx, g->Bfc, g->flat_p, g->hid64, g->hid64, planes);
                 if (rc != DCS_OK) {
-                    (void)hipFree(planes);
+                    dcs_dev_free(planes);
                     return rc;
                 }
                 g->Bfcq = planes;
@@ -2027,17 +2027,18 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
             if (g->Bdh[s2]) continue;
             void* planes = nullptr;
             float* bias_h = nullptr;
-            if (hipMalloc(&planes, dcs_gemm_bh_bytes(g->hid64, n_out)) != hipSuccess || hipMalloc((void**)&bias_h, (size_t)n_out * 4) != hipSuccess) {
+            if (dcs_dev_alloc(&planes, dcs_gemm_bh_bytes(g->hid64, n_out), "generic.Bdh") != hipSuccess ||
+                dcs_dev_alloc((void**)&bias_h, (size_t)n_out * 4, "generic.biasd_h") != hipSuccess) {
                 (void)hipGetLastError();
-                if (planes) (void)hipFree(planes);
+                dcs_dev_free(planes);
                 g->bdh_failed = true;
                 break;
             }
             int rc = dcs_gemm_pack_bh(ctx, g->Bd[s2], g->hid64, g->flat64, n_out, d.nf2, npos, 32, planes);
             if (rc == DCS_OK) rc = dcs_gemm_pack_bias_cl(ctx, g->biasd[s2], n_out, d.nf2, npos, 32, bias_h);
             if (rc != DCS_OK) {
-                (void)hipFree(planes);
-                (void)hipFree(bias_h);
+                dcs_dev_free(planes);
+                dcs_dev_free(bias_h);
                 return rc;
             }
             g->Bdh[s2] = planes;                         // published only when packed
@@ -2086,14 +2087,15 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
             // would multiply by uninitialised memory).  Out of memory here (~0.7 GB for Bach10, outside the chunk budget) is
             // not an error of the forward pass: the layer stays on the f32 GEMM (q.Bq == nullptr) for the model's lifetime.
             void* planes = nullptr;
-            if (hipMalloc(&planes, win ? dcs_gemm_b32_bytes(rows, g->flat64) : dcs_gemm_bq_bytes(rows, g->flat64)) != hipSuccess) {
+            if (dcs_dev_alloc(&planes, win ? dcs_gemm_b32_bytes(rows, g->flat64) : dcs_gemm_bq_bytes(rows, g->flat64),
+                              win ? "generic.Bd32" : "generic.Bdq") != hipSuccess) {
                 (void)hipGetLastError();
                 g->bdq_failed = true;
                 break;
             }
             const int rc = pack(g->Bd[s2], planes);
             if (rc != DCS_OK) {
-                (void)hipFree(planes);
+                dcs_dev_free(planes);
                 return rc;
             }
             store[s2] = planes;
@@ -2419,10 +2421,10 @@ int dcs_generic_separate(DcsGenericNet* g, dcs_stft* plan, const float* audio, i
         }
         if (g->rise_d) {
             DCS_HIP(hipStreamSynchronize(ctx->stream));
-            (void)hipFree(g->rise_d);
+            dcs_dev_free(g->rise_d);
             g->rise_d = nullptr;
         }
-        DCS_HIP(hipMalloc((void**)&g->rise_d, r.size() * sizeof(float)));
+        DCS_HIP(dcs_dev_alloc((void**)&g->rise_d, r.size() * sizeof(float), "generic.rise"));
         DCS_HIP(hipMemcpy(g->rise_d, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
         g->rise_ov = ov;
     }

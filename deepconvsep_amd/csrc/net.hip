@@ -74,8 +74,8 @@ int arch_dims(int arch, int C, int tc, int F, Dims* d) {
 }
 
 template <typename T>
-int upload(T** dst, const std::vector<T>& src) {
-    DCS_HIP(hipMalloc((void**)dst, src.size() * sizeof(T)));
+int upload(T** dst, const std::vector<T>& src, const char* name) {
+    DCS_HIP(dcs_dev_alloc((void**)dst, src.size() * sizeof(T), name));
     DCS_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return DCS_OK;
 }
@@ -161,7 +161,7 @@ int ensure_rise(dcs_model* m, int ov) {
         r[ov - 1] = 1.0f;
     }
     float* d = nullptr;
-    DCS_HIP(hipMalloc((void**)&d, r.size() * sizeof(float)));
+    DCS_HIP(dcs_dev_alloc((void**)&d, r.size() * sizeof(float), "dsd.rise"));
     DCS_HIP(hipMemcpy(d, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
     m->rise_tabs.emplace_back(ov, d);
     m->rise_d = d;
@@ -280,17 +280,18 @@ int pack_dsd(dcs_model* m, const std::vector<std::vector<float>>& P) {
                 Bfin[(size_t)c * m->Fpad + ch * ldF + f] = W1[((size_t)c * C + ch) * F + (F - 1 - f)];
     std::vector<float> bout(P[8 + 2 * d.n_fc].begin(), P[8 + 2 * d.n_fc].end());
 
-    DCS_CHECK(upload(&m->B1, B1));
-    DCS_CHECK(upload(&m->bias1, bias1));
-    DCS_CHECK(upload(&m->B2, B2));
-    DCS_CHECK(upload(&m->bias2, bias2));
-    DCS_CHECK(upload(&m->Bfc, Bfc));
-    DCS_CHECK(upload(&m->biasfc, biasfc));
+    DCS_CHECK(upload(&m->B1, B1, "dsd.B1"));
+    DCS_CHECK(upload(&m->bias1, bias1, "dsd.bias1"));
+    DCS_CHECK(upload(&m->B2, B2, "dsd.B2"));
+    DCS_CHECK(upload(&m->bias2, bias2, "dsd.bias2"));
+    DCS_CHECK(upload(&m->Bfc, Bfc, "dsd.Bfc"));
+    DCS_CHECK(upload(&m->biasfc, biasfc, "dsd.biasfc"));
     if (d.h2 + kh - 1 == m->tc) {   // (always: h2 = tc - kh + 1)
-        DCS_CHECK(upload(&m->B2fc, B2fc));
-        DCS_CHECK(upload(&m->bias2fc, bias2fc));
-        {   // fragment order of the few-rows GEMM (launch groups of up to ~1000 tiles take that kernel for this layer)
-            const int K = m->tc * CI, kc = (K + 15) / 16, nt = m->hid64 / 16;
+        DCS_CHECK(upload(&m->B2fc, B2fc, "dsd.B2fc"));
+        DCS_CHECK(upload(&m->bias2fc, bias2fc, "dsd.bias2fc"));
+        {   // fragment order of the few-rows GEMM (launch groups of up to ~1000 tiles take that kernel for this layer); whole
+            // 64-K steps per column block, the chunks past K zero
+            const int K = m->tc * CI, kc = dcs_bfrag_chunks(K), nt = m->hid64 / 16;
             std::vector<float> fr((size_t)nt * kc * 64 * 4, 0.f);
             for (int t = 0; t < nt; ++t)
                 for (int c = 0; c < kc; ++c)
@@ -299,20 +300,20 @@ int pack_dsd(dcs_model* m, const std::vector<std::vector<float>>& P) {
                             const int k = 16 * c + 4 * (lane >> 4) + e;
                             if (k < K) fr[(((size_t)t * kc + c) * 64 + lane) * 4 + e] = B2fc[(size_t)k * m->hid64 + 16 * t + (lane & 15)];
                         }
-            DCS_CHECK(upload(&m->B2fc_frag, fr));
+            DCS_CHECK(upload(&m->B2fc_frag, fr, "dsd.B2fc_frag"));
         }
     }
-    DCS_CHECK(upload(&m->Bd, Bd));
-    DCS_CHECK(upload(&m->biasd, biasd));
-    DCS_CHECK(upload(&m->Bw2, Bw2));
-    DCS_CHECK(upload(&m->Bw2s, Bw2s));
-    DCS_CHECK(upload(&m->Bfin, Bfin));
-    DCS_CHECK(upload(&m->bout, bout));
+    DCS_CHECK(upload(&m->Bd, Bd, "dsd.Bd"));
+    DCS_CHECK(upload(&m->biasd, biasd, "dsd.biasd"));
+    DCS_CHECK(upload(&m->Bw2, Bw2, "dsd.Bw2"));
+    DCS_CHECK(upload(&m->Bw2s, Bw2s, "dsd.Bw2s"));
+    DCS_CHECK(upload(&m->Bfin, Bfin, "dsd.Bfin"));
+    DCS_CHECK(upload(&m->bout, bout, "dsd.bout"));
     {
         // the per-source dense weights once more as three bf16 planes, split on the device (the wide-B GEMM of large
         // launches runs on the bf16 matrix pipe; the encoder GEMMs are latency-bound and stay f32)
         const int rows = (int)dcs_round_up(m->hid64, 128);
-        DCS_HIP(hipMalloc(&m->Bdq, dcs_gemm_bq_bytes(rows, m->nd64)));
+        DCS_HIP(dcs_dev_alloc(&m->Bdq, dcs_gemm_bq_bytes(rows, m->nd64), "dsd.Bdq"));
         DCS_CHECK(dcs_gemm_pack_bq(m->ctx, m->Bd, rows, m->nd64, m->nd64, m->Bdq));
     }
     if (C == 1) {
@@ -334,7 +335,7 @@ int pack_dsd(dcs_model* m, const std::vector<std::vector<float>>& P) {
                     Bpk[((((size_t)f * 3 + pl) * 2 + kb) * 4 + g) * 8 + j] = (uint16_t)(bits >> 16);
                 }
             }
-        DCS_CHECK(upload(&m->Bpk, Bpk));
+        DCS_CHECK(upload(&m->Bpk, Bpk, "dsd.Bpk"));
         // streaming deconv2 on the bf16 pipe: Bw2q[group][channel 8][tap 16][25 pieces][8 bf16]; piece plane * 8 + kb * 4 +
         // kq holds filters co = 32 kb + 8 kq + j of W2c[co, ci, dt]; x = plane0 + plane1 + plane2 exactly
         std::vector<uint16_t> Bw2q(dsd_d2q_bytes(CI) / 2, 0);
@@ -354,22 +355,22 @@ int pack_dsd(dcs_model* m, const std::vector<std::vector<float>>& P) {
                             Bw2q[(((size_t)ci * 16 + dt) * kDsdD2qTapU4 + pl * 8 + kb * 4 + kq) * 8 + j] = (uint16_t)(bits >> 16);
                         }
                     }
-        DCS_CHECK(upload(&m->Bw2q, Bw2q));
+        DCS_CHECK(upload(&m->Bw2q, Bw2q, "dsd.Bw2q"));
     }
     // one-batch kernels (dsd_lat.hip): built for the reference's DSD shapes (50 + 50 filters, time_context 30, 128 hidden units)
     if (C == 1 && CI == 52 && CP == 52 && d.h2 == 16 && kh == 15 && m->tc == 30 && m->hid64 == 128 && d.n_fc == 3 && m->Bpk) {
         std::vector<float> pk;
         m->lat_slice1 = (int)dcs_round_up((m->K1 + 15) / 16, 4);
         dcs_lat_pack_b(B1.data(), 64, m->K1, 4, m->lat_slice1, 16, &pk);
-        DCS_CHECK(upload(&m->L1p, pk));
+        DCS_CHECK(upload(&m->L1p, pk, "dsd.L1p"));
         dcs_lat_pack_b(B2.data(), 64, kh * CI, 4, CI, kh, &pk);       // one slice per tap
-        DCS_CHECK(upload(&m->L2p, pk));
+        DCS_CHECK(upload(&m->L2p, pk, "dsd.L2p"));
         dcs_lat_pack_b(Bfc.data(), m->hid64, d.h2 * CP, m->hid64 / 16, CP, d.h2, &pk);
-        DCS_CHECK(upload(&m->Lfcp, pk));
+        DCS_CHECK(upload(&m->Lfcp, pk, "dsd.Lfcp"));
         dcs_lat_pack_b(Bd.data(), m->nd64, m->hid64, m->nd64 / 16, 32, 4, &pk);
-        DCS_CHECK(upload(&m->Ldp, pk));
+        DCS_CHECK(upload(&m->Ldp, pk, "dsd.Ldp"));
         dcs_lat_pack_deconv2(Bw2s.data(), (int)dcs_round_up(CI, kDsdGch), &pk);
-        DCS_CHECK(upload(&m->Lw2p, pk));
+        DCS_CHECK(upload(&m->Lw2p, pk, "dsd.Lw2p"));
         m->lat_ok = true;
     }
     return DCS_OK;
@@ -602,21 +603,18 @@ extern "C" int dcs_model_destroy(dcs_model* m) {
     DCS_ON_DEVICE(m->ctx->device);
     float* ptrs[] = {m->B1, m->bias1, m->B2, m->bias2, m->Bfc, m->biasfc, m->Bd, m->biasd, m->Bw2, m->Bw2s, m->Bfin, m->bout,
                      m->B2fc, m->bias2fc, m->B2fc_frag};
-    for (float* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto& t : m->rise_tabs)
-        if (t.second) (void)hipFree(t.second);
+    for (float* p : ptrs) dcs_dev_free(p);
+    for (auto& t : m->rise_tabs) dcs_dev_free(t.second);
     float* lat[] = {m->L1p, m->L2p, m->Lfcp, m->Ldp, m->Lw2p};
-    for (float* p : lat)
-        if (p) (void)hipFree(p);
+    for (float* p : lat) dcs_dev_free(p);
     if (m->gen) dcs_generic_destroy(m->gen);
     for (auto& g : m->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     m->ws.release();
     m->clip_ring.release();
-    if (m->Bpk) (void)hipFree(m->Bpk);
-    if (m->Bw2q) (void)hipFree(m->Bw2q);
-    if (m->Bdq) (void)hipFree(m->Bdq);
+    dcs_dev_free(m->Bpk);
+    dcs_dev_free(m->Bw2q);
+    dcs_dev_free(m->Bdq);
     delete m;
     return DCS_OK;
 }

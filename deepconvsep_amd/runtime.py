@@ -91,7 +91,8 @@ class Context(object):
 
     def check_guards(self):
         """``dcs_debug_check_guards``: with ``DCS_WS_GUARD=<bytes>`` in the environment, verify the red zones around every
-        scratch block libdcs holds (raises on damage); returns the number of guarded blocks."""
+        device block libdcs holds -- scratch, model weights and their packed copies, plan tables, ramps (raises on damage,
+        naming the block); returns the number of guarded blocks."""
         n = c_int64()
         _lib.check(self._lib.dcs_debug_check_guards(self._h, byref(n)))
         return n.value

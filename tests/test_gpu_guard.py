@@ -2,9 +2,13 @@
 
 Parity tests cannot see an out-of-bounds READ that lands in mapped memory, and the kernels use "load everything with a
 clamped index, multiply by 0" tricks exactly where such reads would hide.  Here every device buffer handed to the C ABI
-(inputs, weights, outputs) is carved out of a larger allocation with a >= 64 KiB red zone on either side, red zones AND
-output payloads are filled with a poison byte before the call, and libdcs's own scratch blocks get the same treatment
-(DCS_WS_GUARD / DCS_WS_POISON, dcs_debug_check_guards).  The main launch shapes of every entry point run in a child process,
+(inputs, the caller's copies of the weights, outputs) is carved out of a larger allocation with a >= 64 KiB red zone on
+either side, red zones AND output payloads are filled with a poison byte before the call.  The kernels never read the
+caller's weights: they read libdcs's own device copies (packed, fragment-ordered, split into bf16 / f16 planes -- made with
+the model, or on first need), and those, the STFT plan tables, the cross-fade ramps and libdcs's scratch blocks all get the
+same treatment from libdcs itself, payload poisoned too (DCS_WS_GUARD / DCS_WS_POISON: dcs_dev_alloc and DcsBuffer,
+checked by dcs_debug_check_guards).  Each model's creation must add at least as many guarded blocks as the device buffers
+it keeps (a model whose weights escaped the harness fails).  The main launch shapes of every entry point run in a child process,
 once with poison 0xFF (every float32 / bf16 / f16 word a NaN, every int64 -1) and once with 0x4B (float32 1.3e7, finite):
   (i)   no red zone byte may change (out-of-bounds writes, ABI buffers and scratch);
   (ii)  every output must be finite (a NaN read from a red zone, from unwritten scratch or from an unwritten output element
@@ -101,6 +105,15 @@ runtime._torch = lambda: _proxy
 
 ctx = default_context()
 results = {}
+model_blocks = {}
+
+
+def guarded_model(name, make):
+    """make() -> a Separator / Network; the guarded blocks libdcs gained across its creation are the model's own"""
+    before = ctx.check_guards()
+    obj = make()
+    model_blocks[name] = ctx.check_guards() - before
+    return obj
 
 
 def record(name, *outs):
@@ -133,7 +146,7 @@ def tiles_samples(n, tc=30, ov=25, hop=512):
 # ---- DSD fused path, both kernel families ---------------------------------------------------------------------------
 N, F = 2048, 1025
 P_DSD = synth_params("dsd", 30, F, seed=2)
-sep = dcs.Separator("dsd", P_DSD, 0.3, 30, 25, 32, F, N, 512, np.hanning)
+sep = guarded_model("dsd", lambda: dcs.Separator("dsd", P_DSD, 0.3, 30, 25, 32, F, N, 512, np.hanning))
 if want("dsd_1"):
     record("dsd_1", sep.separate(synth_audio(tiles_samples(1) + 77, seed=1)))           # one tile, ragged tail
 if want("dsd_32_onebatch"):
@@ -162,7 +175,8 @@ if want("dsd_spectra_stepwise"):
     record("dsd_spectra_stepwise", s_d, m_d, p_d, sep.separate_stepwise(synth_audio(2 * 44100, seed=6)))
 del sep
 if want("dsd_n1024"):
-    s1 = dcs.Separator("dsd", synth_params("dsd", 30, 513, seed=2), 0.3, 30, 25, 32, 513, 1024, 512, np.hanning)
+    s1 = guarded_model("dsd_n1024", lambda: dcs.Separator("dsd", synth_params("dsd", 30, 513, seed=2), 0.3, 30, 25, 32, 513, 1024, 512,
+                                                          np.hanning))
     record("dsd_n1024", s1.separate(synth_audio(5 * 44100 + 3, seed=7)), *s1.separate_many(
         [synth_audio(44100 * 2 + 17 * i, seed=40 + i) for i in range(3)]))
     del s1
@@ -179,7 +193,7 @@ if want("transform"):
     pcm = ctx.to_device(np.linspace(-1.2, 1.2, 100003), np.float32)
     record("pcm_int16", runtime.pcm_to_int16(ctx, pcm))
 if want("operators"):
-    net = runtime.Network(ctx, "dsd", synth_params("dsd", 30, 513, seed=2), 30, 513)
+    net = guarded_model("operators", lambda: runtime.Network(ctx, "dsd", synth_params("dsd", 30, 513, seed=2), 30, 513))
     rs = np.random.RandomState(3)
     x = ctx.to_device(np.abs(rs.randn(37, 1, 30, 513)).astype(np.float32), np.float32)
     out = net.forward_masked(x)
@@ -189,22 +203,31 @@ if want("operators"):
 # ---- generic graphs -----------------------------------------------------------------------------------------------
 if want("ikala"):
     for nm, seed in (("ikala", 1), ("ikala_nopool", 6)):
-        sp = dcs.Separator("ikala", synth_params(nm, 30, 1025, seed=seed), 0.3, 30, 20, 32, 1025, 2048, 512, np.hanning)
+        sp = guarded_model(nm, lambda: dcs.Separator("ikala", synth_params(nm, 30, 1025, seed=seed), 0.3, 30, 20, 32, 1025, 2048, 512,
+                                                     np.hanning))
         st = synth_audio(5 * 44100 + 9, seed=9, channels=2)
         record(nm, sp.separate(st[:, 0] + st[:, 1]), *sp.separate_many([synth_audio(44100 * 2 + 100 * i, seed=50 + i) for i in range(3)]))
         del sp
 if want("bach10"):
     for f16 in (False, True):
-        sp = dcs.Separator("bach10", synth_params("bach10", 30, 2049, seed=3), 0.3, 30, 25, 32, 2049, 4096, 512, dcs.blackmanharris)
+        nm = "bach10_f16" if f16 else "bach10_f32"
+        sp = guarded_model(nm, lambda: dcs.Separator("bach10", synth_params("bach10", 30, 2049, seed=3), 0.3, 30, 25, 32, 2049, 4096, 512,
+                                                     dcs.blackmanharris))
         if f16:
             sp.net.set_conv_precision("f16")
-        record("bach10_f16" if f16 else "bach10_f32", sp.separate(synth_audio(6 * 44100 + 1, seed=11)))    # 100 tiles: >= 128-row GEMM shapes need 10 s
+        record(nm, sp.separate(synth_audio(6 * 44100 + 1, seed=11)))    # 100 tiles: >= 128-row GEMM shapes need 10 s
         del sp
 if want("bach10_10s"):
-    sp = dcs.Separator("bach10", synth_params("bach10", 30, 2049, seed=3), 0.3, 30, 25, 32, 2049, 4096, 512, dcs.blackmanharris)
-    sp.net.set_conv_precision("f16")
-    record("bach10_10s_f16", sp.separate(synth_audio(441000, seed=0)))
-    del sp
+    # 167 tiles: f32 -- the bottleneck layer on the long-K bf16 x 3 kernel (b32 pieces made on first need), the dense layers on
+    # the all-rows wide-B kernel (Bd32); f16 -- both on the f16 planes (gemm_f16.hip)
+    for f16 in (False, True):
+        nm = "bach10_10s_f16" if f16 else "bach10_10s_f32"
+        sp = guarded_model(nm, lambda: dcs.Separator("bach10", synth_params("bach10", 30, 2049, seed=3), 0.3, 30, 25, 32, 2049, 4096,
+                                                     512, dcs.blackmanharris))
+        if f16:
+            sp.net.set_conv_precision("f16")
+        record(nm, sp.separate(synth_audio(441000, seed=0)))
+        del sp
 if want("score_informed"):
     import tempfile
     tmp = tempfile.mkdtemp()
@@ -216,8 +239,8 @@ if want("score_informed"):
             fh.write(synth_score_text(40 + i, Lc / 44100.0 + 0.5, 40 + 5 * i, 64 + 6 * i))
     nframes = int(np.ceil(Lc / 512.0)) + 2
     mel = score.melody_table(files, tmp, nframes, 44100, 512, 4096)
-    sp = dcs.Separator("bach10_si", synth_params("bach10_si", 30, 2049, seed=5), 0.3, 30, 25, 128, 2049, 4096, 512,
-                       dcs.blackmanharris, tiler="library")
+    sp = guarded_model("score_informed", lambda: dcs.Separator("bach10_si", synth_params("bach10_si", 30, 2049, seed=5), 0.3, 30, 25, 128,
+                                                               2049, 4096, 512, dcs.blackmanharris, tiler="library"))
     audio = synth_audio(Lc, seed=4)
     a = ctx.to_device(audio, np.float32)
     mag, _ = sp.plan.forward(a, phase=False)
@@ -225,7 +248,8 @@ if want("score_informed"):
     record("score_informed", sp.separate_scoreinformed(audio, mel), inp, mask)
     del sp
 if want("stereo"):
-    sp = dcs.Separator("dsd_ild", synth_params("dsd_ild", 30, 513, seed=7), 0.3, 30, 25, 32, 513, 1024, 512, np.hanning, tiler="library")
+    sp = guarded_model("stereo", lambda: dcs.Separator("dsd_ild", synth_params("dsd_ild", 30, 513, seed=7), 0.3, 30, 25, 32, 513, 1024, 512,
+                                                       np.hanning, tiler="library"))
     record("stereo", sp.separate_stereo(synth_audio(4 * 44100 + 21, seed=12, channels=2)))
     del sp
 
@@ -234,9 +258,32 @@ probe = ARENA.alloc((1000,), torch.float32, ctx.device)
 before = ARENA.check()
 ARENA.blocks[-1][0][G + 4000 + 24] = (POISON ^ 0x55)                                   # 24 bytes past the 4000-byte payload
 results["_selftest"] = {"before": before, "after_one_stray_byte": ARENA.check()}
+results["_model_blocks"] = model_blocks
 
 json.dump(results, open(OUT, "w"), indent=1)
 '''
+
+
+# Device blocks each model keeps from its creation on, from the code: net.hip pack_dsd, generic.hip dcs_generic_create (the
+# conditional ones at the graphs' shapes and the default DCS_SLABCONV / DCS_COLCONV / DCS_FOLD_CONV2), plus the 6 tables of a
+# Separator's STFT plan (api.hip).  Blocks made on first need (planes, ramps) come on top, later.
+_PLAN = 6
+_DSD = 15 + 1 + 2 + 5           # B1 .. bout and the folded B2fc, bias2fc, B2fc_frag; Bdq; Bpk, Bw2q (one channel); the 5 one-batch packs
+_DSD_ILD = 15 + 1               # two channels: no bf16x3 final kernel, no one-batch kernels
+_GENERIC = 15                   # W1c .. W2t_h
+
+
+def _generic(n_fc, extra):
+    return _GENERIC + 3 * n_fc + 1 + extra     # Bd, biasd, biasd_cl per dense layer; bout
+
+
+_IKALA = _generic(2, 1 + 10 + 2)              # W1p; the slab-conv weights (10); the folded B2fc, bias2fc
+_BACH10 = _generic(4, 1 + 2 + 8 + 1 + 2)      # W1p; W1m, W1dq; the column-conv weights (8); Wfx3; W1q, Wx3
+_BACH10_SI = _generic(1, 1 + 2 + 8 + 1 + 2)   # the same, one dense layer: the 17 arrays run as the 11-array graph (arch.py)
+MODEL_BLOCKS_MIN = {"dsd": _DSD + _PLAN, "dsd_n1024": _DSD + _PLAN, "operators": _DSD, "stereo": _DSD_ILD + _PLAN,
+                    "ikala": _IKALA + _PLAN, "ikala_nopool": _IKALA + _PLAN, "bach10_f32": _BACH10 + _PLAN,
+                    "bach10_f16": _BACH10 + _PLAN, "bach10_10s_f32": _BACH10 + _PLAN, "bach10_10s_f16": _BACH10 + _PLAN,
+                    "score_informed": _BACH10_SI + _PLAN}
 
 
 def _start(poison, out, only=""):
@@ -263,10 +310,11 @@ def test_red_zones_untouched_outputs_finite_and_independent_of_the_poison(tmp_pa
     for run in (nan_run, big_run):
         st = run.pop("_selftest")
         assert st["before"] == 0 and st["after_one_stray_byte"] == 1, st        # a stray byte in a red zone IS seen
+    model_blocks = nan_run.pop("_model_blocks"), big_run.pop("_model_blocks")
     assert sorted(nan_run) == sorted(big_run) and len(nan_run) >= (1 if only else 20)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "guard_harness.json"), "w") as fh:
-        json.dump({"poison_0xFF": nan_run, "poison_0x4B": big_run}, fh, indent=1)
+        json.dump({"poison_0xFF": nan_run, "poison_0x4B": big_run, "model_blocks": model_blocks[0]}, fh, indent=1)
     problems = []
     for name in sorted(nan_run):
         for tag, run in (("0xFF", nan_run), ("0x4B", big_run)):
@@ -281,8 +329,14 @@ def test_red_zones_untouched_outputs_finite_and_independent_of_the_poison(tmp_pa
                 problems.append("%s [%s]: dcs_debug_check_guards failed" % (name, tag))
         if nan_run[name]["sha256"] != big_run[name]["sha256"]:
             problems.append("%s: outputs differ between the two poison values" % name)
+    # libdcs's own copies of every model's weights are guarded: a model whose device buffers escaped dcs_dev_alloc fails here
+    assert model_blocks[0] == model_blocks[1], model_blocks
+    assert only or sorted(model_blocks[0]) == sorted(MODEL_BLOCKS_MIN), sorted(model_blocks[0])
+    for name, n in sorted(model_blocks[0].items()):
+        if n < MODEL_BLOCKS_MIN[name]:
+            problems.append("%s: its creation added %d guarded device blocks, the model keeps at least %d" % (name, n, MODEL_BLOCKS_MIN[name]))
     assert not problems, "\n".join(problems)
-    # the switch was honoured: the cases that hold a model see its guarded scratch blocks (the transform API has none)
+    # the switch was honoured: the cases that hold a model see its guarded scratch blocks (the transform API has none of those)
     if not only:
         for name in ("dsd_640_batch", "dsd_4096", "ikala", "bach10_f16", "score_informed", "stereo"):
             assert nan_run[name]["scratch_blocks"] >= 1 and nan_run[name]["abi_blocks"] >= 10, (name, nan_run[name])
