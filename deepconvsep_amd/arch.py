@@ -12,11 +12,14 @@ script; the HIP model (``csrc/``) is instantiated from it.
   bach10_si1    examples/bach10_scoreinformed/trainCNNrwc_samp.py:195-235   (the single-branch form, 11 arrays: the branch
                 ``predict_function2`` reads from the 17-array graph, written out on its own)
   dsd_ild       examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py:66-115   (stereo input, 4 branches x 2 channels)
+  bach10_si_1x1 examples/bach10_scoreinformed/trainCNNrwc.py:66-132   (``--function build_ca_1x1``: six strided convolutions,
+                a 1x1 convolution sliced into four branches, per branch the six InverseLayers; 22 arrays)
 """
 import numpy as np
 
 # enum values shared with include/dcs.h
 ARCH_DSD, ARCH_IKALA, ARCH_BACH10, ARCH_BACH10_SI, ARCH_DSD_ILD, ARCH_IKALA_NOPOOL, ARCH_BACH10_SI1 = 0, 1, 2, 3, 4, 5, 6
+ARCH_BACH10_SI_1X1 = 7
 SCORE_NORM_MAX, SCORE_NORM_SUM = 0, 1     # harmonic masks / own maximum (script) | / sum over instruments (trainers)
 MIX_CH0, MIX_SUM = 0, 1                   # soft masks x input channel 0 (script) | x channel sum (trainers)
 EPS_A, EPS_B = 0, 1
@@ -95,9 +98,63 @@ ARCHS = {
     'dsd_ild': Arch('dsd_ild', ARCH_DSD_ILD, 2, (50, 'F', 1), 0, (50, lambda tc: int(tc / 2), 1), 256,
                     [0, 1, 2, 3], 4, EPS_ILD, ['vocals', 'bass', 'drums', 'other']),
 }
+class Deep1x1Arch(object):
+    """``build_ca_1x1`` (trainCNNrwc.py:66-132): conv1 .. conv6 with ``filters`` filters of ``rows`` x 5, stride (1, 2), each
+    rectified and followed by a BiasLayer; a rectified 1x1 convolution of 4 x 200 filters + BiasLayer, sliced into four
+    branches of 200 channels (SliceLayer); per branch ``InverseLayer`` of conv6 .. conv1; the four 4-channel branches
+    concatenated, a BiasLayer(16) and a rectify.  ``predict_function2`` reads channels 0..3 = branch 0 alone
+    (trainCNNrwc.py:243-263)."""
+    filters = (30, 50, 70, 100, 200, 200)
+    rows = (1, 1, 1, 1, 10, 10)
+    kw = 5
+    nf = 200            # nfilt_conv: channels of one branch of the 1x1 convolution
+
+    def __init__(self):
+        self.name = 'bach10_si_1x1'
+        self.code = ARCH_BACH10_SI_1X1
+        self.C = 4
+        self.S = 4
+        self.n_branches = 4
+        self.eps_mode = EPS_B
+        self.source_names = ['bassoon', 'clarinet', 'saxphone', 'violin']
+
+    def dims(self, tc, F):
+        """Per convolution (input rows, input columns, output rows, output columns, Cin, Cout, filter rows)."""
+        if tc < 19 or F < 253:
+            raise ValueError("build_ca_1x1 needs time_context >= 19 and feat_size >= 253 (got %d, %d)" % (tc, F))
+        layers, h, w, cin = [], tc, F, self.C
+        for nf, kh in zip(self.filters, self.rows):
+            ho, wo = h - kh + 1, (w - self.kw) // 2 + 1
+            layers.append(dict(hi=h, wi=w, ho=ho, wo=wo, cin=cin, cout=nf, kh=kh))
+            h, w, cin = ho, wo, nf
+        return dict(layers=layers, h6=h, w6=w)
+
+    def param_shapes(self, tc, F, branches=4):
+        """Shapes in ``get_all_params`` order; ``branches`` < 4: the live-only layout (1x1 rows and final bias cut)."""
+        shapes = []
+        for l in self.dims(tc, F)['layers']:
+            shapes += [(l['cout'], l['cin'], l['kh'], self.kw), (l['cout'],), (l['cout'],)]
+        n11 = self.nf * branches
+        shapes += [(n11, self.nf, 1, 1), (n11,), (n11,), (self.C * branches,)]
+        return shapes
+
+    def live_branches(self):
+        return 1
+
+    def flops_per_tile(self, tc, F, live_only=False):
+        """Multiply-add FLOPs (2 per MAC) of one tile: the encoder, the 1x1 conv (its live rows only with ``live_only``),
+        and per computed branch the transposed convolutions (each costs what its forward convolution costs)."""
+        d = self.dims(tc, F)
+        enc = sum(2 * l['cout'] * l['cin'] * l['kh'] * self.kw * l['ho'] * l['wo'] for l in d['layers'])
+        nb = self.live_branches() if live_only else self.n_branches
+        conv11 = 2 * self.nf * nb * self.nf * d['h6'] * d['w6']
+        return enc + conv11 + nb * enc
+
+
 ARCHS['bach10_si1'] = Arch('bach10_si1', ARCH_BACH10_SI1, 4, (30, 30, 4), 0, (30, lambda tc: int(2 * tc / 3), 1), 256, [0], 4,
                            EPS_B, ['bassoon', 'clarinet', 'saxphone', 'violin'])
 ARCHS['hiphop'] = ARCHS['dsd']
+ARCHS['bach10_si_1x1'] = Deep1x1Arch()
 ARCHS['ikala_nopool'] = Arch('ikala_nopool', ARCH_IKALA_NOPOOL, 1, (30, 30, 3), 0, (30, lambda tc: 10, 20), 256,
                              [0, 1], 2, EPS_A, ['voice', 'music'])
 
@@ -111,6 +168,9 @@ def resolve(arch, params, tc, F):
     # trainCNNrwc_samp.py:195-235 -- the same script loads either .pkl
     if a.name == 'bach10_si' and len(params) == len(ARCHS['bach10_si1'].param_shapes(tc, F)):
         return ARCHS['bach10_si1']
+    # the deep graph of trainCNNrwc.py --function build_ca_1x1 (model_*_x_*.pkl, :638): 22 arrays, whole or live-only
+    if a.name == 'bach10_si' and len(params) == 3 * len(Deep1x1Arch.filters) + 4:
+        return ARCHS['bach10_si_1x1']
     if a.name == 'ikala' and len(params) > 6 and np.ndim(params[6]) == 2:
         rows = int(np.shape(params[6])[0])
         if rows != a.dims(tc, F)['flat'] and rows == ARCHS['ikala_nopool'].dims(tc, F)['flat']:
@@ -126,6 +186,12 @@ def live_params(arch, params):
     if arch.name == 'bach10_si' and len(params) == 17:
         live = list(params[:10]) + [np.asarray(params[16])[:arch.C]]
         return ARCHS['bach10_si1'], live
+    if arch.name == 'bach10_si_1x1':
+        # build_ca_1x1: the 1x1 convolution's rows 0..199 (branch 0) and the final bias [0:4]; the graph stays the same
+        nf = arch.nf
+        live = list(params[:18]) + [np.asarray(params[18])[:nf], np.asarray(params[19])[:nf], np.asarray(params[20])[:nf],
+                                    np.asarray(params[21])[:arch.C]]
+        return arch, live
     return arch, params
 
 
@@ -133,6 +199,10 @@ def check_params(arch, params, tc, F):
     """Same failure behaviour as ``lasagne.layers.set_all_param_values``
     (separate_dsd.py:250): ValueError on a count or shape mismatch."""
     shapes = arch.param_shapes(tc, F)
+    if arch.name == 'bach10_si_1x1' and len(params) == len(shapes) and np.ndim(params[18]) == 4:
+        rows = int(np.shape(params[18])[0])
+        if rows % arch.nf == 0 and 1 <= rows // arch.nf < arch.n_branches:   # the live-only layout: k branches of the 1x1 conv
+            shapes = arch.param_shapes(tc, F, branches=rows // arch.nf)
     if len(params) != len(shapes):
         raise ValueError("mismatch: got %d values to set %d parameters" % (len(params), len(shapes)))
     for p, s in zip(params, shapes):

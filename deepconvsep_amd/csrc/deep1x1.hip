@@ -1,0 +1,556 @@
+// build_ca_1x1, the deep score-informed graph of examples/bach10_scoreinformed/trainCNNrwc.py:66-132, on the f32 matrix pipe.
+//
+//   conv1 .. conv6   Conv2DLayer(k x 5, stride (1, 2), rectify) + BiasLayer        d1_igemm_kernel<MODE_FWD>
+//   conv (1 x 1)     800 filters, rectify + BiasLayer, sliced into 4 x 200       d1_igemm_kernel<MODE_1X1>
+//   per branch       InverseLayer of conv6 .. conv2                               d1_igemm_kernel<MODE_TR>
+//                    InverseLayer of conv1 + final BiasLayer + rectify            d1_igemm_kernel<MODE_LAST>
+//   soft masks       separate_bach10.py / trainCNNrwc.py mask expressions         d1_mask_kernel
+//
+// Every convolution is an implicit GEMM over channels-last activations: M = output pixels, N = output channels,
+// K = (filter row, filter tap, input channel) with the channel fastest, so one tap row of a pixel is kw * Cin contiguous
+// floats.  Channel counts are padded to a multiple of 4 (the pad channels hold 0) so that a lane reads 4 consecutive K
+// values as one 16-byte load.  A wave owns 32 pixels x 16 NT channels: each lane loads a 4-K quad of A and of B and feeds
+// element e of both to the e-th of four v_mfma_f32_16x16x4_f32 -- the K order inside the sum differs from a plain k loop,
+// the arithmetic is still a chain of exact f32 fma (f32-class results).  Operands come straight from global memory (L1 /
+// L2 carry the reuse), so the kernel has no LDS and no barrier.
+//
+// InverseLayer(conv_k) is theano.grad through conv_k's rectify: g_{k-1} = conv_k^T(g_k * r'(pre_k)) with Theano's
+// relu = 0.5 (x + |x|), r'(0) = 0.5.  The forward epilogue records r'(pre_k) as one byte per element (0, 1, 2 = 0, 0.5, 1);
+// the transposed kernel multiplies g by it while loading.  The transposed conv runs once per output-column parity: the
+// stride-2 taps that reach an even column are j = 0, 2, 4 and an odd one j = 1, 3, so each parity is a dense conv with 3 or 2
+// taps.  A column no tap reaches (conv3's last input column at 2049 bins) has no valid operand and is written 0.
+//
+// Only branch 0 reaches predict_function2's masks (trainCNNrwc.py:243-263), so the masked modes run that branch alone.
+#include <string.h>
+
+#include "deep1x1.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMT = 2;                      // 16-pixel MFMA tiles per wave
+constexpr int kBM = kWaves * kMT * 16;      // 128 output pixels per workgroup
+constexpr int kChunk = 32;                  // tiles per pass: bounds the scratch whatever the batch
+constexpr int kLayers = 6;
+constexpr int kKw = 5;
+constexpr int kNf = 200;                    // filters of conv6 / of one branch of the 1x1 conv (nfilt_conv)
+const int kFilters[kLayers] = {30, 50, 70, 100, 200, 200};
+const int kKh[kLayers] = {1, 1, 1, 1, 10, 10};
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+enum { MODE_FWD = 0, MODE_1X1 = 1, MODE_TR = 2, MODE_LAST = 3 };
+
+struct D1Args {
+    const float* in;            // channels-last [img][Hi][Wi][Ci]
+    const uint8_t* code;        // MODE_TR / MODE_LAST: r'(pre) codes of `in`, same layout
+    int Hi, Wi, Ci;
+    int Ho, Wo, Wq, par;        // output rows / columns; this launch's columns q -> f = stride q (FWD) or 2 q + par (TR)
+    int kh, ntap, stride;
+    const float* B;             // [Npad][Kpad] weights, one output channel's K contiguous, zero past K and past N
+    int K, Kpad, N;
+    const float* b0;            // FWD / 1X1: the layer's b; LAST: this branch's slice of the final BiasLayer
+    const float* b1;            // FWD / 1X1: BiasLayer.b
+    float* out;                 // FWD / TR: [img][Ho][Wo][Co]; 1X1: [branch][pixel][kNf]; LAST: [ch][n_total][Ho][Wo]
+    uint8_t* code_out;          // FWD: [img][Ho][Wo][Co]
+    int Co;                     // FWD / TR: channel pitch of `out` (channels N .. Co-1 are written 0)
+    int64_t M;                  // output pixels of this launch
+    int64_t n_total, k_first;   // LAST: tiles of the whole output, first tile of this chunk
+    int ch_off;                 // LAST: output channel of this branch's first source
+};
+
+template <int MODE, int NT>
+__global__ __launch_bounds__(kThreads) void d1_igemm_kernel(const D1Args a) {
+    constexpr bool kTr = MODE == MODE_TR || MODE == MODE_LAST;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int64_t m0 = (int64_t)blockIdx.x * kBM + wave * (kMT * 16);
+    const int n0 = blockIdx.y * (NT * 16);
+    const int64_t img_px = (int64_t)a.Ho * a.Wq;
+
+    int64_t base[kMT];
+    int trow[kMT], fcol[kMT];
+    bool ok[kMT];
+#pragma unroll
+    for (int mt = 0; mt < kMT; ++mt) {
+        const int64_t m = m0 + mt * 16 + r16;
+        ok[mt] = m < a.M;
+        const int64_t mm = ok[mt] ? m : 0;
+        const int64_t img = mm / img_px;
+        const int rem = (int)(mm - img * img_px);
+        const int t = rem / a.Wq, q = rem - t * a.Wq;
+        trow[mt] = t;
+        fcol[mt] = q;
+        base[mt] = kTr ? img * a.Hi * a.Wi * (int64_t)a.Ci
+                       : ((img * a.Hi + t) * (int64_t)a.Wi + (int64_t)a.stride * q) * a.Ci;
+    }
+    const float* Bp[NT];
+#pragma unroll
+    for (int s = 0; s < NT; ++s) Bp[s] = a.B + (int64_t)(n0 + s * 16 + r16) * a.Kpad + 4 * kq;
+
+    f32x4 acc[kMT][NT];
+#pragma unroll
+    for (int mt = 0; mt < kMT; ++mt)
+#pragma unroll
+        for (int s = 0; s < NT; ++s) acc[mt][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // this lane's K quad k0 + 4 kq as (filter row ki, offset kr in the row) -- TR: (row ki, tap jt, channel c)
+    const int seg = a.ntap * a.Ci;
+    const int64_t row_pitch = (int64_t)a.Wi * a.Ci;
+    int ki = 0, kr = 4 * kq, jt = 0, c = 4 * kq;
+    for (int k0 = 0; k0 < a.Kpad; k0 += 16) {
+        const bool kin = k0 + 4 * kq < a.K;
+        f32x4 av[kMT];
+#pragma unroll
+        for (int mt = 0; mt < kMT; ++mt) {
+            av[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (!kTr) {
+                if (ok[mt] && kin) av[mt] = *(const f32x4*)(a.in + base[mt] + ki * row_pitch + kr);
+            } else {
+                const int t = trow[mt] - ki, f = fcol[mt] - jt;
+                if (ok[mt] && kin && t >= 0 && t < a.Hi && f >= 0 && f < a.Wi) {
+                    const int64_t off = base[mt] + ((int64_t)t * a.Wi + f) * a.Ci + c;
+                    const f32x4 g = *(const f32x4*)(a.in + off);
+                    const uint32_t cd = *(const uint32_t*)(a.code + off);
+                    av[mt] = f32x4{g[0] * (0.5f * (float)(cd & 0xff)), g[1] * (0.5f * (float)((cd >> 8) & 0xff)),
+                                   g[2] * (0.5f * (float)((cd >> 16) & 0xff)), g[3] * (0.5f * (float)(cd >> 24))};
+                }
+            }
+        }
+        f32x4 bv[NT];
+#pragma unroll
+        for (int s = 0; s < NT; ++s) bv[s] = *(const f32x4*)(Bp[s] + k0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int mt = 0; mt < kMT; ++mt)
+#pragma unroll
+                for (int s = 0; s < NT; ++s)
+                    acc[mt][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][e], bv[s][e], acc[mt][s], 0, 0, 0);
+        if (!kTr) {
+            kr += 16;
+            while (kr >= seg) { kr -= seg; ++ki; }
+        } else {
+            c += 16;
+            while (c >= a.Ci) {
+                c -= a.Ci;
+                if (++jt == a.ntap) { jt = 0; ++ki; }
+            }
+        }
+    }
+
+    // C/D map of the 16x16 tile: column = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+    for (int mt = 0; mt < kMT; ++mt)
+#pragma unroll
+        for (int s = 0; s < NT; ++s)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int64_t m = m0 + mt * 16 + 4 * kq + reg;
+                const int col = n0 + s * 16 + r16;
+                if (m >= a.M) continue;
+                const float v = acc[mt][s][reg];
+                if (MODE == MODE_FWD) {
+                    if (col >= a.Co) continue;
+                    float y = 0.f;
+                    uint8_t cd = 0;
+                    if (col < a.N) {
+                        const float pre = v + a.b0[col];
+                        cd = pre > 0.f ? 2 : (pre == 0.f ? 1 : 0);
+                        y = fmaxf(pre, 0.f) + a.b1[col];
+                    }
+                    a.out[m * a.Co + col] = y;
+                    a.code_out[m * a.Co + col] = cd;
+                } else if (MODE == MODE_1X1) {
+                    if (col >= a.N) continue;
+                    const int br = col / kNf;
+                    a.out[((int64_t)br * a.M + m) * kNf + (col - br * kNf)] = fmaxf(v + a.b0[col], 0.f) + a.b1[col];
+                } else {
+                    const int64_t img = m / img_px;
+                    const int rem = (int)(m - img * img_px);
+                    const int t = rem / a.Wq, f = 2 * (rem - t * a.Wq) + a.par;
+                    if (MODE == MODE_TR) {
+                        if (col >= a.Co) continue;
+                        a.out[((img * a.Ho + t) * (int64_t)a.Wo + f) * a.Co + col] = col < a.N ? v : 0.f;
+                    } else {
+                        if (col >= a.N) continue;
+                        const int64_t ch = a.ch_off + col;
+                        a.out[((ch * a.n_total + a.k_first + img) * a.Ho + t) * (int64_t)a.Wo + f] = fmaxf(v + a.b0[col], 0.f);
+                    }
+                }
+            }
+}
+
+// tiles [n][C][tc][F] -> channels-last [n][tc][F][C] (C == 4)
+__global__ __launch_bounds__(kThreads) void d1_to_cl_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n_px,
+                                                            int64_t plane) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n_px) return;
+    const int64_t k = i / plane, r = i - k * plane;
+    const float* s = x + k * 4 * plane + r;
+    *(f32x4*)(y + 4 * i) = f32x4{s[0], s[plane], s[2 * plane], s[3 * plane]};
+}
+
+// The soft masks of mask_kernel (generic.hip) on p = rectify(o + bias) already formed: p [4][n][plane] of this chunk,
+// x its tiles [n][C][plane]; out [4][n_total][plane] from tile k_first.  mode 0 / 1 = DCS_EPS_A / DCS_EPS_B.
+__global__ __launch_bounds__(kThreads) void d1_mask_kernel(const float* __restrict__ pin, const float* __restrict__ x,
+                                                           float* __restrict__ out, int64_t n, int64_t n_total, int64_t k_first,
+                                                           int C, int64_t plane, int mode, int mix_n) {
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= n * plane) return;
+    const int64_t k = idx / plane, r = idx - k * plane;
+    const float eps_r = 5e-19f;
+    float p[4];
+    float den = 0.f;
+    for (int s = 0; s < 4; ++s) {
+        p[s] = pin[((int64_t)s * n + k) * plane + r];
+        if (mode == 0) p[s] += eps_r;
+        den = (s == 0) ? p[s] : den + p[s];
+    }
+    if (mode == 1) den += eps_r;
+    float mix = x[(k * C) * plane + r];
+    for (int c = 1; c < mix_n; ++c) mix += x[(k * C + c) * plane + r];
+    for (int s = 0; s < 4; ++s) out[((int64_t)s * n_total + k_first + k) * plane + r] = (p[s] / den) * mix;
+}
+
+struct D1Layer {
+    int Cin, Cinp, Cout, Coutp, kh;
+    int Hi, Wi, Ho, Wo;
+    int K, Kpad;                // forward
+    int Kt[2], Ktpad[2];        // transposed, per output-column parity
+    float *B = nullptr, *b0 = nullptr, *b1 = nullptr, *Bt[2] = {nullptr, nullptr};
+};
+
+int ntap_of(int par) { return par == 0 ? 3 : 2; }
+int nt_for(int N) { return N <= 16 ? 1 : (N <= 32 ? 2 : 4); }
+
+template <int MODE>
+void launch(dcs_ctx* ctx, const D1Args& a) {
+    const int nt = nt_for(a.N);
+    const dim3 grid((unsigned)((a.M + kBM - 1) / kBM), (unsigned)dcs_cdiv(a.N, 16 * nt));
+    if (nt == 1) hipLaunchKernelGGL((d1_igemm_kernel<MODE, 1>), grid, dim3(kThreads), 0, ctx->stream, a);
+    else if (nt == 2) hipLaunchKernelGGL((d1_igemm_kernel<MODE, 2>), grid, dim3(kThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((d1_igemm_kernel<MODE, 4>), grid, dim3(kThreads), 0, ctx->stream, a);
+}
+
+int upload_f32(float** dst, const std::vector<float>& src, const char* name) {
+    DCS_HIP(dcs_dev_alloc((void**)dst, src.size() * sizeof(float), name));
+    DCS_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+    return DCS_OK;
+}
+
+}  // namespace
+
+struct DcsDeep1x1Net {
+    dcs_ctx* ctx = nullptr;
+    int C = 4, tc = 0, F = 0, nb = 1;
+    D1Layer L[kLayers];
+    float *B11 = nullptr, *b11_0 = nullptr, *b11_1 = nullptr, *fbias = nullptr;
+    int K11pad = 0;
+    int score_norm = DCS_SCORE_NORM_MAX, mix_sum = 0;
+    DcsBuffer ws;
+    float* rise_d = nullptr;
+    int rise_ov = -1;
+};
+
+void dcs_deep1x1_destroy(DcsDeep1x1Net* g) {
+    if (!g) return;
+    for (auto& l : g->L) {
+        dcs_dev_free(l.B); dcs_dev_free(l.b0); dcs_dev_free(l.b1); dcs_dev_free(l.Bt[0]); dcs_dev_free(l.Bt[1]);
+    }
+    dcs_dev_free(g->B11); dcs_dev_free(g->b11_0); dcs_dev_free(g->b11_1); dcs_dev_free(g->fbias); dcs_dev_free(g->rise_d);
+    g->ws.release();
+    delete g;
+}
+
+int dcs_deep1x1_create(dcs_ctx* ctx, int C, int tc, int F, const float* const* params_d, const int64_t* shapes, int nparams,
+                       DcsDeep1x1Net** out) {
+    if (C != 4) DCS_FAIL(DCS_EINVAL, "the deep score-informed network takes 4 input channels");
+    if (tc < 19 || F < 253)
+        DCS_FAIL(DCS_EINVAL, "time_context %d / feature size %d too small for build_ca_1x1 (needs >= 19 / >= 253)", tc, F);
+    if (nparams != 3 * (kLayers + 1) + 1)
+        DCS_FAIL(DCS_ESHAPE, "mismatch: got %d values to set %d parameters", nparams, 3 * (kLayers + 1) + 1);
+    // branches the 1x1 layer holds: 4 (the whole graph) or 1 .. 3 (live-only layouts); any other row count is checked
+    // against the whole graph's 800 and fails below
+    const int64_t rows11 = shapes[4 * 3 * kLayers];
+    const int nb_ok = (rows11 % kNf == 0 && rows11 >= kNf && rows11 <= 4 * kNf) ? (int)(rows11 / kNf) : 4;
+    std::vector<std::vector<int64_t>> expect;
+    int cin = C;
+    for (int k = 0; k < kLayers; ++k) {
+        expect.push_back({kFilters[k], cin, kKh[k], kKw});
+        expect.push_back({kFilters[k]});
+        expect.push_back({kFilters[k]});
+        cin = kFilters[k];
+    }
+    expect.push_back({(int64_t)kNf * nb_ok, kNf, 1, 1});
+    expect.push_back({(int64_t)kNf * nb_ok});
+    expect.push_back({(int64_t)kNf * nb_ok});
+    expect.push_back({(int64_t)C * nb_ok});
+    std::vector<std::vector<float>> P(nparams);
+    for (int i = 0; i < nparams; ++i) {
+        int64_t cnt = 1;
+        for (int k = 0; k < 4; ++k) {
+            const int64_t want = k < (int)expect[i].size() ? expect[i][k] : 1;
+            if (shapes[i * 4 + k] != want)
+                DCS_FAIL(DCS_ESHAPE, "mismatch: parameter %d has shape dim %d = %lld but value to set has %lld", i, k,
+                         (long long)want, (long long)shapes[i * 4 + k]);
+            cnt *= want;
+        }
+        if (!params_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_model_create: parameter %d is null", i);
+        P[i].resize((size_t)cnt);
+        DCS_HIP(hipMemcpy(P[i].data(), params_d[i], (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    DcsDeep1x1Net* g = new DcsDeep1x1Net();
+    g->ctx = ctx;
+    g->C = C; g->tc = tc; g->F = F; g->nb = nb_ok;
+    int H = tc, W = F;
+    cin = C;
+    int rc = DCS_OK;
+    for (int k = 0; k < kLayers && rc == DCS_OK; ++k) {
+        D1Layer& l = g->L[k];
+        l.Cin = cin; l.Cinp = (int)dcs_round_up(cin, 4); l.Cout = kFilters[k]; l.Coutp = (int)dcs_round_up(l.Cout, 4);
+        l.kh = kKh[k];
+        l.Hi = H; l.Wi = W; l.Ho = H - l.kh + 1; l.Wo = (W - kKw) / 2 + 1;
+        const std::vector<float>& Wk = P[3 * k];   // [Cout][Cin][kh][5]; Lasagne flips the filter (flip_filters=True)
+        auto w = [&](int co, int ci, int i, int j) { return Wk[(((size_t)co * l.Cin + ci) * l.kh + i) * kKw + j]; };
+        // forward: B[co][(i * 5 + j) * Cinp + ci] = W[co][ci][kh-1-i][4-j]
+        l.K = l.kh * kKw * l.Cinp; l.Kpad = (int)dcs_round_up(l.K, 16);
+        const int npad = dcs_cdiv(l.Cout, 16 * nt_for(l.Cout)) * 16 * nt_for(l.Cout);
+        std::vector<float> B((size_t)npad * l.Kpad, 0.f);
+        for (int co = 0; co < l.Cout; ++co)
+            for (int i = 0; i < l.kh; ++i)
+                for (int j = 0; j < kKw; ++j)
+                    for (int ci = 0; ci < l.Cin; ++ci)
+                        B[(size_t)co * l.Kpad + (i * kKw + j) * l.Cinp + ci] = w(co, ci, l.kh - 1 - i, kKw - 1 - j);
+        // transposed, parity p: Bt[ci][(i * ntap + jt) * Coutp + co] = W[co][ci][kh-1-i][4-(p+2jt)]
+        const int npad_t = dcs_cdiv(l.Cin, 16 * nt_for(l.Cin)) * 16 * nt_for(l.Cin);
+        std::vector<float> Bt[2];
+        for (int p = 0; p < 2; ++p) {
+            const int nt = ntap_of(p);
+            l.Kt[p] = l.kh * nt * l.Coutp; l.Ktpad[p] = (int)dcs_round_up(l.Kt[p], 16);
+            Bt[p].assign((size_t)npad_t * l.Ktpad[p], 0.f);
+            for (int ci = 0; ci < l.Cin; ++ci)
+                for (int i = 0; i < l.kh; ++i)
+                    for (int jt = 0; jt < nt; ++jt)
+                        for (int co = 0; co < l.Cout; ++co)
+                            Bt[p][(size_t)ci * l.Ktpad[p] + (i * nt + jt) * l.Coutp + co] =
+                                w(co, ci, l.kh - 1 - i, kKw - 1 - (p + 2 * jt));
+        }
+        char name[32];
+        snprintf(name, sizeof name, "deep1x1.conv%d_B", k + 1);
+        rc = upload_f32(&l.B, B, name);
+        snprintf(name, sizeof name, "deep1x1.conv%d_Bt0", k + 1);
+        if (rc == DCS_OK) rc = upload_f32(&l.Bt[0], Bt[0], name);
+        snprintf(name, sizeof name, "deep1x1.conv%d_Bt1", k + 1);
+        if (rc == DCS_OK) rc = upload_f32(&l.Bt[1], Bt[1], name);
+        snprintf(name, sizeof name, "deep1x1.conv%d_b", k + 1);
+        if (rc == DCS_OK) rc = upload_f32(&l.b0, P[3 * k + 1], name);
+        snprintf(name, sizeof name, "deep1x1.conv%d_bias", k + 1);
+        if (rc == DCS_OK) rc = upload_f32(&l.b1, P[3 * k + 2], name);
+        H = l.Ho; W = l.Wo; cin = l.Cout;
+    }
+    if (rc == DCS_OK) {
+        // 1x1: B[co][ci] = W[co][ci][0][0]
+        const int n11 = kNf * nb_ok;
+        g->K11pad = (int)dcs_round_up(kNf, 16);
+        std::vector<float> B((size_t)dcs_cdiv(n11, 64) * 64 * g->K11pad, 0.f);
+        for (int co = 0; co < n11; ++co)
+            for (int ci = 0; ci < kNf; ++ci) B[(size_t)co * g->K11pad + ci] = P[18][(size_t)co * kNf + ci];
+        rc = upload_f32(&g->B11, B, "deep1x1.conv1x1_B");
+        if (rc == DCS_OK) rc = upload_f32(&g->b11_0, P[19], "deep1x1.conv1x1_b");
+        if (rc == DCS_OK) rc = upload_f32(&g->b11_1, P[20], "deep1x1.conv1x1_bias");
+        if (rc == DCS_OK) rc = upload_f32(&g->fbias, P[21], "deep1x1.out_bias");
+    }
+    if (rc != DCS_OK) {
+        dcs_deep1x1_destroy(g);
+        return rc;
+    }
+    *out = g;
+    return DCS_OK;
+}
+
+int dcs_deep1x1_out_channels(const DcsDeep1x1Net* g) { return g->C * g->nb; }
+
+int dcs_deep1x1_set_score_semantics(DcsDeep1x1Net* g, int normalise, int mixture) {
+    if ((normalise != DCS_SCORE_NORM_MAX && normalise != DCS_SCORE_NORM_SUM) || (mixture != DCS_MIX_CH0 && mixture != DCS_MIX_SUM))
+        DCS_FAIL(DCS_EINVAL, "dcs_model_set_score_semantics: normalise %d / mixture %d", normalise, mixture);
+    g->score_norm = normalise;
+    g->mix_sum = mixture == DCS_MIX_SUM;
+    return DCS_OK;
+}
+
+namespace {
+
+struct D1Scratch {
+    float *xcl, *a, *b, *g, *pm;
+    uint8_t* code[kLayers];
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// bytes of one chunk of nc tiles; p != nullptr: also carve s out of p
+size_t scratch_bytes(const DcsDeep1x1Net* g, int64_t nc, D1Scratch* s, char* p) {
+    size_t act = (size_t)g->tc * g->F * g->C;
+    for (const auto& l : g->L) act = std::max(act, (size_t)l.Ho * l.Wo * l.Coutp);
+    const D1Layer& l6 = g->L[kLayers - 1];
+    const size_t sz[5] = {align256((size_t)nc * g->tc * g->F * g->C * 4), align256((size_t)nc * act * 4),
+                          align256((size_t)nc * act * 4), align256((size_t)g->nb * nc * l6.Ho * l6.Wo * kNf * 4),
+                          align256((size_t)4 * nc * g->tc * g->F * 4)};
+    size_t off = 0;
+    float** f[5] = {&s->xcl, &s->a, &s->b, &s->g, &s->pm};
+    for (int i = 0; i < 5; ++i) {
+        if (p) *f[i] = (float*)(p + off);
+        off += sz[i];
+    }
+    for (int k = 0; k < kLayers; ++k) {
+        if (p) s->code[k] = (uint8_t*)(p + off);
+        off += align256((size_t)nc * g->L[k].Ho * g->L[k].Wo * g->L[k].Coutp);
+    }
+    return off;
+}
+
+// nc tiles at x (from tile k_first of n_total) -> mask_mode 0/1: out [4][n_total] masked; 2: p [4 nb][n_total]
+int forward_chunk(DcsDeep1x1Net* g, const float* x, int64_t nc, int64_t k_first, int64_t n_total, int mask_mode, float* out,
+                  const D1Scratch& s) {
+    dcs_ctx* ctx = g->ctx;
+    const int64_t plane = (int64_t)g->tc * g->F;
+    hipLaunchKernelGGL(d1_to_cl_kernel, dim3((unsigned)dcs_cdiv(nc * plane, kThreads)), dim3(kThreads), 0, ctx->stream, x, s.xcl,
+                       nc * plane, plane);
+    const float* cur = s.xcl;
+    float* bufs[2] = {s.a, s.b};
+    for (int k = 0; k < kLayers; ++k) {
+        const D1Layer& l = g->L[k];
+        D1Args a{};
+        a.in = cur; a.Hi = l.Hi; a.Wi = l.Wi; a.Ci = l.Cinp;
+        a.Ho = l.Ho; a.Wo = l.Wo; a.Wq = l.Wo; a.kh = l.kh; a.ntap = kKw; a.stride = 2;
+        a.B = l.B; a.K = l.K; a.Kpad = l.Kpad; a.N = l.Cout; a.b0 = l.b0; a.b1 = l.b1;
+        a.out = bufs[k & 1]; a.code_out = s.code[k]; a.Co = l.Coutp;
+        a.M = nc * l.Ho * l.Wo;
+        launch<MODE_FWD>(ctx, a);
+        cur = bufs[k & 1];
+    }
+    const D1Layer& l6 = g->L[kLayers - 1];
+    const int64_t m11 = nc * l6.Ho * l6.Wo;
+    // the masks read branch 0 alone; the raw output wants every branch the model holds
+    const int nb_run = mask_mode == 2 ? g->nb : 1;
+    {
+        D1Args a{};
+        a.in = cur; a.Hi = l6.Ho; a.Wi = l6.Wo; a.Ci = kNf;
+        a.Ho = l6.Ho; a.Wo = l6.Wo; a.Wq = l6.Wo; a.kh = 1; a.ntap = 1; a.stride = 1;
+        a.B = g->B11; a.K = kNf; a.Kpad = g->K11pad; a.N = kNf * nb_run; a.b0 = g->b11_0; a.b1 = g->b11_1;
+        a.out = s.g; a.M = m11;
+        launch<MODE_1X1>(ctx, a);
+    }
+    for (int br = 0; br < nb_run; ++br) {
+        cur = s.g + (int64_t)br * m11 * kNf;
+        for (int k = kLayers - 1; k >= 0; --k) {
+            const D1Layer& l = g->L[k];
+            float* dst = bufs[k & 1];   // conv_k's input size; k = 0 writes p instead
+            for (int par = 0; par < 2; ++par) {
+                D1Args a{};
+                a.in = cur; a.code = s.code[k]; a.Hi = l.Ho; a.Wi = l.Wo; a.Ci = l.Coutp;
+                a.Ho = l.Hi; a.Wo = l.Wi; a.Wq = (l.Wi - par + 1) / 2; a.par = par;
+                a.kh = l.kh; a.ntap = ntap_of(par);
+                a.B = l.Bt[par]; a.K = l.Kt[par]; a.Kpad = l.Ktpad[par]; a.N = l.Cin;
+                a.M = nc * l.Hi * a.Wq;
+                if (a.M == 0) continue;
+                if (k > 0) {
+                    a.out = dst; a.Co = l.Cinp;
+                    launch<MODE_TR>(ctx, a);
+                } else {
+                    a.b0 = g->fbias + g->C * br;
+                    if (mask_mode == 2) {
+                        a.out = out; a.n_total = n_total; a.k_first = k_first; a.ch_off = g->C * br;
+                    } else {
+                        a.out = s.pm; a.n_total = nc; a.k_first = 0; a.ch_off = 0;
+                    }
+                    launch<MODE_LAST>(ctx, a);
+                }
+            }
+            cur = dst;
+        }
+    }
+    if (mask_mode != 2)
+        hipLaunchKernelGGL(d1_mask_kernel, dim3((unsigned)dcs_cdiv(nc * plane, kThreads)), dim3(kThreads), 0, ctx->stream, s.pm, x,
+                           out, nc, n_total, k_first, g->C, plane, mask_mode, g->mix_sum ? g->C : 1);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+}  // namespace
+
+int dcs_deep1x1_forward(DcsDeep1x1Net* g, const float* tiles, int64_t n, int mask_mode, float* out) {
+    if (mask_mode < 0 || mask_mode > 2) DCS_FAIL(DCS_EINVAL, "bad mask mode %d", mask_mode);
+    if (n == 0) return DCS_OK;
+    const int64_t nc_max = std::min<int64_t>(n, kChunk);
+    D1Scratch s;
+    DCS_CHECK(g->ws.ensure(scratch_bytes(g, nc_max, &s, nullptr)));
+    scratch_bytes(g, nc_max, &s, (char*)g->ws.ptr);
+    const int64_t tile = (int64_t)g->C * g->tc * g->F;
+    for (int64_t k0 = 0; k0 < n; k0 += nc_max) {
+        const int64_t nc = std::min(nc_max, n - k0);
+        DCS_CHECK(forward_chunk(g, tiles + k0 * tile, nc, k0, n, mask_mode, out, s));
+    }
+    return DCS_OK;
+}
+
+int dcs_deep1x1_separate(DcsDeep1x1Net* g, dcs_stft* plan, const float* audio, int64_t L, int ov, float scale, int eps_mode,
+                         const DcsScoreNotes& notes, float* pcm, int64_t* n_tiles_out, int64_t* n_frames_out) {
+    // separate_bach10.py / trainCNNrwc.py:357-416 with the library tiler: the composition of dcs_generic_separate's
+    // score-informed branch, the network replaced by build_ca_1x1
+    dcs_ctx* ctx = g->ctx;
+    if (notes.ninst != g->C) DCS_FAIL(DCS_EINVAL, "score-informed path: %d score channels (got %d)", g->C, notes.ninst);
+    if (eps_mode != DCS_EPS_A && eps_mode != DCS_EPS_B) DCS_FAIL(DCS_EINVAL, "bad eps_mode");
+    const int tc = g->tc, F = g->F, st = tc - ov, S = 4;
+    const int64_t T = dcs_frame_count(L, plan->hop);
+    const int64_t n = dcs_tile_count(T, tc, ov, DCS_TILER_LIBRARY);
+    if (n < 1) DCS_FAIL(DCS_EINVAL, "dcs_separate_scoreinformed: the tiler yields no tile");
+    const int64_t ld = dcs_round_up(F, 4);
+    const int64_t rows = n * st + tc;
+    if (g->rise_ov != ov) {
+        std::vector<float> r(ov > 0 ? ov : 1, 0.f);
+        if (ov > 1) {
+            const double step = 1.0 / (double)(ov - 1);
+            for (int i = 0; i < ov; ++i) r[i] = (float)((double)i * step);
+            r[ov - 1] = 1.0f;
+        }
+        if (g->rise_d) {
+            DCS_HIP(hipStreamSynchronize(ctx->stream));
+            dcs_dev_free(g->rise_d);
+            g->rise_d = nullptr;
+        }
+        DCS_CHECK(upload_f32(&g->rise_d, r, "deep1x1.rise"));
+        g->rise_ov = ov;
+    }
+    // the network's scratch first (ws grows to the larger of the two uses; the pipeline's buffers follow it)
+    const int64_t nc_max = std::min<int64_t>(n, kChunk);
+    D1Scratch s;
+    const size_t b_net = align256(scratch_bytes(g, nc_max, &s, nullptr));
+    const size_t b_mag = align256((size_t)T * ld * 4), b_unit = 2 * b_mag;
+    const size_t b_inp = align256((size_t)g->C * T * F * 4);
+    const size_t b_tiles = align256((size_t)n * g->C * tc * F * 4), b_out = align256((size_t)S * n * tc * F * 4);
+    const size_t b_sep = align256((size_t)S * rows * ld * 4);
+    DCS_CHECK(g->ws.ensure(b_net + b_mag + b_unit + b_inp + b_tiles + b_out + b_sep));
+    char* p = (char*)g->ws.ptr;
+    scratch_bytes(g, nc_max, &s, p); p += b_net;
+    float* mag = (float*)p; p += b_mag;
+    float2* unit = (float2*)p; p += b_unit;
+    float* inp = (float*)p; p += b_inp;
+    float* tiles = (float*)p; p += b_tiles;
+    float* outm = (float*)p; p += b_out;
+    float* sep = (float*)p;
+    DCS_CHECK(dcs_launch_stft_forward_f32_clips(plan, audio, L, 0, 1, mag, nullptr, unit, ld, T, T));
+    DCS_CHECK(dcs_score_masks_scaled(ctx, mag, ld, T, F, notes.notes_h, notes.ninst, notes.n_notes, notes.width, 0, T, scale, inp,
+                                     nullptr, g->score_norm));
+    DCS_CHECK(dcs_launch_tile(ctx, inp, T * (int64_t)F, F, g->C, T, F, tc, ov, DCS_TILER_LIBRARY, 1.0f, tiles, n));
+    for (int64_t k0 = 0; k0 < n; k0 += nc_max) {
+        const int64_t nc = std::min(nc_max, n - k0);
+        DCS_CHECK(forward_chunk(g, tiles + k0 * g->C * tc * (int64_t)F, nc, k0, n, eps_mode, outm, s));
+    }
+    DCS_CHECK(dcs_launch_overlap_add(ctx, outm, n, S, tc, ov, F, g->rise_d, sep, rows * ld, ld, n * tc * (int64_t)F));
+    DCS_CHECK(dcs_launch_stft_inverse_f32_clips(plan, sep, rows * ld, unit, T * ld, ld, T, S, 1, scale, pcm, L));
+    if (n_tiles_out) *n_tiles_out = n;
+    if (n_frames_out) *n_frames_out = T;
+    return DCS_OK;
+}

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "dcs_internal.h"
+#include "deep1x1.h"
 #include "dsd.h"
 #include "dsd_lat.h"
 #include "generic.h"
@@ -98,6 +99,8 @@ struct dcs_model {
     float* B2fc_frag = nullptr;   // the same weights in gemm_rows_splitk_kernel's fragment order (DcsGemm::Bfrag)
     // ---- generic path (ikala / bach10 / score-informed)
     DcsGenericNet* gen = nullptr;
+    // ---- the deep score-informed graph build_ca_1x1 (deep1x1.hip)
+    DcsDeep1x1Net* deep = nullptr;
     // ---- scratch
     DcsBuffer ws;
     // bf16x3 kernels: the transposed-conv1 and conv2 weights split into three bf16 planes
@@ -540,6 +543,19 @@ extern "C" int dcs_model_create(dcs_ctx* ctx, int arch, int C, int tc, int F, co
                                 const int64_t* shapes, int nparams, dcs_model** out) {
     if (!ctx || !params_d || !shapes || !out) DCS_FAIL(DCS_EINVAL, "dcs_model_create: null argument");
     if (tc < 2 || F < 1) DCS_FAIL(DCS_EINVAL, "dcs_model_create: bad time_context / feature size");
+    if (arch == DCS_ARCH_BACH10_SI_1X1) {
+        DCS_ON_DEVICE(ctx->device);
+        DcsDeep1x1Net* deep = nullptr;
+        DCS_CHECK(dcs_deep1x1_create(ctx, C, tc, F, params_d, shapes, nparams, &deep));
+        dcs_model* m = new dcs_model();
+        m->ctx = ctx; m->arch = arch; m->C = C; m->tc = tc; m->F = F;
+        memset(&m->d, 0, sizeof(m->d));
+        m->d.S = 4;
+        m->d.n_branch = dcs_deep1x1_out_channels(deep) / C;
+        m->deep = deep;
+        *out = m;
+        return DCS_OK;
+    }
     Dims d;
     DCS_CHECK(arch_dims(arch, C, tc, F, &d));
     // expected shapes in get_all_params order
@@ -608,6 +624,7 @@ extern "C" int dcs_model_destroy(dcs_model* m) {
     float* lat[] = {m->L1p, m->L2p, m->Lfcp, m->Ldp, m->Lw2p};
     for (float* p : lat) dcs_dev_free(p);
     if (m->gen) dcs_generic_destroy(m->gen);
+    if (m->deep) dcs_deep1x1_destroy(m->deep);
     for (auto& g : m->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     m->ws.release();
@@ -621,12 +638,14 @@ extern "C" int dcs_model_destroy(dcs_model* m) {
 
 extern "C" int dcs_model_set_score_semantics(dcs_model* m, int normalise, int mixture) {
     if (!m) DCS_FAIL(DCS_EINVAL, "dcs_model_set_score_semantics: null model");
+    if (m->deep) return dcs_deep1x1_set_score_semantics(m->deep, normalise, mixture);
     if (!m->gen) DCS_FAIL(DCS_EUNSUPPORTED, "score semantics belong to the score-informed graphs");
     return dcs_generic_set_score_semantics(m->gen, normalise, mixture);
 }
 
 extern "C" int dcs_model_set_conv_precision(dcs_model* m, int f16) {
     if (!m) DCS_FAIL(DCS_EINVAL, "dcs_model_set_conv_precision: null model");
+    if (f16 && m->deep) DCS_FAIL(DCS_EUNSUPPORTED, "the deep score-informed graph (build_ca_1x1) runs in f32 only");
     if (f16 && !m->gen)
         DCS_FAIL(DCS_EUNSUPPORTED, "the f16 MFMA conv path exists for the ikala / bach10 / score-informed graphs");
     if (m->gen) return dcs_generic_set_conv_f16(m->gen, f16);
@@ -684,6 +703,7 @@ static int forward_any(dcs_model* m, const float* tiles_d, int64_t n, int mask_m
     if (n == 0) return DCS_OK;
     DCS_ON_DEVICE(m->ctx->device);
     if (m->arch == DCS_ARCH_DSD) return dsd_forward_tiles(m, tiles_d, n, mask_mode, out_d);
+    if (m->deep) return dcs_deep1x1_forward(m->deep, tiles_d, n, mask_mode, out_d);   // no pooling: tie_mode has no effect
     if (m->arch == DCS_ARCH_DSD_ILD)
         DCS_FAIL(DCS_EUNSUPPORTED, "the stereo (ILD) graph runs through dcs_separate_stereo (frames shared between tiles)");
     return dcs_generic_forward(m->gen, tiles_d, n, mask_mode, tie_mode, out_d);
@@ -707,12 +727,14 @@ static int separate_impl(dcs_model* m, dcs_stft* plan, const float* audio_d, int
                          int64_t audio_stride = 0, const int64_t* lens_h = nullptr, int64_t pcm_stride = 0,
                          const DcsScoreNotes* notes = nullptr) {
     if (!m || !plan || !audio_d) DCS_FAIL(DCS_EINVAL, "dcs_separate: null argument");
+    if (m->deep && !(notes && n_clips == 1 && !lens_h && pcm_d && !sep_out && !mag_out && !phase_out))
+        DCS_FAIL(DCS_EUNSUPPORTED, "the deep score-informed graph (build_ca_1x1) separates through dcs_separate_scoreinformed only");
     if (plan->ctx != m->ctx) DCS_FAIL(DCS_EINVAL, "dcs_separate: plan and model belong to different contexts");
     if (plan->frame / 2 + 1 != m->F)
         DCS_FAIL(DCS_EINVAL, "dcs_separate: frameSize %d gives %d bins, network was built for %d", plan->frame,
                  plan->frame / 2 + 1, m->F);
     if (notes) {
-        if (!m->gen || m->C != notes->ninst || n_clips != 1 || lens_h)
+        if (!(m->gen || m->deep) || m->C != notes->ninst || n_clips != 1 || lens_h)
             DCS_FAIL(DCS_EINVAL, "dcs_separate_scoreinformed: the model takes %d score channels, the note table has %d", m->C,
                      notes->ninst);
     } else if (m->C != 1)
@@ -725,6 +747,7 @@ static int separate_impl(dcs_model* m, dcs_stft* plan, const float* audio_d, int
     if (n_clips > 1 && (m->arch == DCS_ARCH_DSD_ILD || sep_out || mag_out || phase_out || audio_stride < L))
         DCS_FAIL(DCS_EUNSUPPORTED, "dcs_separate_batch: mono graphs, PCM output and clip stride >= length only");
     DCS_ON_DEVICE(m->ctx->device);
+    if (m->deep) return dcs_deep1x1_separate(m->deep, plan, audio_d, L, ov, scale, eps_mode, *notes, pcm_d, n_tiles_out, n_frames_out);
     const int tc = m->tc, F = m->F, st = tc - ov, S = m->d.S;
     int64_t T = dcs_frame_count(L, plan->hop);
     int64_t n = dcs_tile_count(T, tc, ov, tiler);

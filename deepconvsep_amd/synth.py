@@ -41,6 +41,11 @@ def synth_params(arch_name, tc=30, F=513, seed=1, bias_scale=0.05, gain=1.0):
         elif len(shp) == 2:
             lim = gain * np.sqrt(6.0 / (shp[0] + shp[1]))
             p = rs.uniform(-lim, lim, shp)
+        elif arch_name == 'bach10_si_1x1':
+            # He-uniform on the fan-in: the signal keeps its scale through six rectified convolutions (a Glorot draw
+            # shrinks it layer by layer until the masks see little but the biases)
+            lim = gain * np.sqrt(6.0 / (shp[1] * shp[2] * shp[3]))
+            p = rs.uniform(-lim, lim, shp)
         else:
             rf = shp[2] * shp[3]
             lim = gain * np.sqrt(6.0 / ((shp[0] + shp[1]) * rf))

@@ -8,8 +8,9 @@ are read from the directory of the input wav, as in the reference (:455, :516). 
 (:572) and output names ``<name>_{bassoon,clarinet,saxphone,violin}.wav`` (:453, :545).  The reference script itself
 does not run as shipped (``bisect``/``itertools``/``util``/``slicefft_slices`` are not imported, ``sources``,
 ``toverlap`` and ``source[i]`` are undefined or misspelt names); the behaviour reproduced here is the one its helper
-code in ``util.py`` defines.  Either .pkl of the reference loads: the 17-array graph (:388-447, trainCNNrwc.py) or the
-single-branch 11-array graph of trainCNNrwc_samp.py:195-235.
+code in ``util.py`` defines.  Every .pkl of the reference loads: the 17-array graph (:388-447, trainCNNrwc.py
+``--function build_ca``), the single-branch 11-array graph of trainCNNrwc_samp.py:195-235, and the 22-array deep graph of
+trainCNNrwc.py ``--function build_ca_1x1`` (:66-132, ``model_*_x_*.pkl``); the graph is picked from the arrays.
 
 One extra long option, ``--trainer-semantics``: harmonic masks divided by their sum over the instruments
 (``LargeDatasetMask2.filterSpec``, dataset.py:862) and soft masks applied to the sum of the four input channels

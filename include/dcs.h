@@ -57,7 +57,17 @@ enum { DCS_ARCH_DSD = 0, DCS_ARCH_IKALA = 1, DCS_ARCH_BACH10 = 2, DCS_ARCH_BACH1
        DCS_ARCH_BACH10_SI1 = 6 /* the single-branch score-informed graph (examples/bach10_scoreinformed/trainCNNrwc_samp.py:
                                   195-235): 4 input channels, ONE per-source dense layer and pair of InverseLayers, 4 output
                                   channels, 11 arrays -- also what predict_function2 of the 17-array DCS_ARCH_BACH10_SI graph
-                                  evaluates (its other three branches never reach the masks) */ };
+                                  evaluates (its other three branches never reach the masks) */,
+       DCS_ARCH_BACH10_SI_1X1 = 7 /* the deep score-informed graph build_ca_1x1 (examples/bach10_scoreinformed/trainCNNrwc.py:
+                                     66-132): 4 input channels, six strided (1|10 x 5, stride (1, 2)) rectified convolutions with
+                                     30 / 50 / 70 / 100 / 200 / 200 filters, a rectified 1x1 convolution of 800 filters sliced into
+                                     4 x 200, and per slice the InverseLayers of conv6 .. conv1; 22 arrays (per convolution W, b,
+                                     BiasLayer.b, then the final bias of 16).  The live-only layout (1x1 W / b / BiasLayer.b of
+                                     200 k rows, final bias of 4 k, k = 1 .. 4) is accepted too; output channels = 4 k.  Needs
+                                     time_context >= 19 and F >= 253.  dcs_model_forward / _forward_masked, dcs_model_set_score_semantics
+                                     and dcs_separate_scoreinformed take it (tie_mode is ignored: no pooling); the f16 switch, the
+                                     one-batch stages and the single-channel / batch / ragged / stereo / spectra paths are
+                                     DCS_EUNSUPPORTED.  f32 MFMA throughout (csrc/deep1x1.hip) */ };
 /* soft-mask epsilon convention: A = separate_dsd.py:258-266, B = separate_bach10.py:251-259 */
 enum { DCS_EPS_A = 0, DCS_EPS_B = 1 };
 /* max-pool gradient tie routing: ALL = Theano 0.9 CPU MaxPoolGrad, FIRST = cuDNN */
@@ -160,7 +170,7 @@ DCS_API int dcs_model_num_sources(const dcs_model* m);
  * (gemm_f16.hip); the measured error of the network output is unchanged (3e-5: the f16 convolutions dominate).  The ikala
  * graph (10 x 20 filters) takes the same slab kernel in either precision (one f16 plane instead of three bf16 planes). */
 DCS_API int dcs_model_set_conv_precision(dcs_model* m, int f16);
-/* Score-informed graphs (DCS_ARCH_BACH10_SI / _SI1): which of the reference's two semantics dcs_separate_scoreinformed and
+/* Score-informed graphs (DCS_ARCH_BACH10_SI / _SI1 / _SI_1X1): which of the reference's two semantics dcs_separate_scoreinformed and
  * dcs_model_forward_masked follow (the enums above).  Default = the separate script's: DCS_SCORE_NORM_MAX, DCS_MIX_CH0.
  * A model trained by trainCNNrwc.py saw sum-normalised inputs and a channel-sum mixture: (DCS_SCORE_NORM_SUM, DCS_MIX_SUM).
  * DCS_MIX_SUM adds the C input channels left to right in float32.  DCS_EUNSUPPORTED for single-channel graphs. */
