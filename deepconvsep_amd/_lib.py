@@ -110,6 +110,8 @@ def load():
     proto("dcs_timing_reset", i32, vp)
     proto("dcs_timing_query", i32, vp, i32, POINTER(c_double), POINTER(i64))
     proto("dcs_debug_check_guards", i32, vp, POINTER(i64))
+    proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
+    proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     _lib = lib
     return lib
 

@@ -148,6 +148,7 @@ struct dcs_ctx {
     float* ola_rise_d = nullptr;
     std::vector<float> ola_rise_h;
     DcsUploadRing score_ring;  // note rectangles and floor values of dcs_score_masks
+    DcsBuffer bss_ws;          // dcs_bss_energies / dcs_bss_lagcorr: segment sums, lag correlations, Gram matrices
 };
 
 // RAII-ish helper: records a start event on construction and a stop event in done().

@@ -344,6 +344,34 @@ DCS_API int dcs_score_masks_norm(dcs_ctx* ctx, const float* mag_d, int64_t ld, i
                          int ninst, int n_notes, int width, int64_t start, int64_t stop, int normalise, float* out_d,
                          float* mask_d);
 
+/* ------------------------------------------------------------------ BSS Eval v3 energies (deepconvsep_amd/evaluation.py) */
+/* The separation-quality step the reference runs in MATLAB after separating: bss_eval_sources
+ * (evaluation/bss_eval/bss_eval_sources.m; evaluation/evaluate_SS_iKala.m, evaluation/Bach10_eval_only.m), bss_eval_images
+ * (evaluation/bss_eval/bss_eval_images.m) and its framewise driver bss_eval (evaluation/DSD100_eval_only.m), restated as the
+ * five energies every criterion follows from (DESIGN.md "BSS Eval").  float64 throughout; deterministic (no atomics).
+ *
+ * Layout: ref_d [nsrc_ref * nchan][nsampl] and est_d [nsrc_est * nchan][nsampl], row k = source * nchan + channel, float64
+ * device arrays.  Window w covers samples [w * hop, w * hop + win) and is evaluated as an isolated signal (zero outside);
+ * (nwin - 1) * hop + win <= nsampl.  flen: distortion filter length, a multiple of 16 in [16, 512] (512 in the reference).
+ * At most 16 reference and 16 estimate channels (DCS_EUNSUPPORTED beyond).
+ *
+ * out_d [nwin][nsrc_est][nsrc_ref][nchan][5] with all_pairs != 0, [nwin][nsrc][nchan][5] (jest == jtrue) with all_pairs == 0
+ * (then nsrc_est == nsrc_ref).  For estimate channel e = est(jest, i) and s = ref(jtrue, i), the five float64 are
+ *   ||e||^2, ||s||^2, <e, s>, ||P_jtrue e||^2, ||e - P_all e||^2
+ * where P_j / P_all project orthogonally, in the zero-padded domain of length win + flen - 1, onto the span of r_k(t - a),
+ * a in [0, flen), k over the channels of source j / over all channels.  A pivot <= N * eps * max(diag G) of the Gram matrix
+ * (N its order) drops its basis vector, so a silent or dependent reference channel leaves the span without harm.
+ * Window groups bound the scratch to ~3 GB for any length.  Enqueued on the ctx stream. */
+DCS_API int dcs_bss_energies(dcs_ctx* ctx, const double* ref_d, const double* est_d, int nsrc_ref, int nsrc_est, int nchan,
+                             int64_t nsampl, int64_t win, int64_t hop, int64_t nwin, int flen, int all_pairs, double* out_d);
+
+/* Stage (a) of dcs_bss_energies alone, for one whole signal: out_d[k][n][d + flen - 1] = sum_t r_k(t + d) z_n(t),
+ * d in [-(flen - 1), flen - 1], k < n_ref, z = the n_ref rows of ref_d then the n_est rows of est_d ([n][n_samples] each),
+ * signals zero outside [0, n_samples).  The Gram matrix of the delayed references is G[(k1,a),(k2,b)] = c_{k1,k2}(b - a)
+ * (the correlations bss_eval_sources.m / bss_eval_images.m take with fftfilt).  Enqueued on the ctx stream. */
+DCS_API int dcs_bss_lagcorr(dcs_ctx* ctx, const double* ref_d, const double* est_d, int n_ref, int n_est, int64_t n_samples,
+                            int flen, double* out_d);
+
 /* ------------------------------------------------------------------ timing aid for bench.py */
 /* Average duration (ms) of the kernels tagged `which` since the last reset, measured with HIP events
  * on the ctx stream.  tag_mask bit t enables the tag t (two event records per tagged launch);
@@ -352,7 +380,9 @@ enum { DCS_TAG_STFT = 0, DCS_TAG_CONV1 = 1, DCS_TAG_CONV2 = 2, DCS_TAG_FC = 3, D
        DCS_TAG_DECONV2 = 5, DCS_TAG_FINAL = 6, DCS_TAG_ISTFT = 7, DCS_TAG_OLA = 8, DCS_TAG_TILE = 9, DCS_TAG_POOL = 10,
        DCS_TAG_UNPOOL = 11, DCS_TAG_MASK = 12, DCS_TAG_SCORE = 13,
        DCS_TAG_DECODER = 14 /* transposed conv2 + transposed conv1 in one kernel (Bach10 graph, f16 switch) */,
-       DCS_TAG_COUNT = 15 };
+       DCS_TAG_BSS_CORR = 15 /* dcs_bss_energies / dcs_bss_lagcorr: lag correlations, one bracket per window group */,
+       DCS_TAG_BSS_CHOL = 16 /* dcs_bss_energies: Gram assembly, partial Cholesky, energies, one bracket per window group */,
+       DCS_TAG_COUNT = 17 };
 DCS_API int dcs_timing_enable(dcs_ctx* ctx, unsigned tag_mask);
 /* bracket only every stride-th launch of an enabled tag (an event pair costs ~6 us of stream time each side) */
 DCS_API int dcs_timing_stride(dcs_ctx* ctx, int stride);
