@@ -34,10 +34,10 @@ struct DcsColConv {
     int out_f16;                // 1: `out` holds f16 ([image][Cout][Ho][W] halves, out_n_stride in halves) -- the f16 forward conv2 feeding
                                 // the f16 bottleneck layer (colconv_wreg_scatter_kernel only: dcs_colconv_wreg_scatter_ok)
 };
-// slab convolution (general kh x kw): see slabconv_kernel in generic.hip for the operation
+// slab convolution (general kh x kw): see slabconv_mx_kernel in generic.hip for the operation
 struct DcsSlabConv {
     const float* in; int64_t in_n_stride; int Cin, H, W;
-    const float* Wk;            // [kh][kw][32][32] (ci, co swizzled: colconv_wslot(0, ci, co) within a tap)
+    const float* Wk;            // not read: the slab kernels take their weights packed, as a separate argument
     const float* bias;          // [32]
     float* out; int64_t out_n_stride; int Cout, Ho, Wo;
     int kh, kw, ph, pw;

@@ -613,144 +613,26 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_f16_kernel(const IgemmArg
 }
 
 // ------------------------------------------------------------------------------------------------
-// Slab convolution for general kh x kw filters (conv2 of the iKala graph, 10 x 20, and its transpose).
+// Slab convolution for general kh x kw filters (conv2 of the iKala graph, 10 x 20, and its transpose) on the 16-bit matrix
+// pipe.
 //   out[co][y][x] = bias[co] + sum_{u,v} sum_ci Wk[u][v][ci][co] * in[ci][y + u - ph][x + v - pw]   (zero outside)
 // A workgroup owns a band of output rows of one image.  The input rows the band can touch -- at most band + kh - 1
-// -- sit in LDS for the whole workgroup, the weights stream through LDS a few taps at a time (double buffered), and
-// each wave keeps the accumulators of its (row, 16-column) blocks in registers across all taps.  Per tap a wave reads
-// the 16 weight fragments once and, for each of its blocks, 8 slab values (lane = column; a lane whose shifted column
-// falls outside the input gets 0) for 16 MFMAs; taps whose input row lies outside the image, and (tap, block) pairs
-// whose shifted columns all do, are skipped -- the implicit GEMM multiplies all of them (63 % of its K loop for the
-// iKala transpose) and re-gathers every operand from L2.
-// ------------------------------------------------------------------------------------------------
-typedef DcsSlabConv SlabConvArgs;
-
-__global__ __launch_bounds__(kColThreads) void slabconv_kernel(const SlabConvArgs g) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wstage = g.tstage * 1024;            // floats per weight stage
-    float* Wl = smem;                              // [2][tstage][32][32]
-    float* slab = smem + 2 * wstage;               // [32][rows_max][W]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fi = lane & 15, kq = lane >> 4;
-    const int64_t img = blockIdx.x / g.n_bands;
-    const int y0 = (int)(blockIdx.x - img * g.n_bands) * g.band;
-    const int yb = y0 + g.band < g.Ho ? y0 + g.band : g.Ho;   // rows [y0, yb)
-    const float* in = g.in + img * g.in_n_stride;
-    float* out = g.out + img * g.out_n_stride;
-    // input rows the band can touch
-    int rbase = y0 - g.ph, rtop = yb - 1 - g.ph + g.kh - 1;
-    if (rbase < 0) rbase = 0;
-    if (rtop > g.H - 1) rtop = g.H - 1;
-    const int rows = rtop - rbase + 1;
-    const int PS = g.rows_max * g.W;               // plane stride of the slab
-    for (int i = tid; i < 32 * PS; i += kColThreads) {
-        const int ci = i / PS, rem = i - ci * PS;
-        const int r = rem / g.W;
-        slab[i] = (ci < g.Cin && r < rows) ? in[((int64_t)ci * g.H + rbase + r) * g.W + (rem - r * g.W)] : 0.f;
-    }
-    // this wave's blocks: b = wave + 8 i -> (row y0 + b / nxb, column block b % nxb)
-    const int nxb = (g.Wo + 15) >> 4, nblk = (yb - y0) * nxb;
-    int by[4], bx[4];
-    f32x4 acc0[4], acc1[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int b = wave + 8 * i;
-        by[i] = b < nblk ? y0 + b / nxb : -1;
-        bx[i] = b < nblk ? (b % nxb) * 16 : 0;
-        acc0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        acc1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int c0 = (fi + 16 * (kq & 1)) & 31, c1 = (fi + 16 + 16 * (kq & 1)) & 31;
-    const int nvs = (g.kw + g.tstage - 1) / g.tstage;   // stages per tap row
-    // taps rows u that touch the band at all: 0 <= y + u - ph < H for some y in [y0, yb)
-    int u_lo = g.ph - (yb - 1), u_hi = g.ph - y0 + g.H - 1;
-    if (u_lo < 0) u_lo = 0;
-    if (u_hi > g.kh - 1) u_hi = g.kh - 1;
-    const int n_stage = (u_hi - u_lo + 1) * nvs;
-    f32x4 wpre[2];                                  // 2 float4 per thread cover a stage of <= 4 taps (4096 floats)
-#define DCS_SLAB_WFETCH(st_)                                                                             \
-    {                                                                                                    \
-        const int u_ = u_lo + (st_) / nvs, v_ = ((st_) % nvs) * g.tstage;                                \
-        const int nt_ = v_ + g.tstage <= g.kw ? g.tstage : g.kw - v_;                                     \
-        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                  \
-            const int e = (tid + q * kColThreads) * 4;                                                   \
-            wpre[q] = e < nt_ * 1024 ? *reinterpret_cast<const f32x4*>(g.Wk + ((int64_t)(u_ * g.kw + v_)) * 1024 + e) \
-                                     : f32x4{0.f, 0.f, 0.f, 0.f};                                        \
-        }                                                                                                \
-    }
-    if (n_stage > 0) DCS_SLAB_WFETCH(0)
-    for (int st = 0; st < n_stage; ++st) {
-        float* Wb = Wl + (st & 1) * wstage;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int e = (tid + q * kColThreads) * 4;
-            if (e < wstage) *reinterpret_cast<f32x4*>(Wb + e) = wpre[q];
-        }
-        __syncthreads();       // also orders the slab fill before the first use; buffer st&1 was last read at st-2
-        if (st + 1 < n_stage) DCS_SLAB_WFETCH(st + 1)
-        const int u = u_lo + st / nvs, v0 = (st % nvs) * g.tstage;
-        const int nt = v0 + g.tstage <= g.kw ? g.tstage : g.kw - v0;
-        for (int tv = 0; tv < nt; ++tv) {
-            const int v = v0 + tv;
-            const float* wp = Wb + tv * 1024 + kq * 32;
-            float a0[8], a1[8];
-            bool have = false;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (by[i] < 0) continue;
-                const int r = by[i] + u - g.ph;                      // input row (uniform per block)
-                const int xs = bx[i] + v - g.pw;                     // shifted column of lane 0
-                if (r < 0 || r >= g.H || xs + 15 < 0 || xs >= g.W) continue;
-                if (!have) {
-#pragma unroll
-                    for (int kk = 0; kk < 8; ++kk) {
-                        a0[kk] = wp[4 * kk * 32 + c0];
-                        a1[kk] = wp[4 * kk * 32 + c1];
-                    }
-                    have = true;
-                }
-                const int xl = xs + fi;
-                const bool ok = xl >= 0 && xl < g.W;
-                const float* sp = slab + kq * PS + (r - rbase) * g.W + (ok ? xl : 0);
-#pragma unroll
-                for (int kk = 0; kk < 8; ++kk) {
-                    const float bv = sp[4 * kk * PS];
-                    const float b = ok ? bv : 0.f;
-                    acc0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[kk], b, acc0[i], 0, 0, 0);
-                    acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[kk], b, acc1[i], 0, 0, 0);
-                }
-            }
-        }
-    }
-#undef DCS_SLAB_WFETCH
-    const int HoWo = g.Ho * g.Wo;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (by[i] < 0 || bx[i] + fi >= g.Wo) continue;
-        float* op = out + (int64_t)by[i] * g.Wo + bx[i] + fi;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int co = 4 * kq + e;
-            if (co < g.Cout) op[(int64_t)co * HoWo] = acc0[i][e] + g.bias[co];
-            if (co + 16 < g.Cout) op[(int64_t)(co + 16) * HoWo] = acc1[i][e] + g.bias[co + 16];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The slab convolution on the 16-bit matrix pipe.  One MFMA (16 x 16 x 32) covers a whole tap -- 32 input channels --
-// for 16 output channels x 16 columns:
+// -- sit in LDS for the whole workgroup, the weights stream through LDS two taps at a time (double buffered), and
+// each wave keeps the accumulators of its (row, 16-column) blocks in registers across all taps; taps whose input row
+// lies outside the image, and (tap, block) pairs whose shifted columns all do, are skipped -- the implicit GEMM
+// multiplies all of them (63 % of its K loop for the iKala transpose) and re-gathers every operand from L2.
+// One MFMA (16 x 16 x 32) covers a whole tap -- 32 input channels -- for 16 output channels x 16 columns:
 //   MODE 0 (default, f32-class results): both operands split exactly into three bf16 terms (x = hi + mid + lo by
 //           truncation), the six term products above 2^-24 accumulated in f32 -- 12 MFMAs of 16 cycles per (tap, block)
-//           instead of 16 of 32, with the VALU (splitting the slab values) running beside the matrix pipe;
+//           instead of 16 f32 MFMAs of 32, with the VALU (splitting the slab values) running beside the matrix pipe;
 //   MODE 1 (dcs_model_set_conv_precision(f16)): operands rounded to f16, one product -- 2 MFMAs per (tap, block).
 // The slab stays f32 in LDS, channel-fastest [row][x][36] (32 channels + 4 words: a lane's 8 channels are two 16-byte
 // reads, 16 consecutive x start in 16 different bank quads); a lane converts its 8 values when it uses them.  The
 // weights are packed per model [tap][plane][32 co][4 pieces] (a 16-byte piece = the 8 input channels a lane multiplies)
-// and stream through LDS two taps at a time with a row stride of 5 pieces.  Bands, tap / block skipping and the
-// accumulator layout are those of slabconv_kernel.
+// and stream through LDS with a row stride of 5 pieces.
 // ------------------------------------------------------------------------------------------------
+typedef DcsSlabConv SlabConvArgs;
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -793,10 +675,14 @@ __device__ __forceinline__ f32x4 slab_mma(u32x4 a, u32x4 b, f32x4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-template <int MODE, int NW /* waves per workgroup: 8 or 16 */>
-__global__ __launch_bounds__(64 * NW) void slabconv_mx_kernel(const SlabConvArgs g, const u32x4* __restrict__ Wq) {
+// 16 waves per workgroup: LDS allows one workgroup per CU, so the waves that hide each other's LDS latency have to come
+// from inside it
+constexpr int kSlabWaves = 16;
+
+template <int MODE>
+__global__ __launch_bounds__(64 * kSlabWaves) void slabconv_mx_kernel(const SlabConvArgs g, const u32x4* __restrict__ Wq) {
     constexpr int NP = MODE == 0 ? 3 : 1;
-    constexpr int NTH = 64 * NW, NBW = 32 / NW;          // threads; (row, 16-column) blocks per wave
+    constexpr int NW = kSlabWaves, NTH = 64 * NW, NBW = 32 / NW;   // waves, threads; (row, 16-column) blocks per wave
     constexpr int kTapLds = NP * 32 * kSlabWRow;          // pieces per tap in LDS
     constexpr int kTapGlb = NP * 32 * 4;                  // pieces per tap in the packed array
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -840,14 +726,14 @@ __global__ __launch_bounds__(64 * NW) void slabconv_mx_kernel(const SlabConvArgs
     if (u_hi > g.kh - 1) u_hi = g.kh - 1;
     const int n_stage = (u_hi - u_lo + 1) * nvs;
     // weight staging: a stage is tstage * NP * 128 <= 768 pieces
-    constexpr int WPRE = NW == 8 ? 2 : 1;
+    constexpr int WPRE = (2 * 3 * 128 + NTH - 1) / NTH;   // pieces per thread
     u32x4 wpre[WPRE];
 #define DCS_SLABQ_WFETCH(st_)                                                                           \
     {                                                                                                   \
         const int u_ = u_lo + (st_) / nvs, v_ = ((st_) % nvs) * g.tstage;                               \
         const int nt_ = v_ + g.tstage <= g.kw ? g.tstage : g.kw - v_;                                    \
         _Pragma("unroll") for (int q = 0; q < WPRE; ++q) {                                              \
-            const int e = tid + q * NTH;                                                        \
+            const int e = tid + q * NTH;                                                                \
             wpre[q] = e < nt_ * kTapGlb ? Wq[(int64_t)(u_ * g.kw + v_) * kTapGlb + e] : u32x4{0u, 0u, 0u, 0u}; \
         }                                                                                               \
     }
@@ -1277,6 +1163,33 @@ __global__ __launch_bounds__(kThreads) void mask_ola_kernel(const float* __restr
     }
 }
 
+// generic.hip's switches (scripts/README.md), read once per process, on first use
+struct GenericEnv {
+    bool slabconv, colconv, fold_conv2, conv1_reg, deconv1_reg, pool_fused, decoder_cl, gemm_bf16, mask_ola;
+    int64_t chunk;   // DCS_GENERIC_CHUNK: tiles per scratch chunk (<= 0: sized by the scratch budget)
+};
+
+bool env_on(const char* v) { return !(v && atoi(v) == 0); }   // unset: on
+
+const GenericEnv& env() {
+    static const GenericEnv e = [] {
+        GenericEnv r;
+        r.slabconv = env_on(getenv("DCS_SLABCONV"));
+        r.colconv = env_on(getenv("DCS_COLCONV"));
+        r.fold_conv2 = env_on(getenv("DCS_FOLD_CONV2"));
+        r.conv1_reg = env_on(getenv("DCS_CONV1_REG"));
+        r.deconv1_reg = env_on(getenv("DCS_DECONV1_REG"));
+        r.pool_fused = env_on(getenv("DCS_POOL_FUSED"));
+        r.decoder_cl = env_on(getenv("DCS_DECODER_CL"));
+        r.gemm_bf16 = env_on(getenv("DCS_GEMM_BF16"));
+        r.mask_ola = env_on(getenv("DCS_MASK_OLA"));
+        const char* chunk = getenv("DCS_GENERIC_CHUNK");
+        r.chunk = chunk ? atoll(chunk) : 0;
+        return r;
+    }();
+    return e;
+}
+
 template <typename T>
 int upload(T** dst, const std::vector<T>& src, const char* field) {   // field: the UP macro's spelling, "g->W1c"
     const std::string name = std::string("generic.") + (strncmp(field, "g->", 3) ? field : field + 3);
@@ -1306,8 +1219,8 @@ struct DcsGenericNet {
     _Float16 *W2m_h = nullptr, *W2t_h = nullptr;
     int conv_f16 = 0;
     // column convolution (kw2 == 1): weights [kh][32 ci][32 co swizzled] of conv2 and of its transpose
-    float *Wslab = nullptr, *Wslab_t = nullptr;   // [kh][kw][32][32] conv2 / its transpose for slabconv_kernel
-    // the same for slabconv_mx_kernel: [tap][plane][32 co][4 pieces of 8 ci]; q3 = three bf16 planes, h = one f16 plane
+    // general (kh x kw) conv2 / its transpose for slabconv_mx_kernel: [tap][plane][32 co][4 pieces of 8 ci]; q3 = three bf16
+    // planes, h = one f16 plane
     uint16_t *Wslab_q3 = nullptr, *Wslab_t_q3 = nullptr, *Wslab_h = nullptr, *Wslab_t_h = nullptr;
     uint16_t *Wps_q3 = nullptr, *Wps_t_q3 = nullptr, *Wps_h = nullptr, *Wps_t_h = nullptr;   // slabconv_ps.hip orders
     uint16_t *Wpc_q3 = nullptr, *Wpc_t_q3 = nullptr;     // the kh x 1 filters in the same orders (bf16 x 3)
@@ -1347,7 +1260,7 @@ struct DcsGenericNet {
     void* Bfch = nullptr;                                        // the bottleneck weights as one f16 plane (long-K launches under the switch)
     bool bfch_failed = false;
     void* Bdh[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* biasd_h[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* biasd_h[4] = {nullptr, nullptr, nullptr, nullptr};     // float
     int n_out16 = 0;
     bool bdh_failed = false;
     float* bout = nullptr;
@@ -1437,8 +1350,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
     // slab convolution (general kh x kw): Wslab[u][v][ci][co] = W2[co][ci][kh-1-u][kw-1-v]; transpose
     // Wslab_t[u][v][co][ci] = W2[co][ci][u][v]
     std::vector<float> Wslab, Wslab_t;
-    static const int slab_env = getenv("DCS_SLABCONV") ? atoi(getenv("DCS_SLABCONV")) : 1;
-    g->use_slabconv = (kw > 1 && nf1 <= 32 && nf2 <= 32 && slab_env) ? 1 : 0;
+    g->use_slabconv = (kw > 1 && nf1 <= 32 && nf2 <= 32 && env().slabconv) ? 1 : 0;
     if (g->use_slabconv) {
         Wslab.assign((size_t)kh * kw * 1024, 0.f);
         Wslab_t.assign((size_t)kh * kw * 1024, 0.f);
@@ -1495,8 +1407,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
     std::vector<_Float16> Wcol_h, Wcol_t_h;
     std::vector<float> Wcol_t_f;                         // the transposed filter once more in f32, [kh][32 out][40] (colconv_x3.hip)
     std::vector<float> Wcol_f;                           // the forward filter in that format (colconv_fwd_x3.hip)
-    static const int col_env = getenv("DCS_COLCONV") ? atoi(getenv("DCS_COLCONV")) : 1;
-    g->use_colconv = (kw == 1 && nf1 <= 32 && nf2 <= 32 && col_env) ? 1 : 0;
+    g->use_colconv = (kw == 1 && nf1 <= 32 && nf2 <= 32 && env().colconv) ? 1 : 0;
     if (g->use_colconv) {
         Wcol.assign((size_t)kh * 1024, 0.f);
         Wcol_t.assign((size_t)kh * 1024, 0.f);
@@ -1544,10 +1455,9 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
     // dense layer -- folded; the column-filter graphs (Bach10: 200 against 147, on a layer that is bound by its weight
     // stream) stay layer by layer.  DCS_FOLD_CONV2=0: off.
     {
-        static const bool fold_env = !(getenv("DCS_FOLD_CONV2") && atoi(getenv("DCS_FOLD_CONV2")) == 0);
         const int64_t Kf = (int64_t)nf1 * tc * d.wp;
         const double conv2_flop = 2.0 * nf2 * nf1 * kh * kw * d.h2 * d.w2, more_fc_flop = 2.0 * (double)(Kf - d.flat) * d.hidden;
-        if (rc == DCS_OK && fold_env && kw > 1 && (Kf & 3) == 0 && Kf < (1 << 30) && conv2_flop >= 4.0 * more_fc_flop) {
+        if (rc == DCS_OK && env().fold_conv2 && kw > 1 && (Kf & 3) == 0 && Kf < (1 << 30) && conv2_flop >= 4.0 * more_fc_flop) {
             std::vector<float> Wf2((size_t)kh * kw * nf2 * nf1);
             for (int co = 0; co < nf2; ++co)
                 for (int ci = 0; ci < nf1; ++ci)
@@ -1582,7 +1492,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
             dcs_dev_free(Wf2_d);
         }
     }
-    if (g->use_slabconv) { UP(g->Wslab, Wslab) UP(g->Wslab_t, Wslab_t) UP(g->Wslab_q3, Wslab_q3) UP(g->Wslab_t_q3, Wslab_t_q3) UP(g->Wslab_h, Wslab_h) UP(g->Wslab_t_h, Wslab_t_h) UP(g->Wps_q3, Wps_q3) UP(g->Wps_t_q3, Wps_t_q3) UP(g->Wps_h, Wps_h) UP(g->Wps_t_h, Wps_t_h) }
+    if (g->use_slabconv) { UP(g->Wslab_q3, Wslab_q3) UP(g->Wslab_t_q3, Wslab_t_q3) UP(g->Wslab_h, Wslab_h) UP(g->Wslab_t_h, Wslab_t_h) UP(g->Wps_q3, Wps_q3) UP(g->Wps_t_q3, Wps_t_q3) UP(g->Wps_h, Wps_h) UP(g->Wps_t_h, Wps_t_h) }
     if (g->use_colconv) {
         std::vector<_Float16> Wcol_r, Wcol_t_r;
         dcs_colconv_wreg_pack(Wcol_h.data(), kh, &Wcol_r);
@@ -1619,7 +1529,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
         memcpy(bd.data(), P[9 + 2 * s].data(), d.flat * sizeof(float));
         UP(g->Bd[s], Bd) UP(g->biasd[s], bd)
         {
-            // channels-last order of the same bias (see forward_chunk: the fused decoder reads D as [row][x][channel])
+            // channels-last order of the same bias (see dense_stage: the fused decoder reads D as [row][x][channel])
             std::vector<float> bd_cl(bd);
             const int Cc = d.nf2, Pp = d.h2 * d.w2;
             for (int j = 0; j < Cc * Pp; ++j) bd_cl[j] = bd[(size_t)(j % Cc) * Pp + j / Cc];
@@ -1630,7 +1540,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
     UP(g->bout, bout)
 #undef UP
     // (the per-source dense weights as three bf16 planes -- 1.5x their f32 size, a gigabyte for Bach10 -- are made by the
-    // first forward pass large enough to run on the bf16 matrix pipe: ensure_bdq)
+    // first forward pass large enough to run on the bf16 matrix pipe: dense_stage)
     if (rc != DCS_OK) {
         dcs_generic_destroy(g);
         return rc;
@@ -1641,7 +1551,7 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
 
 void dcs_generic_destroy(DcsGenericNet* g) {
     if (!g) return;
-    void* ptrs[] = {g->Wpc_q3, g->Wpc_t_q3, g->Wps_q3, g->Wps_t_q3, g->Wps_h, g->Wps_t_h, g->W1t, g->Wslab, g->Wslab_t, g->Wslab_q3, g->Wslab_t_q3, g->Wslab_h, g->Wslab_t_h, g->W1p, g->Wcol, g->Wcol_t, g->Wcol_h, g->Wcol_t_h, g->Wcol_r, g->Wcol_t_r, g->W1q, g->W1m, g->W1dq, g->W2m_h, g->W2t_h, g->W1c, g->bias1, g->W2m, g->bias2, g->k2off, g->k2uv, g->W2t, g->bias0, g->kt_off, g->kt_uv,
+    void* ptrs[] = {g->Wpc_q3, g->Wpc_t_q3, g->Wps_q3, g->Wps_t_q3, g->Wps_h, g->Wps_t_h, g->W1t, g->Wslab_q3, g->Wslab_t_q3, g->Wslab_h, g->Wslab_t_h, g->W1p, g->Wcol, g->Wcol_t, g->Wcol_h, g->Wcol_t_h, g->Wcol_r, g->Wcol_t_r, g->W1q, g->W1m, g->W1dq, g->W2m_h, g->W2t_h, g->W1c, g->bias1, g->W2m, g->bias2, g->k2off, g->k2uv, g->W2t, g->bias0, g->kt_off, g->kt_uv,
                     g->Bfc, g->biasfc, g->Bd[0], g->Bd[1], g->Bd[2], g->Bd[3], g->biasd[0], g->biasd[1], g->biasd[2],
                     g->biasd[3], g->bout, g->rise_d, g->Bdq[0], g->Bdq[1], g->Bdq[2], g->Bdq[3], g->biasd_cl[0], g->biasd_cl[1],
                     g->biasd_cl[2], g->biasd_cl[3], g->Wx3, g->Bfcq, g->Wfx3, g->Bdh[0], g->Bdh[1], g->Bdh[2], g->Bdh[3], g->biasd_h[0],
@@ -1655,15 +1565,14 @@ namespace {
 
 // false: the shape does not fit (LDS); the caller falls back to the implicit GEMM.
 // Wq: weights packed for the 16-bit matrix pipe (mode 0: three bf16 planes, f32-class results -- the default; mode 1: one
-// f16 plane); null: the f32-MFMA kernel (DCS_SLABCONV_MX=0).
-bool launch_slabconv(dcs_ctx* ctx, SlabConvArgs a, int64_t n_images, const uint16_t* Wq = nullptr, int mode = 0,
-                     const uint16_t* Wps = nullptr) {
-    if (Wq && Wps && dcs_launch_slabconv_ps(ctx, a, n_images, Wps, mode)) return true;
+// f16 plane); Wps: the same in slabconv_ps.hip's order, tried first.
+bool launch_slabconv(dcs_ctx* ctx, SlabConvArgs a, int64_t n_images, const uint16_t* Wq, int mode, const uint16_t* Wps) {
+    if (Wps && dcs_launch_slabconv_ps(ctx, a, n_images, Wps, mode)) return true;
     const int nxb = (a.Wo + 15) / 16;
     const int np = mode == 0 ? 3 : 1;
-    a.tstage = Wq ? (a.kw < 2 ? a.kw : 2) : (a.kw < 4 ? a.kw : 4);
-    const size_t w_bytes = Wq ? (size_t)2 * a.tstage * np * 32 * kSlabWRow * 16 : (size_t)2 * a.tstage * 1024 * sizeof(float);
-    const size_t row_bytes = Wq ? (size_t)a.W * kSlabCi * sizeof(float) : (size_t)32 * a.W * sizeof(float);
+    a.tstage = a.kw < 2 ? a.kw : 2;
+    const size_t w_bytes = (size_t)2 * a.tstage * np * 32 * kSlabWRow * 16;
+    const size_t row_bytes = (size_t)a.W * kSlabCi * sizeof(float);
     int band = 32 / nxb;                                   // 4 blocks per wave at most
     if (band < 1) return false;
     if (band > a.Ho) band = a.Ho;
@@ -1680,24 +1589,12 @@ bool launch_slabconv(dcs_ctx* ctx, SlabConvArgs a, int64_t n_images, const uint1
     a.band = band;
     a.n_bands = (a.Ho + band - 1) / band;
     a.rows_max = band + a.kh - 1;
-    const dim3 grid((unsigned)(n_images * a.n_bands));
-    if (Wq) {
-        // 16 waves per workgroup: LDS allows one workgroup per CU, so the waves that hide each other's LDS latency have
-        // to come from inside it
-        constexpr int nw_env = 16;
-        auto kern = nw_env == 8 ? (mode == 0 ? slabconv_mx_kernel<0, 8> : slabconv_mx_kernel<1, 8>)
-                                : (mode == 0 ? slabconv_mx_kernel<0, 16> : slabconv_mx_kernel<1, 16>);
-        if (lds > 48 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return false;
-        hipLaunchKernelGGL(kern, grid, dim3(nw_env == 8 ? 512 : 1024), lds, ctx->stream, a, reinterpret_cast<const u32x4*>(Wq));
-        return true;
-    }
-    auto kern = slabconv_kernel;
+    auto kern = mode == 0 ? slabconv_mx_kernel<0> : slabconv_mx_kernel<1>;
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
-    hipLaunchKernelGGL(kern, grid, dim3(kColThreads), lds, ctx->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n_images * a.n_bands)), dim3(64 * kSlabWaves), lds, ctx->stream, a,
+                       reinterpret_cast<const u32x4*>(Wq));
     return true;
 }
 
@@ -1706,11 +1603,10 @@ int launch_colconv(dcs_ctx* ctx, ColConvArgs a, int64_t n_images, const _Float16
     a.n_xb = (a.W + 15) / 16;
     if (Wh && Wr && dcs_launch_colconv_wreg(ctx, a, n_images, Wr)) return DCS_OK;
     if (a.out_f16 || a.in_f16) DCS_FAIL(DCS_EHIP, "column convolution: f16 input / output asked of a kernel that cannot take it");
-    constexpr bool ps_col = true;
     // f32-class forward conv2: bf16 x 3 with the slab pre-split in LDS (0.41 -> 0.25 ms on the score-informed batch).  The
     // transpose stays with the f32 column kernel: 7 of 20 taps are valid on average there and that kernel walks only
     // those (0.34 against 0.38 ms)
-    if (!Wh && Wps && ps_col && a.ph == 0) {
+    if (!Wh && Wps && a.ph == 0) {
         SlabConvArgs c{};
         c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
         c.Wk = a.Wk; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride;
@@ -1746,12 +1642,9 @@ int launch_colconv(dcs_ctx* ctx, ColConvArgs a, int64_t n_images, const _Float16
     return DCS_OK;
 }
 
-constexpr bool kF16Igemm = false;
-constexpr bool kSlabMx = true;
-
 // Will both InverseLayers run as ONE kernel, and does that kernel want the dense output channels-last?  One place decides it:
-// forward_chunk (layout of the dense layers' output) and dcs_generic_forward (chunk size: the layout can only be produced by
-// the all-rows dense kernel, 128 .. 176 tiles per launch).
+// dense_stage (layout of the dense layers' output), decoder_stage and dcs_generic_forward (chunk size: the layout can only be
+// produced by the all-rows dense kernel, 128 .. 176 tiles per launch).
 bool plans_channels_last(const DcsGenericNet* g, bool* fuse_planned_out, bool* fuse_x3_out) {
     const DcsGenericDims& d = g->d;
     bool fuse_planned = false, fuse_x3 = false;
@@ -1761,52 +1654,125 @@ bool plans_channels_last(const DcsGenericNet* g, bool* fuse_planned_out, bool* f
         fuse_planned = g->conv_f16 ? (g->C == 1 && dcs_decoder_fused_ok(c0, g->F)) : dcs_decoder_x3_ok(c0, g->F, g->C);
         fuse_x3 = fuse_planned && !g->conv_f16;
     }
-    static const bool cl_env = !(getenv("DCS_DECODER_CL") && atoi(getenv("DCS_DECODER_CL")) == 0);
     if (fuse_planned_out) *fuse_planned_out = fuse_planned;
     if (fuse_x3_out) *fuse_x3_out = fuse_x3;
-    return fuse_planned && (cl_env || fuse_x3) && (d.nf2 & 1) == 0 && (g->flat_p & 1) == 0;
+    return fuse_planned && (env().decoder_cl || fuse_x3) && (d.nf2 & 1) == 0 && (g->flat_p & 1) == 0;
 }
 
-// one chunk of tiles through the graph; scratch carved from `w`
-int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_total, int64_t k_first, int mask_mode,
-                  int tie_mode, float* out, char* w) {
+// iKala: max-pool fused into conv1 and its VJP into conv1^T (register kernels, 30 filters of 30 taps at a stride of 3, pool
+// width 4).  The full-resolution activations a1b then never exist; their region holds the routing words instead
+// (pool_words + 1 <= w1 words per row).  DCS_POOL_FUSED=0: the four separate kernels.
+int pool_words(const DcsGenericDims& d) { return (int)dcs_cdiv(d.w1, 64) * 2; }
+
+bool pool_fused(const DcsGenericNet* g) {
+    const DcsGenericDims& d = g->d;
+    const GenericEnv& e = env();
+    return e.pool_fused && e.conv1_reg && e.deconv1_reg && d.pool_w == 4 && d.nf1 == 30 && d.sw1 == 3 && d.kw1 <= 32 &&
+           (d.kw1 + 2) / 3 == 10 && g->W1t && g->W1p && !g->W1m && !g->W1dq && pool_words(d) + 1 <= d.w1 && d.wp * 4 <= d.w1;
+}
+
+// Weights re-packed on first need, in one block or two (`slot2`): allocated, filled by pack(block, block2) and published only
+// once packed -- a failed pack must not leave a non-null, unpacked block behind (later calls would multiply by uninitialised
+// memory).  Out of memory is not an error of the forward pass: *failed is set, nothing is published, and the layers that
+// would use the blocks stay on the kernels that do without them for the model's lifetime.  Same stream: no synchronisation.
+template <typename Pack>
+int pack_once(bool* failed, Pack pack, void** slot, size_t bytes, const char* name, void** slot2 = nullptr, size_t bytes2 = 0,
+              const char* name2 = nullptr) {
+    if (*slot || *failed) return DCS_OK;
+    void *p = nullptr, *p2 = nullptr;
+    if (dcs_dev_alloc(&p, bytes, name) != hipSuccess || (slot2 && dcs_dev_alloc(&p2, bytes2, name2) != hipSuccess)) {
+        (void)hipGetLastError();
+        dcs_dev_free(p);
+        *failed = true;
+        return DCS_OK;
+    }
+    const int rc = pack(p, p2);
+    if (rc != DCS_OK) {
+        dcs_dev_free(p);
+        dcs_dev_free(p2);
+        return rc;
+    }
+    *slot = p;
+    if (slot2) *slot2 = p2;
+    return DCS_OK;
+}
+
+// per-source dense layer b (rectify) on its f32 weights: Z -> the channel-first slice b of D[n][NB][flat_p]
+DcsGemm dense_gemm(const DcsGenericNet* g, const float* Z, float* D, int64_t n, int NB, int b) {
+    const int s = g->d.branch_fc[b];
+    DcsGemm q{};
+    q.A = Z; q.lda = g->hid64; q.a_gdiv = 1 << 30; q.a_gmul = 0; q.a_scale = 1.f;
+    q.B = g->Bd[s]; q.ldb = g->flat64; q.bias = g->biasd[s];
+    q.C = D + (int64_t)b * g->flat_p; q.ldc = (int64_t)NB * g->flat_p; q.c_gdiv = 1 << 30; q.c_gmul = 0;
+    q.M = n; q.n_cols = g->flat64; q.n_store = g->d.flat; q.K = g->hid64; q.relu = 1; q.a_vec = 1;
+    return q;
+}
+
+// conv2 (transpose = false) or its transpose with general kh x kw filters (iKala): the slab kernels in the precision of the
+// switch, else the implicit GEMM; without the slab kernels (DCS_SLABCONV=0) the f16 switch takes the f16 implicit GEMM
+void launch_conv2_general(const DcsGenericNet* g, const IgemmArgs& a, int64_t n_images, bool transpose) {
+    dcs_ctx* ctx = g->ctx;
+    const int f16 = g->conv_f16 ? 1 : 0;
+    if (f16 && !g->use_slabconv) {
+        hipLaunchKernelGGL(conv_igemm_f16_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a,
+                           transpose ? g->W2t_h : g->W2m_h);
+        return;
+    }
+    if (g->use_slabconv) {
+        SlabConvArgs c{};
+        c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
+        c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride;
+        c.Cout = a.Cout; c.Ho = a.Ho; c.Wo = a.Wo; c.kh = g->d.kh2; c.kw = g->d.kw2; c.ph = a.ph; c.pw = a.pw;
+        const uint16_t* Wq = transpose ? (f16 ? g->Wslab_t_h : g->Wslab_t_q3) : (f16 ? g->Wslab_h : g->Wslab_q3);
+        const uint16_t* Wps = transpose ? (f16 ? g->Wps_t_h : g->Wps_t_q3) : (f16 ? g->Wps_h : g->Wps_q3);
+        if (launch_slabconv(ctx, c, n_images, Wq, f16, Wps)) return;
+    }
+    hipLaunchKernelGGL(conv_igemm_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a);
+}
+
+// How a map handed from one stage to the next is laid out: channel-first f32 (the reference's NCHW), or channels-last as
+// f32 or as f16 with 32 channels per position
+enum MapLayout { kChannelFirst, kChannelsLastF32, kChannelsLastF16 };
+
+// one chunk of tiles and its scratch, carved by forward_chunk
+struct Chunk {
+    const float* tiles;
+    int64_t n, n_total, k_first;   // tiles in the chunk, in the call, index of the chunk's first
+    int NB;                        // live branches
+    int mask_mode, tie_mode;
+    float* out;
+    float* a1b;                    // conv1's output (fused pool: the un-pooling routing words)
+    float* p1;                     // the pooled rows (pool), else a1b
+    float* a2b;                    // conv2's output
+    float* Z;                      // the bottleneck layer's output [n][hid64]
+    void* Zq;                      // Z as bf16 x 3 planes for the all-rows dense kernel
+    float* D;                      // the per-source dense layers' output
+    float *g2, *g1;                // InverseLayer(conv2)'s output; un-pooled (pool), else g2
+    float* o;                      // the decoder's output [n][NB * C][tc][F]
+    char* stage;                   // mask staging of chunked batches
+};
+
+// what the stages hand on: nothing else is shared between them
+struct Handoff {
+    const float* a1 = nullptr;     // conv1's map as conv2 reads it (pooled if the graph pools)
+    MapLayout a1_layout = kChannelFirst;
+    int a1_rows = 0;               // rows from one tile's first row to the next's in a channels-last map (per-frame conv1: the stride)
+    bool fold2 = false;            // conv2 + bottleneck layer ran as one folded map of a1: nothing at a2b
+    bool a2_f16 = false;           // conv2's map at a2b: f32 rows of flat_p floats, or f16 rows of pitch16 halves
+    MapLayout d_layout = kChannelFirst;   // D as the decoder finds it
+};
+
+int pitch16_of(const DcsGenericDims& d) { return (int)dcs_round_up(d.flat, 32); }
+
+// conv1 + both biases, with the max-pool fused or after it
+int conv1_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
     const DcsGenericDims& d = g->d;
     dcs_ctx* ctx = g->ctx;
     const int C = g->C, tc = g->tc, F = g->F;
-    // Branches that reach the requested output.  The masks use the first S output channels (prediction2[:, 0:S]); with C
-    // input channels per branch those belong to the first ceil(S / C) branches -- for the score-informed graph (C = 4,
-    // S = 4) branch 0 alone: the other three branches of its decoder are dead code for predict_function2
-    // (bach10_scoreinformed/separate_bach10.py:475-488; Theano prunes them from the compiled function as well).
-    // dcs_model_forward (mask_mode 2: the whole network output) evaluates all of them.
-    const int NB = mask_mode == 2 ? d.n_branch : (d.S + C - 1) / C < d.n_branch ? (d.S + C - 1) / C : d.n_branch;
-    const int64_t plane1 = (int64_t)tc * d.w1, planep = (int64_t)tc * d.wp;
-    bool want_a1_cl = false, a1_cl = false;             // conv1's output channels-last: asked for / written that way
-    bool want_a1_16 = false, a1_16 = false;             // ... as f16 with 32 channels per position (f16 switch)
-    int a1_rows = tc;                                   // rows from one tile's first row to the next's in the channels-last map (per-frame conv1: the stride)
-    float* a1b = (float*)w; w += align256((size_t)n * d.nf1 * plane1 * 4);
-    float* p1 = a1b;
-    if (d.pool_w) { p1 = (float*)w; w += align256((size_t)n * d.nf1 * planep * 4); }
-    float* a2b = (float*)w; w += align256((size_t)n * g->flat_p * 4);
-    float* Z = (float*)w; w += align256((size_t)n * g->hid64 * 4);
-    void* Zq = (void*)w; w += align256(dcs_gemm_aq_bytes(g->hid64, 176));   // Z as bf16 x 3 planes for the all-rows dense kernel
-    float* D = (float*)w; w += align256((size_t)n * NB * g->flat_p * 4);
-    float* g2 = (float*)w; w += align256((size_t)n * NB * d.nf1 * planep * 4);
-    float* g1 = g2;
-    if (d.pool_w) { g1 = (float*)w; w += align256((size_t)n * NB * d.nf1 * plane1 * 4); }
-    float* o = (float*)w; w += align256((size_t)n * NB * C * tc * F * 4);
-    // iKala: max-pool fused into conv1 and its VJP into conv1^T (register kernels, 30 filters of 30 taps at a stride of 3, pool
-    // width 4).  The full-resolution activations a1b then never exist; their region holds the routing words instead
-    // (pool_mw + 1 <= w1 words per row).  DCS_POOL_FUSED=0: the four separate kernels.
-    static const int pool_fused_env = getenv("DCS_POOL_FUSED") ? atoi(getenv("DCS_POOL_FUSED")) : 1;
-    static const int reg1_env = getenv("DCS_CONV1_REG") ? atoi(getenv("DCS_CONV1_REG")) : 1;
-    static const int dreg_env = getenv("DCS_DECONV1_REG") ? atoi(getenv("DCS_DECONV1_REG")) : 1;
-    const int pool_mw = (int)dcs_cdiv(d.w1, 64) * 2;
-    const bool pool_fused = pool_fused_env && reg1_env && dreg_env && d.pool_w == 4 && d.nf1 == 30 && d.sw1 == 3 && d.kw1 <= 32 &&
-                            (d.kw1 + 2) / 3 == 10 && g->W1t && g->W1p && !g->W1m && !g->W1dq &&
-                            pool_mw + 1 <= d.w1 && d.wp * 4 <= d.w1;
-    unsigned* pool_bits = reinterpret_cast<unsigned*>(a1b);
-
-    // conv1 + both biases
+    const int64_t n = k.n, plane1 = (int64_t)tc * d.w1;
+    const bool fused_pool = pool_fused(g);
+    h.a1 = k.p1;
+    h.a1_rows = tc;
     {
         const size_t lds = ((size_t)d.nf1 * C * d.kw1 + (size_t)C * (kThreads * d.sw1 + d.kw1)) * 4;
         auto kern = conv1_kernel<30>;
@@ -1816,194 +1782,176 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
         DcsTimer tm(ctx, DCS_TAG_CONV1);
         // f32-class column conv2 with the weights in registers (colconv_fwd_x3.hip) reads a position's channels together: conv1
         // then writes its output channels-last (only the bf16-pipe conv1 kernel can; nothing else reads a1b in these graphs)
-        {
-            ColConvArgs c2{};
-            c2.in = a1b; c2.in_n_stride = (int64_t)d.nf1 * plane1; c2.Cin = d.nf1; c2.H = tc; c2.W = d.w1;
-            c2.Cout = d.nf2; c2.Ho = d.h2; c2.ph = 0; c2.kh = d.kh2;
-            want_a1_cl = !g->conv_f16 && g->use_colconv && g->Wfx3 && g->W1m && !d.pool_w && d.wp == d.w1 && dcs_colconv_fwd_x3_ok(c2) &&
-                         (c2.in_n_stride & 1) == 0 && (reinterpret_cast<uintptr_t>(a1b) & 7) == 0;
-            // f16 switch, one input channel (round 6): the weights-in-registers f16 conv2 takes its input as f16, channels-last, 32
-            // channels per position -- conv1 writes a1b16[n][t][x][32] halves (half the bytes; a lane of conv2 loads 16 bytes per row)
-            static const bool cl_on = !(getenv("DCS_DECODER_CL") && atoi(getenv("DCS_DECODER_CL")) == 0);
-            want_a1_16 = cl_on && g->conv_f16 && C == 1 && g->use_colconv && g->Wcol_h && g->Wcol_r && g->W1m && !d.pool_w && d.wp == d.w1 &&
-                         d.nf1 <= 32 && dcs_colconv_wreg_scatter_ok(c2) && (reinterpret_cast<uintptr_t>(a1b) & 15) == 0;
-        }
+        ColConvArgs c2{};
+        c2.in = k.a1b; c2.in_n_stride = (int64_t)d.nf1 * plane1; c2.Cin = d.nf1; c2.H = tc; c2.W = d.w1;
+        c2.Cout = d.nf2; c2.Ho = d.h2; c2.ph = 0; c2.kh = d.kh2;
+        const bool want_cl = !g->conv_f16 && g->use_colconv && g->Wfx3 && g->W1m && !d.pool_w && d.wp == d.w1 &&
+                             dcs_colconv_fwd_x3_ok(c2) && (c2.in_n_stride & 1) == 0 && (reinterpret_cast<uintptr_t>(k.a1b) & 7) == 0;
+        // f16 switch, one input channel (round 6): the weights-in-registers f16 conv2 takes its input as f16, channels-last, 32
+        // channels per position -- conv1 writes a1b16[n][t][x][32] halves (half the bytes; a lane of conv2 loads 16 bytes per row)
+        const bool want_16 = env().decoder_cl && g->conv_f16 && C == 1 && g->use_colconv && g->Wcol_h && g->Wcol_r && g->W1m &&
+                             !d.pool_w && d.wp == d.w1 && d.nf1 <= 32 && dcs_colconv_wreg_scatter_ok(c2) &&
+                             (reinterpret_cast<uintptr_t>(k.a1b) & 15) == 0;
         // One clip, all its tiles in this chunk, a channels-last hand-over to conv2: conv1 (a per-row operation) runs once per
         // FRAME of the clip instead of once per tile row -- tc / (tc - overlap) = 6 x fewer rows at the reference's settings --
         // and conv2 takes tile k as the window of tc rows from row k * st of that map (its tile stride is a parameter).
         // Same arithmetic per row: bit-identical to the per-tile form.
-        const bool per_frame = g->frames_src && n == n_total && k_first == 0 && g->frames_st > 0 &&
+        const bool per_frame = g->frames_src && n == k.n_total && k.k_first == 0 && g->frames_st > 0 &&
                                g->frames_rows == (n - 1) * g->frames_st + tc && g->frames_st < tc;
-        static const int reg1 = getenv("DCS_CONV1_REG") ? atoi(getenv("DCS_CONV1_REG")) : 1;
         const dim3 grid1((unsigned)dcs_cdiv(d.w1, kThreads), (unsigned)(n * tc));
-        if (pool_fused) {   // conv1 + max-pool: pooled rows to p1, the un-pooling routing bits where the activations would go
-            hipLaunchKernelGGL((conv1_reg_kernel<30, 3, true>), grid1, dim3(kThreads), 0, ctx->stream, tiles, g->W1t, g->bias1, p1, C,
-                               tc, F, d.kw1, d.w1, pool_bits, d.wp, pool_mw, tie_mode == DCS_TIE_FIRST ? 1 : 0);
-        } else if (per_frame && want_a1_16 &&
-                   dcs_launch_conv1_mfma(ctx, g->frames_src, g->W1m, g->bias1, a1b, 1, C, d.nf1, g->frames_rows, F, d.kw1, d.sw1, d.w1, true, true)) {
-            a1_16 = true; a1_rows = g->frames_st;
-        } else if (per_frame && want_a1_cl &&
-                   dcs_launch_conv1_mfma(ctx, g->frames_src, g->W1m, g->bias1, a1b, 1, C, d.nf1, g->frames_rows, F, d.kw1, d.sw1, d.w1, true)) {
-            a1_cl = true; a1_rows = g->frames_st;
-        } else if (want_a1_16 && dcs_launch_conv1_mfma(ctx, tiles, g->W1m, g->bias1, a1b, n, C, d.nf1, tc, F, d.kw1, d.sw1, d.w1, true, true)) {
-            a1_16 = true;
-        } else if (g->W1m && dcs_launch_conv1_mfma(ctx, tiles, g->W1m, g->bias1, a1b, n, C, d.nf1, tc, F, d.kw1, d.sw1, d.w1, want_a1_cl)) {
-            a1_cl = want_a1_cl;
-        } else if (reg1 && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 4)   // the register kernel is built for 30 filters
-            hipLaunchKernelGGL((conv1_reg_kernel<30, 4>), grid1, dim3(kThreads), 0, ctx->stream, tiles, g->W1t, g->bias1, a1b, C,
+        if (fused_pool) {   // conv1 + max-pool: pooled rows to p1, the un-pooling routing bits where the activations would go
+            hipLaunchKernelGGL((conv1_reg_kernel<30, 3, true>), grid1, dim3(kThreads), 0, ctx->stream, k.tiles, g->W1t, g->bias1, k.p1,
+                               C, tc, F, d.kw1, d.w1, reinterpret_cast<unsigned*>(k.a1b), d.wp, pool_words(d),
+                               k.tie_mode == DCS_TIE_FIRST ? 1 : 0);
+        } else if (per_frame && want_16 &&
+                   dcs_launch_conv1_mfma(ctx, g->frames_src, g->W1m, g->bias1, k.a1b, 1, C, d.nf1, g->frames_rows, F, d.kw1, d.sw1, d.w1,
+                                         true, true)) {
+            h.a1_layout = kChannelsLastF16; h.a1_rows = g->frames_st;
+        } else if (per_frame && want_cl &&
+                   dcs_launch_conv1_mfma(ctx, g->frames_src, g->W1m, g->bias1, k.a1b, 1, C, d.nf1, g->frames_rows, F, d.kw1, d.sw1, d.w1,
+                                         true)) {
+            h.a1_layout = kChannelsLastF32; h.a1_rows = g->frames_st;
+        } else if (want_16 && dcs_launch_conv1_mfma(ctx, k.tiles, g->W1m, g->bias1, k.a1b, n, C, d.nf1, tc, F, d.kw1, d.sw1, d.w1, true,
+                                                    true)) {
+            h.a1_layout = kChannelsLastF16;
+        } else if (g->W1m && dcs_launch_conv1_mfma(ctx, k.tiles, g->W1m, g->bias1, k.a1b, n, C, d.nf1, tc, F, d.kw1, d.sw1, d.w1, want_cl)) {
+            if (want_cl) h.a1_layout = kChannelsLastF32;
+        } else if (env().conv1_reg && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 4)   // the register kernel is built for 30 filters
+            hipLaunchKernelGGL((conv1_reg_kernel<30, 4>), grid1, dim3(kThreads), 0, ctx->stream, k.tiles, g->W1t, g->bias1, k.a1b, C,
                                tc, F, d.kw1, d.w1);
-        else if (reg1 && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 3)
-            hipLaunchKernelGGL((conv1_reg_kernel<30, 3>), grid1, dim3(kThreads), 0, ctx->stream, tiles, g->W1t, g->bias1, a1b, C,
+        else if (env().conv1_reg && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 3)
+            hipLaunchKernelGGL((conv1_reg_kernel<30, 3>), grid1, dim3(kThreads), 0, ctx->stream, k.tiles, g->W1t, g->bias1, k.a1b, C,
                                tc, F, d.kw1, d.w1);
         else
-            hipLaunchKernelGGL(kern, grid1, dim3(kThreads), lds, ctx->stream, tiles, g->W1c, g->bias1, a1b, C, tc, F, d.kw1,
+            hipLaunchKernelGGL(kern, grid1, dim3(kThreads), lds, ctx->stream, k.tiles, g->W1c, g->bias1, k.a1b, C, tc, F, d.kw1,
                                d.sw1, d.w1);
         tm.done();
     }
-    if (d.pool_w && !pool_fused) {
+    if (d.pool_w && !fused_pool) {
         DcsTimer tm(ctx, DCS_TAG_POOL);
         hipLaunchKernelGGL(pool_kernel, dim3((unsigned)dcs_cdiv(n * d.nf1 * tc * d.wp, kThreads)), dim3(kThreads), 0,
-                           ctx->stream, a1b, p1, n * d.nf1 * tc, d.w1, d.wp, d.pool_w);
+                           ctx->stream, k.a1b, k.p1, n * d.nf1 * tc, d.w1, d.wp, d.pool_w);
         tm.done();
     }
+    return DCS_OK;
+}
+
+// conv2 + both biases -> a2b[n][flat_p] (pad columns zeroed; f16: the pitch16 - flat pad halves, as flat / 2 .. pitch16 / 2
+// floats), or nothing when it is folded into the bottleneck layer
+int conv2_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
+    const DcsGenericDims& d = g->d;
+    dcs_ctx* ctx = g->ctx;
+    const int tc = g->tc;
+    const int64_t n = k.n, planep = (int64_t)tc * d.wp;
     // f16 switch (round 6): when the bottleneck layer will run on its f16 weight plane (gemm_f16_longk_kernel: 128 .. 176 tiles, K >=
     // 16 384) AND conv2 is the weights-in-registers f16 kernel, conv2 writes its map as f16 -- a2b16[n][pitch16] halves, pitch16 =
     // flat rounded up to 32 so that every K tile of the layer lies inside a row -- and the layer multiplies those rows as they
     // are: half the bytes on both sides of the hand-over, one MFMA per block instead of two.  The plane is made on first need.
-    static const bool fc16_on = !(getenv("DCS_GEMM_BF16") && atoi(getenv("DCS_GEMM_BF16")) == 0);
-    const int pitch16 = (int)dcs_round_up(d.flat, 32);
-    int ks16 = 0;
-    bool a2b16 = false;
-    if (fc16_on && g->conv_f16 && !g->bfch_failed) {
-        ks16 = dcs_gemm_f16_longk_slices(ctx, (int)n, pitch16, g->hid64);
-        if (ks16 >= 2 && !g->Bfch) {
-            void* plane = nullptr;
-            if (dcs_dev_alloc(&plane, dcs_gemm_bh_bytes(g->flat_p, g->hid64), "generic.Bfch") != hipSuccess) {
-                (void)hipGetLastError();
-                g->bfch_failed = true;
-            } else {
-                const int rc = dcs_gemm_pack_bh_plain(ctx, g->Bfc, g->flat_p, g->hid64, g->hid64, plane);
-                if (rc != DCS_OK) {
-                    dcs_dev_free(plane);
-                    return rc;
-                }
-                g->Bfch = plane;
-            }
-        }
+    const int pitch16 = pitch16_of(d);
+    if (env().gemm_bf16 && g->conv_f16 && !g->bfch_failed) {
+        const int ks16 = dcs_gemm_f16_longk_slices(ctx, (int)n, pitch16, g->hid64);
+        if (ks16 >= 2)
+            DCS_CHECK(pack_once(&g->bfch_failed, [&](void* p, void*) { return dcs_gemm_pack_bh_plain(ctx, g->Bfc, g->flat_p, g->hid64, g->hid64, p); },
+                                &g->Bfch, dcs_gemm_bh_bytes(g->flat_p, g->hid64), "generic.Bfch"));
         if (ks16 >= 2 && g->Bfch && g->use_colconv && g->Wcol_h && g->Wcol_r && !d.pool_w && (d.flat & 1) == 0) {
             ColConvArgs c2{};
             c2.Cin = d.nf1; c2.H = tc; c2.W = d.wp; c2.Cout = d.nf2; c2.Ho = d.h2; c2.ph = 0; c2.kh = d.kh2;
-            a2b16 = dcs_colconv_wreg_scatter_ok(c2);
+            h.a2_f16 = dcs_colconv_wreg_scatter_ok(c2);
         }
     }
     // conv2 + BiasLayer + bottleneck layer as one folded affine map of conv2's input (created with the model where it pays:
     // the iKala graph; f32-class only -- the f16 switch asks for conv2 in f16)
-    const bool fold2 = g->B2fc && g->K2fc > 0 && !g->conv_f16 && !a1_cl && !a1_16;
-    // conv2 + both biases -> a2b[n][flat_p] (pad columns zeroed; f16: the pitch16 - flat pad halves, as flat / 2 .. pitch16 / 2 floats)
-    if (fold2) {
-    } else if (a2b16) {
+    h.fold2 = g->B2fc && g->K2fc > 0 && !g->conv_f16 && h.a1_layout == kChannelFirst;
+    if (h.fold2) return DCS_OK;
+    if (h.a2_f16) {
         if (pitch16 != d.flat)
             hipLaunchKernelGGL(zero_pad_cols_kernel, dim3((unsigned)dcs_cdiv(n * ((pitch16 - d.flat) / 2), kThreads)), dim3(kThreads), 0,
-                               ctx->stream, a2b, n, d.flat / 2, pitch16 / 2);
+                               ctx->stream, k.a2b, n, d.flat / 2, pitch16 / 2);
     } else if (g->flat_p != d.flat)
         hipLaunchKernelGGL(zero_pad_cols_kernel, dim3((unsigned)dcs_cdiv(n * (g->flat_p - d.flat), kThreads)), dim3(kThreads), 0,
-                           ctx->stream, a2b, n, d.flat, g->flat_p);
-    if (!fold2) {
-        IgemmArgs a{};
-        a.in = p1; a.in_n_stride = (int64_t)d.nf1 * planep; a.Cin = d.nf1; a.H = tc; a.W = d.wp;
-        a.Wm = g->W2m; a.koff = g->k2off; a.kuv = g->k2uv; a.bias = g->bias2;
-        a.out = a2b; a.out_n_stride = g->flat_p; a.Cout = d.nf2; a.Ho = d.h2; a.Wo = d.w2;
-        a.ph = 0; a.pw = 0; a.K = g->K2; a.M = n * d.h2 * d.w2;
-        DcsTimer tm(ctx, DCS_TAG_CONV2);
-        if (g->use_colconv) {
-            ColConvArgs c{};
-            c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
-            c.Wk = g->Wcol; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride; c.Cout = a.Cout; c.Ho = a.Ho;
-            c.ph = 0; c.kh = d.kh2;
-            if (a2b16) { c.out_f16 = 1; c.out_n_stride = pitch16; }
-            if (a1_16) { c.in_f16 = 1; c.in_n_stride = (int64_t)a1_rows * d.w1 * 32; }
-            else if (a1_cl) c.in_n_stride = (int64_t)a1_rows * d.w1 * d.nf1;
-            if (a1_cl) {
-                if (!dcs_launch_colconv_fwd_x3(ctx, c, n, g->Wfx3))
-                    DCS_FAIL(DCS_EHIP, "generic graph: conv2 refused the channels-last input conv1 was asked to write");
-            } else
+                           ctx->stream, k.a2b, n, d.flat, g->flat_p);
+    IgemmArgs a{};
+    a.in = h.a1; a.in_n_stride = (int64_t)d.nf1 * planep; a.Cin = d.nf1; a.H = tc; a.W = d.wp;
+    a.Wm = g->W2m; a.koff = g->k2off; a.kuv = g->k2uv; a.bias = g->bias2;
+    a.out = k.a2b; a.out_n_stride = g->flat_p; a.Cout = d.nf2; a.Ho = d.h2; a.Wo = d.w2;
+    a.ph = 0; a.pw = 0; a.K = g->K2; a.M = n * d.h2 * d.w2;
+    DcsTimer tm(ctx, DCS_TAG_CONV2);
+    if (g->use_colconv) {
+        ColConvArgs c{};
+        c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
+        c.Wk = g->Wcol; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride; c.Cout = a.Cout; c.Ho = a.Ho;
+        c.ph = 0; c.kh = d.kh2;
+        if (h.a2_f16) { c.out_f16 = 1; c.out_n_stride = pitch16; }
+        if (h.a1_layout == kChannelsLastF16) { c.in_f16 = 1; c.in_n_stride = (int64_t)h.a1_rows * d.w1 * 32; }
+        else if (h.a1_layout == kChannelsLastF32) c.in_n_stride = (int64_t)h.a1_rows * d.w1 * d.nf1;
+        if (h.a1_layout == kChannelsLastF32) {
+            if (!dcs_launch_colconv_fwd_x3(ctx, c, n, g->Wfx3))
+                DCS_FAIL(DCS_EHIP, "generic graph: conv2 refused the channels-last input conv1 was asked to write");
+        } else
             DCS_CHECK(launch_colconv(ctx, c, n, g->conv_f16 ? g->Wcol_h : nullptr, g->Wcol_r, g->Wpc_q3));
-            // (launch_colconv fails a launch that asks for f16 output and is not taken by the weights-in-registers kernel)
-        } else if (g->conv_f16 && !(g->use_slabconv && !kF16Igemm))
-            // general filters (iKala, 10 x 20) go through the slab kernel in either precision unless DCS_F16_IGEMM=1 asks
-            // for the f16 implicit GEMM
-            hipLaunchKernelGGL(conv_igemm_f16_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a,
-                               g->W2m_h);
-        else {
-            bool done = false;
-            if (g->use_slabconv) {
-                SlabConvArgs c{};
-                c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
-                c.Wk = g->Wslab; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride;
-                c.Cout = a.Cout; c.Ho = a.Ho; c.Wo = a.Wo; c.kh = d.kh2; c.kw = d.kw2; c.ph = 0; c.pw = 0;
-                done = launch_slabconv(ctx, c, n, kSlabMx ? (g->conv_f16 ? g->Wslab_h : g->Wslab_q3) : nullptr, g->conv_f16 ? 1 : 0,
-                                       g->conv_f16 ? g->Wps_h : g->Wps_q3);
-            }
-            if (!done)
-                hipLaunchKernelGGL(conv_igemm_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a);
-        }
-        tm.done();
+        // (launch_colconv fails a launch that asks for f16 output and is not taken by the weights-in-registers kernel)
+    } else
+        launch_conv2_general(g, a, n, false);
+    tm.done();
+    return DCS_OK;
+}
+
+// bottleneck dense (rectify): a2b (or, folded, conv2's input) -> Z
+int bottleneck_stage(DcsGenericNet* g, const Chunk& k, const Handoff& h) {
+    const DcsGenericDims& d = g->d;
+    dcs_ctx* ctx = g->ctx;
+    const int64_t n = k.n;
+    DcsGemm q{};
+    q.A = k.a2b; q.lda = g->flat_p; q.a_gdiv = 1 << 30; q.a_gmul = 0; q.a_scale = 1.f;
+    q.B = g->Bfc; q.ldb = g->hid64; q.bias = g->biasfc;
+    q.C = k.Z; q.ldc = g->hid64; q.c_gdiv = 1 << 30; q.c_gmul = 0;
+    q.M = n; q.n_cols = g->hid64; q.n_store = g->hid64; q.K = g->flat_p; q.relu = 1; q.a_vec = 1;
+    if (h.fold2) {   // the tile's conv2 input p1[ci][row][x], contiguous per tile
+        q.A = h.a1; q.lda = (int64_t)d.nf1 * g->tc * d.wp; q.K = g->K2fc; q.B = g->B2fc; q.bias = g->bias2fc;
     }
-    // bottleneck dense (rectify)
-    {
-        DcsGemm q{};
-        q.A = a2b; q.lda = g->flat_p; q.a_gdiv = 1 << 30; q.a_gmul = 0; q.a_scale = 1.f;
-        q.B = g->Bfc; q.ldb = g->hid64; q.bias = g->biasfc;
-        q.C = Z; q.ldc = g->hid64; q.c_gdiv = 1 << 30; q.c_gmul = 0;
-        q.M = n; q.n_cols = g->hid64; q.n_store = g->hid64; q.K = g->flat_p; q.relu = 1; q.a_vec = 1;
-        if (fold2) {   // the tile's conv2 input p1[ci][row][x], contiguous per tile
-            q.A = p1; q.lda = (int64_t)d.nf1 * planep; q.K = g->K2fc; q.B = g->B2fc; q.bias = g->bias2fc;
-        }
-        // 128 .. 176 tiles against a very long K (166 650 for the Bach10 graphs): the all-rows bf16 x 3 kernel with K cut into
-        // slices (dcs_launch_gemm_bf16x3_longk) -- the planes (1.5 x the f32 weights) are made on first need; without them,
-        // or for any other row count, the f32 K-split of gemm.hip
-        static const bool fcq_on = !(getenv("DCS_GEMM_BF16") && atoi(getenv("DCS_GEMM_BF16")) == 0);
-        if (!fold2 && fcq_on && n >= 128 && n <= 176 && g->flat_p >= 16384 && (g->hid64 % 128) == 0 && !g->Bfcq && !g->bfcq_failed &&
-            (!g->conv_f16 || g->bfch_failed)) {           // (under the f16 switch the layer takes the f16 plane below instead)
-            void* planes = nullptr;                       // (unsplit 32-byte pieces since round 6: the long-K launch is the all-rows kernel)
-            if (dcs_dev_alloc(&planes, dcs_gemm_b32_bytes(g->flat_p, g->hid64), "generic.Bfcq") != hipSuccess) {
-                (void)hipGetLastError();
-                g->bfcq_failed = true;
-            } else {
-                const int rc = dcs_gemm_pack_b32(ctx, g->Bfc, g->flat_p, g->hid64, g->hid64, planes);
-                if (rc != DCS_OK) {
-                    dcs_dev_free(planes);
-                    return rc;
-                }
-                g->Bfcq = planes;
-            }
-        }
-        q.Bq = fold2 ? nullptr : g->Bfcq;
-        q.bq_f32 = 1;
-        // f16 switch: the same long-K launch on f16 weights (gemm_f16.hip: one plane, 2 bytes per weight instead of 6); the rows
-        // of A are conv2's f16 map (a2b16, above) or, when conv2 could not write it, f32 rows split into two f16 terms on their
-        // way into LDS; the slices are added by the same second pass
-        bool fc16 = false;
-        const int ks_fc = a2b16 ? ks16 : ((fc16_on && g->conv_f16 && g->Bfch) ? dcs_gemm_f16_longk_slices(ctx, (int)n, g->flat_p, g->hid64) : 0);
-        if (ks_fc >= 2 && g->Bfch && ctx->gemm_ws.ensure((size_t)ks_fc * n * g->hid64 * sizeof(float)) == DCS_OK) {
-            DcsTimer tm(ctx, DCS_TAG_FC);
-            fc16 = a2b16 ? dcs_launch_gemm_f16_longk(ctx, a2b, pitch16, (int)n, pitch16, g->hid64, g->Bfch, (float*)ctx->gemm_ws.ptr, true)
-                         : dcs_launch_gemm_f16_longk(ctx, a2b, g->flat_p, (int)n, g->flat_p, g->hid64, g->Bfch, (float*)ctx->gemm_ws.ptr, false);
-            if (fc16) {
-                DcsGemm r = q;
-                r.partial = (float*)ctx->gemm_ws.ptr;
-                dcs_launch_gemm_longk_reduce(ctx, r, ks_fc);
-                tm.done();
-            } else
-                tm.cancel();
-        }
-        if (a2b16 && !fc16) DCS_FAIL(DCS_EHIP, "generic graph: conv2 wrote an f16 map and the f16 bottleneck layer refused it");
-        if (!fc16) DCS_CHECK(dcs_launch_gemm_rows(ctx, q, DCS_TAG_FC));
+    // 128 .. 176 tiles against a very long K (166 650 for the Bach10 graphs): the all-rows bf16 x 3 kernel with K cut into
+    // slices (dcs_launch_gemm_bf16x3_longk) -- the planes (1.5 x the f32 weights; unsplit 32-byte pieces since round 6: the
+    // long-K launch is the all-rows kernel) are made on first need; without them, or for any other row count, the f32 K-split
+    // of gemm.hip.  (Under the f16 switch the layer takes the f16 plane below instead.)
+    if (!h.fold2 && env().gemm_bf16 && n >= 128 && n <= 176 && g->flat_p >= 16384 && (g->hid64 % 128) == 0 &&
+        (!g->conv_f16 || g->bfch_failed))
+        DCS_CHECK(pack_once(&g->bfcq_failed, [&](void* p, void*) { return dcs_gemm_pack_b32(ctx, g->Bfc, g->flat_p, g->hid64, g->hid64, p); },
+                            &g->Bfcq, dcs_gemm_b32_bytes(g->flat_p, g->hid64), "generic.Bfcq"));
+    q.Bq = h.fold2 ? nullptr : g->Bfcq;
+    q.bq_f32 = 1;
+    // f16 switch: the same long-K launch on f16 weights (gemm_f16.hip: one plane, 2 bytes per weight instead of 6); the rows
+    // of A are conv2's f16 map (a2_f16) or, when conv2 could not write it, f32 rows split into two f16 terms on their way into
+    // LDS; the slices are added by the same second pass
+    const int pitch16 = pitch16_of(d);
+    bool fc16 = false;
+    const int ks_fc = h.a2_f16 ? dcs_gemm_f16_longk_slices(ctx, (int)n, pitch16, g->hid64)
+                               : ((env().gemm_bf16 && g->conv_f16 && g->Bfch) ? dcs_gemm_f16_longk_slices(ctx, (int)n, g->flat_p, g->hid64) : 0);
+    if (ks_fc >= 2 && g->Bfch && ctx->gemm_ws.ensure((size_t)ks_fc * n * g->hid64 * sizeof(float)) == DCS_OK) {
+        DcsTimer tm(ctx, DCS_TAG_FC);
+        fc16 = h.a2_f16 ? dcs_launch_gemm_f16_longk(ctx, k.a2b, pitch16, (int)n, pitch16, g->hid64, g->Bfch, (float*)ctx->gemm_ws.ptr, true)
+                        : dcs_launch_gemm_f16_longk(ctx, k.a2b, g->flat_p, (int)n, g->flat_p, g->hid64, g->Bfch, (float*)ctx->gemm_ws.ptr, false);
+        if (fc16) {
+            DcsGemm r = q;
+            r.partial = (float*)ctx->gemm_ws.ptr;
+            dcs_launch_gemm_longk_reduce(ctx, r, ks_fc);
+            tm.done();
+        } else
+            tm.cancel();
     }
-    // per-source dense (rectify): D[n][branch][flat_p]; aliased branches (none in these graphs) would reuse a layer
+    if (h.a2_f16 && !fc16) DCS_FAIL(DCS_EHIP, "generic graph: conv2 wrote an f16 map and the f16 bottleneck layer refused it");
+    if (!fc16) DCS_CHECK(dcs_launch_gemm_rows(ctx, q, DCS_TAG_FC));
+    return DCS_OK;
+}
+
+// per-source dense (rectify): Z -> D[n][branch][flat_p]; aliased branches (none in these graphs) would reuse a layer
+int dense_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
+    const DcsGenericDims& d = g->d;
+    dcs_ctx* ctx = g->ctx;
+    const int64_t n = k.n;
+    const int NB = k.NB;
     if (g->flat_p != d.flat)
         hipLaunchKernelGGL(zero_pad_cols_kernel, dim3((unsigned)dcs_cdiv(n * NB * (g->flat_p - d.flat), kThreads)), dim3(kThreads), 0,
-                           ctx->stream, D, n * NB, d.flat, g->flat_p);
+                           ctx->stream, k.D, n * NB, d.flat, g->flat_p);
     // Will both InverseLayers run as ONE kernel (Bach10 graph with the f16 switch)?  Known before the dense layers run, and it
     // decides their output layout: the fused decoder reads a position's channels together, so D is written CHANNELS-LAST
     // ([branch][row][x][channel]) by packing the bf16 planes of the dense weights with permuted columns (DCS_DECODER_CL=0:
@@ -2012,62 +1960,50 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
     // block); that kernel takes the channels-last layout only, so it is planned when the layout can be had.
     bool fuse_planned = false, fuse_x3 = false;
     const bool want_cl = plans_channels_last(g, &fuse_planned, &fuse_x3);
+    h.d_layout = kChannelFirst;
     // f16 switch, fused decoder, 128 .. 176 tiles, one input channel: the per-source dense layers on f16 weights with an f16,
     // channels-last (32 channels per position) output -- gemm_f16.hip: 2 bytes per weight instead of 6, and D written and read
     // at half the size.  The planes (0.36 GB for Bach10) are made on first need; if they do not fit, the f32-class path stays.
     // (same-box A/B against the f32-class dense layers in front of the same decoder: profiles/r06_f_bach10_f16_dense_legs_ab.txt)
-    bool dense16 = false, d_cl = false;
-    if (g->conv_f16 && fuse_planned && !fuse_x3 && want_cl && C == 1 && n >= 128 && n <= 176 && !g->bdh_failed &&
+    if (g->conv_f16 && fuse_planned && !fuse_x3 && want_cl && g->C == 1 && n >= 128 && n <= 176 && !g->bdh_failed &&
         (g->hid64 & 31) == 0) {
         const int npos = d.h2 * d.w2;
         const int n_out = (int)dcs_round_up((int64_t)npos * 32, 128);
         g->n_out16 = n_out;
         for (int b = 0; b < NB && !g->bdh_failed; ++b) {
-            const int s2 = d.branch_fc[b];
-            if (g->Bdh[s2]) continue;
-            void* planes = nullptr;
-            float* bias_h = nullptr;
-            if (dcs_dev_alloc(&planes, dcs_gemm_bh_bytes(g->hid64, n_out), "generic.Bdh") != hipSuccess ||
-                dcs_dev_alloc((void**)&bias_h, (size_t)n_out * 4, "generic.biasd_h") != hipSuccess) {
-                (void)hipGetLastError();
-                dcs_dev_free(planes);
-                g->bdh_failed = true;
-                break;
-            }
-            int rc = dcs_gemm_pack_bh(ctx, g->Bd[s2], g->hid64, g->flat64, n_out, d.nf2, npos, 32, planes);
-            if (rc == DCS_OK) rc = dcs_gemm_pack_bias_cl(ctx, g->biasd[s2], n_out, d.nf2, npos, 32, bias_h);
-            if (rc != DCS_OK) {
-                dcs_dev_free(planes);
-                dcs_dev_free(bias_h);
-                return rc;
-            }
-            g->Bdh[s2] = planes;                         // published only when packed
-            g->biasd_h[s2] = bias_h;
+            const int s = d.branch_fc[b];
+            auto pack = [&](void* planes, void* bias) {
+                const int rc = dcs_gemm_pack_bh(ctx, g->Bd[s], g->hid64, g->flat64, n_out, d.nf2, npos, 32, planes);
+                return rc != DCS_OK ? rc : dcs_gemm_pack_bias_cl(ctx, g->biasd[s], n_out, d.nf2, npos, 32, static_cast<float*>(bias));
+            };
+            DCS_CHECK(pack_once(&g->bdh_failed, pack, &g->Bdh[s], dcs_gemm_bh_bytes(g->hid64, n_out), "generic.Bdh", &g->biasd_h[s],
+                                (size_t)n_out * 4, "generic.biasd_h"));
         }
         if (!g->bdh_failed) {
             const void* bh[4] = {nullptr, nullptr, nullptr, nullptr};
             const float* bs[4] = {nullptr, nullptr, nullptr, nullptr};
             void* cs[4] = {nullptr, nullptr, nullptr, nullptr};
             for (int b = 0; b < NB; ++b) {
-                const int s2 = d.branch_fc[b];
-                bh[b] = g->Bdh[s2]; bs[b] = g->biasd_h[s2];
-                cs[b] = reinterpret_cast<_Float16*>(D) + (int64_t)b * n_out;      // D16[tile][branch][position][32]
+                const int s = d.branch_fc[b];
+                bh[b] = g->Bdh[s]; bs[b] = static_cast<const float*>(g->biasd_h[s]);
+                cs[b] = reinterpret_cast<_Float16*>(k.D) + (int64_t)b * n_out;      // D16[tile][branch][position][32]
             }
             DcsTimer tm(ctx, DCS_TAG_FC1X);
-            dense16 = dcs_launch_gemm_f16_skinny(ctx, Z, g->hid64, (int)n, g->hid64, n_out, NB, bh, bs, cs, (int64_t)NB * n_out, Zq);
-            if (dense16) tm.done(); else tm.cancel();
-            d_cl = dense16;
+            if (dcs_launch_gemm_f16_skinny(ctx, k.Z, g->hid64, (int)n, g->hid64, n_out, NB, bh, bs, cs, (int64_t)NB * n_out, k.Zq)) {
+                tm.done();
+                h.d_layout = kChannelsLastF16;
+                return DCS_OK;
+            }
+            tm.cancel();
         }
     }
-    if (!dense16) {
     // the bf16 planes of the dense weights, on first need: a launch of >= 128 rows against >= 1024 columns (smaller ones stay
-    // on the f32 kernels whatever is packed, dcs_launch_gemm_bf16x3); same stream, so no synchronisation
-    static const bool bf16_on = !(getenv("DCS_GEMM_BF16") && atoi(getenv("DCS_GEMM_BF16")) == 0);
+    // on the f32 kernels whatever is packed, dcs_launch_gemm_bf16x3)
     // (same-box A/B against the planes: Bach10 fc1x 0.396 -> 0.352 ms, profiles/r06_m_unsplit_weight_pieces_legs_ab.txt)
     const bool win = n <= 176;                           // the all-rows kernel's window: unsplit pieces (Bd32), else planes (Bdq)
     void** store = win ? g->Bd32 : g->Bdq;
     bool& store_cl = win ? g->bd32_cl : g->bdq_cl;
-    if (bf16_on && n >= 128 && g->flat64 >= 1024) {
+    if (env().gemm_bf16 && n >= 128 && g->flat64 >= 1024) {
         const int rows = (int)dcs_round_up(g->hid64, 128);
         const int pc = want_cl ? d.nf2 : 0, pp = want_cl ? d.h2 * d.w2 : 0;
         auto pack = [&](const float* B, void* dst) {
@@ -2077,197 +2013,213 @@ int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_tot
         if (store_cl != want_cl) {
             // the precision switch was flipped since the weights were packed: the existing blocks are re-packed in place, in
             // the other column order (stream-ordered behind every earlier use)
-            for (int s2 = 0; s2 < d.n_fc; ++s2)
-                if (store[s2]) DCS_CHECK(pack(g->Bd[s2], store[s2]));
+            for (int s = 0; s < d.n_fc; ++s)
+                if (store[s]) DCS_CHECK(pack(g->Bd[s], store[s]));
             store_cl = want_cl;
         }
-        for (int s2 = 0; s2 < d.n_fc && !g->bdq_failed; ++s2) {
-            if (store[s2]) continue;
-            // published only when packed: a failed pack must not leave a non-null, unpacked block behind (later calls
-            // would multiply by uninitialised memory).  Out of memory here (~0.7 GB for Bach10, outside the chunk budget) is
-            // not an error of the forward pass: the layer stays on the f32 GEMM (q.Bq == nullptr) for the model's lifetime.
-            void* planes = nullptr;
-            if (dcs_dev_alloc(&planes, win ? dcs_gemm_b32_bytes(rows, g->flat64) : dcs_gemm_bq_bytes(rows, g->flat64),
-                              win ? "generic.Bd32" : "generic.Bdq") != hipSuccess) {
-                (void)hipGetLastError();
-                g->bdq_failed = true;
-                break;
-            }
-            const int rc = pack(g->Bd[s2], planes);
-            if (rc != DCS_OK) {
-                dcs_dev_free(planes);
-                return rc;
-            }
-            store[s2] = planes;
-        }
+        // (~0.7 GB for Bach10, outside the chunk budget; one flag for both stores)
+        for (int s = 0; s < d.n_fc && !g->bdq_failed; ++s)
+            DCS_CHECK(pack_once(&g->bdq_failed, [&](void* p, void*) { return pack(g->Bd[s], p); }, &store[s],
+                                win ? dcs_gemm_b32_bytes(rows, g->flat64) : dcs_gemm_bq_bytes(rows, g->flat64),
+                                win ? "generic.Bd32" : "generic.Bdq"));
     }
     // planes in channels-last order serve the all-branches launch below and nothing else: a launch that falls back to the
     // per-branch GEMMs runs them on the f32 weights (channel-first), and the decoder is told which layout it got
     const bool planes_cl = store_cl;
-    bool branches_done = false;
     if (NB > 1 || want_cl) {                             // every live branch in one launch when the shape allows it
-        DcsGemm q{};
-        q.A = Z; q.lda = g->hid64; q.a_gdiv = 1 << 30; q.a_gmul = 0; q.a_scale = 1.f;
-        q.ldb = g->flat64; q.ldc = (int64_t)NB * g->flat_p; q.c_gdiv = 1 << 30; q.c_gmul = 0;
-        q.M = n; q.n_cols = g->flat64; q.n_store = d.flat; q.K = g->hid64; q.relu = 1; q.a_vec = 1;
+        DcsGemm q = dense_gemm(g, k.Z, k.D, n, NB, 0);
         DcsGemmBranches br{};
         br.n = NB;
         for (int b = 0; b < NB; ++b) {
             const int s = d.branch_fc[b];
-            br.Bq[b] = store[s]; br.bias[b] = planes_cl ? g->biasd_cl[s] : g->biasd[s]; br.C[b] = D + (int64_t)b * g->flat_p;
+            br.Bq[b] = store[s]; br.bias[b] = planes_cl ? g->biasd_cl[s] : g->biasd[s]; br.C[b] = k.D + (int64_t)b * g->flat_p;
         }
-        q.B = g->Bd[d.branch_fc[0]]; q.bias = br.bias[0]; q.Bq = br.Bq[0]; q.C = br.C[0]; q.bq_f32 = win ? 1 : 0;
+        q.bias = br.bias[0]; q.Bq = br.Bq[0]; q.bq_f32 = win ? 1 : 0;
         DcsTimer tm(ctx, DCS_TAG_FC1X);
         // the launch below takes the all-rows kernel: split Z once for all its workgroups (several branches: 0.413 -> 0.392 ms for
         // Bach10; with one branch the extra launch costs what it saves)
         if (NB > 1 && n >= 128 && n <= 176 && br.Bq[0]) {
             const int rows_pad = n <= 128 ? 128 : 176;
-            DCS_CHECK(dcs_gemm_split_a(ctx, Z, g->hid64, n, g->hid64, rows_pad, Zq));
-            q.Aq = Zq; q.aq_rows = rows_pad;
+            DCS_CHECK(dcs_gemm_split_a(ctx, k.Z, g->hid64, n, g->hid64, rows_pad, k.Zq));
+            q.Aq = k.Zq; q.aq_rows = rows_pad;
         }
-        branches_done = dcs_launch_gemm_bf16x3_skinny(ctx, q, &br);
-        if (branches_done) tm.done(); else tm.cancel();
+        if (dcs_launch_gemm_bf16x3_skinny(ctx, q, &br)) {
+            tm.done();
+            if (planes_cl) h.d_layout = kChannelsLastF32;
+            return DCS_OK;
+        }
+        tm.cancel();
     }
-    d_cl = branches_done && planes_cl;                   // layout of D as the decoder will find it
-    for (int b = 0; b < NB && !branches_done; ++b) {
-        const int s = d.branch_fc[b];
-        DcsGemm q{};
-        q.A = Z; q.lda = g->hid64; q.a_gdiv = 1 << 30; q.a_gmul = 0; q.a_scale = 1.f;
-        q.B = g->Bd[s]; q.ldb = g->flat64; q.bias = g->biasd[s]; q.Bq = planes_cl ? nullptr : store[s]; q.bq_f32 = win ? 1 : 0;
-        q.C = D + (int64_t)b * g->flat_p; q.ldc = (int64_t)NB * g->flat_p; q.c_gdiv = 1 << 30; q.c_gmul = 0;
-        q.M = n; q.n_cols = g->flat64; q.n_store = d.flat; q.K = g->hid64; q.relu = 1; q.a_vec = 1;
+    for (int b = 0; b < NB; ++b) {
+        DcsGemm q = dense_gemm(g, k.Z, k.D, n, NB, b);
+        q.Bq = planes_cl ? nullptr : store[d.branch_fc[b]]; q.bq_f32 = win ? 1 : 0;
         DCS_CHECK(dcs_launch_gemm_rows(ctx, q, DCS_TAG_FC1X));
     }
-    }
+    return DCS_OK;
+}
+
+// the decoder: both InverseLayers as one kernel, or InverseLayer(conv2), InverseLayer(pool) and InverseLayer(conv1)
+int decoder_stage(DcsGenericNet* g, const Chunk& k, const Handoff& h) {
+    const DcsGenericDims& d = g->d;
+    dcs_ctx* ctx = g->ctx;
+    const int C = g->C, tc = g->tc, F = g->F, NB = k.NB;
+    const int64_t n = k.n, planep = (int64_t)tc * d.wp;
+    const bool dense16 = h.d_layout == kChannelsLastF16, d_cl = h.d_layout != kChannelFirst;
     // InverseLayer(., conv2): [n*NB, nf2, h2, w2] -> [n*NB, nf1, tc, wp]
-    bool decoder_fused = false;
+    IgemmArgs a{};
+    a.in = k.D; a.in_n_stride = g->flat_p; a.Cin = d.nf2; a.H = d.h2; a.W = d.w2;
+    a.Wm = g->W2t; a.koff = g->kt_off; a.kuv = g->kt_uv; a.bias = g->bias0;
+    a.out = k.g2; a.out_n_stride = (int64_t)d.nf1 * planep; a.Cout = d.nf1; a.Ho = tc; a.Wo = d.wp;
+    a.ph = d.kh2 - 1; a.pw = d.kw2 - 1; a.K = g->K2; a.M = n * NB * planep;
+    a.kh = d.kh2; a.k_per_u = d.nf2 * d.kw2;
+    ColConvArgs c{};
+    bool fused = false;
+    if (g->use_colconv) {
+        c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
+        c.Wk = g->Wcol_t; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride; c.Cout = a.Cout; c.Ho = a.Ho;
+        c.ph = d.kh2 - 1; c.kh = d.kh2; c.n_xb = (c.W + 15) / 16;
+        bool fuse_x3 = false;
+        plans_channels_last(g, nullptr, &fuse_x3);
+        fused = g->conv_f16 ? (C == 1 && g->W1q && g->Wcol_t_r && dcs_decoder_fused_ok(c, F))
+                            : (fuse_x3 && d_cl);       // f32-class: only on the channels-last layout
+        if (dense16) {
+            if (!fused) DCS_FAIL(DCS_EHIP, "generic graph: f16 dense output planned without the fused decoder");
+            c.in_n_stride = g->n_out16;                    // halves: D16[image = tile * NB + branch][position][32]
+        }
+    }
+    if (d_cl && !fused) {
+        // cannot happen while the plan above and the launch conditions agree (the layout is only asked for when the fused
+        // decoder is planned); if they ever disagree, redo the dense layers channel-first on the f32 weights instead of
+        // failing the call: every other consumer takes that layout
+        for (int b = 0; b < NB; ++b) DCS_CHECK(dcs_launch_gemm_rows(ctx, dense_gemm(g, k.Z, k.D, n, NB, b), DCS_TAG_FC1X));
+    }
+    if (fused) {   // both InverseLayers in one kernel: o directly (the fused decoder is made for graphs without a pool layer)
+        DcsTimer tm(ctx, DCS_TAG_DECODER);
+        const bool ok = g->conv_f16 ? dcs_launch_decoder_fused(ctx, c, n * NB, g->Wcol_t_r, g->W1q, k.o, F, d_cl, dense16)
+                                    : dcs_launch_decoder_x3(ctx, c, n * NB, g->Wx3, g->W1q, k.o, F, C);
+        tm.done();
+        if (!ok) DCS_FAIL(DCS_EHIP, "generic graph: the fused decoder refused a launch it had accepted (channels-last %d)", (int)d_cl);
+        return DCS_OK;
+    }
     {
-        IgemmArgs a{};
-        a.in = D; a.in_n_stride = g->flat_p; a.Cin = d.nf2; a.H = d.h2; a.W = d.w2;
-        a.Wm = g->W2t; a.koff = g->kt_off; a.kuv = g->kt_uv; a.bias = g->bias0;
-        a.out = g2; a.out_n_stride = (int64_t)d.nf1 * planep; a.Cout = d.nf1; a.Ho = tc; a.Wo = d.wp;
-        a.ph = d.kh2 - 1; a.pw = d.kw2 - 1; a.K = g->K2; a.M = n * NB * planep;
-        a.kh = d.kh2; a.k_per_u = d.nf2 * d.kw2;
-        ColConvArgs c{};
-        if (g->use_colconv) {
-            c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
-            c.Wk = g->Wcol_t; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride; c.Cout = a.Cout; c.Ho = a.Ho;
-            c.ph = d.kh2 - 1; c.kh = d.kh2; c.n_xb = (c.W + 15) / 16;
-            decoder_fused = g->conv_f16 ? (C == 1 && g->W1q && g->Wcol_t_r && dcs_decoder_fused_ok(c, F))
-                                        : (fuse_x3 && d_cl);       // f32-class: only on the channels-last layout
-            if (dense16) {
-                if (!decoder_fused) DCS_FAIL(DCS_EHIP, "generic graph: f16 dense output planned without the fused decoder");
-                c.in_n_stride = g->n_out16;                    // halves: D16[image = tile * NB + branch][position][32]
-            }
-        }
-        if (d_cl && !decoder_fused) {
-            // cannot happen while the plan above and the launch conditions agree (the layout is only asked for when the fused
-            // decoder is planned); if they ever disagree, redo the dense layers channel-first on the f32 weights instead of
-            // failing the call: every other consumer takes that layout
-            for (int b = 0; b < NB; ++b) {
-                const int s = d.branch_fc[b];
-                DcsGemm q{};
-                q.A = Z; q.lda = g->hid64; q.a_gdiv = 1 << 30; q.a_gmul = 0; q.a_scale = 1.f;
-                q.B = g->Bd[s]; q.ldb = g->flat64; q.bias = g->biasd[s]; q.Bq = nullptr;
-                q.C = D + (int64_t)b * g->flat_p; q.ldc = (int64_t)NB * g->flat_p; q.c_gdiv = 1 << 30; q.c_gmul = 0;
-                q.M = n; q.n_cols = g->flat64; q.n_store = d.flat; q.K = g->hid64; q.relu = 1; q.a_vec = 1;
-                DCS_CHECK(dcs_launch_gemm_rows(ctx, q, DCS_TAG_FC1X));
-            }
-        }
-        if (decoder_fused) {                                 // both InverseLayers in one kernel: o directly
-            DcsTimer tmf(ctx, DCS_TAG_DECODER);
-            const bool ok = g->conv_f16 ? dcs_launch_decoder_fused(ctx, c, n * NB, g->Wcol_t_r, g->W1q, o, F, d_cl, dense16)
-                                        : dcs_launch_decoder_x3(ctx, c, n * NB, g->Wx3, g->W1q, o, F, C);
-            tmf.done();
-            if (!ok) DCS_FAIL(DCS_EHIP, "generic graph: the fused decoder refused a launch it had accepted (channels-last %d)", (int)d_cl);
-        }
-        DcsTimer tm(ctx, decoder_fused ? -1 : DCS_TAG_DECONV2);
-        if (decoder_fused) {
-        } else if (g->use_colconv) {
+        DcsTimer tm(ctx, DCS_TAG_DECONV2);
+        if (g->use_colconv)
             DCS_CHECK(launch_colconv(ctx, c, n * NB, g->conv_f16 ? g->Wcol_t_h : nullptr, g->Wcol_t_r, g->Wpc_t_q3));
-        } else if (g->conv_f16 && !(g->use_slabconv && !kF16Igemm))
-            hipLaunchKernelGGL(conv_igemm_f16_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a,
-                               g->W2t_h);
-        else {
-            bool done = false;
-            if (g->use_slabconv) {
-                SlabConvArgs c{};
-                c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
-                c.Wk = g->Wslab_t; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride;
-                c.Cout = a.Cout; c.Ho = a.Ho; c.Wo = a.Wo; c.kh = d.kh2; c.kw = d.kw2; c.ph = d.kh2 - 1; c.pw = d.kw2 - 1;
-                done = launch_slabconv(ctx, c, n * NB, kSlabMx ? (g->conv_f16 ? g->Wslab_t_h : g->Wslab_t_q3) : nullptr,
-                                       g->conv_f16 ? 1 : 0, g->conv_f16 ? g->Wps_t_h : g->Wps_t_q3);
-            }
-            if (!done)
-                hipLaunchKernelGGL(conv_igemm_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a);
-        }
+        else
+            launch_conv2_general(g, a, n * NB, true);
         tm.done();
     }
+    const bool fused_pool = pool_fused(g);
+    const unsigned* pool_bits = reinterpret_cast<const unsigned*>(k.a1b);
     // InverseLayer(., pool)
-    if (d.pool_w && !pool_fused) {
+    if (d.pool_w && !fused_pool) {
         DcsTimer tm(ctx, DCS_TAG_UNPOOL);
         const int64_t rows_g = n * NB * d.nf1 * tc;
         if (d.pool_w != 4 || rows_g > 0x7fffffff) DCS_FAIL(DCS_EUNSUPPORTED, "un-pool: pool width %d, %lld rows", d.pool_w, (long long)rows_g);
         hipLaunchKernelGGL((unpool_kernel<4>), dim3((unsigned)dcs_cdiv(rows_g, 4)), dim3(kThreads), 0,
-                           ctx->stream, g2, a1b, g1, (unsigned)rows_g, (unsigned)(d.nf1 * tc), (unsigned)NB, d.w1, d.wp,
-                           tie_mode == DCS_TIE_FIRST ? 1 : 0);
+                           ctx->stream, k.g2, k.a1b, k.g1, (unsigned)rows_g, (unsigned)(d.nf1 * tc), (unsigned)NB, d.w1, d.wp,
+                           k.tie_mode == DCS_TIE_FIRST ? 1 : 0);
         tm.done();
     }
     // InverseLayer(., conv1): [n*NB, nf1, tc, w1] -> [n*NB, C, tc, F] = [n, NB*C, tc, F]
-    if (!decoder_fused) {
-        const int span = kThreads / d.sw1 + d.kw1 / d.sw1 + 3;
-        const size_t lds = ((size_t)d.nf1 * C * d.kw1 + (size_t)d.nf1 * span) * 4;
-        auto kern = deconv1_kernel<30>;
-        if (lds > 48 * 1024)
-            DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds));
-        DcsTimer tm(ctx, DCS_TAG_FINAL);
-        static const int reg_env = getenv("DCS_DECONV1_REG") ? atoi(getenv("DCS_DECONV1_REG")) : 1;
-        if (pool_fused) {   // un-pool + conv1^T: reads the pooled gradient and the routing bits
-            const int nqb = (F + 11) / 12;
-            hipLaunchKernelGGL((deconv1_reg_kernel<3, 10, true>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
-                               dim3(kThreads), 0, ctx->stream, g2, g->W1p, o, d.nf1, C, tc, F, d.w1, nqb, pool_bits, d.wp, pool_mw, NB);
-        } else if (g->W1dq && dcs_launch_deconv1_mfma(ctx, g1, g->W1dq, o, n * NB, d.nf1, C, tc, F, d.w1)) {
-        } else if (g->W1p && reg_env && d.sw1 == 3 && (d.kw1 + 2) / 3 == 10) {
-            const int nqb = (F + 11) / 12;
-            hipLaunchKernelGGL((deconv1_reg_kernel<3, 10>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
-                               dim3(kThreads), 0, ctx->stream, g1, g->W1p, o, d.nf1, C, tc, F, d.w1, nqb);
-        } else if (g->W1p && reg_env && d.sw1 == 4 && (d.kw1 + 3) / 4 == 8) {
-            const int nqb = (F + 15) / 16;
-            hipLaunchKernelGGL((deconv1_reg_kernel<4, 8>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
-                               dim3(kThreads), 0, ctx->stream, g1, g->W1p, o, d.nf1, C, tc, F, d.w1, nqb);
-        } else {
-            hipLaunchKernelGGL(kern, dim3((unsigned)dcs_cdiv(F, kThreads), (unsigned)(n * NB * tc)), dim3(kThreads), lds,
-                               ctx->stream, g1, g->W1c, o, C, tc, F, d.kw1, d.sw1, d.w1);
-        }
-        tm.done();
-    }
-    // concat + bias + rectify + mask.  out is [S or CH][n_total][tc][F]; this chunk starts at tile k_first.
-    if (mask_mode < 0) {                                 // deferred to mask_ola_kernel (single chunk): o stays in scratch
-        g->raw_o = o;
-        g->raw_ch = NB * C;
+    const int span = kThreads / d.sw1 + d.kw1 / d.sw1 + 3;
+    const size_t lds = ((size_t)d.nf1 * C * d.kw1 + (size_t)d.nf1 * span) * 4;
+    auto kern = deconv1_kernel<30>;
+    if (lds > 48 * 1024)
+        DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds));
+    DcsTimer tm(ctx, DCS_TAG_FINAL);
+    if (fused_pool) {   // un-pool + conv1^T: reads the pooled gradient and the routing bits
+        const int nqb = (F + 11) / 12;
+        hipLaunchKernelGGL((deconv1_reg_kernel<3, 10, true>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
+                           dim3(kThreads), 0, ctx->stream, k.g2, g->W1p, k.o, d.nf1, C, tc, F, d.w1, nqb, pool_bits, d.wp,
+                           pool_words(d), NB);
+    } else if (g->W1dq && dcs_launch_deconv1_mfma(ctx, k.g1, g->W1dq, k.o, n * NB, d.nf1, C, tc, F, d.w1)) {
+    } else if (g->W1p && env().deconv1_reg && d.sw1 == 3 && (d.kw1 + 2) / 3 == 10) {
+        const int nqb = (F + 11) / 12;
+        hipLaunchKernelGGL((deconv1_reg_kernel<3, 10>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
+                           dim3(kThreads), 0, ctx->stream, k.g1, g->W1p, k.o, d.nf1, C, tc, F, d.w1, nqb);
+    } else if (g->W1p && env().deconv1_reg && d.sw1 == 4 && (d.kw1 + 3) / 4 == 8) {
+        const int nqb = (F + 15) / 16;
+        hipLaunchKernelGGL((deconv1_reg_kernel<4, 8>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
+                           dim3(kThreads), 0, ctx->stream, k.g1, g->W1p, k.o, d.nf1, C, tc, F, d.w1, nqb);
     } else {
-        const int64_t plane = (int64_t)tc * F;
-        const int CH = NB * C;
-        DcsTimer tm(ctx, DCS_TAG_MASK);
-        // the kernel indexes out as [ch][n][plane] with n = chunk size; point it at the chunk and pass the
-        // total tile count as the channel stride through a strided launch: do it per channel group instead
-        // -> simplest exact form: launch with n_total as `n` stride when the chunk is the whole batch.
-        if (n == n_total) {
-            hipLaunchKernelGGL(mask_kernel, dim3((unsigned)dcs_cdiv(n * plane, kThreads)), dim3(kThreads), 0, ctx->stream,
-                               o, g->bout, tiles, out, n, CH, d.S, C, plane, mask_mode, g->mix_sum ? C : 1);
-        } else {
-            // chunked batch: write into a compact [ch][n][plane] staging area, then scatter rows
-            float* stage = (float*)w;
-            const int nch = mask_mode == 2 ? CH : d.S;
-            hipLaunchKernelGGL(mask_kernel, dim3((unsigned)dcs_cdiv(n * plane, kThreads)), dim3(kThreads), 0, ctx->stream,
-                               o, g->bout, tiles, stage, n, CH, d.S, C, plane, mask_mode, g->mix_sum ? C : 1);
-            for (int ch = 0; ch < nch; ++ch)
-                DCS_HIP(hipMemcpyAsync(out + ((int64_t)ch * n_total + k_first) * plane, stage + (int64_t)ch * n * plane,
-                                       (size_t)n * plane * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        tm.done();
+        hipLaunchKernelGGL(kern, dim3((unsigned)dcs_cdiv(F, kThreads), (unsigned)(n * NB * tc)), dim3(kThreads), lds,
+                           ctx->stream, k.g1, g->W1c, k.o, C, tc, F, d.kw1, d.sw1, d.w1);
     }
+    tm.done();
+    return DCS_OK;
+}
+
+// concat + bias + rectify + mask.  out is [S or CH][n_total][tc][F]; this chunk starts at tile k_first.
+int mask_stage(DcsGenericNet* g, const Chunk& k) {
+    const DcsGenericDims& d = g->d;
+    dcs_ctx* ctx = g->ctx;
+    const int C = g->C, CH = k.NB * C;
+    const int64_t n = k.n;
+    if (k.mask_mode < 0) {                               // deferred to mask_ola_kernel (single chunk): o stays in scratch
+        g->raw_o = k.o;
+        g->raw_ch = CH;
+        return DCS_OK;
+    }
+    const int64_t plane = (int64_t)g->tc * g->F;
+    DcsTimer tm(ctx, DCS_TAG_MASK);
+    // the kernel indexes out as [ch][n][plane] with n = chunk size; point it at the chunk and pass the
+    // total tile count as the channel stride through a strided launch: do it per channel group instead
+    // -> simplest exact form: launch with n_total as `n` stride when the chunk is the whole batch.
+    if (n == k.n_total) {
+        hipLaunchKernelGGL(mask_kernel, dim3((unsigned)dcs_cdiv(n * plane, kThreads)), dim3(kThreads), 0, ctx->stream,
+                           k.o, g->bout, k.tiles, k.out, n, CH, d.S, C, plane, k.mask_mode, g->mix_sum ? C : 1);
+    } else {
+        // chunked batch: write into a compact [ch][n][plane] staging area, then scatter rows
+        float* stage = (float*)k.stage;
+        const int nch = k.mask_mode == 2 ? CH : d.S;
+        hipLaunchKernelGGL(mask_kernel, dim3((unsigned)dcs_cdiv(n * plane, kThreads)), dim3(kThreads), 0, ctx->stream,
+                           k.o, g->bout, k.tiles, stage, n, CH, d.S, C, plane, k.mask_mode, g->mix_sum ? C : 1);
+        for (int ch = 0; ch < nch; ++ch)
+            DCS_HIP(hipMemcpyAsync(k.out + ((int64_t)ch * k.n_total + k.k_first) * plane, stage + (int64_t)ch * n * plane,
+                                   (size_t)n * plane * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    tm.done();
+    return DCS_OK;
+}
+
+// one chunk of tiles through the graph; scratch carved from `w`
+int forward_chunk(DcsGenericNet* g, const float* tiles, int64_t n, int64_t n_total, int64_t k_first, int mask_mode,
+                  int tie_mode, float* out, char* w) {
+    const DcsGenericDims& d = g->d;
+    const int C = g->C, tc = g->tc, F = g->F;
+    Chunk k{};
+    k.tiles = tiles; k.n = n; k.n_total = n_total; k.k_first = k_first; k.mask_mode = mask_mode; k.tie_mode = tie_mode; k.out = out;
+    // Branches that reach the requested output.  The masks use the first S output channels (prediction2[:, 0:S]); with C
+    // input channels per branch those belong to the first ceil(S / C) branches -- for the score-informed graph (C = 4,
+    // S = 4) branch 0 alone: the other three branches of its decoder are dead code for predict_function2
+    // (bach10_scoreinformed/separate_bach10.py:475-488; Theano prunes them from the compiled function as well).
+    // dcs_model_forward (mask_mode 2: the whole network output) evaluates all of them.
+    k.NB = mask_mode == 2 ? d.n_branch : (d.S + C - 1) / C < d.n_branch ? (d.S + C - 1) / C : d.n_branch;
+    const int64_t plane1 = (int64_t)tc * d.w1, planep = (int64_t)tc * d.wp;
+    auto take = [&w](size_t bytes) {
+        char* p = w;
+        w += align256(bytes);
+        return p;
+    };
+    k.a1b = (float*)take((size_t)n * d.nf1 * plane1 * 4);
+    k.p1 = d.pool_w ? (float*)take((size_t)n * d.nf1 * planep * 4) : k.a1b;
+    k.a2b = (float*)take((size_t)n * g->flat_p * 4);
+    k.Z = (float*)take((size_t)n * g->hid64 * 4);
+    k.Zq = take(dcs_gemm_aq_bytes(g->hid64, 176));
+    k.D = (float*)take((size_t)n * k.NB * g->flat_p * 4);
+    k.g2 = (float*)take((size_t)n * k.NB * d.nf1 * planep * 4);
+    k.g1 = d.pool_w ? (float*)take((size_t)n * k.NB * d.nf1 * plane1 * 4) : k.g2;
+    k.o = (float*)take((size_t)n * k.NB * C * tc * F * 4);
+    k.stage = w;
+    Handoff h;
+    DCS_CHECK(conv1_stage(g, k, h));
+    DCS_CHECK(conv2_stage(g, k, h));
+    DCS_CHECK(bottleneck_stage(g, k, h));
+    DCS_CHECK(dense_stage(g, k, h));
+    DCS_CHECK(decoder_stage(g, k, h));
+    DCS_CHECK(mask_stage(g, k));
     DCS_HIP(hipGetLastError());
     return DCS_OK;
 }
@@ -2307,7 +2259,7 @@ int dcs_generic_forward(DcsGenericNet* g, const float* tiles, int64_t n, int mas
     if (!g) DCS_FAIL(DCS_EINVAL, "generic forward: null network");
     // Tiles go through the graph in chunks that bound the scratch (the Bach10 graph needs ~13 MB per tile) at 4 GiB of
     // the 288 GB: every chunk re-reads the dense weights (170 MB + 4 x 170 MB for Bach10), so few large chunks.
-    static const int64_t chunk_env = getenv("DCS_GENERIC_CHUNK") ? atoll(getenv("DCS_GENERIC_CHUNK")) : 0;
+    const int64_t chunk_env = env().chunk;
     int64_t chunk = chunk_env > 0 ? chunk_env : (int64_t)(((size_t)4 << 30) / (chunk_bytes(g, 64) / 64 + 1));
     if (chunk < 64 && chunk_env <= 0) chunk = 64;
     // Graphs whose decoder is the fused kernel on channels-last input (Bach10, f32-class score-informed): that layout only comes out of the all-rows dense
@@ -2315,8 +2267,7 @@ int dcs_generic_forward(DcsGenericNet* g, const float* tiles, int64_t n, int mas
     // layers AND to the two-kernel decoder -- a 20 s clip several times slower per tile than a 10 s one.  Cut such passes into
     // equal pieces inside the window instead (the dense weights are re-read once per piece: 0.85 GB, ~0.2 ms; the deferred-mask
     // form below is single-chunk, so such a pass takes the separate mask and cross-fade kernels).
-    constexpr bool cap_env = true;
-    if (cap_env && chunk_env <= 0 && n > 176 && g->flat64 >= 8192 && plans_channels_last(g, nullptr, nullptr)) {
+    if (chunk_env <= 0 && n > 176 && g->flat64 >= 8192 && plans_channels_last(g, nullptr, nullptr)) {
         const int64_t pieces = (n + 175) / 176, per = (n + pieces - 1) / pieces;
         const int64_t capped = per >= 128 ? per : 176;
         if (capped < chunk) chunk = capped;
@@ -2361,13 +2312,9 @@ int dcs_generic_separate(DcsGenericNet* g, dcs_stft* plan, const float* audio, i
     const size_t b_sep = align256((size_t)n_clips * S * rows * ld * 4);
     const size_t b_inp = notes ? align256((size_t)g->C * T * F * 4) : 0;   // score-informed network input [C][T][F]
     // one clip through a graph whose conv1 can hand its map to conv2 channels-last: the clip's scaled frames once more as
-    // [C][Tn][F] rows (a sixth of the tiles), so that conv1 runs per frame instead of per tile row (forward_chunk: per_frame)
+    // [C][Tn][F] rows (a sixth of the tiles), so that conv1 runs per frame instead of per tile row (conv1_stage: per_frame)
     const int64_t Tn = (n - 1) * st + tc;
-#ifdef DCS_EXP_NO_PER_FRAME      // experiment build (scripts/build_exp.sh): the per-tile conv1 of round 5 for a same-box A/B
-    const bool want_frames = false;
-#else
     const bool want_frames = n_clips == 1 && !lens_h && n >= 2 && st > 0 && st < tc && g->W1m && g->use_colconv && g->C * Tn <= 65535;
-#endif
     const size_t b_frames = want_frames ? align256((size_t)g->C * Tn * F * 4) : 0;
     if (notes && (n_clips != 1 || notes->ninst != g->C))
         DCS_FAIL(DCS_EINVAL, "score-informed path: one clip, %d score channels (got %d)", g->C, notes->ninst);
@@ -2404,9 +2351,8 @@ int dcs_generic_separate(DcsGenericNet* g, dcs_stft* plan, const float* audio, i
         g->frames_src = frames; g->frames_rows = (int)Tn; g->frames_st = st;
     }
     // mask + cross-fade in one kernel when all tiles go through the graph in one chunk (the masked tiles then never exist)
-    static const bool fuse_env = !(getenv("DCS_MASK_OLA") && atoi(getenv("DCS_MASK_OLA")) == 0);
     bool mask_fused = false;
-    if (fuse_env && S <= 4) {
+    if (env().mask_ola && S <= 4) {
         const int rc = dcs_generic_forward(g, tiles, n_all, -1, tie_mode, outm);
         if (rc == DCS_OK) mask_fused = true;
         else if (rc != DCS_EUNSUPPORTED) return rc;
@@ -2432,7 +2378,6 @@ int dcs_generic_separate(DcsGenericNet* g, dcs_stft* plan, const float* audio, i
     // past its own n_c * st + tc stay unwritten (the iSTFT only reads its own T_c frames)
     if (mask_fused) {
         DcsTimer tm(ctx, DCS_TAG_MASK);
-        constexpr int mm_env = 1;   // (0 selected the loop form: 2.6 TB/s on the Bach10 clip against the all-requests-first form)
         const int mmax = (ov + st - 1) / st + 1;             // tiles that can reach one frame
         for (int64_t c = 0; c < n_clips; ++c) {
             const dim3 grid((unsigned)(nc[c] * st + tc), (unsigned)dcs_cdiv(F, kThreads));
@@ -2440,7 +2385,7 @@ int dcs_generic_separate(DcsGenericNet* g, dcs_stft* plan, const float* audio, i
             hipLaunchKernelGGL((mask_ola_kernel<MM_>), grid, dim3(kThreads), 0, ctx->stream, g->raw_o, g->bout, tiles, nc[c], off[c], \
                                g->raw_ch, S, g->C, tc, ov, F, g->rise_d, sep + c * S * rows * ld, rows * ld, ld, eps_mode,         \
                                g->mix_sum ? g->C : 1)
-            if (mm_env && S == 4 && mmax <= 6) DCS_MASK_OLA(6);
+            if (S == 4 && mmax <= 6) DCS_MASK_OLA(6);
             else DCS_MASK_OLA(0);
 #undef DCS_MASK_OLA
         }

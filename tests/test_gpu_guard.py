@@ -277,7 +277,7 @@ def _generic(n_fc, extra):
     return _GENERIC + 3 * n_fc + 1 + extra     # Bd, biasd, biasd_cl per dense layer; bout
 
 
-_IKALA = _generic(2, 1 + 10 + 2)              # W1p; the slab-conv weights (10); the folded B2fc, bias2fc
+_IKALA = _generic(2, 1 + 8 + 2)               # W1p; the slab-conv weights (8); the folded B2fc, bias2fc
 _BACH10 = _generic(4, 1 + 2 + 8 + 1 + 2)      # W1p; W1m, W1dq; the column-conv weights (8); Wfx3; W1q, Wx3
 _BACH10_SI = _generic(1, 1 + 2 + 8 + 1 + 2)   # the same, one dense layer: the 17 arrays run as the 11-array graph (arch.py)
 MODEL_BLOCKS_MIN = {"dsd": _DSD + _PLAN, "dsd_n1024": _DSD + _PLAN, "operators": _DSD, "stereo": _DSD_ILD + _PLAN,
@@ -300,7 +300,7 @@ def _finish(proc, poison, out):
         return json.load(fh)
 
 
-def test_red_zones_untouched_outputs_finite_and_independent_of_the_poison(tmp_path):
+def test_red_zones_untouched_outputs_finite_and_model_blocks_guarded(tmp_path):
     only = os.environ.get("DCS_GUARD_CASES", "")
     # the two poison runs are independent processes: side by side on the one GPU (each is ~10 s of start-up and small launches)
     f_nan, f_big = str(tmp_path / "nan.json"), str(tmp_path / "big.json")
