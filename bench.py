@@ -2,7 +2,7 @@
 """Benchmark of the MI355X separation hot path (BASELINE.json metric: spectrogram-frames/s,
 DSD100 4-source model, frameSize=2048 hop=512).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -28,21 +28,29 @@ profiles/r02_g_group_size_sweep.txt: 14 -> 20.2 M frames/s, 16 -> 20.7, 24 -> 21
 Timing: W warm-up steps, then ONE timed round of EXACTLY K steps bracketed by a barrier +
 torch.cuda.synchronize() on both sides (max over ranks); `ms_per_step` = round time / K.  With
 `--min-time S` rounds of K steps are repeated until S seconds have been timed and `value` comes from
-the median round (`rounds`, `round_ms` in the line).  The launches of the dominant kernel are timed
-with HIP events in a separate pass after the timed rounds, on stream 0 alone, because with kernels
-of other streams sharing the CUs an event pair measures a time-sliced duration.
+the median round (`rounds`, `round_ms` in the line).  With --full the launches of the dominant kernel
+are timed with HIP events in a separate pass after the timed rounds, on stream 0 alone, because with
+kernels of other streams sharing the CUs an event pair measures a time-sliced duration.
 
 `--dump-outputs DIR` writes what the timed path computed in its last step -- the float32 PCM
 [4 sources, samples] of the last batch of the last timed round -- as DIR/pcm.npy (rank 0).  The
 inputs depend only on the arguments, so two builds can be compared output for output.
 
-Rank 0 prints ONE compact JSON line (< 4 KB, strict JSON) as the LAST line of stdout: the contract keys, `roofline`
-of the dominant kernel of the headline workload (transposed conv1 + bias + rectify + soft mask + cross-fade),
-`cpu_baseline` (the CPU oracle -- reference-equivalent NumPy + torch-CPU float64 path -- timed on this host) and
-`parity_check`.  The full result object is written to bench_detail.json next to this file (and with --detail-stdout
-printed on an earlier stdout line): `legs` holds the other BASELINE configs (iKala 10 s, Bach10 with the f16 MFMA conv
-path, score-informed batch of 128), each with its own `roofline` and `cpu_baseline`; `saturating` repeats the headline
-measurement on a long clip (4096 tiles, 3 min 58 s) where one launch fills the chip (DESIGN.md "measurement").
+A plain run stops there: set-up, warm-up, the timed rounds, the dump, and the result line with the contract keys, the
+figures derived from the timed rounds (x_realtime, whole-path TFLOP/s) and `config`.  `--full` goes on with everything
+else, each part outside the timed rounds: the HIP-event passes of the dominant kernel and the per-kernel breakdowns, the
+one-batch-per-launch regime, the saturating and host-fed regimes, the collective's split for N > 1, the CPU baseline,
+the other BASELINE configs (`--legs`), the command-line leg and the oracle parity check.  The `--legs`, `--sat-tiles`
+and `--no-*` switches select among those (`--only-legs` runs the legs alone, without the headline rounds).
+
+Rank 0 prints ONE compact JSON line (< 4 KB, strict JSON) as the LAST line of stdout: the contract keys and, with
+--full, `roofline` of the dominant kernel of the headline workload (transposed conv1 + bias + rectify + soft mask +
+cross-fade), `cpu_baseline` (the CPU oracle -- reference-equivalent NumPy + torch-CPU float64 path -- timed on this
+host) and `parity_check` (null in a plain run).  The full result object is written to bench_detail.json next to this
+file (and with --detail-stdout printed on an earlier stdout line): `legs` holds the other BASELINE configs (iKala 10 s,
+Bach10 with the f16 MFMA conv path, score-informed batch of 128), each with its own `roofline` and `cpu_baseline`;
+`saturating` repeats the headline measurement on a long clip (4096 tiles, 3 min 58 s) where one launch fills the chip
+(DESIGN.md "measurement").
 """
 import argparse
 import json
@@ -291,8 +299,9 @@ def mask_bin_report(net, arch_name, params, tiles, conv):
     S = net.S
     x64 = np.asarray(tiles, dtype=np.float64)
     xd = net.ctx.to_device(np.asarray(tiles, dtype=np.float32), np.float32)
-    p_got = net.forward_raw(xd).cpu().numpy()
-    got = net.forward_masked(xd).cpu().numpy()
+    # (to_host: the copies are ordered after the kernels on the context's stream, which need not be the current one)
+    p_got = net.ctx.to_host(net.forward_raw(xd))
+    got = net.ctx.to_host(net.forward_masked(xd))
     p_ref = net_ref.forward(arch_name, params, x64, inverse='explicit').numpy()
     ref = np.stack([r[:, 0] for r in net_ref.predict(arch_name, params, x64, inverse='explicit')])
     rec = check_masked(got, ref, p_ref, p_got, x64[:, 0], S, conv, report=None, strict=False)
@@ -327,9 +336,13 @@ def main():
     ap.add_argument("--max-rounds", type=int, default=4000)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the PCM the last timed step computed as DIR/pcm.npy (float32)")
-    ap.add_argument("--sat-tiles", type=int, default=4096, help="tiles of the saturating extra run (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed rounds, also measure and check everything beyond the headline figure: per-kernel "
+                         "times and rooflines, the one-batch, saturating and host-fed regimes, the collective's split, the CPU "
+                         "baseline, the other BASELINE configs, the command-line leg and the oracle parity check")
+    ap.add_argument("--sat-tiles", type=int, default=4096, help="(--full) tiles of the saturating extra run (0 = skip)")
     ap.add_argument("--legs", default="ikala,bach10_f16,bach10_f32,score_informed,transform",
-                    help="comma list of extra BASELINE configs to measure on rank 0 at N=1 ('' = none)")
+                    help="(--full) comma list of extra BASELINE configs to measure on rank 0 at N=1 ('' = none)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-fed", action="store_true", help="skip the PCIe-inclusive extra leg")
     ap.add_argument("--no-cli", action="store_true", help="skip the command-line leg (separate_dsd.py on one wav, separate_batch.py on 50)")
@@ -545,6 +558,47 @@ def main():
     value = world * frames_per_step * K / med
     if args.dump_outputs and rank == 0:                     # the last step: the last batch of the last launch group
         dump_outputs(args.dump_outputs, {"pcm": lanes[(len(groups) - 1) % NS].pcm[groups[-1] - 1].cpu().numpy()})
+
+    whole_flops_step = n_tiles * ARCHS["dsd"].flops_per_tile(TC, F)
+    line = {
+        "metric": "spectrogram-frames/s", "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
+        "steps": K, "warmup": args.warmup, "ms_per_step": round(med / K * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "x_realtime": round(value * HOP / SR, 1),
+        "whole_path_algorithmic_tflops": round(world * whole_flops_step * K / med / 1e12, 2),
+        "whole_path_frac_of_f32_peak": round(whole_flops_step * K / med / 1e12 / PEAK_F32_TFLOPS, 4),
+        "rounds": len(round_s), "timed_region_s": round(total, 4),
+        "round_ms": {"median": round(med * 1e3, 4), "min": round(min(round_s) * 1e3, 4),
+                     "max": round(max(round_s) * 1e3, 4)},
+        "config": {"workload": "DSD100 4-source separate_dsd path (BASELINE configs[1]): frameSize=%d hop=512 "
+                               "hann, time_context=30 overlap=25 scale=0.3, one batch of %d tiles = %.2f s of "
+                               "44.1 kHz audio per GPU per step, STFT->net->mask->overlap-add->iSTFT, "
+                               "input and output resident in HBM; the %d steps of a round go out as launch "
+                               "groups of %s batches (dcs_separate_batch, the batch-of-files driver) over %d "
+                               "HIP streams per GPU%s; a round = exactly %d steps between barrier+synchronize, "
+                               "median of %d rounds"
+                               % (N, n_tiles, L / SR, K, "/".join(str(g) for g in sorted(set(groups), reverse=True)),
+                                  NS, (", int16 PCM %s over RCCL%s" % ({"root": "gathered to rank 0", "allgather": "all-gathered", "none": "kept per rank"}[args.gather],
+                                                                         ", two half-groups pipelined (collective of one under the compute of the other)" if pipelined else ""))
+                                  if world > 1 else "", K, len(round_s)),
+                   "tiles_per_gpu_per_step": n_tiles, "frames_per_gpu_per_step": frames_per_step,
+                   "frame_size": N, "bins": F, "launch_groups_per_round": groups, "streams_per_gpu": NS,
+                   "weights": "synthetic Glorot-uniform, seed 2, 15-array DSD .pkl layout",
+                   "parallelism": "tiles sharded by rank (dp%d)" % world},
+    }
+
+    def finish():
+        if rank == 0:
+            emit(line, detail_stdout=args.detail_stdout)
+        if gathering:
+            for ln in lanes:
+                if ln.comm is not None:
+                    ln.comm.close()
+            dist.destroy_process_group()
+
+    if not args.full:                                       # a plain run: the headline figure and nothing else
+        finish()
+        return
 
     # ---- HIP events around every launch of the dominant kernel: the round's launch groups (at most 12) issued on stream 0
     # alone -- with other streams' kernels sharing the CUs an event pair would measure a time-sliced duration
@@ -930,7 +984,6 @@ def main():
                                           "final_kernel": net0.final_kernel(T, 1)},
                         "ranks": int(world)}
 
-    whole_flops_step = n_tiles * ARCHS["dsd"].flops_per_tile(TC, F)
     cli = None
     if rank == 0 and world == 1 and not args.no_cli:
         try:
@@ -938,52 +991,22 @@ def main():
         except Exception as exc:
             cli = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
-    if rank == 0:
-        line = {
-            "metric": "spectrogram-frames/s", "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
-            "steps": K, "warmup": args.warmup, "ms_per_step": round(med / K * 1e3, 5),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "x_realtime": round(value * HOP / SR, 1),
-            "whole_path_algorithmic_tflops": round(world * whole_flops_step * K / med / 1e12, 2),
-            "whole_path_frac_of_f32_peak": round(whole_flops_step * K / med / 1e12 / PEAK_F32_TFLOPS, 4),
-            "parity_check": parity_check,
-            # BASELINE configs[1] exactly as the reference issues it -- predict_function2 on ONE batch of 32 tiles per call
-            # (separate_dsd.py:296-298), one stream, no batching across calls; details in `single_stream`
-            "single_stream_ms_per_step": single["ms_per_step"], "single_stream_value": single["value"],
-            "single_stream_x_realtime": round(single["value"] * HOP / SR, 1),
-            "rounds": len(round_s), "timed_region_s": round(total, 4),
-            "round_ms": {"median": round(med * 1e3, 4), "min": round(min(round_s) * 1e3, 4),
-                         "max": round(max(round_s) * 1e3, 4)},
-            "config": {"workload": "DSD100 4-source separate_dsd path (BASELINE configs[1]): frameSize=%d hop=512 "
-                                   "hann, time_context=30 overlap=25 scale=0.3, one batch of %d tiles = %.2f s of "
-                                   "44.1 kHz audio per GPU per step, STFT->net->mask->overlap-add->iSTFT, "
-                                   "input and output resident in HBM; the %d steps of a round go out as launch "
-                                   "groups of %s batches (dcs_separate_batch, the batch-of-files driver) over %d "
-                                   "HIP streams per GPU%s; a round = exactly %d steps between barrier+synchronize, "
-                                   "median of %d rounds"
-                                   % (N, n_tiles, L / SR, K, "/".join(str(g) for g in sorted(set(groups), reverse=True)),
-                                      NS, (", int16 PCM %s over RCCL%s" % ({"root": "gathered to rank 0", "allgather": "all-gathered", "none": "kept per rank"}[args.gather],
-                                                                             ", two half-groups pipelined (collective of one under the compute of the other)" if pipelined else ""))
-                                      if world > 1 else "", K, len(round_s)),
-                       "tiles_per_gpu_per_step": n_tiles, "frames_per_gpu_per_step": frames_per_step,
-                       "frame_size": N, "bins": F, "launch_groups_per_round": groups, "streams_per_gpu": NS,
-                       "weights": "synthetic Glorot-uniform, seed 2, 15-array DSD .pkl layout",
-                       "parallelism": "tiles sharded by rank (dp%d)" % world},
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "single_stream": single, "launch_group": launch_group,
-            "saturating": saturating, "host_fed": host_fed, "legs": legs, "cli": cli,
-            # the two HBM-bound kernels of the launch group against 8 TB/s (algorithmic bytes of SURVEY 8d over HIP-event time)
-            "hbm_stages": hbm_stages,
-        }
-        if gather_check is not None:
-            line["gather_check"] = gather_check
-        if gather_split is not None:
-            line["gather"] = gather_split
-        emit(line, detail_stdout=args.detail_stdout)
-    if gathering:
-        for ln in lanes:
-            if ln.comm is not None:
-                ln.comm.close()
-        dist.destroy_process_group()
+    line.update({
+        "parity_check": parity_check,
+        # BASELINE configs[1] exactly as the reference issues it -- predict_function2 on ONE batch of 32 tiles per call
+        # (separate_dsd.py:296-298), one stream, no batching across calls; details in `single_stream`
+        "single_stream_ms_per_step": single["ms_per_step"], "single_stream_value": single["value"],
+        "single_stream_x_realtime": round(single["value"] * HOP / SR, 1),
+        "roofline": roofline, "cpu_baseline": cpu_baseline, "single_stream": single, "launch_group": launch_group,
+        "saturating": saturating, "host_fed": host_fed, "legs": legs, "cli": cli,
+        # the two HBM-bound kernels of the launch group against 8 TB/s (algorithmic bytes of SURVEY 8d over HIP-event time)
+        "hbm_stages": hbm_stages,
+    })
+    if gather_check is not None:
+        line["gather_check"] = gather_check
+    if gather_split is not None:
+        line["gather"] = gather_split
+    finish()
 
 
 # ------------------------------------------------------------------------------------------------ the command lines

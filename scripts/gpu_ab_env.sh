@@ -9,7 +9,7 @@ fi
 for v in ${DCS_AB_VARIANTS:-default}; do
   envs=""; [ "$v" != "default" ] && envs="$v"
   vn=${v//\//_}
-  env $envs timeout 300 python bench.py --steps 384 --warmup 40 --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --legs= > $OUT/ab_$vn.json 2> $OUT/ab_$vn.err; echo "== $v exit $?"; tail -n 2 $OUT/ab_$vn.err
+  env $envs timeout 300 python bench.py --full --steps 384 --warmup 40 --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --legs= > $OUT/ab_$vn.json 2> $OUT/ab_$vn.err; echo "== $v exit $?"; tail -n 2 $OUT/ab_$vn.err
   python - <<PY
 import json
 d=json.load(open("$OUT/ab_$vn.json"))

@@ -3,9 +3,10 @@
 #   DCS_PMC_LEG=bach10_f16   DCS_PMC_ENV="NAME=V ..."   DCS_PMC_SETS="A,B,C;D,E"  (';' separates passes)
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 LEG=${DCS_PMC_LEG:-bach10_f16}
-CMD="env ${DCS_PMC_ENV:-} python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-host-fed --legs=$LEG --sat-tiles 0 --min-time 0.01"
+CMD="env ${DCS_PMC_ENV:-} python $ROOT/bench.py --full --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-host-fed --legs=$LEG --sat-tiles 0 --min-time 0.01"
 cd /tmp
 rocprofv3 -L 2>/dev/null | grep -o "\b\(SQC\?_[A-Z_0-9]*\)\b" | sort -u > $OUT/pmc_avail_sq.txt
 i=0

@@ -13,7 +13,7 @@ done
 for v in ${DCS_EXP_BENCH:-}; do   # S<streams>C<clips per launch>K<steps>
   s=${v#S}; s=${s%%C*}; c=${v#*C}; c=${c%%K*}; k=${v#*K}
   echo "== bench --steps $k --streams $s --clips-per-launch $c" | tee -a $LOG
-  timeout 300 python bench.py --steps $k --warmup 5 --streams $s --clips-per-launch $c --no-cpu-baseline --legs "" --sat-tiles 0 --no-host-fed > $OUT/exp_bench_$v.json 2> $OUT/exp_bench_$v.err
+  timeout 300 python bench.py --full --steps $k --warmup 5 --streams $s --clips-per-launch $c --no-cpu-baseline --legs "" --sat-tiles 0 --no-host-fed > $OUT/exp_bench_$v.json 2> $OUT/exp_bench_$v.err
   python - <<PY | tee -a $LOG
 import json
 d=json.loads(open("$OUT/exp_bench_$v.json").read().strip().splitlines()[-1])

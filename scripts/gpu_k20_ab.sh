@@ -5,6 +5,7 @@
 #   DCS_AB_K="expr" runs `pytest -m gpu -k expr` first
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=gpurun_out; mkdir -p $OUT
 if [ -n "${DCS_AB_K:-}" ]; then
   timeout 1200 python -m pytest tests -m gpu -q -x --timeout=300 -p no:cacheprovider -k "$DCS_AB_K" > $OUT/k20_pytest.log 2>&1; echo "pytest exit $?"; tail -n 8 $OUT/k20_pytest.log
@@ -15,7 +16,7 @@ for v in ${DCS_AB_VARIANTS:-default}; do
   case "$envs" in DCS_LIB=*) envs="DCS_LIB=$PWD/${envs#DCS_LIB=}";; esac
   vn=${v//\//_}
   for rep in $(seq 1 ${DCS_K20_REPS:-2}); do
-    env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-fed --no-cli --legs= --sat-tiles 0 \
+    env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-fed --no-cli --legs= --sat-tiles 0 \
         ${DCS_K20_ARGS:-} > $OUT/k20_$vn.line 2> $OUT/k20_$vn.err || { echo "== $v FAILED"; tail -n 3 $OUT/k20_$vn.err; }
     cp bench_detail.json $OUT/k20_$vn.json 2>/dev/null   # the full result (the stdout line is the compact headline)
     python - "$v" "$OUT/k20_$vn.json" <<'PY' | tee -a $OUT/k20_ab.txt
@@ -35,7 +36,7 @@ PY
 done
 if [ "${DCS_K20_TRACE:-1}" = "1" ]; then
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof_k20 -o bench -- \
-      python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-fed --no-cli --legs= --sat-tiles 0 --no-parity-check \
+      python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-fed --no-cli --legs= --sat-tiles 0 --no-parity-check \
       > $GRAFT_REPO_ROOT/$OUT/prof_k20_bench.line 2> $GRAFT_REPO_ROOT/$OUT/prof_k20.err)
   cp bench_detail.json $OUT/prof_k20_bench.json 2>/dev/null
   echo "rocprof exit $?"

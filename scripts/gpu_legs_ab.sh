@@ -10,7 +10,7 @@ fi
 i=0
 for v in "" ${DCS_AB_VARIANTS:-}; do
   echo "== variant '$v'" | tee -a $LOG
-  env $(echo "$v" | tr ';' ' ') timeout 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --sat-tiles 0 --no-host-fed \
+  env $(echo "$v" | tr ';' ' ') timeout 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --sat-tiles 0 --no-host-fed \
       --legs "${DCS_AB_LEGS:-bach10_f16,score_informed}" > $OUT/legs_ab_$i.json 2> $OUT/legs_ab_$i.err
   python - <<PY | tee -a $LOG
 import json

@@ -2,12 +2,13 @@
 # PMC pass (own run, kernel-trace only): effective clock and wait breakdown per kernel.
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 cd /tmp
 run() { # name, counters...
   name=$1; shift
   timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$name -o p -- \
-     python $GRAFT_REPO_ROOT/bench.py --steps ${STEPS:-20} --warmup 3 --streams ${STREAMS:-2} --no-cpu-baseline --sat-tiles ${SAT:-1024} > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
+     python $ROOT/bench.py --full --steps ${STEPS:-20} --warmup 3 --streams ${STREAMS:-2} --no-cpu-baseline --sat-tiles ${SAT:-1024} > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
   echo "pmc $name exit $?"
 }
 run a GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU

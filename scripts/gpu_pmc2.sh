@@ -1,12 +1,13 @@
 #!/bin/bash
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 cd /tmp
 rocprofv3 -L 2>/dev/null | grep -o -E "SQ_[A-Z_0-9]*MFMA[A-Z_0-9]*|SQ_BUSY_CU_CYCLES|SQ_VALU_[A-Z_0-9]*|SQ_INST_CYCLES_[A-Z_0-9]*" | sort -u | tr '\n' ' ' > $OUT/pmc_list.txt; cat $OUT/pmc_list.txt; echo
 run() { name=$1; shift
   timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc2_$name -o p -- \
-     python $GRAFT_REPO_ROOT/bench.py --steps 8 --warmup 2 --streams 1 --no-cpu-baseline --sat-tiles 4096 > $OUT/pmc2_$name.json 2> $OUT/pmc2_$name.err; echo "pmc2 $name exit $?"; }
+     python $ROOT/bench.py --full --steps 8 --warmup 2 --streams 1 --no-cpu-baseline --sat-tiles 4096 > $OUT/pmc2_$name.json 2> $OUT/pmc2_$name.err; echo "pmc2 $name exit $?"; }
 run m GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS
 python - <<'PY'
 import csv, glob, os, collections

@@ -4,8 +4,9 @@
 #   DCS_PMC_TRAFFIC=1 adds the FETCH_SIZE / WRITE_SIZE passes;  DCS_PMC_ENV="NAME=VAL ..." environment of the workload
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
-CMD="env ${DCS_PMC_ENV:-} python $GRAFT_REPO_ROOT/bench.py --steps ${DCS_PMC_STEPS:-20} --warmup 5 --streams 1 --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --legs= --sat-tiles ${DCS_PMC_SAT:-0} --min-time 0.02 --max-rounds 6"
+CMD="env ${DCS_PMC_ENV:-} python $ROOT/bench.py --full --steps ${DCS_PMC_STEPS:-20} --warmup 5 --streams 1 --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --legs= --sat-tiles ${DCS_PMC_SAT:-0} --min-time 0.02 --max-rounds 6"
 cd /tmp
 run() { name=$1; shift
   rm -rf $OUT/pmc_$name

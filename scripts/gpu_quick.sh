@@ -18,7 +18,7 @@ for v in ${DCS_VARIANTS:-default}; do
     *) envs="$v";;
   esac
   echo "== bench variant $v ($envs $extra)"
-  env $envs timeout 600 python bench.py --steps $steps --warmup 40 --no-cpu-baseline $sat $extra > $OUT/quick_bench_$vn.json 2> $OUT/quick_bench_$vn.err; echo "exit $?"; tail -n 3 $OUT/quick_bench_$vn.err
+  env $envs timeout 600 python bench.py --full --steps $steps --warmup 40 --no-cpu-baseline $sat $extra > $OUT/quick_bench_$vn.json 2> $OUT/quick_bench_$vn.err; echo "exit $?"; tail -n 3 $OUT/quick_bench_$vn.err
   python - <<PY
 import json
 d=json.load(open("$OUT/quick_bench_$vn.json"))

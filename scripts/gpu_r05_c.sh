@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests -m gpu -q -x --timeout=600 -p no:cacheprovid
 echo "pytest exit $?"; tail -n 15 $OUT/r05_c_pytest.log
 DCS_AB_VARIANTS="default DCS_ISTFT_CHAIN=0 DCS_ISTFT_CHAIN=7 DCS_ISTFT_CHAIN=9" DCS_K20_REPS=1 DCS_K20_TRACE=0 bash scripts/gpu_k20_ab.sh
 # the default shape (32 x 32 tiles x 3 streams) and the transform / cli legs
-timeout 900 python bench.py --legs transform --no-cpu-baseline --no-host-fed --sat-tiles 4096 > $OUT/r05_c_bench.line 2> $OUT/r05_c_bench.err; echo "bench exit $?"; tail -n 3 $OUT/r05_c_bench.err
+timeout 900 python bench.py --full --legs transform --no-cpu-baseline --no-host-fed --sat-tiles 4096 > $OUT/r05_c_bench.line 2> $OUT/r05_c_bench.err; echo "bench exit $?"; tail -n 3 $OUT/r05_c_bench.err
 cp bench_detail.json $OUT/r05_c_bench_detail.json
 python - <<'PY'
 import json

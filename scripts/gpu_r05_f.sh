@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests -m gpu -q --timeout=900 -p no:cacheprovider 
 echo "pytest exit $?"; tail -n 6 $OUT/r05_f_pytest.log | cut -c1-200
 bash scripts/gpu_traffic_r05.sh 2>&1 | tail -45
 cp profiles/r04_traffic.json /tmp/r05_traffic.json; python scripts/traffic_merge.py $OUT/traffic.json /tmp/r05_traffic.json; cp /tmp/r05_traffic.json profiles/r05_traffic.json; cp /tmp/r05_traffic.json $OUT/r05_traffic.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r05_f_driver_stdout.txt 2> $OUT/r05_f_driver.err; echo "driver cmd exit $?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r05_f_driver_stdout.txt 2> $OUT/r05_f_driver.err; echo "driver cmd exit $?"
 cp bench_detail.json $OUT/r05_f_bench_detail.json
 tail -c 2600 $OUT/r05_f_driver_stdout.txt; echo
 python - <<'PY'

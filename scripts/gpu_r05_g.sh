@@ -10,7 +10,7 @@ echo "pytest exit $?"; tail -n 8 $OUT/r05_g_pytest.log | cut -c1-200
 DCS_AB_VARIANTS="default DCS_LIB=deepconvsep_amd/_exp_nonyq.so default DCS_LIB=deepconvsep_amd/_exp_nonyq.so" DCS_K20_REPS=1 DCS_K20_TRACE=1 bash scripts/gpu_k20_ab.sh
 bash scripts/gpu_traffic_r05.sh 2>&1 | grep -E "exit|final_bf16x3|istft_chain|stft_forward"
 cp profiles/r05_traffic.json /tmp/r05_traffic.json; python scripts/traffic_merge.py $OUT/traffic.json /tmp/r05_traffic.json; cp /tmp/r05_traffic.json profiles/r05_traffic.json; cp /tmp/r05_traffic.json $OUT/r05_traffic.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r05_g_driver_stdout.txt 2> $OUT/r05_g_driver.err; echo "driver cmd exit $?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r05_g_driver_stdout.txt 2> $OUT/r05_g_driver.err; echo "driver cmd exit $?"
 cp bench_detail.json $OUT/r05_g_bench_detail.json
 tail -c 2600 $OUT/r05_g_driver_stdout.txt; echo
 python - <<'PY'

@@ -9,7 +9,7 @@ echo "pytest exit $?"; tail -n 6 $OUT/r05_h_pytest.log | cut -c1-200
 DCS_AB_VARIANTS="default DCS_STFT_ROWS_PER_WAVE=1 default DCS_STFT_ROWS_PER_WAVE=1 DCS_STFT_ROWS_PER_WAVE=3" DCS_K20_REPS=1 DCS_K20_TRACE=0 bash scripts/gpu_k20_ab.sh
 for v in default DCS_STFT_ROWS_PER_WAVE=1; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --legs= --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --sat-tiles 4096 > $OUT/r05_h_$v.line 2> $OUT/r05_h_$v.err
+  env $envs timeout 600 python bench.py --full --legs= --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --sat-tiles 4096 > $OUT/r05_h_$v.line 2> $OUT/r05_h_$v.err
   python - "$v" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json"))

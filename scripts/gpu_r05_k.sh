@@ -8,7 +8,7 @@ timeout 2400 python -m pytest tests -m gpu -q --timeout=900 -p no:cacheprovider 
 echo "pytest exit $?"; tail -n 12 $OUT/r05_k_pytest.log | cut -c1-220
 for v in default DCS_DECODER_X3=0; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 900 python bench.py --steps 20 --warmup 5 --legs score_informed,bach10_f32 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_k_$v.line 2> $OUT/r05_k_$v.err || tail -n 5 $OUT/r05_k_$v.err
+  env $envs timeout 900 python bench.py --full --steps 20 --warmup 5 --legs score_informed,bach10_f32 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_k_$v.line 2> $OUT/r05_k_$v.err || tail -n 5 $OUT/r05_k_$v.err
   cp bench_detail.json $OUT/r05_k_$v.json
   python - "$v" <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ echo "pytest exit $?"; tail -n 6 $OUT/r05_l_pytest.log | cut -c1-220
 for v in default ${DCS_L_VARIANTS:-}; do
   envs=""; [ "$v" != "default" ] && envs="$v"
   case "$envs" in DCS_LIB=*) envs="DCS_LIB=$PWD/${envs#DCS_LIB=}";; esac
-  env $envs timeout 900 python bench.py --steps 20 --warmup 5 --legs score_informed --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_l.line 2> $OUT/r05_l.err || tail -n 5 $OUT/r05_l.err
+  env $envs timeout 900 python bench.py --full --steps 20 --warmup 5 --legs score_informed --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_l.line 2> $OUT/r05_l.err || tail -n 5 $OUT/r05_l.err
   python - "$v" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -n 3
 t0=$(date +%s.%N)
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r05_o_driver_stdout.txt 2> $OUT/r05_o_driver.err; echo "driver cmd exit $? in $(echo "$(date +%s.%N) - $t0" | bc) s"
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r05_o_driver_stdout.txt 2> $OUT/r05_o_driver.err; echo "driver cmd exit $? in $(echo "$(date +%s.%N) - $t0" | bc) s"
 cp bench_detail.json $OUT/r05_o_bench_detail.json
 tail -n 1 $OUT/r05_o_driver_stdout.txt | wc -c
 tail -n 1 $OUT/r05_o_driver_stdout.txt | cut -c1-2600; echo

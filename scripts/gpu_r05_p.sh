@@ -9,7 +9,7 @@ echo "pytest exit $?"; tail -n 5 $OUT/r05_p_pytest.log | cut -c1-220
 for v in default ${DCS_P_VARIANTS:-}; do
   envs=""; [ "$v" != "default" ] && envs="$v"
   case "$envs" in DCS_LIB=*) envs="DCS_LIB=$PWD/${envs#DCS_LIB=}";; esac
-  env $envs timeout 900 python bench.py --steps 20 --warmup 5 --legs ${DCS_P_LEGS:-score_informed,bach10_f32,bach10_f16} --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_p.line 2> $OUT/r05_p.err || tail -n 5 $OUT/r05_p.err
+  env $envs timeout 900 python bench.py --full --steps 20 --warmup 5 --legs ${DCS_P_LEGS:-score_informed,bach10_f32,bach10_f16} --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_p.line 2> $OUT/r05_p.err || tail -n 5 $OUT/r05_p.err
   python - "$v" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json"))

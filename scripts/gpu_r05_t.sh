@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 timeout 1400 python -m pytest tests/ -x -q -m gpu > $OUT/r05_t_pytest_gpu.log 2>&1; echo "pytest exit $?"
 grep -v "^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" $OUT/r05_t_pytest_gpu.log | tail -n 6 | cut -c1-200
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 2
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r05_t_driver_stdout.txt 2> $OUT/r05_t_driver.err; echo "driver cmd exit $?"
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r05_t_driver_stdout.txt 2> $OUT/r05_t_driver.err; echo "driver cmd exit $?"
 cp bench_detail.json $OUT/r05_t_bench_detail.json
 tail -n 1 $OUT/r05_t_driver_stdout.txt | wc -c
 tail -n 1 $OUT/r05_t_driver_stdout.txt | python -c "

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests -m gpu -q --timeout=600 -p no:cacheprovider -
 echo "pytest exit $?"; tail -n 4 $OUT/r05_w_pytest.log | cut -c1-200
 for v in default DCS_CONV2_X3=0 default DCS_CONV2_X3=0; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --steps 20 --warmup 5 --legs score_informed,bach10_f32 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_w.line 2> $OUT/r05_w.err || tail -n 5 $OUT/r05_w.err
+  env $envs timeout 600 python bench.py --full --steps 20 --warmup 5 --legs score_informed,bach10_f32 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r05_w.line 2> $OUT/r05_w.err || tail -n 5 $OUT/r05_w.err
   python - "$v" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -19,13 +19,13 @@ rm -f $OUT/mask_bins.txt
 DCS_CONV2_X3=0 timeout 600 python -m pytest tests/test_gpu_random.py -m gpu -q -p no:cacheprovider > $OUT/r06_a_random_x3off.log 2>&1; echo "exit $?"; tail -n 3 $OUT/r06_a_random_x3off.log
 cp $OUT/mask_bins.txt $OUT/r06_a_mask_bins_x3off.txt 2>/dev/null
 echo "== the driver's command"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r06_a_driver_stdout.txt 2> $OUT/r06_a_driver.err; echo "bench exit $?"; tail -n 3 $OUT/r06_a_driver.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r06_a_driver_stdout.txt 2> $OUT/r06_a_driver.err; echo "bench exit $?"; tail -n 3 $OUT/r06_a_driver.err
 tail -n 1 $OUT/r06_a_driver_stdout.txt | cut -c1-3000
 cp bench_detail.json $OUT/r06_a_bench_detail.json
 echo "== legs A/B"
 for v in default DCS_CONV2_X3=0 default DCS_CONV2_X3=0; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --steps 20 --warmup 5 --legs score_informed,bach10_f32,bach10_f16 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_a.line 2> $OUT/r06_a.err || tail -n 5 $OUT/r06_a.err
+  env $envs timeout 600 python bench.py --full --steps 20 --warmup 5 --legs score_informed,bach10_f32,bach10_f16 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_a.line 2> $OUT/r06_a.err || tail -n 5 $OUT/r06_a.err
   python - "$v" <<'PY' | tee -a $OUT/r06_a_legs_ab.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

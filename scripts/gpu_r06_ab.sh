@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 : > $OUT/r06_ab.txt
 for rep in 1 2 3; do
 for v in 1 0; do
-  DCS_GRAPH=$v timeout 600 python bench.py --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check > $OUT/r06_ab.line 2> $OUT/r06_ab.err || tail -n 5 $OUT/r06_ab.err
+  DCS_GRAPH=$v timeout 600 python bench.py --full --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check > $OUT/r06_ab.line 2> $OUT/r06_ab.err || tail -n 5 $OUT/r06_ab.err
   python - "$v" <<'PY' | tee -a $OUT/r06_ab.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

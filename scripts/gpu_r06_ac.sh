@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 : > $OUT/r06_ac.txt
 for args in "" "--steps 64 --warmup 8" "--steps 8 --warmup 4" "--steps 4 --warmup 4" "--steps 2 --warmup 4"; do
 for v in 1 0; do
-  DCS_GRAPH=$v timeout 600 python bench.py $args --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check > $OUT/r06_ac.line 2> $OUT/r06_ac.err || tail -n 5 $OUT/r06_ac.err
+  DCS_GRAPH=$v timeout 600 python bench.py --full $args --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check > $OUT/r06_ac.line 2> $OUT/r06_ac.err || tail -n 5 $OUT/r06_ac.err
   python - "$v" "$args" <<'PY' | tee -a $OUT/r06_ac.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -12,7 +12,7 @@ cat $OUT/f16_stats.txt 2>/dev/null
 : > $OUT/r06_f_legs_ab.txt
 for v in default DCS_DENSE_F16=0 default DCS_DENSE_F16=0; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --steps 20 --warmup 5 --legs bach10_f16 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_f.line 2> $OUT/r06_f.err || tail -n 5 $OUT/r06_f.err
+  env $envs timeout 600 python bench.py --full --steps 20 --warmup 5 --legs bach10_f16 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_f.line 2> $OUT/r06_f.err || tail -n 5 $OUT/r06_f.err
   python - "$v" <<'PY' | tee -a $OUT/r06_f_legs_ab.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -13,11 +13,11 @@ echo "pytest exit $? after $((SECONDS - t0)) s"; tail -n 4 $OUT/r06_z_pytest_gpu
 cp $OUT/mask_bins.txt $OUT/r06_z_mask_bins.txt 2>/dev/null; cp $OUT/f16_stats.txt $OUT/r06_z_f16_stats.txt 2>/dev/null
 timeout 300 python __graft_entry__.py smoke > $OUT/r06_z_smoke.log 2>&1; echo "smoke exit $?"; tail -n 1 $OUT/r06_z_smoke.log
 t0=$SECONDS
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r06_z_driver_cmd_stdout.txt 2> $OUT/r06_z_driver.err; echo "driver bench exit $? after $((SECONDS - t0)) s"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r06_z_driver_cmd_stdout.txt 2> $OUT/r06_z_driver.err; echo "driver bench exit $? after $((SECONDS - t0)) s"
 tail -n 1 $OUT/r06_z_driver_cmd_stdout.txt | cut -c1-2600
 cp bench_detail.json $OUT/r06_z_bench_detail_driver_cmd.json
 t0=$SECONDS
-timeout 900 python bench.py > $OUT/r06_z_default_stdout.txt 2> $OUT/r06_z_default.err; echo "default bench exit $? after $((SECONDS - t0)) s"
+timeout 900 python bench.py --full > $OUT/r06_z_default_stdout.txt 2> $OUT/r06_z_default.err; echo "default bench exit $? after $((SECONDS - t0)) s"
 tail -n 1 $OUT/r06_z_default_stdout.txt | cut -c1-1200
 cp bench_detail.json $OUT/r06_z_bench_detail_default.json
 bash scripts/gpu_r06_measure.sh 2>&1 | tail -n 45

@@ -10,7 +10,7 @@ echo "pytest exit $?"; tail -n 6 $OUT/r06_g_pytest.log | cut -c1-250
 : > $OUT/r06_g_ikala_ab.txt
 for v in default DCS_SLABCONV_STRIP=0 default DCS_SLABCONV_STRIP=0; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --steps 20 --warmup 5 --legs ikala --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_g.line 2> $OUT/r06_g.err || tail -n 5 $OUT/r06_g.err
+  env $envs timeout 600 python bench.py --full --steps 20 --warmup 5 --legs ikala --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_g.line 2> $OUT/r06_g.err || tail -n 5 $OUT/r06_g.err
   python - "$v" <<'PY' | tee -a $OUT/r06_g_ikala_ab.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

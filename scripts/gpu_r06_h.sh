@@ -11,7 +11,7 @@ echo "pytest exit $?"; tail -n 22 $OUT/r06_h_pytest.log | cut -c1-220
 : > $OUT/r06_h_stft_ab.txt
 for v in default DCS_STFT_FPW=4 default DCS_STFT_FPW=4 default DCS_STFT_FPW=4; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --legs "" --sat-tiles 4096 --no-host-fed --no-cli > $OUT/r06_h.line 2> $OUT/r06_h.err || tail -n 5 $OUT/r06_h.err
+  env $envs timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --legs "" --sat-tiles 4096 --no-host-fed --no-cli > $OUT/r06_h.line 2> $OUT/r06_h.err || tail -n 5 $OUT/r06_h.err
   python - "$v" <<'PY' | tee -a $OUT/r06_h_stft_ab.txt
 import json, sys
 d = json.load(open("bench_detail.json"))
@@ -23,7 +23,7 @@ PY
 done
 for v in default DCS_STFT_FPW=4 default DCS_STFT_FPW=4; do
   envs=""; [ "$v" != "default" ] && envs="$v"
-  env $envs timeout 600 python bench.py --no-cpu-baseline --legs "" --sat-tiles 0 --no-host-fed --no-cli > $OUT/r06_h.line 2> $OUT/r06_h.err || tail -n 5 $OUT/r06_h.err
+  env $envs timeout 600 python bench.py --full --no-cpu-baseline --legs "" --sat-tiles 0 --no-host-fed --no-cli > $OUT/r06_h.line 2> $OUT/r06_h.err || tail -n 5 $OUT/r06_h.err
   python - "$v" <<'PY' | tee -a $OUT/r06_h_stft_ab.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

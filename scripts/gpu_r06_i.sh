@@ -10,7 +10,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q --timeout=600 -p no:cacheprovid
 echo "pytest exit $? after $((SECONDS - t0)) s"; tail -n 32 $OUT/r06_i_pytest.log | cut -c1-200
 cat $OUT/f16_stats.txt
 for i in 1; do
-timeout 600 python bench.py --steps 20 --warmup 5 --legs bach10_f16,ikala,score_informed,bach10_f32 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_i.line 2> $OUT/r06_i.err || tail -n 5 $OUT/r06_i.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --legs bach10_f16,ikala,score_informed,bach10_f32 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_i.line 2> $OUT/r06_i.err || tail -n 5 $OUT/r06_i.err
 python - <<'PY' | tee -a $OUT/r06_i_legs.txt
 import json
 d = json.load(open("bench_detail.json"))

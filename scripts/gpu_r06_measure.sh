@@ -5,12 +5,13 @@
 # instruction-mix passes at the driver's shape (20 x 32 tiles, one stream) -> counters_summary_k20.txt.
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 rm -rf $OUT/pmc_* $OUT/prof_k20 $OUT/prof_legs
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --min-time 0.02 --max-rounds 6"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --min-time 0.02 --max-rounds 6"
 cd /tmp
 echo "== (1) kernel traces"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_k20 -o bench -- python $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --legs= --sat-tiles 0 --no-cpu-baseline --no-host-fed --no-cli > $OUT/prof_k20.json 2> $OUT/prof_k20.err; echo "trace k20 exit $?"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_k20 -o bench -- python $ROOT/bench.py --full --gpus 1 --steps 20 --warmup 5 --legs= --sat-tiles 0 --no-cpu-baseline --no-host-fed --no-cli > $OUT/prof_k20.json 2> $OUT/prof_k20.err; echo "trace k20 exit $?"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_legs -o bench -- $B --only-legs --legs ikala,bach10_f16,bach10_f32,score_informed > $OUT/prof_legs.json 2> $OUT/prof_legs.err; echo "trace legs exit $?"
 (cd $GRAFT_REPO_ROOT && python scripts/trace_by_grid.py $OUT/prof_k20 > $OUT/r06_kernel_durations_by_grid_k20.txt 2>&1; python scripts/trace_by_grid.py $OUT/prof_legs > $OUT/r06_kernel_durations_by_grid_legs.txt 2>&1)
 for f in $(find $OUT/prof_k20 -name "*kernel_stats*.csv" | head -1); do cp $f $OUT/r06_k20_kernel_stats.csv; head -n 12 $f; done
@@ -30,7 +31,7 @@ cd $GRAFT_REPO_ROOT
 python scripts/traffic_summary.py $OUT | tee $OUT/r06_traffic_summary.txt | tail -70
 echo "== (3) counters at the driver's shape"
 cd /tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --legs= --sat-tiles 0 --min-time 0.02 --max-rounds 6"
+CMD="python $ROOT/bench.py --full --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --legs= --sat-tiles 0 --min-time 0.02 --max-rounds 6"
 runc() { name=$1; shift
   rm -rf $OUT/pmc_$name
   timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$name -o p -- $CMD > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err

@@ -7,7 +7,7 @@ rm -f $OUT/mask_bins.txt $OUT/f16_stats.txt
 timeout 1500 python -m pytest tests -m gpu -x -q --timeout=600 -p no:cacheprovider -k "bach10 or f16 or channels_last or fused_decoder or variants or guard" > $OUT/r06_n_pytest.log 2>&1
 echo "pytest exit $?"; tail -n 4 $OUT/r06_n_pytest.log | cut -c1-200; cat $OUT/f16_stats.txt
 for i in 1 2 3; do
-timeout 600 python bench.py --steps 20 --warmup 5 --legs bach10_f16 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_n.line 2> $OUT/r06_n.err || tail -n 5 $OUT/r06_n.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --legs bach10_f16 --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_n.line 2> $OUT/r06_n.err || tail -n 5 $OUT/r06_n.err
 python - <<'PY' | tee -a $OUT/r06_n_legs.txt
 import json
 d = json.load(open("bench_detail.json"))

@@ -7,7 +7,7 @@ OUT=gpurun_out; mkdir -p $OUT
 for rep in 1 2; do
 for cfg in "32 3" "10 2" "10 3" "7 3" "5 4" "14 2"; do
   set -- $cfg
-  timeout 600 python bench.py --steps 20 --warmup 5 --clips-per-launch $1 --streams $2 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check > $OUT/r06_o.line 2> $OUT/r06_o.err || tail -n 5 $OUT/r06_o.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --clips-per-launch $1 --streams $2 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check > $OUT/r06_o.line 2> $OUT/r06_o.err || tail -n 5 $OUT/r06_o.err
   python - "$1" "$2" <<'PY' | tee -a $OUT/r06_o_split.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

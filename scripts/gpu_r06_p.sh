@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 : > $OUT/r06_p_stagger.txt
 for rep in 1 2; do
 for st in 0 2 4 7 10 14; do
-  DCS_LIB=deepconvsep_amd/_exp_stagger.so DCS_FINAL_STAGGER=$st timeout 600 python bench.py --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_p.line 2> $OUT/r06_p.err || tail -n 5 $OUT/r06_p.err
+  DCS_LIB=deepconvsep_amd/_exp_stagger.so DCS_FINAL_STAGGER=$st timeout 600 python bench.py --full --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_p.line 2> $OUT/r06_p.err || tail -n 5 $OUT/r06_p.err
   python - "$st" <<'PY' | tee -a $OUT/r06_p_stagger.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -8,7 +8,7 @@ echo "pytest exit $?"; tail -n 4 $OUT/r06_q_pytest.log | cut -c1-200
 : > $OUT/r06_q_upw.txt
 for rep in 1 2; do
 for u in 1 2 3 0 4; do
-  DCS_FINAL_UPW=$u timeout 600 python bench.py --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 4096 > $OUT/r06_q.line 2> $OUT/r06_q.err || tail -n 5 $OUT/r06_q.err
+  DCS_FINAL_UPW=$u timeout 600 python bench.py --full --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 4096 > $OUT/r06_q.line 2> $OUT/r06_q.err || tail -n 5 $OUT/r06_q.err
   python - "$u" <<'PY' | tee -a $OUT/r06_q_upw.txt
 import json, sys
 d = json.load(open("bench_detail.json"))
@@ -19,7 +19,7 @@ PY
 done
 done
 for u in 1 0; do
-  DCS_FINAL_UPW=$u timeout 600 python bench.py --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_q.line 2> $OUT/r06_q.err || tail -n 5 $OUT/r06_q.err
+  DCS_FINAL_UPW=$u timeout 600 python bench.py --full --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_q.line 2> $OUT/r06_q.err || tail -n 5 $OUT/r06_q.err
   python - "$u" <<'PY' | tee -a $OUT/r06_q_upw.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -8,7 +8,7 @@ echo "pytest exit $?"; tail -n 4 $OUT/r06_r_pytest.log | cut -c1-200
 : > $OUT/r06_r_istft.txt
 for rep in 1 2 3; do
 for v in 1 0; do
-  DCS_ISTFT_LEAN=$v timeout 600 python bench.py --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_r.line 2> $OUT/r06_r.err || tail -n 5 $OUT/r06_r.err
+  DCS_ISTFT_LEAN=$v timeout 600 python bench.py --full --steps 20 --warmup 5 --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_r.line 2> $OUT/r06_r.err || tail -n 5 $OUT/r06_r.err
   python - "$v" <<'PY' | tee -a $OUT/r06_r_istft.txt
 import json, sys
 d = json.load(open("bench_detail.json"))
@@ -19,7 +19,7 @@ PY
 done
 done
 for v in 1 0; do
-  DCS_ISTFT_LEAN=$v timeout 600 python bench.py --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_r.line 2> $OUT/r06_r.err || tail -n 5 $OUT/r06_r.err
+  DCS_ISTFT_LEAN=$v timeout 600 python bench.py --full --legs "" --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_r.line 2> $OUT/r06_r.err || tail -n 5 $OUT/r06_r.err
   python - "$v" <<'PY' | tee -a $OUT/r06_r_istft.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

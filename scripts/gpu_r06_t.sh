@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
 rocprofv3 --list-avail > $OUT/r06_t_avail.txt 2>&1 || rocprofv3 -L > $OUT/r06_t_avail.txt 2>&1
 grep -o "\b\(TA\|TCP\|TCC\|TD\|SQ\|SQC\|GRBM\)_[A-Za-z0-9_]*" $OUT/r06_t_avail.txt | sort -u > $OUT/r06_t_names.txt; wc -l $OUT/r06_t_names.txt
-CMD="python bench.py --steps 20 --warmup 5 --legs= --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check --max-rounds 60"
+CMD="python bench.py --full --steps 20 --warmup 5 --legs= --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 --no-parity-check --max-rounds 60"
 n=0
 while read -r line; do
   n=$((n+1))

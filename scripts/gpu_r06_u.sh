@@ -8,7 +8,7 @@ echo "pytest exit $?"; tail -n 4 $OUT/r06_u_pytest.log | cut -c1-200
 : > $OUT/r06_u_legs.txt
 for rep in 1 2 3; do
 for v in 1 0; do
-DCS_SLABCONV_PS_SPLIT=$v timeout 600 python bench.py --steps 20 --warmup 5 --legs ikala --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_u.line 2> $OUT/r06_u.err || tail -n 5 $OUT/r06_u.err
+DCS_SLABCONV_PS_SPLIT=$v timeout 600 python bench.py --full --steps 20 --warmup 5 --legs ikala --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_u.line 2> $OUT/r06_u.err || tail -n 5 $OUT/r06_u.err
 python - "$v" <<'PY' | tee -a $OUT/r06_u_legs.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -9,7 +9,7 @@ echo "pytest exit $?"; tail -n 4 $OUT/r06_x_pytest.log | cut -c1-200
 : > $OUT/r06_x_legs.txt
 for rep in 1 2 3; do
 for v in 1 0; do
-DCS_FOLD_CONV2=$v timeout 600 python bench.py --steps 20 --warmup 5 --legs ikala --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_x.line 2> $OUT/r06_x.err || tail -n 5 $OUT/r06_x.err
+DCS_FOLD_CONV2=$v timeout 600 python bench.py --full --steps 20 --warmup 5 --legs ikala --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_x.line 2> $OUT/r06_x.err || tail -n 5 $OUT/r06_x.err
 python - "$v" <<'PY' | tee -a $OUT/r06_x_legs.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

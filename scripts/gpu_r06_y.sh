@@ -10,7 +10,7 @@ echo "pytest exit $?"; tail -n 4 $OUT/r06_y_pytest.log | cut -c1-200
 for rep in 1 2; do
 for v in new old; do
 LIB=""; [ $v = old ] && LIB=deepconvsep_amd/_exp_noperframe.so
-DCS_LIB=$LIB timeout 600 python bench.py --steps 20 --warmup 5 --legs bach10_f16,bach10_f32,score_informed --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_y.line 2> $OUT/r06_y.err || tail -n 5 $OUT/r06_y.err
+DCS_LIB=$LIB timeout 600 python bench.py --full --steps 20 --warmup 5 --legs bach10_f16,bach10_f32,score_informed --no-cpu-baseline --no-host-fed --no-cli --sat-tiles 0 > $OUT/r06_y.line 2> $OUT/r06_y.err || tail -n 5 $OUT/r06_y.err
 python - "$v" <<'PY' | tee -a $OUT/r06_y_legs.txt
 import json, sys
 d = json.load(open("bench_detail.json"))

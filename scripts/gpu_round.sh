@@ -5,6 +5,7 @@
 #   DCS_SKIP_TESTS=1 skips pytest; DCS_PROFILE=0 skips rocprof; DCS_BENCH_ARGS="..." extra arguments of the default bench run
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=gpurun_out
 mkdir -p $OUT
 rm -f $OUT/mask_bins.txt $OUT/f16_stats.txt
@@ -19,9 +20,9 @@ if [ "${DCS_SKIP_TESTS:-0}" != "1" ]; then
   timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log; tail -n 5 $OUT/smoke.log
 fi
 echo "== bench (default)"
-timeout 900 python bench.py ${DCS_BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"; tail -n 5 $OUT/bench.err
+timeout 900 python bench.py --full ${DCS_BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"; tail -n 5 $OUT/bench.err
 echo "== bench as the driver runs it (--steps 20 --warmup 5)"
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --legs "" --sat-tiles 0 --no-host-fed > $OUT/bench_k20.json 2> $OUT/bench_k20.err; echo "bench k20 exit $?"; tail -n 3 $OUT/bench_k20.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --legs "" --sat-tiles 0 --no-host-fed > $OUT/bench_k20.json 2> $OUT/bench_k20.err; echo "bench k20 exit $?"; tail -n 3 $OUT/bench_k20.err
 python - <<'PY'
 import json
 for f in ("gpurun_out/bench.json", "gpurun_out/bench_k20.json"):
@@ -46,14 +47,14 @@ PY
 if [ "${DCS_PROFILE:-1}" = "1" ]; then
   echo "== rocprofv3 kernel stats"
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o bench -- \
-      python $GRAFT_REPO_ROOT/bench.py --steps 160 --warmup 32 --no-cpu-baseline --no-host-fed > $GRAFT_REPO_ROOT/$OUT/prof_bench.json 2> $GRAFT_REPO_ROOT/$OUT/prof.err)
+      python $ROOT/bench.py --full --steps 160 --warmup 32 --no-cpu-baseline --no-host-fed > $ROOT/$OUT/prof_bench.json 2> $ROOT/$OUT/prof.err)
   echo "rocprof exit $?"
   for f in $(find $OUT/prof -name "*kernel_stats*.csv" | head -1); do head -n 14 $f; done
   python scripts/trace_by_grid.py $OUT/prof > $OUT/kernel_durations_by_grid.txt 2>&1
   # the same on ONE stream: kernel durations that are not time-sliced with another stream's kernels (what the HIP events of
   # bench.py's event rounds measure)
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof1 -o bench -- \
-      python $GRAFT_REPO_ROOT/bench.py --steps 160 --warmup 32 --streams 1 --no-cpu-baseline --no-host-fed --legs= > $GRAFT_REPO_ROOT/$OUT/prof1_bench.json 2> $GRAFT_REPO_ROOT/$OUT/prof1.err)
+      python $ROOT/bench.py --full --steps 160 --warmup 32 --streams 1 --no-cpu-baseline --no-host-fed --legs= > $ROOT/$OUT/prof1_bench.json 2> $ROOT/$OUT/prof1.err)
   echo "rocprof (1 stream) exit $?"
   python scripts/trace_by_grid.py $OUT/prof1 > $OUT/kernel_durations_by_grid_1stream.txt 2>&1; grep -E "final|istft|deconv2_stream|stft_forward_wave" $OUT/kernel_durations_by_grid_1stream.txt
 fi

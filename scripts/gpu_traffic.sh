@@ -4,11 +4,12 @@
 # WRITE_SIZE; FETCH_SIZE is doubled on gfx950 for wide coalesced reads (the guide's correction).
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/traffic_$c -o p -- \
-     python $GRAFT_REPO_ROOT/bench.py --steps 32 --warmup 16 --no-cpu-baseline --sat-tiles 4096 > $OUT/traffic_$c.json 2> $OUT/traffic_$c.err
+     python $ROOT/bench.py --full --steps 32 --warmup 16 --no-cpu-baseline --sat-tiles 4096 > $OUT/traffic_$c.json 2> $OUT/traffic_$c.err
   echo "pmc $c exit $?"
 done
 python - <<'PY'

@@ -6,8 +6,9 @@
 #      python scripts/traffic_merge.py gpurun_out/traffic.json profiles/r05_traffic.json
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --min-time 0.02 --max-rounds 6"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --min-time 0.02 --max-rounds 6"
 cd /tmp
 run() { tag=$1; shift
   for c in fetch:FETCH_SIZE write:WRITE_SIZE; do

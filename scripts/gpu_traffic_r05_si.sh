@@ -4,9 +4,10 @@
 #   -> gpurun_out/traffic.json; then python scripts/traffic_merge.py gpurun_out/traffic.json profiles/r05_traffic.json
 set -u
 export TMPDIR=/tmp
+ROOT=$PWD                   # the repository root: run from there
 OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 rm -rf $OUT/pmc_*
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --min-time 0.02 --max-rounds 6"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-host-fed --no-cli --no-parity-check --min-time 0.02 --max-rounds 6"
 cd /tmp
 for leg in ${DCS_TRAFFIC_LEGS:-score_informed}; do
 for c in fetch:FETCH_SIZE write:WRITE_SIZE; do

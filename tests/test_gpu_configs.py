@@ -306,7 +306,7 @@ def test_bench_two_ranks_on_this_gpu_gather_is_exact():
     env = dict(os.environ, DCS_BENCH_SAME_DEVICE="1", DCS_BENCH_CHECK_GATHER="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "2", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "", "--gather", "allgather"]
+           "--warmup", "2", "--full", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "", "--gather", "allgather"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -387,7 +387,7 @@ def test_bench_two_ranks_gather_modes(mode):
         env["DCS_BENCH_CHECK_GATHER"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "2", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "", "--gather", mode]
+           "--warmup", "2", "--full", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "", "--gather", mode]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     if r.returncode != 0 and mode == "root" and "gloo" in (r.stderr + r.stdout).lower() and "gather" in (r.stderr + r.stdout).lower():
         pytest.skip("gloo cannot gather device tensors to a root here")
@@ -468,7 +468,7 @@ needs_two_gpus = pytest.mark.skipif(_gpu_count() < 2, reason="needs two GPUs (RC
 def _run_bench(n, extra, env_extra, timeout=900):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", **env_extra)
     env.pop("DCS_BENCH_SAME_DEVICE", None)
-    args = ["--gpus", str(n), "--steps", "6", "--warmup", "2", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "",
+    args = ["--gpus", str(n), "--steps", "6", "--warmup", "2", "--full", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "",
             "--no-cpu-baseline", "--no-host-fed", "--no-cli"] + extra
     if n > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
@@ -492,8 +492,8 @@ def test_bench_gather_code_path_with_a_world_of_one_rank():
     procs = []
     for i, (impl, mode, serial) in enumerate(variants):
         # (the oracle check of the timed launches' output -- seconds of float64 CPU work -- once: the compute path is the same in all four)
-        args = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "", "--no-cpu-baseline",
-                "--no-host-fed", "--no-cli", "--gather", mode, "--gather-impl", impl] + (["--no-pipeline"] if serial else []) + \
+        args = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--sat-tiles", "0", "--min-time", "0.02", "--legs", "",
+                "--no-cpu-baseline", "--no-host-fed", "--no-cli", "--gather", mode, "--gather-impl", impl] + (["--no-pipeline"] if serial else []) + \
                (["--no-parity-check"] if i else [])
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True, cwd=ROOT))
