@@ -112,6 +112,13 @@ def load():
     proto("dcs_debug_check_guards", i32, vp, POINTER(i64))
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
+    proto("dcs_trainer_create", i32, vp, i32, i32, i32, i32, POINTER(vp), POINTER(i64), i32, vp, POINTER(c_double),
+          POINTER(vp))
+    proto("dcs_trainer_destroy", i32, vp)
+    proto("dcs_trainer_step", i32, vp, vp, vp, i32, vp)
+    proto("dcs_trainer_forward", i32, vp, vp, vp)
+    proto("dcs_trainer_get", i32, vp, i32, POINTER(vp), i32)
+    proto("dcs_trainer_gather", i32, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp)
     _lib = lib
     return lib
 
