@@ -119,6 +119,7 @@ def load():
     proto("dcs_trainer_forward", i32, vp, vp, vp)
     proto("dcs_trainer_get", i32, vp, i32, POINTER(vp), i32)
     proto("dcs_trainer_gather", i32, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp)
+    proto("dcs_trainer_gather_sources", i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp)
     _lib = lib
     return lib
 

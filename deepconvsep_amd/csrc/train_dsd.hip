@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include "dcs_internal.h"
+#include "train_ikala.h"
 
 namespace {
 
@@ -396,6 +397,7 @@ __global__ __launch_bounds__(kThreads) void tr_gather_kernel(const float* __rest
 
 struct dcs_trainer {
     dcs_ctx* ctx = nullptr;
+    ik_trainer* ik = nullptr;    // the iKala graph (train_ikala.hip); null for the DSD graph
     int tc = 0, F = 0, B = 0, kh = 0, h2 = 0, hp = 0;
     int64_t R = 0, Rh = 0, map = 0, P = 0;
     double hyp[7] = {0};
@@ -702,7 +704,18 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
                                dcs_trainer** out) {
     if (!ctx || !out || !rand_d || !hyper_h) DCS_FAIL(DCS_EINVAL, "dcs_trainer_create: null argument");
     *out = nullptr;
-    if (arch != DCS_ARCH_DSD) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d) trains here", DCS_ARCH_DSD);
+    if (arch == DCS_ARCH_IKALA_NOPOOL) {
+        ik_trainer* ik = nullptr;
+        DCS_CHECK(ik_trainer_create(ctx, time_context, F, batch, params_d, shapes, nparams, rand_d, hyper_h, &ik));
+        dcs_trainer* t = new dcs_trainer();
+        t->ctx = ctx;
+        t->ik = ik;
+        *out = t;
+        return DCS_OK;
+    }
+    if (arch != DCS_ARCH_DSD)
+        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d) and the no-pool iKala graph (arch %d) "
+                 "train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL);
     if (time_context < 4 || time_context > 64 || time_context % 2 || F < 1 || F > 2049 || batch < 1 || batch > 1024)
         DCS_FAIL(DCS_EINVAL, "dcs_trainer_create: time_context %d (even, 4 .. 64), F %d (1 .. 2049), batch %d (1 .. 1024)",
                  time_context, F, batch);
@@ -778,6 +791,11 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
 
 DCS_API int dcs_trainer_destroy(dcs_trainer* t) {
     if (!t) return DCS_OK;
+    if (t->ik) {
+        const int rc = ik_trainer_destroy(t->ik);
+        delete t;
+        return rc;
+    }
     DCS_ON_DEVICE(t->ctx->device);
     DCS_HIP(hipStreamSynchronize(t->ctx->stream));
     trainer_free(t);
@@ -787,6 +805,7 @@ DCS_API int dcs_trainer_destroy(dcs_trainer* t) {
 DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float* targets_d, int mode, double* out7_d) {
     if (!t || !inputs_d || !targets_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: null argument");
     if (mode < 0 || mode > 2) DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: mode %d (0 loss, 1 gradients, 2 update)", mode);
+    if (t->ik) return ik_trainer_step(t->ik, inputs_d, targets_d, mode, out7_d);
     DCS_ON_DEVICE(t->ctx->device);
     DCS_CHECK(forward(t, inputs_d));
     DCS_CHECK(loss(t, inputs_d, targets_d, out7_d));
@@ -801,6 +820,7 @@ DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float*
 
 DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d) {
     if (!t || !inputs_d || !p_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_forward: null argument");
+    if (t->ik) return ik_trainer_forward(t->ik, inputs_d, p_d);
     DCS_ON_DEVICE(t->ctx->device);
     DCS_CHECK(forward(t, inputs_d));
     const int64_t n = 4 * t->R * t->F;
@@ -813,6 +833,7 @@ DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_
 DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams) {
     if (!t || !out_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: null argument");
     if (which < 0 || which > 3) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: which %d (0 params, 1 grads, 2 accu, 3 delta_accu)", which);
+    if (t->ik) return ik_trainer_get(t->ik, which, out_d, nparams);
     if (nparams != kNparams) DCS_FAIL(DCS_ESHAPE, "dcs_trainer_get: %d buffers for %d parameters", nparams, kNparams);
     for (int i = 0; i < kNparams; ++i)
         if (!out_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: buffer %d is null", i);

@@ -1,9 +1,10 @@
-"""Training of the DSD100 graph on the MI355X: the first half of the reference's ``train_auto``
-(examples/dsd100/trainCNN.py:132-263) and the data feed of ``dataset.LargeDataset`` (dataset.py:383-602).
+"""Training on the MI355X: the first half of the reference's ``train_auto`` for the DSD100 graph
+(examples/dsd100/trainCNN.py:132-263) and for the iKala singing-voice graph (examples/ikala/trainCNN.py:120-235, arch
+``'ikala_nopool'``), and the data feed of ``dataset.LargeDataset`` (dataset.py:383-602).
 
-``Trainer`` holds the 15 parameters, Adadelta's state and the baked-in uniform draw on the device and runs
-``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the six loss components) as HIP kernels
-(csrc/train_dsd.hip behind ``dcs_trainer_*``).  ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files
+``Trainer`` holds the parameters (15 for DSD, 13 for iKala), Adadelta's state and the baked-in uniform draw on the device
+and runs ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the loss components) as HIP kernels
+(csrc/train_dsd.hip and csrc/train_ikala.hip behind ``dcs_trainer_*``).  ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files
 resident on the device and cuts the reference's windows from them.  There is no CPU fallback.
 """
 import math
@@ -21,12 +22,24 @@ from .transform import read_shape_file
 EPS, ALPHA, BETA, BETA_VOC = 1e-8, 0.001, 0.01, 0.03
 LEARNING_RATE, RHO, ADA_EPSILON = 1.0, 0.95, 1e-6
 COMPONENTS = ("vocals", "bass", "drums", "negative", "alpha", "negative_voc")
+# examples/ikala/trainCNN.py:152-155; train_fn1's four components (:197)
+IKALA_EPS, IKALA_ALPHA, IKALA_BETA_ACC, IKALA_BETA_VOC = 1e-8, 0.9, 0.005, 0.02
+IKALA_COMPONENTS = ("vocals", "acc", "negative_voc", "negative_acc")
+TRAINABLE = ('dsd', 'ikala_nopool')
+
+
+def n_sources(arch):
+    """Targets / output channels of a trainable graph: 4 for DSD, 2 for iKala."""
+    return 2 if arch == 'ikala_nopool' else 4
 
 
 def param_shapes(arch, tc, F):
-    """The 15 .pkl shapes of build_ca (trainCNN.py:66-130); only the DSD graph trains here."""
+    """The .pkl shapes of build_ca: 15 for DSD (dsd100/trainCNN.py:66-130), 13 for 'ikala_nopool' (ikala/trainCNN.py:
+    66-118).  Only these two graphs train here."""
+    if arch == 'ikala_nopool':
+        return [tuple(s) for s in ARCHS['ikala_nopool'].param_shapes(tc, F)]
     if arch != 'dsd':
-        raise NotImplementedError("training is built for the DSD graph only, not %r" % (arch,))
+        raise NotImplementedError("training is built for the DSD and 'ikala_nopool' graphs only, not %r" % (arch,))
     kh = int(tc / 2)
     flat = 50 * (tc - kh + 1)
     shapes = [(50, 1, 1, F), (50,), (50,), (50, 50, kh, 1), (50,), (50,), (flat, 128), (128,)]
@@ -36,7 +49,7 @@ def param_shapes(arch, tc, F):
 
 
 def glorot_init(arch='dsd', tc=30, F=513, seed=0):
-    """Lasagne's defaults for build_ca (trainCNN.py:66-130): every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
+    """Lasagne's defaults for build_ca (either trainCNN.py): every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
     sqrt(2 / ((n1 + n2) * receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32."""
     rs = np.random.RandomState(seed)
     out = []
@@ -51,11 +64,13 @@ def glorot_init(arch='dsd', tc=30, F=513, seed=0):
 
 
 class Trainer(object):
-    """``train_fn`` / ``train_fn1`` of trainCNN.py:262-263 for the DSD graph, resident on one GPU.
+    """``train_fn`` / ``train_fn1`` of trainCNN.py:262-263 for the DSD graph, resident on one GPU; ``arch='ikala_nopool'``:
+    the same pair of examples/ikala/trainCNN.py:195-197 for the iKala graph.
 
-    ``params``: the 15 arrays in .pkl order (``load_model``), default :func:`glorot_init`.  ``rand``: the uniform draw of
-    trainCNN.py:180 ``[batch, 1, tc, F]``; default ``RandomState(seed).uniform``.  The batch size is fixed, as in the
-    reference's compiled graph."""
+    ``params``: the 15 (DSD) or 13 (iKala) arrays in .pkl order (``load_model``), default :func:`glorot_init`.  ``rand``: the
+    uniform draw of trainCNN.py:180 ``[batch, 1, tc, F]``; default ``RandomState(seed).uniform``.  The batch size is fixed,
+    as in the reference's compiled graph.  For iKala, ``beta`` is beta_acc, and loss hyper-parameters left at their DSD
+    defaults take iKala's values (ikala/trainCNN.py:152-155: eps 1e-8, alpha 0.9, beta_acc 0.005, beta_voc 0.02)."""
 
     def __init__(self, ctx=None, arch='dsd', params=None, batch_size=32, time_context=30, feat_size=513, seed=0,
                  rand=None, eps=EPS, alpha=ALPHA, beta=BETA, beta_voc=BETA_VOC, learning_rate=LEARNING_RATE, rho=RHO,
@@ -63,6 +78,12 @@ class Trainer(object):
         torch = require_gpu()
         self.ctx = ctx if ctx is not None else default_context()
         self.arch = arch
+        self.S = n_sources(arch)
+        if arch == 'ikala_nopool':
+            eps = IKALA_EPS if eps is EPS else eps
+            alpha = IKALA_ALPHA if alpha is ALPHA else alpha
+            beta = IKALA_BETA_ACC if beta is BETA else beta
+            beta_voc = IKALA_BETA_VOC if beta_voc is BETA_VOC else beta_voc
         self.B, self.tc, self.F = int(batch_size), int(time_context), int(feat_size)
         if params is None:
             params = glorot_init(arch, self.tc, self.F, seed)
@@ -98,14 +119,14 @@ class Trainer(object):
         t = targets if isinstance(targets, torch.Tensor) else self.ctx.to_device(targets, np.float32)
         x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
         t = t.to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        if tuple(x.shape) != (self.B, 1, self.tc, self.F) or tuple(t.shape) != (self.B, 4, self.tc, self.F):
-            raise ValueError("inputs %r / targets %r, the trainer takes (%d, 1, %d, %d) / (%d, 4, %d, %d)"
-                             % (tuple(x.shape), tuple(t.shape), self.B, self.tc, self.F, self.B, self.tc, self.F))
+        if tuple(x.shape) != (self.B, 1, self.tc, self.F) or tuple(t.shape) != (self.B, self.S, self.tc, self.F):
+            raise ValueError("inputs %r / targets %r, the trainer takes (%d, 1, %d, %d) / (%d, %d, %d, %d)"
+                             % (tuple(x.shape), tuple(t.shape), self.B, self.tc, self.F, self.B, self.S, self.tc, self.F))
         return x, t
 
     @_on_ctx_stream
     def run(self, inputs, targets, mode):
-        """``dcs_trainer_step``; returns the device tensor of (loss, six components) before any update."""
+        """``dcs_trainer_step``; returns the device tensor of (loss, components, zeros to 7) before any update."""
         x, t = self._io(inputs, targets)
         _lib.check(self.ctx._lib.dcs_trainer_step(self._h, _ptr(x), _ptr(t), int(mode), _ptr(self._out7)))
         self._last_io = (x, t)
@@ -116,11 +137,13 @@ class Trainer(object):
         return float(self.ctx.to_host(self.run(inputs, targets, 2))[0])
 
     def losses(self, inputs, targets):
-        """``train_fn1`` (trainCNN.py:263): vocals, bass, drums, negative, alpha, negative_voc at the current parameters."""
-        return [float(v) for v in self.ctx.to_host(self.run(inputs, targets, 0))[1:]]
+        """``train_fn1`` (trainCNN.py:263): vocals, bass, drums, negative, alpha, negative_voc at the current parameters;
+        iKala (ikala/trainCNN.py:197): vocals_error, acc_error, negative_error_voc, negative_error_acc."""
+        n = len(COMPONENTS) if self.arch == 'dsd' else len(IKALA_COMPONENTS)
+        return [float(v) for v in self.ctx.to_host(self.run(inputs, targets, 0))[1:1 + n]]
 
     def loss_and_gradients(self, inputs, targets):
-        """Testing aid: loss and the 15 gradients of |E| at the current parameters, no update."""
+        """Testing aid: loss and the gradients of |E| (one per parameter) at the current parameters, no update."""
         out = self.ctx.to_host(self.run(inputs, targets, 1)).copy()
         return out, self.gradients()
 
@@ -133,7 +156,7 @@ class Trainer(object):
         return [o.cpu().numpy() for o in outs]
 
     def params(self):
-        """``lasagne.layers.get_all_param_values`` (trainCNN.py:60): 15 float32 arrays in .pkl order."""
+        """``lasagne.layers.get_all_param_values`` (trainCNN.py:60): float32 arrays in .pkl order."""
         return self._get(0)
 
     def gradients(self):
@@ -146,15 +169,17 @@ class Trainer(object):
 
     @_on_ctx_stream
     def forward(self, inputs):
-        """``lasagne.layers.get_output(network2)``: ``[B, 4, tc, F]`` before masking (device tensor)."""
+        """``lasagne.layers.get_output(network2)``: ``[B, 4, tc, F]`` (iKala ``[B, 2, tc, F]``) before masking (device
+        tensor)."""
         torch = require_gpu()
-        x, _ = self._io(inputs, torch.zeros((self.B, 4, self.tc, self.F), dtype=torch.float32, device=self.ctx.device))
-        p = torch.empty((self.B, 4, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+        x, _ = self._io(inputs, torch.zeros((self.B, self.S, self.tc, self.F), dtype=torch.float32, device=self.ctx.device))
+        p = torch.empty((self.B, self.S, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
         _lib.check(self.ctx._lib.dcs_trainer_forward(self._h, _ptr(x), _ptr(p)))
         return p
 
     def save_model(self, path):
-        """trainCNN.py:59-64: the pickled list ``Network('dsd', ...)`` and separate_dsd.py load."""
+        """trainCNN.py:59-64: the pickled list ``Network('dsd', ...)`` and separate_dsd.py load (iKala: ``Network('ikala',
+        ...)``, ``Separator('ikala', ...)`` and separate_ikala.py, which resolve it to the no-pool graph)."""
         _save_model(path, self.params())
 
     def close(self):
@@ -194,16 +219,20 @@ def all_slots(T, tc, overlap):
 class FeatureWindows(object):
     """The training data of ``LargeDataset`` (dataset.py) resident on the device.
 
-    ``paths``: ``.data`` files of float64 ``[5, T, F]`` (mixture, vocals, bass, drums, other; each with its ``.shape``),
-    as examples/dsd100/compute_features.py writes them.  ``windows='reference'`` reproduces loadFile's slots, zero slots
+    ``paths``: ``.data`` files of float64 ``[1 + sources, T, F]`` (each with its ``.shape``): by default ``[5, T, F]``
+    (mixture, vocals, bass, drums, other) as examples/dsd100/compute_features.py writes them; ``sources=2``: ``[3, T, F]``
+    (mixture, voice, accompaniment) as examples/ikala/compute_features.py writes them.  ``windows='reference'`` reproduces loadFile's slots, zero slots
     included (at tc 30 / overlap 25 only about the first third of each 30 s chunk is used); ``'all'`` takes every full
     window.  ``batches(epoch)`` yields ``total // batch_size`` batches in the order of ``RandomState(seed + epoch)
     .permutation`` -- seeded, where the reference's shuffle is not."""
 
     def __init__(self, paths, time_context=30, overlap=25, mult_factor=0.3, windows='reference', batch_size=32, seed=0,
-                 ctx=None):
+                 ctx=None, sources=4):
         if windows not in ('reference', 'all'):
             raise ValueError("windows must be 'reference' or 'all'")
+        self.sources = int(sources)
+        if not 1 <= self.sources <= 8:
+            raise ValueError("sources must be 1 .. 8, got %r" % (sources,))
         self.tc, self.overlap, self.mult, self.batch_size, self.seed = int(time_context), int(overlap), float(mult_factor), \
             int(batch_size), int(seed)
         self.paths = list(paths)
@@ -211,8 +240,8 @@ class FeatureWindows(object):
         self.shapes, table = [], []
         for i, p in enumerate(self.paths):
             shp = read_shape_file(p.replace('.data', '.shape'))
-            if len(shp) != 3 or shp[0] != 5:
-                raise ValueError("%s: shape %r, expected (5, T, F)" % (p, shp))
+            if len(shp) != 3 or shp[0] != 1 + self.sources:
+                raise ValueError("%s: shape %r, expected (%d, T, F)" % (p, shp, 1 + self.sources))
             self.shapes.append(shp)
             table += [(i if s is not None else -1, s if s is not None else 0) for s in slots(shp[1], self.tc, self.overlap)]
         if len(set(s[2] for s in self.shapes)) > 1:
@@ -239,7 +268,7 @@ class FeatureWindows(object):
             self._files = torch.from_numpy(np.asarray(files, dtype=np.int64).reshape(-1, 2)).to(self.ctx.device)
 
     def gather(self, rows):
-        """Inputs ``[B, 1, tc, F]`` and targets ``[B, 4, tc, F]`` (device tensors) of the window-table rows ``rows``."""
+        """Inputs ``[B, 1, tc, F]`` and targets ``[B, sources, tc, F]`` (device tensors) of the window-table rows ``rows``."""
         self._upload()
         import torch
         win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
@@ -247,9 +276,14 @@ class FeatureWindows(object):
         with self.ctx.stream_scope():
             win_d = torch.from_numpy(win).to(self.ctx.device)
             x = torch.empty((B, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            t = torch.empty((B, 4, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            _lib.check(self.ctx._lib.dcs_trainer_gather(self.ctx._h, _ptr(self._data), _ptr(self._files), _ptr(win_d), B,
-                                                        self.tc, self.F, self.mult, _ptr(x), _ptr(t)))
+            t = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            if self.sources == 4:
+                _lib.check(self.ctx._lib.dcs_trainer_gather(self.ctx._h, _ptr(self._data), _ptr(self._files), _ptr(win_d), B,
+                                                            self.tc, self.F, self.mult, _ptr(x), _ptr(t)))
+            else:
+                _lib.check(self.ctx._lib.dcs_trainer_gather_sources(self.ctx._h, _ptr(self._data), _ptr(self._files),
+                                                                    _ptr(win_d), B, self.tc, self.F, self.sources,
+                                                                    self.mult, _ptr(x), _ptr(t)))
         return x, t
 
     def batches(self, epoch=0):

@@ -390,25 +390,34 @@ DCS_API int dcs_timing_stride(dcs_ctx* ctx, int stride);
 DCS_API int dcs_timing_reset(dcs_ctx* ctx);
 DCS_API int dcs_timing_query(dcs_ctx* ctx, int which, double* avg_ms, int64_t* launches);
 
-/* ------------------------------------------------------------------ training (examples/dsd100/trainCNN.py, csrc/train_dsd.hip) */
+/* ------------------------------------------------------------------ training (examples/dsd100/trainCNN.py, csrc/train_dsd.hip;
+ *                                                                     examples/ikala/trainCNN.py, csrc/train_ikala.hip) */
 /* The train_fn / train_fn1 pair of train_auto (trainCNN.py:132-263) for the DSD graph build_ca (:66-130; also what
- * examples/hiphopss/trainCNN.py trains).  Only arch DCS_ARCH_DSD; any other arch is DCS_EUNSUPPORTED.  time_context even in
- * [4, 64], F <= 2049, batch 1 .. 1024, else DCS_EINVAL.  params_d / shapes / nparams as for dcs_model_create (15 arrays, .pkl
+ * examples/hiphopss/trainCNN.py trains): arch DCS_ARCH_DSD, time_context even in [4, 64], F <= 2049, batch 1 .. 1024, else
+ * DCS_EINVAL; 15 arrays.  Or the pair of examples/ikala/trainCNN.py:120-197 for the iKala graph (:66-118): arch
+ * DCS_ARCH_IKALA_NOPOOL, time_context 10 .. 64 (conv2 is 10 rows high), F 87 .. 2049 (conv2's output keeps a column),
+ * batch 1 .. 1024, else DCS_EINVAL; 13 arrays.  Any other arch (DCS_ARCH_IKALA, the pooled graph of separate_ikala.py,
+ * included: the reference never trains it) is DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
  * order), copied into the trainer.  rand_d [batch][1][tc][F]: the uniform draw baked into the loss (trainCNN.py:174), copied.
- * hyper_h: eps, alpha, beta, beta_voc (:169-172), then adadelta's learning_rate, rho, epsilon (lasagne defaults 1, 0.95,
- * 1e-6).  Adadelta's accu / delta_accu start at zero (lasagne.updates.adadelta). */
+ * hyper_h: eps, alpha, beta, beta_voc (:169-172) -- for iKala eps, alpha, beta_acc, beta_voc (ikala/trainCNN.py:152-155) --
+ * then adadelta's learning_rate, rho, epsilon (lasagne defaults 1, 0.95, 1e-6).  Adadelta's accu / delta_accu start at zero
+ * (lasagne.updates.adadelta). */
 DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, int batch, const float* const* params_d,
                                const int64_t* shapes, int nparams, const float* rand_d, const double* hyper_h,
                                dcs_trainer** out);
 DCS_API int dcs_trainer_destroy(dcs_trainer* t);
-/* One step on inputs_d [batch][1][tc][F] and targets_d [batch][4][tc][F] (trainCNN.py:243-263), no host synchronisation:
- * mode 0 = train_fn1 (:263): forward, loss and components; 1 also the 15 gradients of |E| (Theano conventions: rectify'(0)
- * = 0.5, abs'(0) = 0); 2 = train_fn (:262): also the adadelta update (:223).  out7_d (device, nullable): 7 doubles, the loss
- * |E| then vocals, bass, drums, negative, alpha, negative_voc (:217, :263), all at the parameters BEFORE this step's update. */
+/* One step on inputs_d [batch][1][tc][F] and targets_d [batch][4][tc][F] (iKala: [batch][2][tc][F], voice then
+ * accompaniment) (trainCNN.py:243-263), no host synchronisation: mode 0 = train_fn1 (:263): forward, loss and components;
+ * 1 also the gradients of |E|, one per parameter (Theano conventions: rectify'(0) = 0.5, abs'(0) = 0); 2 = train_fn (:262):
+ * also the adadelta update (:223).  out7_d (device, nullable): 7 doubles, all at the parameters BEFORE this step's update:
+ * DSD the loss |E| then vocals, bass, drums, negative, alpha, negative_voc (:217, :263); iKala the loss |E| with E =
+ * vocals_error + acc_error - negative_error_voc, then vocals_error, acc_error, negative_error_voc, negative_error_acc
+ * (ikala/trainCNN.py:189, :197), then two zeros. */
 DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float* targets_d, int mode, double* out7_d);
-/* lasagne.layers.get_output(network2) (trainCNN.py:165) at the current parameters: p_d [batch][4][tc][F], before masking */
+/* lasagne.layers.get_output(network2) (trainCNN.py:165) at the current parameters: p_d [batch][4][tc][F] (iKala
+ * [batch][2][tc][F]), before masking */
 DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d);
-/* Copy one section of the trainer's state into 15 caller buffers in .pkl layout: which 0 = parameters
+/* Copy one section of the trainer's state into 15 (iKala 13) caller buffers in .pkl layout: which 0 = parameters
  * (get_all_param_values, trainCNN.py:59-64), 1 = the gradients of the last mode 1 / 2 step, 2 = adadelta accu,
  * 3 = adadelta delta_accu. */
 DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams);
@@ -419,6 +428,11 @@ DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int 
  * targets_d [batch][4][tc][F] = scale * sources (mult_factor_in / _out, :421-428). */
 DCS_API int dcs_trainer_gather(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d, int batch,
                                int time_context, int F, float scale, float* inputs_d, float* targets_d);
+/* dcs_trainer_gather for feature files of nsrc sources (1 .. 8): data_d holds [1 + nsrc][T_i][F] blocks (mixture, then
+ * the sources; iKala: mixture, voice, accompaniment, examples/ikala/compute_features.py), targets_d [batch][nsrc][tc][F]. */
+DCS_API int dcs_trainer_gather_sources(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d,
+                                       int batch, int time_context, int F, int nsrc, float scale, float* inputs_d,
+                                       float* targets_d);
 
 /* ------------------------------------------------------------------ memory-safety aid (tests/test_gpu_guard.py) */
 /* With DCS_WS_GUARD=<bytes> in the environment (read once per process) every scratch block libdcs allocates -- the

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) against the same float32 graph, loss and Adadelta written in
-torch and run with autograd on the same GPU.  Prints one JSON line per batch size.
+"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool, the iKala graph
+(csrc/train_ikala.hip) against the same float32 graph, loss and Adadelta written in torch and run with autograd on the same
+GPU.  Prints one JSON line per batch size.
 
-    python scripts/bench_train.py [--batches 32 256] [--steps 50] [--warmup 10]
+    python scripts/bench_train.py [--arch dsd|ikala_nopool] [--batches 32 256] [--steps 50] [--warmup 10]
 
 ms/step is wall time over --steps steps of train_fn (forward, loss, gradients, Adadelta; no host synchronisation inside
 the timed loop) divided by the steps, after --warmup steps; windows/s = batch / (ms/step).  A kernel breakdown comes from
@@ -22,15 +23,18 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # kernels per train_fn step: 6 forward GEMMs, loss + reduce, 5 backward GEMMs, 4 weight-gradient GEMMs, split-K reduce,
 # Adadelta (csrc/train_dsd.hip)
 LAUNCHES_PER_STEP = 19
+# iKala: 7 forward launches (F3 split-K GEMM + its sum), loss + reduce, 6 backward (B3 likewise), 4 weight-gradient GEMMs,
+# split-K reduce, Adadelta (csrc/train_ikala.hip)
+LAUNCHES_PER_STEP_IKALA = 21
 
 
-def bench_hip(B, tc, F, steps, warmup):
+def bench_hip(B, tc, F, steps, warmup, arch="dsd"):
     import torch
-    from deepconvsep_amd.training import Trainer, glorot_init
+    from deepconvsep_amd.training import Trainer, glorot_init, n_sources
     rs = np.random.RandomState(0)
-    t = Trainer(params=glorot_init("dsd", tc, F, 0), batch_size=B, time_context=tc, feat_size=F)
+    t = Trainer(arch=arch, params=glorot_init(arch, tc, F, 0), batch_size=B, time_context=tc, feat_size=F)
     x = torch.from_numpy((0.3 * rs.uniform(size=(B, 1, tc, F))).astype(np.float32)).cuda()
-    y = torch.from_numpy((0.1 * rs.uniform(size=(B, 4, tc, F))).astype(np.float32)).cuda()
+    y = torch.from_numpy((0.1 * rs.uniform(size=(B, n_sources(arch), tc, F))).astype(np.float32)).cuda()
     for _ in range(warmup):
         t.run(x, y, 2)
     torch.cuda.synchronize()
@@ -41,20 +45,22 @@ def bench_hip(B, tc, F, steps, warmup):
     return (time.perf_counter() - t0) * 1e3 / steps
 
 
-def bench_torch(B, tc, F, steps, warmup):
+def bench_torch(B, tc, F, steps, warmup, arch="dsd"):
     import torch
+    import train_ikala_ref
     import train_ref
-    from deepconvsep_amd.training import glorot_init
+    from deepconvsep_amd.training import glorot_init, n_sources
+    ref = train_ikala_ref if arch == "ikala_nopool" else train_ref
     rs = np.random.RandomState(0)
-    P = [torch.from_numpy(p).cuda().requires_grad_(True) for p in glorot_init("dsd", tc, F, 0)]
+    P = [torch.from_numpy(p).cuda().requires_grad_(True) for p in glorot_init(arch, tc, F, 0)]
     x = torch.from_numpy((0.3 * rs.uniform(size=(B, 1, tc, F))).astype(np.float32)).cuda()
-    y = torch.from_numpy((0.1 * rs.uniform(size=(B, 4, tc, F))).astype(np.float32)).cuda()
+    y = torch.from_numpy((0.1 * rs.uniform(size=(B, n_sources(arch), tc, F))).astype(np.float32)).cuda()
     r = torch.from_numpy(rs.uniform(size=(B, 1, tc, F)).astype(np.float32)).cuda()
     opt = torch.optim.Adadelta(P, lr=1.0, rho=0.95, eps=1e-6)
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = train_ref.components(train_ref.forward(P, x), x, y, r)[0]
+        loss = ref.components(ref.forward(P, x), x, y, r)[0]
         loss.backward()
         opt.step()
     for _ in range(warmup):
@@ -69,6 +75,7 @@ def bench_torch(B, tc, F, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", choices=("dsd", "ikala_nopool"), default="dsd")
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 256])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -76,10 +83,12 @@ def main():
     ap.add_argument("--feat_size", type=int, default=513)
     a = ap.parse_args()
     for B in a.batches:
-        ms = bench_hip(B, a.time_context, a.feat_size, a.steps, a.warmup)
-        tms = bench_torch(B, a.time_context, a.feat_size, a.steps, a.warmup)
-        print(json.dumps(dict(batch=B, time_context=a.time_context, feat_size=a.feat_size, hip_ms_per_step=round(ms, 4),
-                              hip_windows_per_s=round(B / ms * 1e3, 1), launches_per_step=LAUNCHES_PER_STEP,
+        ms = bench_hip(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
+        tms = bench_torch(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
+        extra = {} if a.arch == "dsd" else dict(arch=a.arch)
+        launches = LAUNCHES_PER_STEP if a.arch == "dsd" else LAUNCHES_PER_STEP_IKALA
+        print(json.dumps(dict(extra, batch=B, time_context=a.time_context, feat_size=a.feat_size, hip_ms_per_step=round(ms, 4),
+                              hip_windows_per_s=round(B / ms * 1e3, 1), launches_per_step=launches,
                               torch_ms_per_step=round(tms, 4), torch_windows_per_s=round(B / tms * 1e3, 1),
                               speedup=round(tms / ms, 3))), flush=True)
 
