@@ -1,0 +1,481 @@
+// The training core (train_core.h): the f32-MFMA GEMM template and its split-K helpers, Adadelta, rectify, the window
+// gather, and the dcs_trainer_* entry points.  One step on the ctx stream is forward, loss, backward (the graph's) and the
+// Adadelta update, with no host synchronisation and no float atomics: two runs give bit-identical weights.
+#include "train_core.h"
+
+using namespace train;
+
+namespace train {
+
+Ax ax3(int64_t d0, int64_t d1, int64_t s0, int64_t s1, int64_t s2) {
+    auto fdiv = [](int64_t d) {
+        uint32_t s = 0;
+        while ((int64_t(1) << s) < d) ++s;
+        const uint64_t one = 1;
+        return FDiv{(uint32_t)(((one << 32) * ((one << s) - (uint64_t)d)) / (uint64_t)d + 1), s};
+    };
+    const int64_t d01 = std::min<int64_t>(d0 * d1, kBig);
+    return Ax{fdiv(d0), fdiv(d01), (int)d0, (int)d1, s0, s1, s2};
+}
+
+Gemm gemm0(int M, int N, int K) {
+    Gemm g;
+    memset(&g, 0, sizeof(g));
+    g.M = M; g.N = N; g.K = K;
+    g.ones_row = kBig;
+    g.nbatch = 1;
+    g.splits = 1;
+    g.kchunk = K;
+    g.bias_cs = 1;
+    return g;
+}
+
+void pick_split(int64_t tiles, int64_t K, int* splits, int* kchunk, int64_t target, int64_t cap) {
+    int64_t s = target / (tiles > 0 ? tiles : 1);
+    s = s < 1 ? 1 : (s > cap ? cap : s);
+    int64_t kc = dcs_round_up((K + s - 1) / s, kKT);
+    if (kc < 256) kc = dcs_round_up(256 < K ? 256 : K, kKT);
+    *kchunk = (int)kc;
+    *splits = (int)((K + kc - 1) / kc);
+}
+
+__device__ __forceinline__ int fdq(int n, const FDiv f) {
+    return (int)((__umulhi((uint32_t)n, f.m) + (uint32_t)n) >> f.s);
+}
+
+__device__ __forceinline__ int64_t ax_off(const Ax& a, int i) {
+    const int q0 = fdq(i, a.q0), q2 = fdq(i, a.q01);
+    return (int64_t)(i - q0 * a.d0) * a.s0 + (int64_t)(q0 - q2 * a.d1) * a.s1 + (int64_t)q2 * a.s2;
+}
+
+__device__ __forceinline__ float relu_d(float pre) { return pre > 0.f ? 1.f : (pre == 0.f ? 0.5f : 0.f); }
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// AK: A is loaded K-fastest (lane = k), else M-fastest (lane = m); BK likewise for B (K-fastest, else N-fastest).
+template <int WM, int WN, int FM, int FN, bool AK, bool BK>
+__global__ __launch_bounds__(kThreads) void gemm_kernel(const Gemm g) {
+    constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
+    constexpr int NA = BM * kKT / kThreads, NB = BN * kKT / kThreads;
+    static_assert(WM * WN == 4, "four waves");
+    __shared__ float As[kKT][BM + 1];
+    __shared__ float Bs[kKT][BN + 1];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int wm = (wave / WN) * FM * 16, wn = (wave % WN) * FN * 16;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    const int batch = blockIdx.z / g.splits, split = blockIdx.z - batch * g.splits;
+    const int kbeg = split * g.kchunk;
+    const int kend = min(g.K, kbeg + g.kchunk);
+    const float* Ap = g.A.p + g.A.off + g.boff[batch][0];
+    const float* Bp = g.B.p + g.B.off + g.boff[batch][1];
+
+    // A: AK -> k = t % 32, rows t / 32 + 8 j;  else rows t % BM, k = t / BM + (256 / BM) j
+    const int akl = AK ? (t & 31) : t / BM;
+    const int aml = AK ? (t >> 5) : t % BM;
+    int64_t arow[AK ? NA : 1];
+    bool aok[AK ? NA : 1], aone[AK ? NA : 1];
+#pragma unroll
+    for (int j = 0; j < (AK ? NA : 1); ++j) {
+        const int m = m0 + aml + (AK ? 8 * j : 0);
+        aok[j] = m < g.M;
+        aone[j] = m >= g.ones_row;
+        arow[j] = (aok[j] && !aone[j]) ? ax_off(g.A.r, m) : 0;
+    }
+    // B: BK -> k = t % 32, columns t / 32 + 8 j;  else columns t % BN, k = t / BN + (256 / BN) j
+    const int bkl = BK ? (t & 31) : t / BN;
+    const int bnl = BK ? (t >> 5) : t % BN;
+    int64_t bcol[BK ? NB : 1];
+    bool bok[BK ? NB : 1];
+#pragma unroll
+    for (int j = 0; j < (BK ? NB : 1); ++j) {
+        const int n = n0 + bnl + (BK ? 8 * j : 0);
+        bok[j] = n < g.N;
+        bcol[j] = bok[j] ? ax_off(g.B.c, n) : 0;
+    }
+
+    float ra[NA], rb[NB];
+    auto load = [&](int k0) {
+        if constexpr (AK) {
+            const int ka = k0 + akl;
+            const bool kin = ka < kend;
+            const int64_t acol = kin ? ax_off(g.A.c, ka) : 0;
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                float v = 0.f;
+                if (aok[j] && kin) v = aone[j] ? (ka < g.ones_klim ? 1.f : 0.f) : Ap[arow[j] + acol];
+                ra[j] = v;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const int ka = k0 + akl + (kThreads / BM) * j;
+                float v = 0.f;
+                if (aok[0] && ka < kend) v = aone[0] ? (ka < g.ones_klim ? 1.f : 0.f) : Ap[arow[0] + ax_off(g.A.c, ka)];
+                ra[j] = v;
+            }
+        }
+        if constexpr (BK) {
+            const int kb = k0 + bkl;
+            const bool kin = kb < kend;
+            const int64_t brow = kin ? ax_off(g.B.r, kb) : 0;
+#pragma unroll
+            for (int j = 0; j < NB; ++j) rb[j] = (bok[j] && kin) ? Bp[brow + bcol[j]] : 0.f;
+        } else {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const int kb = k0 + bkl + (kThreads / BN) * j;
+                rb[j] = (bok[0] && kb < kend) ? Bp[ax_off(g.B.r, kb) + bcol[0]] : 0.f;
+            }
+        }
+    };
+
+    f32x4 acc[FM][FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    if (kbeg < kend) load(kbeg);
+    for (int k0 = kbeg; k0 < kend; k0 += kKT) {
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            if constexpr (AK) As[akl][aml + 8 * j] = ra[j];
+            else As[akl + (kThreads / BM) * j][aml] = ra[j];
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            if constexpr (BK) Bs[bkl][bnl + 8 * j] = rb[j];
+            else Bs[bkl + (kThreads / BN) * j][bnl] = rb[j];
+        }
+        __syncthreads();
+        if (k0 + kKT < kend) load(k0 + kKT);
+#pragma unroll
+        for (int s = 0; s < kKT / 4; ++s) {
+            const int kk = 4 * s + kq;
+            float a[FM], b[FN];
+#pragma unroll
+            for (int i = 0; i < FM; ++i) a[i] = As[kk][wm + 16 * i + r16];
+#pragma unroll
+            for (int j = 0; j < FN; ++j) b[j] = Bs[kk][wn + 16 * j + r16];
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    // C/D map of the 16x16 tile: column = lane & 15, row = 4 (lane >> 4) + reg
+    const float sc = g.scale ? *g.scale : 1.f;
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int m = m0 + wm + 16 * i + 4 * kq + reg;
+                const int n = n0 + wn + 16 * j + r16;
+                if (m >= g.M || n >= g.N) continue;
+                float v = acc[i][j][reg];
+                if (g.partial) {
+                    g.partial[((int64_t)blockIdx.z * g.M + m) * g.N + n] = v;
+                    continue;
+                }
+                v *= sc;
+                if (g.bias) v += g.bias[g.boff[batch][4] + (int64_t)n * g.bias_cs];
+                if (g.bias2) v += g.bias2[g.boff[batch][4] + (int64_t)n * g.bias_cs];
+                if (g.epi & (EPI_SAVEPRE | EPI_DRELU)) {
+                    float* x = g.X.p + g.X.off + g.boff[batch][3] + ax_off(g.X.r, m) + ax_off(g.X.c, n);
+                    if (g.epi & EPI_SAVEPRE) *x = v;
+                    else v *= relu_d(*x);
+                }
+                if (g.epi & EPI_RELU) v = v > 0.f ? v : 0.f;
+                g.C.p[g.C.off + g.boff[batch][2] + ax_off(g.C.r, m) + ax_off(g.C.c, n)] = v;
+            }
+}
+
+__global__ __launch_bounds__(kThreads) void finish_kernel(const float* __restrict__ part, int splits, int64_t count, int N,
+                                                          const float* bias, float* C, float* X, int epi) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    float s = 0.f;
+    for (int z = 0; z < splits; ++z) s += part[z * count + i];
+    if (bias) s += bias[i % N];
+    if (epi & EPI_SAVEPRE) X[i] = s;
+    if (epi & EPI_DRELU) s *= relu_d(X[i]);
+    if (epi & EPI_RELU) s = s > 0.f ? s : 0.f;
+    C[i] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void reduce_kernel(const Reduce r) {
+    const int j = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= r.count[j]) return;
+    float s = 0.f;
+    for (int z = 0; z < r.splits[j]; ++z) s += r.part[j][z * r.count[j] + i];
+    s *= *r.scale;
+    r.dst[j][i] = s;
+    if (r.dup[j] && i >= r.count[j] - r.N[j]) r.dst[j][i + r.N[j]] = s;
+}
+
+// lasagne.updates.adadelta (lasagne/updates.py adadelta): accu' = rho accu + (1 - rho) g^2,
+// u = g sqrt(delta + eps) / sqrt(accu' + eps), p -= lr u, delta' = rho delta + (1 - rho) u^2.  P4: the section length in
+// float4s (sections are padded to a multiple of four floats; the pad stays zero).
+__global__ __launch_bounds__(kThreads) void adadelta_kernel(float4* __restrict__ state, int64_t P4, float lr, float rho,
+                                                            float eps) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= P4) return;
+    const float4 g = state[P4 + i];
+    float4 p = state[i], acc = state[2 * P4 + i], del = state[3 * P4 + i];
+    float* pp = &p.x;
+    float* pa = &acc.x;
+    float* pd = &del.x;
+    const float* pg = &g.x;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const float gi = pg[l];
+        const float a = rho * pa[l] + (1.f - rho) * gi * gi;
+        const float u = gi * sqrtf(pd[l] + eps) / sqrtf(a + eps);
+        pp[l] = pp[l] - lr * u;
+        pa[l] = a;
+        pd[l] = rho * pd[l] + (1.f - rho) * u * u;
+    }
+    state[i] = p;
+    state[2 * P4 + i] = acc;
+    state[3 * P4 + i] = del;
+}
+
+__global__ __launch_bounds__(kThreads) void relu_kernel(const float* __restrict__ q, float* __restrict__ p, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) p[i] = q[i] > 0.f ? q[i] : 0.f;
+}
+
+// (file, start) windows of the resident [1 + nsrc][T][F] feature files -> network inputs and targets (dataset.py loadFile /
+// initOutput): data [sum_i (1 + nsrc) T_i F] float32, file i at files[2 i] with T_i = files[2 i + 1] frames; win [B][2];
+// file < 0: an all-zero window; frames past T_i are zero (the padded window of a file shorter than tc).
+__global__ __launch_bounds__(kThreads) void gather_kernel(const float* __restrict__ data, const int64_t* __restrict__ files,
+                                                          const int* __restrict__ win, int B, int tc, int F, int nsrc,
+                                                          float scale, float* __restrict__ inputs,
+                                                          float* __restrict__ targets) {
+    const int64_t plane = (int64_t)tc * F;
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= (int64_t)B * plane) return;
+    const int b = (int)(e / plane);
+    const int64_t rem = e - b * plane;
+    const int t = (int)(rem / F), f = (int)(rem - (int64_t)t * F);
+    const int fi = win[2 * b], start = win[2 * b + 1];
+    const int64_t fr = (int64_t)start + t;
+    int64_t base = 0, T = 0;
+    bool live = false;
+    if (fi >= 0) {
+        base = files[2 * fi];
+        T = files[2 * fi + 1];
+        live = fr < T;
+    }
+    for (int c = 0; c <= nsrc; ++c) {
+        const float v = live ? scale * data[base + ((int64_t)c * T + fr) * F + f] : 0.f;
+        if (c == 0) inputs[e] = v;
+        else targets[((int64_t)b * nsrc + c - 1) * plane + rem] = v;
+    }
+}
+
+}  // namespace train
+
+namespace {
+
+template <int WM, int WN, int FM, int FN>
+void launch_tile(const Gemm& g, bool ak, bool bk, dim3 grid, hipStream_t s) {
+    if (ak && bk) hipLaunchKernelGGL((gemm_kernel<WM, WN, FM, FN, true, true>), grid, dim3(kThreads), 0, s, g);
+    else if (ak) hipLaunchKernelGGL((gemm_kernel<WM, WN, FM, FN, true, false>), grid, dim3(kThreads), 0, s, g);
+    else if (bk) hipLaunchKernelGGL((gemm_kernel<WM, WN, FM, FN, false, true>), grid, dim3(kThreads), 0, s, g);
+    else hipLaunchKernelGGL((gemm_kernel<WM, WN, FM, FN, false, false>), grid, dim3(kThreads), 0, s, g);
+}
+
+int gather(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d, int batch, int time_context, int F,
+           int nsrc, float scale, float* inputs_d, float* targets_d) {
+    DCS_ON_DEVICE(ctx->device);
+    const int64_t n = (int64_t)batch * time_context * F;
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, ctx->stream, data_d, files_d,
+                       windows_d, batch, time_context, F, nsrc, scale, inputs_d, targets_d);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+void trainer_free(dcs_trainer* t) {
+    if (!t) return;
+    dcs_dev_free(t->state);
+    dcs_dev_free(t->work);
+    delete t;
+}
+
+}  // namespace
+
+int dcs_trainer::launch(Gemm g, Tile tile, bool ak, bool bk) {
+    if (g.splits < 1) g.splits = 1;
+    if (g.splits == 1) g.kchunk = g.K;
+    const int bm = tile == T128x32 ? 128 : (tile == T64x64 ? 64 : 32), bn = tile == T64x64 ? 64 : 32;
+    dim3 grid((unsigned)dcs_cdiv(g.M, bm), (unsigned)dcs_cdiv(g.N, bn), (unsigned)(g.nbatch * g.splits));
+    hipStream_t s = ctx->stream;
+    if (tile == T128x32) launch_tile<4, 1, 2, 2>(g, ak, bk, grid, s);
+    else if (tile == T64x64) launch_tile<2, 2, 2, 2>(g, ak, bk, grid, s);
+    else launch_tile<2, 2, 1, 1>(g, ak, bk, grid, s);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+int dcs_trainer::finish(const float* part, int splits, int N, const float* bias, float* C, float* X, int epi) {
+    const int64_t count = (int64_t)B * N;
+    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)dcs_cdiv(count, kThreads)), dim3(kThreads), 0, ctx->stream, part, splits,
+                       count, N, bias, C, X, epi);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+int dcs_trainer::reduce(const Reduce& r) {
+    const int64_t most = std::max(r.count[0], r.count[1]);
+    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)dcs_cdiv(most, kThreads), 2), dim3(kThreads), 0, ctx->stream, r);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+// The graphs, one per file: range checks with their message, then a trainer with its geometry, nsrc, nparams, shapes and
+// loss_sums set.
+int dsd_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
+int ikala_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
+
+extern "C" {
+
+DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, int batch, const float* const* params_d,
+                               const int64_t* shapes, int nparams, const float* rand_d, const double* hyper_h,
+                               dcs_trainer** out) {
+    if (!ctx || !out || !rand_d || !hyper_h) DCS_FAIL(DCS_EINVAL, "dcs_trainer_create: null argument");
+    *out = nullptr;
+    dcs_trainer* t = nullptr;
+    if (arch == DCS_ARCH_DSD) DCS_CHECK(dsd_trainer_new(time_context, F, batch, &t));
+    else if (arch == DCS_ARCH_IKALA_NOPOOL) DCS_CHECK(ikala_trainer_new(time_context, F, batch, &t));
+    else
+        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d) and the no-pool iKala graph (arch %d) "
+                 "train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL);
+    // from here on every return frees t
+    struct Guard {
+        dcs_trainer* t;
+        ~Guard() { trainer_free(t); }
+    } guard{t};
+    if (!params_d || !shapes || nparams != t->nparams)
+        DCS_FAIL(DCS_ESHAPE, "mismatch: got %d values to set %d parameters", nparams, t->nparams);
+    for (int i = 0; i < nparams; ++i) {
+        if (!params_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_create: parameter %d is null", i);
+        const int64_t* want = t->shapes[i];
+        for (int k = 0; k < 4; ++k)
+            if (shapes[4 * i + k] != want[k])
+                DCS_FAIL(DCS_ESHAPE, "mismatch: parameter %d has shape (%lld, %lld, %lld, %lld) but value to set has shape "
+                         "(%lld, %lld, %lld, %lld)", i, (long long)want[0], (long long)want[1], (long long)want[2],
+                         (long long)want[3], (long long)shapes[4 * i], (long long)shapes[4 * i + 1],
+                         (long long)shapes[4 * i + 2], (long long)shapes[4 * i + 3]);
+    }
+    DCS_ON_DEVICE(ctx->device);
+    t->ctx = ctx;
+    t->tc = time_context; t->F = F; t->B = batch;
+    t->RF = (int64_t)batch * time_context * F;
+    memcpy(t->hyp, hyper_h, sizeof(t->hyp));
+    for (int i = 0; i < nparams; ++i)
+        t->off[i + 1] = t->off[i] + t->shapes[i][0] * t->shapes[i][1] * t->shapes[i][2] * t->shapes[i][3];
+    t->P = t->off[nparams];
+    t->P4 = dcs_cdiv(t->P, 4);
+
+    // one work buffer: the views, each rounded to 64 floats, then the f64 loss sums and out7
+    std::vector<std::pair<float**, int64_t>> parts = {{&t->rnd, t->RF}, {&t->sign, 1}};
+    t->plan(parts);
+    int64_t total = 0;
+    for (auto& p : parts) total += dcs_round_up(p.second, 64);
+    const int64_t dbl = (int64_t)kLossBlocks * t->loss_sums + 8;
+    hipError_t e = dcs_dev_alloc((void**)&t->state, 16 * t->P4 * sizeof(float), "trainer state");
+    if (e == hipSuccess) e = dcs_dev_alloc((void**)&t->work, total * sizeof(float) + dbl * sizeof(double), "trainer work");
+    if (e != hipSuccess)
+        DCS_FAIL(e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP, "dcs_trainer_create: device allocation failed: %s",
+                 hipGetErrorString(e));
+    int64_t at = 0;
+    for (auto& p : parts) {
+        *p.first = t->work + at;
+        at += dcs_round_up(p.second, 64);
+    }
+    t->lpart = (double*)(t->work + at);
+    t->out7 = t->lpart + (int64_t)kLossBlocks * t->loss_sums;
+    // zero everything (the graph's zero padding stays zero for good; grads, accu, delta_accu and the section pads start at
+    // zero), then the params
+    if (hipMemsetAsync(t->work, 0, total * sizeof(float) + dbl * sizeof(double), ctx->stream) != hipSuccess ||
+        hipMemsetAsync(t->state, 0, 16 * t->P4 * sizeof(float), ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(t->rnd, rand_d, t->RF * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        DCS_FAIL(DCS_EHIP, "dcs_trainer_create: initialisation failed");
+    DCS_CHECK(t->layout(t->state, (float* const*)params_d, 1));
+    guard.t = nullptr;
+    *out = t;
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_destroy(dcs_trainer* t) {
+    if (!t) return DCS_OK;
+    DCS_ON_DEVICE(t->ctx->device);
+    DCS_HIP(hipStreamSynchronize(t->ctx->stream));
+    trainer_free(t);
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float* targets_d, int mode, double* out7_d) {
+    if (!t || !inputs_d || !targets_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: null argument");
+    if (mode < 0 || mode > 2) DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: mode %d (0 loss, 1 gradients, 2 update)", mode);
+    DCS_ON_DEVICE(t->ctx->device);
+    DCS_CHECK(t->forward(inputs_d));
+    DCS_CHECK(t->loss(inputs_d, targets_d, out7_d));
+    if (mode == 0) return DCS_OK;
+    DCS_CHECK(t->backward());
+    if (mode == 1) return DCS_OK;
+    hipLaunchKernelGGL(adadelta_kernel, dim3((unsigned)dcs_cdiv(t->P4, kThreads)), dim3(kThreads), 0, t->ctx->stream,
+                       (float4*)t->state, t->P4, (float)t->hyp[4], (float)t->hyp[5], (float)t->hyp[6]);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d) {
+    if (!t || !inputs_d || !p_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_forward: null argument");
+    DCS_ON_DEVICE(t->ctx->device);
+    DCS_CHECK(t->forward(inputs_d));
+    const int64_t n = t->nsrc * t->RF;
+    hipLaunchKernelGGL(relu_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, t->ctx->stream,
+                       (const float*)t->Q, p_d, n);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams) {
+    if (!t || !out_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: null argument");
+    if (which < 0 || which > 3) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: which %d (0 params, 1 grads, 2 accu, 3 delta_accu)", which);
+    if (nparams != t->nparams) DCS_FAIL(DCS_ESHAPE, "dcs_trainer_get: %d buffers for %d parameters", nparams, t->nparams);
+    for (int i = 0; i < nparams; ++i)
+        if (!out_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: buffer %d is null", i);
+    DCS_ON_DEVICE(t->ctx->device);
+    return t->layout(t->state + which * 4 * t->P4, out_d, 0);
+}
+
+DCS_API int dcs_trainer_gather(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d, int batch,
+                               int time_context, int F, float scale, float* inputs_d, float* targets_d) {
+    if (!ctx || !data_d || !files_d || !windows_d || !inputs_d || !targets_d)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather: null argument");
+    if (batch < 1 || time_context < 1 || F < 1) DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather: batch %d, time_context %d, F %d",
+                                                          batch, time_context, F);
+    return gather(ctx, data_d, files_d, windows_d, batch, time_context, F, 4, scale, inputs_d, targets_d);
+}
+
+DCS_API int dcs_trainer_gather_sources(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d,
+                                       int batch, int time_context, int F, int nsrc, float scale, float* inputs_d,
+                                       float* targets_d) {
+    if (!ctx || !data_d || !files_d || !windows_d || !inputs_d || !targets_d)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_sources: null argument");
+    if (batch < 1 || time_context < 1 || F < 1 || nsrc < 1 || nsrc > 8)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_sources: batch %d, time_context %d, F %d, nsrc %d (1 .. 8)", batch,
+                 time_context, F, nsrc);
+    return gather(ctx, data_d, files_d, windows_d, batch, time_context, F, nsrc, scale, inputs_d, targets_d);
+}
+
+}  // extern "C"

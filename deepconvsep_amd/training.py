@@ -4,8 +4,9 @@
 
 ``Trainer`` holds the parameters (15 for DSD, 13 for iKala), Adadelta's state and the baked-in uniform draw on the device
 and runs ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the loss components) as HIP kernels
-(csrc/train_dsd.hip and csrc/train_ikala.hip behind ``dcs_trainer_*``).  ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files
-resident on the device and cuts the reference's windows from them.  There is no CPU fallback.
+(the shared core csrc/train_core.hip behind ``dcs_trainer_*``, the graphs in csrc/train_dsd.hip and csrc/train_ikala.hip).
+``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files resident on the device and cuts the reference's windows
+from them.  There is no CPU fallback.
 """
 import math
 from ctypes import byref, c_double, c_int64, c_void_p

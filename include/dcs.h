@@ -390,8 +390,8 @@ DCS_API int dcs_timing_stride(dcs_ctx* ctx, int stride);
 DCS_API int dcs_timing_reset(dcs_ctx* ctx);
 DCS_API int dcs_timing_query(dcs_ctx* ctx, int which, double* avg_ms, int64_t* launches);
 
-/* ------------------------------------------------------------------ training (examples/dsd100/trainCNN.py, csrc/train_dsd.hip;
- *                                                                     examples/ikala/trainCNN.py, csrc/train_ikala.hip) */
+/* ------------------------------------------------------------------ training (csrc/train_core.hip; examples/dsd100/trainCNN.py:
+ *                                                                     csrc/train_dsd.hip; examples/ikala/trainCNN.py: csrc/train_ikala.hip) */
 /* The train_fn / train_fn1 pair of train_auto (trainCNN.py:132-263) for the DSD graph build_ca (:66-130; also what
  * examples/hiphopss/trainCNN.py trains): arch DCS_ARCH_DSD, time_context even in [4, 64], F <= 2049, batch 1 .. 1024, else
  * DCS_EINVAL; 15 arrays.  Or the pair of examples/ikala/trainCNN.py:120-197 for the iKala graph (:66-118): arch

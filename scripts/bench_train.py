@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool, the iKala graph
-(csrc/train_ikala.hip) against the same float32 graph, loss and Adadelta written in torch and run with autograd on the same
-GPU.  Prints one JSON line per batch size.
+(csrc/train_ikala.hip), both on the shared core csrc/train_core.hip, against the same float32 graph, loss and Adadelta
+written in torch and run with autograd on the same GPU.  Prints one JSON line per batch size.
 
     python scripts/bench_train.py [--arch dsd|ikala_nopool] [--batches 32 256] [--steps 50] [--warmup 10]
 
@@ -21,10 +21,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 # kernels per train_fn step: 6 forward GEMMs, loss + reduce, 5 backward GEMMs, 4 weight-gradient GEMMs, split-K reduce,
-# Adadelta (csrc/train_dsd.hip)
+# Adadelta (the graph's launches in csrc/train_dsd.hip, Adadelta in csrc/train_core.hip)
 LAUNCHES_PER_STEP = 19
 # iKala: 7 forward launches (F3 split-K GEMM + its sum), loss + reduce, 6 backward (B3 likewise), 4 weight-gradient GEMMs,
-# split-K reduce, Adadelta (csrc/train_ikala.hip)
+# split-K reduce, Adadelta (csrc/train_ikala.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_IKALA = 21
 
 
