@@ -21,7 +21,7 @@ constexpr int kThreads = 256;
 constexpr int kKT = 32;
 constexpr int kBig = 1 << 30;
 constexpr int kLossBlocks = 1024;
-constexpr int kMaxParams = 16;
+constexpr int kMaxParams = 17;
 
 // n / d for 0 <= n < 2^31 as (umulhi(n, m) + n) >> s (round-up magic numbers)
 struct FDiv {
@@ -137,6 +137,36 @@ __global__ __launch_bounds__(kThreads) void loss_reduce_kernel(const double* __r
         *sign = sg;
         for (int j = 0; j < G::kDbo; ++j) dbo[j] = sg * (float)red[G::kOut + j][0];
     }
+}
+
+// conv1^T (the InverseLayer of a 1 x K1 conv1 of C1 filters, stride (1, S1)) plus the output BiasLayer, for NS sources:
+// q[b][k][t][f] = bo[k] + sum over the taps S1 w + j = f of sum_c g_k[b][t][w][c] W1i[j][c], w and c ascending (one
+// thread per output, fixed order).  Columns f > S1 (w1 - 1) + K1 - 1 get no tap and hold bo alone.  g_k = g + k gslot.
+template <int K1, int C1, int S1, int NS>
+__global__ __launch_bounds__(kThreads) void deconv1_kernel(const float* __restrict__ g, int64_t gslot,
+                                                           const float* __restrict__ W1i, const float* __restrict__ bo,
+                                                           float* __restrict__ q, int B, int tc, int F, int w1) {
+    __shared__ float w[K1 * C1];
+    for (int i = threadIdx.x; i < K1 * C1; i += kThreads) w[i] = W1i[i];
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= (int64_t)B * NS * tc * F) return;
+    const int f = (int)(e % F);
+    int64_t r = e / F;
+    const int t = (int)(r % tc);
+    r /= tc;
+    const int k = (int)(r % NS), b = (int)(r / NS);
+    const float* gr = g + k * gslot + ((int64_t)b * tc + t) * w1 * C1;
+    const int wlo = f >= K1 - 1 ? (f - (K1 - 1) + S1 - 1) / S1 : 0;
+    const int whi = min(w1 - 1, f / S1);
+    float acc = 0.f;
+    for (int x = wlo; x <= whi; ++x) {
+        const float* gw = gr + (int64_t)x * C1;
+        const float* ww = w + (f - S1 * x) * C1;
+#pragma unroll
+        for (int c = 0; c < C1; ++c) acc += gw[c] * ww[c];
+    }
+    q[e] = acc + bo[k];
 }
 
 // map(s, k): the .pkl index of element k of the internal section s

@@ -343,6 +343,7 @@ int dcs_trainer::reduce(const Reduce& r) {
 // loss_sums set.
 int dsd_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int ikala_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
+int bach10_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 
 extern "C" {
 
@@ -354,9 +355,10 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     dcs_trainer* t = nullptr;
     if (arch == DCS_ARCH_DSD) DCS_CHECK(dsd_trainer_new(time_context, F, batch, &t));
     else if (arch == DCS_ARCH_IKALA_NOPOOL) DCS_CHECK(ikala_trainer_new(time_context, F, batch, &t));
+    else if (arch == DCS_ARCH_BACH10) DCS_CHECK(bach10_trainer_new(time_context, F, batch, &t));
     else
-        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d) and the no-pool iKala graph (arch %d) "
-                 "train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL);
+        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d), the no-pool iKala graph (arch %d) and "
+                 "the Bach10 graph (arch %d) train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10);
     // from here on every return frees t
     struct Guard {
         dcs_trainer* t;

@@ -9,7 +9,7 @@
 //             F3 z = rectify(a2b . Wfc + bfc)          gemm 32x32 split-K over flat, finish (saved: z, pre-activation)
 //             F4 d_k = rectify(z . W_k + b_k), k < 2   gemm, 2 batches, into the zero-padded V (saved: pre-activations)
 //             F5 g_k = conv2^T(d_k)                    gemm 128x32  implicit GEMM over V (9 / 19 zero rows / columns)
-//             F6 q = conv1^T(g_k) + bo                 ik_deconv1_kernel: 10 taps x 30 channels per output, fixed order
+//             F6 q = conv1^T(g_k) + bo                 train::deconv1_kernel: 10 taps x 30 channels per output, fixed order
 //   loss      ik_loss_kernel: masks, the four components, dE/dq (rectify' with the 0.5 tie), per-workgroup f64 sums
 //             train::loss_reduce_kernel: fixed-order sum -> loss and components (f64), sign(E), the output-bias gradient
 //   backward  B1 dg_k = conv1(dY_k)    B2 dpre_k = conv2(dg_k) * r'(pre_k)    B3 dprez = (sum_k dpre_k . W_k^T) * r'(prez)
@@ -49,34 +49,6 @@ struct IkalaSums {
     static __device__ double E(const double* s) { return s[0] + s[1] - s[2]; }
 };
 constexpr int kLossSums = IkalaSums::kOut + IkalaSums::kDbo;
-
-// conv1^T (the InverseLayer of conv1) plus the output BiasLayer: q[b][k][t][f] = bo[k] + sum over the taps 3 w + j = f of
-// sum_c g_k[b][t][w][c] W1i[j][c], w and c ascending.  Columns f > 3 (w1 - 1) + 29 get no tap and hold bo alone.
-__global__ __launch_bounds__(kThreads) void ik_deconv1_kernel(const float* __restrict__ g, int64_t gslot,
-                                                              const float* __restrict__ W1i, const float* __restrict__ bo,
-                                                              float* __restrict__ q, int B, int tc, int F, int w1) {
-    __shared__ float w[kK1 * kC1];
-    for (int i = threadIdx.x; i < kK1 * kC1; i += kThreads) w[i] = W1i[i];
-    __syncthreads();
-    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (e >= (int64_t)B * 2 * tc * F) return;
-    const int f = (int)(e % F);
-    int64_t r = e / F;
-    const int t = (int)(r % tc);
-    r /= tc;
-    const int k = (int)(r % 2), b = (int)(r / 2);
-    const float* gr = g + k * gslot + ((int64_t)b * tc + t) * w1 * kC1;
-    const int wlo = f >= kK1 - 1 ? (f - (kK1 - 1) + kS1 - 1) / kS1 : 0;
-    const int whi = min(w1 - 1, f / kS1);
-    float acc = 0.f;
-    for (int x = wlo; x <= whi; ++x) {
-        const float* gw = gr + (int64_t)x * kC1;
-        const float* ww = w + (f - kS1 * x) * kC1;
-#pragma unroll
-        for (int c = 0; c < kC1; ++c) acc += gw[c] * ww[c];
-    }
-    q[e] = acc + bo[k];
-}
 
 struct ILoss {
     const float* q;       // [B][2][tc F] pre-activations of the output layer
@@ -248,9 +220,9 @@ struct IkalaTrainer : dcs_trainer {
         // F6: q = conv1^T(g_k) + bo
         {
             const int64_t n = 2 * (int64_t)B * tc * F;
-            hipLaunchKernelGGL(ik_deconv1_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, ctx->stream,
-                               (const float*)(GA + Uslot), Uslot, (const float*)param(0), (const float*)param(12), Q, B, tc,
-                               F, w1);
+            hipLaunchKernelGGL((deconv1_kernel<kK1, kC1, kS1, 2>), dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads),
+                               0, ctx->stream, (const float*)(GA + Uslot), Uslot, (const float*)param(0),
+                               (const float*)param(12), Q, B, tc, F, w1);
             DCS_HIP(hipGetLastError());
         }
         return DCS_OK;

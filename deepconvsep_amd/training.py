@@ -1,10 +1,12 @@
 """Training on the MI355X: the first half of the reference's ``train_auto`` for the DSD100 graph
-(examples/dsd100/trainCNN.py:132-263) and for the iKala singing-voice graph (examples/ikala/trainCNN.py:120-235, arch
-``'ikala_nopool'``), and the data feed of ``dataset.LargeDataset`` (dataset.py:383-602).
+(examples/dsd100/trainCNN.py:132-263), for the iKala singing-voice graph (examples/ikala/trainCNN.py:120-235, arch
+``'ikala_nopool'``) and for the Bach10 graph (examples/bach10/trainCNNbach10.py:126-254, the graph trainCNNrwc.py and
+trainCNNSibelius.py train too), and the data feed of ``dataset.LargeDataset`` (dataset.py:383-602).
 
-``Trainer`` holds the parameters (15 for DSD, 13 for iKala), Adadelta's state and the baked-in uniform draw on the device
-and runs ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the loss components) as HIP kernels
-(the shared core csrc/train_core.hip behind ``dcs_trainer_*``, the graphs in csrc/train_dsd.hip and csrc/train_ikala.hip).
+``Trainer`` holds the parameters (15 for DSD, 13 for iKala, 17 for Bach10), Adadelta's state and the baked-in uniform draw on
+the device and runs ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the loss components) as HIP kernels
+(the shared core csrc/train_core.hip behind ``dcs_trainer_*``, the graphs in csrc/train_dsd.hip, csrc/train_ikala.hip and
+csrc/train_bach10.hip).
 ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files resident on the device and cuts the reference's windows
 from them.  There is no CPU fallback.
 """
@@ -26,21 +28,24 @@ COMPONENTS = ("vocals", "bass", "drums", "negative", "alpha", "negative_voc")
 # examples/ikala/trainCNN.py:152-155; train_fn1's four components (:197)
 IKALA_EPS, IKALA_ALPHA, IKALA_BETA_ACC, IKALA_BETA_VOC = 1e-8, 0.9, 0.005, 0.02
 IKALA_COMPONENTS = ("vocals", "acc", "negative_voc", "negative_acc")
-TRAINABLE = ('dsd', 'ikala_nopool')
+# examples/bach10/trainCNNbach10.py:160 (alpha of :161 is never used); train_fn1's four errors (:206, :249-252)
+BACH10_EPS = 1e-18
+BACH10_COMPONENTS = ('bassoon', 'clarinet', 'saxophone', 'violin')
+TRAINABLE = ('dsd', 'ikala_nopool', 'bach10')
 
 
 def n_sources(arch):
-    """Targets / output channels of a trainable graph: 4 for DSD, 2 for iKala."""
+    """Targets / output channels of a trainable graph: 4 for DSD and Bach10, 2 for iKala."""
     return 2 if arch == 'ikala_nopool' else 4
 
 
 def param_shapes(arch, tc, F):
     """The .pkl shapes of build_ca: 15 for DSD (dsd100/trainCNN.py:66-130), 13 for 'ikala_nopool' (ikala/trainCNN.py:
-    66-118).  Only these two graphs train here."""
-    if arch == 'ikala_nopool':
-        return [tuple(s) for s in ARCHS['ikala_nopool'].param_shapes(tc, F)]
+    66-118), 17 for 'bach10' (bach10/trainCNNbach10.py:66-123).  Only these three graphs train here."""
+    if arch in ('ikala_nopool', 'bach10'):
+        return [tuple(s) for s in ARCHS[arch].param_shapes(tc, F)]
     if arch != 'dsd':
-        raise NotImplementedError("training is built for the DSD and 'ikala_nopool' graphs only, not %r" % (arch,))
+        raise NotImplementedError("training is built for the DSD, 'ikala_nopool' and 'bach10' graphs only, not %r" % (arch,))
     kh = int(tc / 2)
     flat = 50 * (tc - kh + 1)
     shapes = [(50, 1, 1, F), (50,), (50,), (50, 50, kh, 1), (50,), (50,), (flat, 128), (128,)]
@@ -50,7 +55,7 @@ def param_shapes(arch, tc, F):
 
 
 def glorot_init(arch='dsd', tc=30, F=513, seed=0):
-    """Lasagne's defaults for build_ca (either trainCNN.py): every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
+    """Lasagne's defaults for build_ca (any of the trainers): every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
     sqrt(2 / ((n1 + n2) * receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32."""
     rs = np.random.RandomState(seed)
     out = []
@@ -66,12 +71,15 @@ def glorot_init(arch='dsd', tc=30, F=513, seed=0):
 
 class Trainer(object):
     """``train_fn`` / ``train_fn1`` of trainCNN.py:262-263 for the DSD graph, resident on one GPU; ``arch='ikala_nopool'``:
-    the same pair of examples/ikala/trainCNN.py:195-197 for the iKala graph.
+    the same pair of examples/ikala/trainCNN.py:195-197 for the iKala graph; ``arch='bach10'``: that of
+    examples/bach10/trainCNNbach10.py:204-206 for the Bach10 graph.
 
-    ``params``: the 15 (DSD) or 13 (iKala) arrays in .pkl order (``load_model``), default :func:`glorot_init`.  ``rand``: the
+    ``params``: the 15 (DSD), 13 (iKala) or 17 (Bach10) arrays in .pkl order (``load_model``), default :func:`glorot_init`.  ``rand``: the
     uniform draw of trainCNN.py:180 ``[batch, 1, tc, F]``; default ``RandomState(seed).uniform``.  The batch size is fixed,
     as in the reference's compiled graph.  For iKala, ``beta`` is beta_acc, and loss hyper-parameters left at their DSD
-    defaults take iKala's values (ikala/trainCNN.py:152-155: eps 1e-8, alpha 0.9, beta_acc 0.005, beta_voc 0.02)."""
+    defaults take iKala's values (ikala/trainCNN.py:152-155: eps 1e-8, alpha 0.9, beta_acc 0.005, beta_voc 0.02).  For
+    Bach10, eps left at its default is 1e-18 (bach10/trainCNNbach10.py:160) and alpha, beta and beta_voc are ignored: the
+    loss has no such terms."""
 
     def __init__(self, ctx=None, arch='dsd', params=None, batch_size=32, time_context=30, feat_size=513, seed=0,
                  rand=None, eps=EPS, alpha=ALPHA, beta=BETA, beta_voc=BETA_VOC, learning_rate=LEARNING_RATE, rho=RHO,
@@ -85,6 +93,8 @@ class Trainer(object):
             alpha = IKALA_ALPHA if alpha is ALPHA else alpha
             beta = IKALA_BETA_ACC if beta is BETA else beta
             beta_voc = IKALA_BETA_VOC if beta_voc is BETA_VOC else beta_voc
+        elif arch == 'bach10':
+            eps = BACH10_EPS if eps is EPS else eps
         self.B, self.tc, self.F = int(batch_size), int(time_context), int(feat_size)
         if params is None:
             params = glorot_init(arch, self.tc, self.F, seed)
@@ -139,8 +149,9 @@ class Trainer(object):
 
     def losses(self, inputs, targets):
         """``train_fn1`` (trainCNN.py:263): vocals, bass, drums, negative, alpha, negative_voc at the current parameters;
-        iKala (ikala/trainCNN.py:197): vocals_error, acc_error, negative_error_voc, negative_error_acc."""
-        n = len(COMPONENTS) if self.arch == 'dsd' else len(IKALA_COMPONENTS)
+        iKala (ikala/trainCNN.py:197): vocals_error, acc_error, negative_error_voc, negative_error_acc; Bach10
+        (bach10/trainCNNbach10.py:206): error1 .. error4 (bassoon, clarinet, saxophone, violin)."""
+        n = {'dsd': len(COMPONENTS), 'bach10': len(BACH10_COMPONENTS)}.get(self.arch, len(IKALA_COMPONENTS))
         return [float(v) for v in self.ctx.to_host(self.run(inputs, targets, 0))[1:1 + n]]
 
     def loss_and_gradients(self, inputs, targets):
@@ -180,7 +191,8 @@ class Trainer(object):
 
     def save_model(self, path):
         """trainCNN.py:59-64: the pickled list ``Network('dsd', ...)`` and separate_dsd.py load (iKala: ``Network('ikala',
-        ...)``, ``Separator('ikala', ...)`` and separate_ikala.py, which resolve it to the no-pool graph)."""
+        ...)``, ``Separator('ikala', ...)`` and separate_ikala.py, which resolve it to the no-pool graph; Bach10:
+        ``Network('bach10', ...)``, ``Separator('bach10', ...)`` and separate_bach10.py)."""
         _save_model(path, self.params())
 
     def close(self):

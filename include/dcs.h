@@ -391,33 +391,40 @@ DCS_API int dcs_timing_reset(dcs_ctx* ctx);
 DCS_API int dcs_timing_query(dcs_ctx* ctx, int which, double* avg_ms, int64_t* launches);
 
 /* ------------------------------------------------------------------ training (csrc/train_core.hip; examples/dsd100/trainCNN.py:
- *                                                                     csrc/train_dsd.hip; examples/ikala/trainCNN.py: csrc/train_ikala.hip) */
+ *                                                                     csrc/train_dsd.hip; examples/ikala/trainCNN.py: csrc/train_ikala.hip;
+ *                                                                     examples/bach10/trainCNNbach10.py: csrc/train_bach10.hip) */
 /* The train_fn / train_fn1 pair of train_auto (trainCNN.py:132-263) for the DSD graph build_ca (:66-130; also what
  * examples/hiphopss/trainCNN.py trains): arch DCS_ARCH_DSD, time_context even in [4, 64], F <= 2049, batch 1 .. 1024, else
  * DCS_EINVAL; 15 arrays.  Or the pair of examples/ikala/trainCNN.py:120-197 for the iKala graph (:66-118): arch
  * DCS_ARCH_IKALA_NOPOOL, time_context 10 .. 64 (conv2 is 10 rows high), F 87 .. 2049 (conv2's output keeps a column),
- * batch 1 .. 1024, else DCS_EINVAL; 13 arrays.  Any other arch (DCS_ARCH_IKALA, the pooled graph of separate_ikala.py,
- * included: the reference never trains it) is DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
+ * batch 1 .. 1024, else DCS_EINVAL; 13 arrays.  Or the pair of examples/bach10/trainCNNbach10.py:126-206 for the Bach10 graph
+ * (:66-123; trainCNNrwc.py and trainCNNSibelius.py train the same graph with the same loss): arch DCS_ARCH_BACH10,
+ * time_context 2 .. 47 (conv2 is int(2 tc / 3) rows high; from 48 on dcs_model_create's bach10 graph has no column
+ * convolution to run the result), F 30 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  Any other arch (DCS_ARCH_IKALA,
+ * the pooled graph of separate_ikala.py, included: the reference never trains it; the score-informed graphs) is
+ * DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
  * order), copied into the trainer.  rand_d [batch][1][tc][F]: the uniform draw baked into the loss (trainCNN.py:174), copied.
- * hyper_h: eps, alpha, beta, beta_voc (:169-172) -- for iKala eps, alpha, beta_acc, beta_voc (ikala/trainCNN.py:152-155) --
- * then adadelta's learning_rate, rho, epsilon (lasagne defaults 1, 0.95, 1e-6).  Adadelta's accu / delta_accu start at zero
+ * hyper_h: eps, alpha, beta, beta_voc (:169-172) -- for iKala eps, alpha, beta_acc, beta_voc (ikala/trainCNN.py:152-155); for
+ * Bach10 eps (1e-18, bach10/trainCNNbach10.py:160) and three ignored values -- then adadelta's learning_rate, rho, epsilon (lasagne defaults 1, 0.95, 1e-6).  Adadelta's accu / delta_accu start at zero
  * (lasagne.updates.adadelta). */
 DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, int batch, const float* const* params_d,
                                const int64_t* shapes, int nparams, const float* rand_d, const double* hyper_h,
                                dcs_trainer** out);
 DCS_API int dcs_trainer_destroy(dcs_trainer* t);
 /* One step on inputs_d [batch][1][tc][F] and targets_d [batch][4][tc][F] (iKala: [batch][2][tc][F], voice then
- * accompaniment) (trainCNN.py:243-263), no host synchronisation: mode 0 = train_fn1 (:263): forward, loss and components;
+ * accompaniment; Bach10: bassoon, clarinet, saxophone, violin) (trainCNN.py:243-263), no host synchronisation: mode 0 = train_fn1 (:263): forward, loss and components;
  * 1 also the gradients of |E|, one per parameter (Theano conventions: rectify'(0) = 0.5, abs'(0) = 0); 2 = train_fn (:262):
  * also the adadelta update (:223).  out7_d (device, nullable): 7 doubles, all at the parameters BEFORE this step's update:
  * DSD the loss |E| then vocals, bass, drums, negative, alpha, negative_voc (:217, :263); iKala the loss |E| with E =
  * vocals_error + acc_error - negative_error_voc, then vocals_error, acc_error, negative_error_voc, negative_error_acc
- * (ikala/trainCNN.py:189, :197), then two zeros. */
+ * (ikala/trainCNN.py:189, :197), then two zeros; Bach10 the loss |error1 + error2 + error3 + error4|, then the four errors
+ * (bach10/trainCNNbach10.py:193-198, :206), then two zeros.  Bach10's masks are p_k / (p_1 + .. + p_4 + eps r): where all
+ * four outputs are zero and r = 0 the reference divides 0 by 0, and the NaN is kept. */
 DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float* targets_d, int mode, double* out7_d);
 /* lasagne.layers.get_output(network2) (trainCNN.py:165) at the current parameters: p_d [batch][4][tc][F] (iKala
  * [batch][2][tc][F]), before masking */
 DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d);
-/* Copy one section of the trainer's state into 15 (iKala 13) caller buffers in .pkl layout: which 0 = parameters
+/* Copy one section of the trainer's state into 15 (iKala 13, Bach10 17) caller buffers in .pkl layout: which 0 = parameters
  * (get_all_param_values, trainCNN.py:59-64), 1 = the gradients of the last mode 1 / 2 step, 2 = adadelta accu,
  * 3 = adadelta delta_accu. */
 DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams);

@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
-"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool, the iKala graph
-(csrc/train_ikala.hip), both on the shared core csrc/train_core.hip, against the same float32 graph, loss and Adadelta
-written in torch and run with autograd on the same GPU.  Prints one JSON line per batch size.
+"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10, the iKala graph
+(csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip), all on the shared core csrc/train_core.hip, against the
+same float32 graph, loss and Adadelta written in torch and run with autograd on the same GPU.  Prints one JSON line per
+batch size.
 
-    python scripts/bench_train.py [--arch dsd|ikala_nopool] [--batches 32 256] [--steps 50] [--warmup 10]
+    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10] [--batches 32 256] [--steps 50] [--warmup 10]
+                                  [--feat_size 513]
+
+The Bach10 graph's working size is --feat_size 2049 (frame size 4096); its lines also carry the floor of a step from its
+shapes (``bach10_floor``): the bytes the dense matrices and Adadelta's state must move over the measured HBM rate, and the
+convolutions' multiply-adds over the f32 MFMA peak.
 
 ms/step is wall time over --steps steps of train_fn (forward, loss, gradients, Adadelta; no host synchronisation inside
 the timed loop) divided by the steps, after --warmup steps; windows/s = batch / (ms/step).  A kernel breakdown comes from
@@ -26,6 +32,31 @@ LAUNCHES_PER_STEP = 19
 # iKala: 7 forward launches (F3 split-K GEMM + its sum), loss + reduce, 6 backward (B3 likewise), 4 weight-gradient GEMMs,
 # split-K reduce, Adadelta (csrc/train_ikala.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_IKALA = 21
+# Bach10: the iKala list with four sources per batched launch (csrc/train_bach10.hip, csrc/train_core.hip)
+LAUNCHES_PER_STEP_BACH10 = 21
+# MI355X: HBM3E as a float4 copy reaches it (8 TB/s spec) and the f32 MFMA peak (v_mfma_f32_16x16x4_f32)
+HBM_BYTES_PER_S = 6.29e12
+F32_MFMA_FLOP_PER_S = 157.3e12
+
+
+def bach10_floor(B, tc, F):
+    """What one Bach10 step cannot go below, from its shapes.  Memory: the five dense matrices are read twice (forward, data
+    gradient) and their gradients written once, and Adadelta reads params, grads, accu, delta_accu and writes three of them
+    (activations, a few percent at B = 32, are left out).  Compute: conv2 once forward, per source its transpose forward and
+    conv2 backward, the transpose once more for da1, and the weight gradient over the 5 blocks; conv1 likewise (2 FLOP per
+    multiply-add)."""
+    from deepconvsep_amd.arch import ARCHS
+    from deepconvsep_amd.training import param_shapes
+    d = ARCHS["bach10"].dims(tc, F)
+    dense = 5 * d["flat"] * 256 * 4
+    state = 4 * sum(int(np.prod(s)) for s in param_shapes("bach10", tc, F))
+    nbytes = 3 * dense + 7 * state
+    conv2 = 2 * B * d["h2"] * d["w1"] * 30 * 30 * d["kh2"]           # conv2 over its valid rows
+    conv2t = 2 * B * tc * d["w1"] * 30 * 30 * d["kh2"]               # conv2^T as an implicit GEMM over the padded map
+    conv1 = 2 * B * tc * d["w1"] * 30 * 30
+    flop = (1 + 4 + 5) * conv2 + (4 + 1) * conv2t + (1 + 4 + 4 + 5) * conv1 + 3 * 2 * B * 5 * d["flat"] * 256
+    return dict(bytes=int(nbytes), memory_ms=round(nbytes / HBM_BYTES_PER_S * 1e3, 3), flop=int(flop),
+                compute_ms=round(flop / F32_MFMA_FLOP_PER_S * 1e3, 3))
 
 
 def bench_hip(B, tc, F, steps, warmup, arch="dsd"):
@@ -47,10 +78,11 @@ def bench_hip(B, tc, F, steps, warmup, arch="dsd"):
 
 def bench_torch(B, tc, F, steps, warmup, arch="dsd"):
     import torch
+    import train_bach10_ref
     import train_ikala_ref
     import train_ref
     from deepconvsep_amd.training import glorot_init, n_sources
-    ref = train_ikala_ref if arch == "ikala_nopool" else train_ref
+    ref = {"ikala_nopool": train_ikala_ref, "bach10": train_bach10_ref}.get(arch, train_ref)
     rs = np.random.RandomState(0)
     P = [torch.from_numpy(p).cuda().requires_grad_(True) for p in glorot_init(arch, tc, F, 0)]
     x = torch.from_numpy((0.3 * rs.uniform(size=(B, 1, tc, F))).astype(np.float32)).cuda()
@@ -75,7 +107,7 @@ def bench_torch(B, tc, F, steps, warmup, arch="dsd"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("dsd", "ikala_nopool"), default="dsd")
+    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10"), default="dsd")
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 256])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -86,7 +118,10 @@ def main():
         ms = bench_hip(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
         tms = bench_torch(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
         extra = {} if a.arch == "dsd" else dict(arch=a.arch)
-        launches = LAUNCHES_PER_STEP if a.arch == "dsd" else LAUNCHES_PER_STEP_IKALA
+        launches = {"dsd": LAUNCHES_PER_STEP, "bach10": LAUNCHES_PER_STEP_BACH10}.get(a.arch, LAUNCHES_PER_STEP_IKALA)
+        if a.arch == "bach10":
+            floor = bach10_floor(B, a.time_context, a.feat_size)
+            extra.update(floor=floor, hip_over_floor=round(ms / max(floor["memory_ms"], floor["compute_ms"]), 2))
         print(json.dumps(dict(extra, batch=B, time_context=a.time_context, feat_size=a.feat_size, hip_ms_per_step=round(ms, 4),
                               hip_windows_per_s=round(B / ms * 1e3, 1), launches_per_step=launches,
                               torch_ms_per_step=round(tms, 4), torch_windows_per_s=round(B / tms * 1e3, 1),
