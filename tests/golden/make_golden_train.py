@@ -1,4 +1,4 @@
-"""Writes tests/golden/train_loss.npz and tests/golden/train_windows.npz from the reference's own source.  CPU only; needs the
+"""Writes tests/golden/train_loss.npz, train_windows.npz and train_feed.npz from the reference's own source.  CPU only; needs the
 reference tree (DCS_REFERENCE_ROOT).
 
     python tests/golden/make_golden_train.py
@@ -10,6 +10,10 @@ reference tree (DCS_REFERENCE_ROOT).
 * train_windows: dataset.py's getNum (:596-602), loadFile (:383-488) and initOutput (:509-516) executed on a stub
   LargeDataset whose mixture holds frame number + 1 in every bin; the slots' first bin gives the window start + 1, 0 a
   zero frame.
+* train_feed: the same three methods on a stub whose data holds ``1000 c + 10 t + f + 1`` at (channel c, frame t, bin f)
+  (small integers, exact in float32) with ``mult_factor_in = mult_factor_out`` set and ``tensortype`` float32, as the
+  trainers build the class: per case ``(T, tc, overlap, nsources, F, mult)`` the full ``inputs [n, tc, F]`` and
+  ``outputs [n, tc, nsources F]`` of loadFile, and ``cases`` = the table of the six numbers.
 """
 import os
 import sys
@@ -105,10 +109,56 @@ def window_cases():
     return out
 
 
+# (T, tc, overlap, nsources, F, mult): a file shorter than tc (one padded window), T == tc (loadFile reaches no window:
+# one zero slot), T == tc + 1, more slots than windows (one window, one zero slot), overlapping windows, a scale that is
+# a power of two and scales that are not, 2 and 4 sources
+FEED_CASES = [(7, 10, 5, 4, 5, 0.5), (10, 10, 5, 4, 3, 0.3), (11, 10, 5, 2, 7, 0.3), (60, 30, 0, 4, 3, 0.25),
+              (61, 20, 0, 2, 6, 0.3), (40, 10, 8, 4, 4, 0.7), (23, 6, 2, 2, 5, 2.0)]
+
+
+def feed_data(T, nsources, F):
+    """[1 + nsources, T, F] float64: 1000 c + 10 t + f + 1."""
+    c, t, f = np.meshgrid(np.arange(1 + nsources), np.arange(T), np.arange(F), indexing="ij")
+    return (1000 * c + 10 * t + f + 1).astype(np.float64)
+
+
+class _FeedStub(_Stub):
+    tensortype = np.float32
+
+    def __init__(self, T, tc, ov, nsources, F, mult):
+        _Stub.__init__(self, T, tc, ov)
+        self.nsources, self.F = nsources, F
+        self.input_size, self.output_size = F, nsources * F
+        self.mult_factor_in = self.mult_factor_out = mult
+
+    def get_shape(self, path):
+        return (1 + self.nsources, self.T, self.F)
+
+    def loadInputOutput(self, id):
+        a = feed_data(self.T, self.nsources, self.F)
+        return a[0:1], a[1:]
+
+
+def feed_cases():
+    ns = {"np": np, "os": os}
+    for name, (rel, a, b) in DATASET.items():
+        exec(compile(textwrap.dedent(ref_exec._slice(rel, a, b)), rel, "exec"), ns)
+        setattr(_FeedStub, name, ns[name])
+    out = {"cases": np.asarray(FEED_CASES, dtype=np.float64)}
+    for k, (T, tc, ov, nsrc, F, mult) in enumerate(FEED_CASES):
+        s = _FeedStub(T, tc, ov, nsrc, F, mult)
+        s.num_points = [0, s.getNum(0)]
+        res = s.loadFile(0)
+        assert res["inputs"].dtype == np.float32 and res["outputs"].dtype == np.float32
+        out["inputs_%d" % k], out["outputs_%d" % k] = res["inputs"], res["outputs"]
+    return out
+
+
 def main():
     np.savez_compressed(os.path.join(HERE, "train_loss.npz"), **loss_cases())
     np.savez_compressed(os.path.join(HERE, "train_windows.npz"), **window_cases())
-    print("wrote train_loss.npz, train_windows.npz")
+    np.savez_compressed(os.path.join(HERE, "train_feed.npz"), **feed_cases())
+    print("wrote train_loss.npz, train_windows.npz, train_feed.npz")
 
 
 if __name__ == "__main__":

@@ -5,7 +5,9 @@ import sys
 
 import numpy as np
 import pytest
+import torch
 
+import train_edges
 import train_ref
 
 pytestmark = pytest.mark.gpu
@@ -53,6 +55,9 @@ def test_gradients_and_loss_match_float64(B, tc, F, neg):
     for i, (a, b) in enumerate(zip(g, g64)):
         assert a.shape == b.shape
         assert _rel(a, b) <= 1e-4, (i, _rel(a, b))
+    # elementwise, against the float32 restatement's own error at the same inputs (train_edges.check_gradients)
+    _, g32 = train_ref.loss_and_grads(params, x, tgt, r, dtype=torch.float32)
+    train_edges.check_gradients(g, g64, g32, B, "dsd %r" % ((B, tc, F, neg),))
     # b1 / b1b and b2 / b2b get identical gradients (Theano)
     assert np.array_equal(g[1], g[2]) and np.array_equal(g[4], g[5])
 

@@ -7,7 +7,9 @@ import sys
 
 import numpy as np
 import pytest
+import torch
 
+import train_edges
 import train_bach10_ref
 import train_ref
 
@@ -59,6 +61,9 @@ def test_gradients_and_loss_match_float64(B, tc, F):
         assert a.shape == b.shape
         assert np.linalg.norm(b) > 0, i
         assert rels[i] <= 1e-4, (i, rels[i])
+    # elementwise, against the float32 restatement's own error at the same inputs (train_edges.check_gradients)
+    _, g32 = train_bach10_ref.loss_and_grads(params, x, tgt, r, dtype=torch.float32)
+    train_edges.check_gradients(g, g64, g32, B, "bach10 %r" % ((B, tc, F),))
     # b1 / b1b and b2 / b2b get identical gradients (Theano)
     assert np.array_equal(g[1], g[2]) and np.array_equal(g[4], g[5])
     assert t.losses(x, tgt) == pytest.approx(list(want[1:]), rel=1e-5)

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 import torch.nn.functional as Fnn
 
-from train_ref import _t, adadelta, rectify  # noqa: F401  (adadelta is shared with the DSD restatement)
+from train_ref import _t, adadelta, autograd, rectify  # noqa: F401  (adadelta is shared with the DSD restatement)
 
 EPS = 1e-18
 
@@ -37,13 +37,10 @@ def components(p, x, tgt, r, eps=EPS):
     return [loss] + errors
 
 
-def loss_and_grads(params, x, tgt, r, **hyper):
-    """float64: the five values of ``components`` and the 17 gradients of the loss (ndarrays)."""
-    P = [_t(p, True) for p in params]
-    out = components(forward(P, _t(x)), _t(x), _t(tgt), _t(r), **hyper)
-    grads = torch.autograd.grad(out[0], P, allow_unused=True)
-    grads = [np.zeros(p.shape) if g is None else g.numpy() for p, g in zip(P, grads)]
-    return np.array([float(v) for v in out]), grads
+def loss_and_grads(params, x, tgt, r, **kw):
+    """float64: the five values of ``components`` and the 17 gradients of the loss (ndarrays).  Keywords: eps (bach10/trainCNNbach10.py:160)
+    and those of ``train_ref.autograd`` (tie, dtype, device)."""
+    return autograd(forward, components, params, x, tgt, r, **kw)
 
 
 def forward_np(params, x):

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 import torch.nn.functional as Fnn
 
-from train_ref import _t, adadelta, rectify  # noqa: F401  (adadelta is shared with the DSD restatement)
+from train_ref import _t, adadelta, autograd, rectify  # noqa: F401  (adadelta is shared with the DSD restatement)
 
 EPS, ALPHA, BETA_ACC, BETA_VOC = 1e-8, 0.9, 0.005, 0.02
 
@@ -45,13 +45,10 @@ def components(p, x, tgt, r, eps=EPS, alpha=ALPHA, beta_acc=BETA_ACC, beta_voc=B
     return [loss, vocals_error, acc_error, negative_error_voc, negative_error_acc]
 
 
-def loss_and_grads(params, x, tgt, r, **hyper):
-    """float64: the five values of ``components`` and the 13 gradients of the loss (ndarrays)."""
-    P = [_t(p, True) for p in params]
-    out = components(forward(P, _t(x)), _t(x), _t(tgt), _t(r), **hyper)
-    grads = torch.autograd.grad(out[0], P, allow_unused=True)
-    grads = [np.zeros(p.shape) if g is None else g.numpy() for p, g in zip(P, grads)]
-    return np.array([float(v) for v in out]), grads
+def loss_and_grads(params, x, tgt, r, **kw):
+    """float64: the five values of ``components`` and the 13 gradients of the loss (ndarrays).  Keywords: eps, alpha, beta_acc, beta_voc (ikala/trainCNN.py:152-155)
+    and those of ``train_ref.autograd`` (tie, dtype, device)."""
+    return autograd(forward, components, params, x, tgt, r, **kw)
 
 
 def forward_np(params, x):

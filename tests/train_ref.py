@@ -1,6 +1,11 @@
 """float64 torch restatement of the DSD trainer (test infrastructure): build_ca of examples/dsd100/trainCNN.py:66-130 with
 explicit transposed convolutions (so that autograd reaches the weights through the InverseLayers), the loss of :167-219 with
-Theano's gradient conventions -- rectify = 0.5 (x + |x|) so r'(0) = 0.5, abs'(0) = 0 -- and lasagne.updates.adadelta."""
+Theano's gradient conventions -- rectify = 0.5 (x + |x|) so r'(0) = 0.5, abs'(0) = 0 -- and lasagne.updates.adadelta.
+
+``relu_tie(d)`` is a switch for the controls of tests/test_train_edges_cpu.py: inside it rectify's derivative at exactly 0 is
+``d`` (0 or 1: the conventions a kernel could carry by mistake) in all three restatements; the values are unchanged."""
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn.functional as Fnn
@@ -8,12 +13,28 @@ import torch.nn.functional as Fnn
 EPS, ALPHA, BETA, BETA_VOC = 1e-8, 0.001, 0.01, 0.03
 
 
+_TIE = [0.5]
+
+
+@contextlib.contextmanager
+def relu_tie(d):
+    """rectify'(0) = d inside the block (0.5 is Theano's and the trainers')."""
+    old, _TIE[0] = _TIE[0], float(d)
+    try:
+        yield
+    finally:
+        _TIE[0] = old
+
+
 def rectify(v):
-    return 0.5 * (v + torch.abs(v))
+    y = 0.5 * (v + torch.abs(v))
+    if _TIE[0] != 0.5:   # a term that is 0 everywhere and has derivative (d - 0.5) where v == 0
+        y = y + (_TIE[0] - 0.5) * torch.where(v == 0, v, torch.zeros_like(v))
+    return y
 
 
-def _t(a, grad=False):
-    t = torch.as_tensor(np.asarray(a, dtype=np.float64)).clone()
+def _t(a, grad=False, dtype=torch.float64, device="cpu"):
+    t = torch.as_tensor(np.asarray(a, dtype=np.float64)).to(dtype=dtype, device=device).clone()
     return t.requires_grad_(grad)
 
 
@@ -55,13 +76,23 @@ def components(p, x, tgt, r, eps=EPS, alpha=ALPHA, beta=BETA, beta_voc=BETA_VOC)
     return [loss, vocals, bass, drums, negative, alpha_c, negative_voc]
 
 
-def loss_and_grads(params, x, tgt, r):
-    """float64: the seven values of ``components`` and the 15 gradients of the loss (ndarrays)."""
-    P = [_t(p, True) for p in params]
-    out = components(forward(P, _t(x)), _t(x), _t(tgt), _t(r))
-    grads = torch.autograd.grad(out[0], P, allow_unused=True)
-    grads = [np.zeros(p.shape) if g is None else g.numpy() for p, g in zip(P, grads)]
-    return np.array([float(v) for v in out]), grads
+def autograd(forward_fn, components_fn, params, x, tgt, r, tie=0.5, dtype=torch.float64, device="cpu", **hyper):
+    """The values of ``components_fn`` and the gradients of the loss, as float64 ndarrays, computed in ``dtype`` on
+    ``device`` with rectify'(0) = ``tie``.  float32 gives the restatement's own float32 error (the yardstick of the
+    elementwise gradient bound); the values are still summed in float64 from the ``dtype`` squared errors."""
+    kw = dict(dtype=dtype, device=device)
+    P = [_t(p, True, **kw) for p in params]
+    with relu_tie(tie):
+        out = components_fn(forward_fn(P, _t(x, **kw)), _t(x, **kw), _t(tgt, **kw), _t(r, **kw), **hyper)
+        grads = torch.autograd.grad(out[0], P, allow_unused=True)
+    grads = [np.zeros(p.shape) if g is None else g.detach().cpu().numpy().astype(np.float64) for p, g in zip(P, grads)]
+    return np.array([float(v.detach()) for v in out]), grads
+
+
+def loss_and_grads(params, x, tgt, r, **kw):
+    """float64: the seven values of ``components`` and the 15 gradients of the loss (ndarrays).  Keywords: eps, alpha,
+    beta, beta_voc (trainCNN.py:167-170) and those of :func:`autograd`."""
+    return autograd(forward, components, params, x, tgt, r, **kw)
 
 
 def adadelta(params, grads, accu, delta, lr=1.0, rho=0.95, eps=1e-6):
