@@ -11,8 +11,10 @@ from .evaluation import bss_eval, bss_eval_images, bss_eval_sources
 from .separation import (PredictFunction, Separator, blackmanharris, generate_overlapadd, load_model,
                          overlapadd, overlapadd_multi, save_model, train_auto)
 from .training import FeatureWindows, Trainer, glorot_init
+from .stereo_training import StereoFeatureWindows, StereoTrainer
 
 __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "TILER_SCRIPT", "TransformFFT",
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
            "Separator", "blackmanharris", "generate_overlapadd", "load_model", "save_model", "overlapadd",
-           "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "Trainer", "FeatureWindows", "glorot_init"]
+           "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "Trainer", "FeatureWindows", "glorot_init",
+           "StereoTrainer", "StereoFeatureWindows"]

@@ -189,6 +189,10 @@ struct dcs_trainer {
     int tc = 0, F = 0, B = 0;
     int nsrc = 0;                // output channels: Q and the targets are [B][nsrc][tc][F]
     int nparams = 0, loss_sums = 0;
+    int nout = 7;                // doubles dcs_trainer_step writes
+    int rand_planes = 1;         // the draw is [rand_planes][B][tc][F]
+    bool two_stage = false;      // the graph has a second loss (mode + 4 of dcs_trainer_step)
+    int stage2 = 0;              // set by dcs_trainer_step before loss()
     int64_t RF = 0, P = 0, P4 = 0;
     int64_t shapes[train::kMaxParams][4] = {{0}};   // .pkl shapes
     double hyp[7] = {0};
@@ -197,7 +201,7 @@ struct dcs_trainer {
     float* work = nullptr;
     double* lpart = nullptr;     // [kLossBlocks][loss_sums]
     double* out7 = nullptr;      // when the caller passes none
-    float *rnd = nullptr, *Q = nullptr, *sign = nullptr;   // views into work: the uniform draw, the output layer's
+    float *rnd = nullptr, *Q = nullptr, *sign = nullptr;   // views into work: the draw, the output layer's
                                                            // pre-activations, sign(E)
 
     virtual ~dcs_trainer() {}

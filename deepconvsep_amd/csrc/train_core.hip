@@ -280,6 +280,35 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(const float* __restric
     }
 }
 
+// gather_kernel for files that hold the `in` tensor's cin channels, then the `out` tensor's cout: [cin + cout][T][F]
+// (dataset.py LargeDatasetMulti: the *_in_m_.data / *_out_m_.data pair of one chunk), each with its own factor.
+__global__ __launch_bounds__(kThreads) void gather_channels_kernel(const float* __restrict__ data,
+                                                                   const int64_t* __restrict__ files,
+                                                                   const int* __restrict__ win, int B, int tc, int F, int cin,
+                                                                   int cout, float scale_in, float scale_out,
+                                                                   float* __restrict__ inputs, float* __restrict__ targets) {
+    const int64_t plane = (int64_t)tc * F;
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= (int64_t)B * plane) return;
+    const int b = (int)(e / plane);
+    const int64_t rem = e - b * plane;
+    const int t = (int)(rem / F), f = (int)(rem - (int64_t)t * F);
+    const int fi = win[2 * b], start = win[2 * b + 1];
+    const int64_t fr = (int64_t)start + t;
+    int64_t base = 0, T = 0;
+    bool live = false;
+    if (fi >= 0) {
+        base = files[2 * fi];
+        T = files[2 * fi + 1];
+        live = fr < T;
+    }
+    for (int c = 0; c < cin + cout; ++c) {
+        const float raw = live ? data[base + ((int64_t)c * T + fr) * F + f] : 0.f;
+        if (c < cin) inputs[((int64_t)b * cin + c) * plane + rem] = live ? scale_in * raw : 0.f;
+        else targets[((int64_t)b * cout + c - cin) * plane + rem] = live ? scale_out * raw : 0.f;
+    }
+}
+
 }  // namespace train
 
 namespace {
@@ -344,6 +373,7 @@ int dcs_trainer::reduce(const Reduce& r) {
 int dsd_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int ikala_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int bach10_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
+int dsdild_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 
 extern "C" {
 
@@ -356,9 +386,11 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     if (arch == DCS_ARCH_DSD) DCS_CHECK(dsd_trainer_new(time_context, F, batch, &t));
     else if (arch == DCS_ARCH_IKALA_NOPOOL) DCS_CHECK(ikala_trainer_new(time_context, F, batch, &t));
     else if (arch == DCS_ARCH_BACH10) DCS_CHECK(bach10_trainer_new(time_context, F, batch, &t));
+    else if (arch == DCS_ARCH_DSD_ILD) DCS_CHECK(dsdild_trainer_new(time_context, F, batch, &t));
     else
-        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d), the no-pool iKala graph (arch %d) and "
-                 "the Bach10 graph (arch %d) train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10);
+        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d), the no-pool iKala graph (arch %d), "
+                 "the Bach10 graph (arch %d) and the stereo DSD graph (arch %d) train here", DCS_ARCH_DSD,
+                 DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10, DCS_ARCH_DSD_ILD);
     // from here on every return frees t
     struct Guard {
         dcs_trainer* t;
@@ -387,11 +419,11 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     t->P4 = dcs_cdiv(t->P, 4);
 
     // one work buffer: the views, each rounded to 64 floats, then the f64 loss sums and out7
-    std::vector<std::pair<float**, int64_t>> parts = {{&t->rnd, t->RF}, {&t->sign, 1}};
+    std::vector<std::pair<float**, int64_t>> parts = {{&t->rnd, t->rand_planes * t->RF}, {&t->sign, 1}};
     t->plan(parts);
     int64_t total = 0;
     for (auto& p : parts) total += dcs_round_up(p.second, 64);
-    const int64_t dbl = (int64_t)kLossBlocks * t->loss_sums + 8;
+    const int64_t dbl = (int64_t)kLossBlocks * t->loss_sums + std::max(8, t->nout);
     hipError_t e = dcs_dev_alloc((void**)&t->state, 16 * t->P4 * sizeof(float), "trainer state");
     if (e == hipSuccess) e = dcs_dev_alloc((void**)&t->work, total * sizeof(float) + dbl * sizeof(double), "trainer work");
     if (e != hipSuccess)
@@ -408,7 +440,8 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     // zero), then the params
     if (hipMemsetAsync(t->work, 0, total * sizeof(float) + dbl * sizeof(double), ctx->stream) != hipSuccess ||
         hipMemsetAsync(t->state, 0, 16 * t->P4 * sizeof(float), ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(t->rnd, rand_d, t->RF * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        hipMemcpyAsync(t->rnd, rand_d, t->rand_planes * t->RF * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream) !=
+            hipSuccess)
         DCS_FAIL(DCS_EHIP, "dcs_trainer_create: initialisation failed");
     DCS_CHECK(t->layout(t->state, (float* const*)params_d, 1));
     guard.t = nullptr;
@@ -426,7 +459,12 @@ DCS_API int dcs_trainer_destroy(dcs_trainer* t) {
 
 DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float* targets_d, int mode, double* out7_d) {
     if (!t || !inputs_d || !targets_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: null argument");
-    if (mode < 0 || mode > 2) DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: mode %d (0 loss, 1 gradients, 2 update)", mode);
+    const int stage2 = t->two_stage && mode >= 4;
+    if (stage2) mode -= 4;
+    if (mode < 0 || mode > 2)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_step: mode %d (0 loss, 1 gradients, 2 update%s)", mode + 4 * stage2,
+                 t->two_stage ? "; + 4: the stage-2 loss" : "");
+    t->stage2 = stage2;
     DCS_ON_DEVICE(t->ctx->device);
     DCS_CHECK(t->forward(inputs_d));
     DCS_CHECK(t->loss(inputs_d, targets_d, out7_d));
@@ -436,6 +474,19 @@ DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float*
     hipLaunchKernelGGL(adadelta_kernel, dim3((unsigned)dcs_cdiv(t->P4, kThreads)), dim3(kThreads), 0, t->ctx->stream,
                        (float4*)t->state, t->P4, (float)t->hyp[4], (float)t->hyp[5], (float)t->hyp[6]);
     DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_set_rand(dcs_trainer* t, const float* rand_d) {
+    if (!t || !rand_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_rand: null argument");
+    DCS_ON_DEVICE(t->ctx->device);
+    DCS_HIP(hipMemcpyAsync(t->rnd, rand_d, t->rand_planes * t->RF * sizeof(float), hipMemcpyDeviceToDevice, t->ctx->stream));
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_out_count(dcs_trainer* t, int* count) {
+    if (!t || !count) DCS_FAIL(DCS_EINVAL, "dcs_trainer_out_count: null argument");
+    *count = t->nout;
     return DCS_OK;
 }
 
@@ -478,6 +529,22 @@ DCS_API int dcs_trainer_gather_sources(dcs_ctx* ctx, const float* data_d, const 
         DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_sources: batch %d, time_context %d, F %d, nsrc %d (1 .. 8)", batch,
                  time_context, F, nsrc);
     return gather(ctx, data_d, files_d, windows_d, batch, time_context, F, nsrc, scale, inputs_d, targets_d);
+}
+
+DCS_API int dcs_trainer_gather_channels(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d,
+                                        int batch, int time_context, int F, int cin, int cout, float scale_in,
+                                        float scale_out, float* inputs_d, float* targets_d) {
+    if (!ctx || !data_d || !files_d || !windows_d || !inputs_d || !targets_d)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_channels: null argument");
+    if (batch < 1 || time_context < 1 || F < 1 || cin < 1 || cin > 4 || cout < 1 || cout > 16)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_channels: batch %d, time_context %d, F %d, cin %d (1 .. 4), cout %d (1 .. 16)",
+                 batch, time_context, F, cin, cout);
+    DCS_ON_DEVICE(ctx->device);
+    const int64_t n = (int64_t)batch * time_context * F;
+    hipLaunchKernelGGL(gather_channels_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, ctx->stream, data_d,
+                       files_d, windows_d, batch, time_context, F, cin, cout, scale_in, scale_out, inputs_d, targets_d);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
 }
 
 }  // extern "C"

@@ -411,6 +411,27 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
                                const int64_t* shapes, int nparams, const float* rand_d, const double* hyper_h,
                                dcs_trainer** out);
 DCS_API int dcs_trainer_destroy(dcs_trainer* t);
+/* The stereo (ILD) DSD100 graph (examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py: build_ca :66-113, train_fn_mse / train_fn1
+ * :183-206, train_fn_ILD :210-228 and :268; csrc/train_dsdild.hip): dcs_trainer_create with arch DCS_ARCH_DSD_ILD,
+ * time_context even in [4, 64], F 1 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  rand_d [2][batch][4][tc][F]: the
+ * two normal draws rand_num (:164) then rand_num2 (:210).  hyper_h: eps (1e-12, :152), ild_weight (1 / 500, :228), two
+ * ignored values, then adadelta's three.  dcs_trainer_step takes inputs_d [batch][2][tc][F] and targets_d [batch][8][tc][F]
+ * (channel 2 s + c: source s in input channel c); modes 0 / 1 / 2 use the stage-1 loss sum_j |sum (source_j - target_j)^2|
+ * (:183-198), mode + 4 (4 / 5 / 6) the stage-2 loss, which adds ild_weight |sum_f (mean a_est[f] - mean a_gt[f])^2| with
+ * a = 20 log10 |s_0 / (s_1 + eps r2) + eps r2| (:214-228); on any other graph mode + 4 is DCS_EINVAL.  The output vector
+ * has 16 doubles: [0] the loss, [1 .. 8] errors_insts (:194: mic 0's four sources, then mic 1's), [9] the weighted ILD
+ * term (0 in stage 1), [10 .. 15] zero.  Where all four outputs of a channel are zero and the draw is zero the
+ * reference divides 0 by 0 (and takes log 0 where a level ratio is 0): the NaN / inf is kept.
+ *
+ * dcs_trainer_out_count: the doubles dcs_trainer_step writes for this trainer: 7, or 16 for DCS_ARCH_DSD_ILD. */
+DCS_API int dcs_trainer_out_count(dcs_trainer* t, int* count);
+/* Replace the draw, in stream order: rand_d has the size given at create ([batch][1][tc][F] for the mono graphs,
+ * [2][batch][4][tc][F] for DCS_ARCH_DSD_ILD).  A difference from the reference worth knowing: there rand_num and rand_num2
+ * of the stereo trainer come from RandomStreams(128).normal(std=0.1) and are REDRAWN on every call of a compiled function,
+ * by Theano's MRG31k3p stream, which is not reproduced here; the trainer instead holds one draw until the caller replaces it
+ * (examples/dsd100_2ch_ILD/train_dsd_ild.py does so before every step from a seeded device generator).  With eps = 1e-12
+ * the draw only matters where a denominator would otherwise be zero; in silent target bins the ILD term depends on it. */
+DCS_API int dcs_trainer_set_rand(dcs_trainer* t, const float* rand_d);
 /* One step on inputs_d [batch][1][tc][F] and targets_d [batch][4][tc][F] (iKala: [batch][2][tc][F], voice then
  * accompaniment; Bach10: bassoon, clarinet, saxophone, violin) (trainCNN.py:243-263), no host synchronisation: mode 0 = train_fn1 (:263): forward, loss and components;
  * 1 also the gradients of |E|, one per parameter (Theano conventions: rectify'(0) = 0.5, abs'(0) = 0); 2 = train_fn (:262):
@@ -440,6 +461,13 @@ DCS_API int dcs_trainer_gather(dcs_ctx* ctx, const float* data_d, const int64_t*
 DCS_API int dcs_trainer_gather_sources(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d,
                                        int batch, int time_context, int F, int nsrc, float scale, float* inputs_d,
                                        float* targets_d);
+/* LargeDatasetMulti's windows (dataset.py:921-1007): data_d holds per file one [cin + cout][T_i][F] block, the `in` tensor's
+ * channels (*_in_m_.data) first, then the `out` tensor's (*_out_m_.data); cin 1 .. 4, cout 1 .. 16.  The window table and the
+ * zero / padding rules are dcs_trainer_gather's.  inputs_d [batch][cin][tc][F] = scale_in * in, targets_d
+ * [batch][cout][tc][F] = scale_out * out (mult_factor_in / mult_factor_out). */
+DCS_API int dcs_trainer_gather_channels(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d,
+                                        int batch, int time_context, int F, int cin, int cout, float scale_in,
+                                        float scale_out, float* inputs_d, float* targets_d);
 
 /* ------------------------------------------------------------------ memory-safety aid (tests/test_gpu_guard.py) */
 /* With DCS_WS_GUARD=<bytes> in the environment (read once per process) every scratch block libdcs allocates -- the

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10, the iKala graph
-(csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip), all on the shared core csrc/train_core.hip, against the
-same float32 graph, loss and Adadelta written in torch and run with autograd on the same GPU.  Prints one JSON line per
-batch size.
+"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / dsd_ild, the iKala
+graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the stereo DSD graph (csrc/train_dsdild.hip;
+--ild: its stage-2 loss), all on the shared core csrc/train_core.hip, against the same float32 graph, loss and Adadelta
+written in torch and run with autograd on the same GPU.  Prints one JSON line per batch size.
 
-    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10] [--batches 32 256] [--steps 50] [--warmup 10]
-                                  [--feat_size 513]
+    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10|dsd_ild] [--ild] [--batches 32 256] [--steps 50]
+                                  [--warmup 10] [--feat_size 513]
 
 The Bach10 graph's working size is --feat_size 2049 (frame size 4096); its lines also carry the floor of a step from its
 shapes (``bach10_floor``): the bytes the dense matrices and Adadelta's state must move over the measured HBM rate, and the
@@ -34,6 +34,10 @@ LAUNCHES_PER_STEP = 19
 LAUNCHES_PER_STEP_IKALA = 21
 # Bach10: the iKala list with four sources per batched launch (csrc/train_bach10.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_BACH10 = 21
+# stereo DSD: 8 forward launches (F3 split-K GEMM + its sum, conv1^T once per input channel), loss + reduce (stage 2: the
+# per-bin sums and their means before them), 6 backward (B3 split-K + sum), 4 weight-gradient GEMMs, split-K reduce,
+# Adadelta (csrc/train_dsdild.hip, csrc/train_core.hip)
+LAUNCHES_PER_STEP_ILD = {False: 22, True: 24}
 # MI355X: HBM3E as a float4 copy reaches it (8 TB/s spec) and the f32 MFMA peak (v_mfma_f32_16x16x4_f32)
 HBM_BYTES_PER_S = 6.29e12
 F32_MFMA_FLOP_PER_S = 157.3e12
@@ -57,6 +61,53 @@ def bach10_floor(B, tc, F):
     flop = (1 + 4 + 5) * conv2 + (4 + 1) * conv2t + (1 + 4 + 4 + 5) * conv1 + 3 * 2 * B * 5 * d["flat"] * 256
     return dict(bytes=int(nbytes), memory_ms=round(nbytes / HBM_BYTES_PER_S * 1e3, 3), flop=int(flop),
                 compute_ms=round(flop / F32_MFMA_FLOP_PER_S * 1e3, 3))
+
+
+def _ild_inputs(B, tc, F):
+    rs = np.random.RandomState(0)
+    x = (0.3 * rs.uniform(size=(B, 2, tc, F))).astype(np.float32)
+    y = (0.1 * rs.uniform(size=(B, 8, tc, F))).astype(np.float32)
+    r = (0.1 * rs.randn(2, B, 4, tc, F)).astype(np.float32)
+    return x, y, r
+
+
+def bench_hip_ild(B, tc, F, steps, warmup, ild):
+    import torch
+    from deepconvsep_amd.stereo_training import StereoTrainer, glorot_init
+    x, y, r = _ild_inputs(B, tc, F)
+    t = StereoTrainer(params=glorot_init(tc, F, 0), batch_size=B, time_context=tc, feat_size=F, rand=r)
+    x, y = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    for _ in range(warmup):
+        t.run(x, y, 2, ild)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        t.run(x, y, 2, ild)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def bench_torch_ild(B, tc, F, steps, warmup, ild):
+    import torch
+    import train_ild_ref as ref
+    from deepconvsep_amd.stereo_training import glorot_init
+    x, y, r = (torch.from_numpy(a).cuda() for a in _ild_inputs(B, tc, F))
+    P = [torch.from_numpy(p).cuda().requires_grad_(True) for p in glorot_init(tc, F, 0)]
+    opt = torch.optim.Adadelta(P, lr=1.0, rho=0.95, eps=1e-6)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = ref.components(ref.forward(P, x), x, y, r, stage=2 if ild else 1)[0]
+        loss.backward()
+        opt.step()
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
 
 
 def bench_hip(B, tc, F, steps, warmup, arch="dsd"):
@@ -107,18 +158,28 @@ def bench_torch(B, tc, F, steps, warmup, arch="dsd"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10"), default="dsd")
+    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10", "dsd_ild"), default="dsd")
+    ap.add_argument("--ild", action="store_true", help="dsd_ild: the stage-2 loss (train_fn_ILD)")
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 256])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--time_context", type=int, default=30)
     ap.add_argument("--feat_size", type=int, default=513)
     a = ap.parse_args()
+    if a.ild and a.arch != "dsd_ild":
+        ap.error("--ild goes with --arch dsd_ild")
     for B in a.batches:
-        ms = bench_hip(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
-        tms = bench_torch(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
+        if a.arch == "dsd_ild":
+            ms = bench_hip_ild(B, a.time_context, a.feat_size, a.steps, a.warmup, a.ild)
+            tms = bench_torch_ild(B, a.time_context, a.feat_size, a.steps, a.warmup, a.ild)
+        else:
+            ms = bench_hip(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
+            tms = bench_torch(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
         extra = {} if a.arch == "dsd" else dict(arch=a.arch)
-        launches = {"dsd": LAUNCHES_PER_STEP, "bach10": LAUNCHES_PER_STEP_BACH10}.get(a.arch, LAUNCHES_PER_STEP_IKALA)
+        if a.arch == "dsd_ild":
+            extra.update(ild=bool(a.ild))
+        launches = {"dsd": LAUNCHES_PER_STEP, "bach10": LAUNCHES_PER_STEP_BACH10,
+                    "dsd_ild": LAUNCHES_PER_STEP_ILD[bool(a.ild)]}.get(a.arch, LAUNCHES_PER_STEP_IKALA)
         if a.arch == "bach10":
             floor = bach10_floor(B, a.time_context, a.feat_size)
             extra.update(floor=floor, hip_over_floor=round(ms / max(floor["memory_ms"], floor["compute_ms"]), 2))
