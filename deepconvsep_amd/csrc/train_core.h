@@ -169,6 +169,36 @@ __global__ __launch_bounds__(kThreads) void deconv1_kernel(const float* __restri
     q[e] = acc + bo[k];
 }
 
+// conv1^T of a conv1 with NC input channels (W1 [C1][NC][1][K1]): one decoder slot g writes NC output channels, each through
+// its own weight slab W1i[c] [K1][C1]: q[b][c][t][f] = bo[c] + sum over the taps S1 w + j = f of sum_o g[b][t][w][o]
+// W1i[c][j][o], in deconv1_kernel's order (w and o ascending, one thread per output).
+template <int K1, int C1, int S1, int NC>
+__global__ __launch_bounds__(kThreads) void deconv1_channels_kernel(const float* __restrict__ g, const float* __restrict__ W1i,
+                                                                    const float* __restrict__ bo, float* __restrict__ q, int B,
+                                                                    int tc, int F, int w1) {
+    __shared__ float w[NC * K1 * C1];
+    for (int i = threadIdx.x; i < NC * K1 * C1; i += kThreads) w[i] = W1i[i];
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= (int64_t)B * NC * tc * F) return;
+    const int f = (int)(e % F);
+    int64_t r = e / F;
+    const int t = (int)(r % tc);
+    r /= tc;
+    const int c = (int)(r % NC), b = (int)(r / NC);
+    const float* gr = g + ((int64_t)b * tc + t) * w1 * C1;
+    const int wlo = f >= K1 - 1 ? (f - (K1 - 1) + S1 - 1) / S1 : 0;
+    const int whi = min(w1 - 1, f / S1);
+    float acc = 0.f;
+    for (int x = wlo; x <= whi; ++x) {
+        const float* gw = gr + (int64_t)x * C1;
+        const float* ww = w + (c * K1 + f - S1 * x) * C1;
+#pragma unroll
+        for (int o = 0; o < C1; ++o) acc += gw[o] * ww[o];
+    }
+    q[e] = acc + bo[c];
+}
+
 // map(s, k): the .pkl index of element k of the internal section s
 template <class Map>
 __global__ __launch_bounds__(kThreads) void layout_kernel(float* __restrict__ flat, const Layout L, const Map map) {
@@ -189,6 +219,9 @@ struct dcs_trainer {
     int tc = 0, F = 0, B = 0;
     int nsrc = 0;                // output channels: Q and the targets are [B][nsrc][tc][F]
     int nparams = 0, loss_sums = 0;
+    int nstate = 0;              // sections of the stepped state; 0: nparams.  Fewer than nparams: the graph holds parameters
+                                 // that no gradient reaches outside the state (its layout() serves them), sizes in state_size
+    int64_t state_size[train::kMaxParams] = {0};
     int nout = 7;                // doubles dcs_trainer_step writes
     int rand_planes = 1;         // the draw is [rand_planes][B][tc][F]
     bool two_stage = false;      // the graph has a second loss (mode + 4 of dcs_trainer_step)
@@ -228,12 +261,12 @@ struct dcs_trainer {
 template <class Map>
 int dcs_trainer::run_layout(float* flat, float* const* pkl, int to_internal, const Map& map) {
     train::Layout L;
-    for (int i = 0; i < nparams; ++i) {
+    for (int i = 0; i < nstate; ++i) {
         L.pkl[i] = pkl[i];
         L.off[i] = off[i];
     }
-    L.off[nparams] = off[nparams];
-    L.nparams = nparams;
+    L.off[nstate] = off[nstate];
+    L.nparams = nstate;
     L.to_internal = to_internal;
     hipLaunchKernelGGL(train::layout_kernel<Map>, dim3((unsigned)dcs_cdiv(P, train::kThreads)), dim3(train::kThreads), 0,
                        ctx->stream, flat, L, map);

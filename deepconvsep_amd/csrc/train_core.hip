@@ -309,6 +309,81 @@ __global__ __launch_bounds__(kThreads) void gather_channels_kernel(const float* 
     }
 }
 
+// The score-informed feed (dataset.py LargeDatasetMask2: loadFile :383-488 with filterSpec :839-879, then
+// trainCNNrwc.py:309-320), one workgroup per (frame, window): targets[b][j][t][f] = scale source_j and inputs[b][j][t][f] =
+// mask_j (scale mixture) with mask_j = filtered_j / sum_i filtered_i in float32 (instruments added in order), filtered = 1 on
+// the rectangles of instrument j's notes and 1e-18 elsewhere; every product is rounded once to float32.  data as for
+// gather_kernel with [1 + ninst][T][F] blocks.  notes: per file (note_files[2 i] = offset in ints, note_files[2 i + 1] = P
+// notes per instrument) an int table [ninst][P][2 + 2 npairs] = (first frame, end frame, npairs x (first bin, end bin)),
+// packed and range-checked by dcs_trainer_pack_score: a note paints frames first <= start + t < end of its window, which is
+// filterSpec's int(max(n0, start)) - start .. int(min(n1, stop)) - start for integer start and stop.
+// The workgroup first marks in LDS, one bit per instrument, the bins of the notes that sound in its frame (integer OR: the
+// order does not matter), kScoreBins bins at a time, then sweeps the bins.
+constexpr int kScoreBins = 4096;
+
+__global__ __launch_bounds__(kThreads) void gather_score_kernel(const float* __restrict__ data, const int64_t* __restrict__ files,
+                                                                const int* __restrict__ notes,
+                                                                const int64_t* __restrict__ note_files,
+                                                                const int* __restrict__ win, int tc, int F, int ninst,
+                                                                int npairs, float scale, float* __restrict__ inputs,
+                                                                float* __restrict__ targets) {
+    __shared__ unsigned on[kScoreBins];
+    const int t = blockIdx.x, b = blockIdx.y;
+    const int fi = win[2 * b], start = win[2 * b + 1];
+    const int64_t fr = (int64_t)start + t;
+    const int64_t plane = (int64_t)tc * F;
+    const int64_t out0 = (int64_t)b * ninst * plane + (int64_t)t * F;
+    int64_t base = 0, T = 0;
+    bool live = false;
+    if (fi >= 0) {
+        base = files[2 * fi];
+        T = files[2 * fi + 1];
+        live = fr < T;
+    }
+    if (!live) {   // uniform over the workgroup
+        for (int j = 0; j < ninst; ++j)
+            for (int f = threadIdx.x; f < F; f += kThreads) {
+                inputs[out0 + j * plane + f] = 0.f;
+                targets[out0 + j * plane + f] = 0.f;
+            }
+        return;
+    }
+    const int* tab = notes + note_files[2 * fi];
+    const int P = (int)note_files[2 * fi + 1];
+    const int width = 2 + 2 * npairs;
+    const float* mix = data + base + fr * F;
+    for (int c0 = 0; c0 < F; c0 += kScoreBins) {
+        const int c1 = min(F, c0 + kScoreBins);
+        for (int f = threadIdx.x; f < c1 - c0; f += kThreads) on[f] = 0u;
+        __syncthreads();
+        for (int i = threadIdx.x; i < ninst * P; i += kThreads) {
+            const int* n = tab + (int64_t)i * width;
+            if (fr < n[0] || fr >= n[1]) continue;
+            const unsigned bit = 1u << (i / P);
+            for (int k = 0; k < npairs; ++k) {
+                const int f0 = max(n[2 + 2 * k], c0), f1 = min(n[3 + 2 * k], c1);
+                for (int f = f0; f < f1; ++f) atomicOr(&on[f - c0], bit);
+            }
+        }
+        __syncthreads();
+        for (int f = c0 + threadIdx.x; f < c1; f += kThreads) {
+            const unsigned m = on[f - c0];
+            float total = 0.f;
+            for (int j = 0; j < ninst; ++j) {
+                const float v = ((m >> j) & 1u) ? 1.0f : 1e-18f;
+                total = j == 0 ? v : total + v;
+            }
+            const float x = scale * mix[f];
+            for (int j = 0; j < ninst; ++j) {
+                const float v = (((m >> j) & 1u) ? 1.0f : 1e-18f) / total;
+                inputs[out0 + j * plane + f] = v * x;
+                targets[out0 + j * plane + f] = scale * data[base + ((int64_t)(j + 1) * T + fr) * F + f];
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace train
 
 namespace {
@@ -374,6 +449,7 @@ int dsd_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int ikala_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int bach10_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int dsdild_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
+int bach10si_trainer_new(int arch, int time_context, int F, int batch, dcs_trainer** out);
 
 extern "C" {
 
@@ -387,10 +463,13 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     else if (arch == DCS_ARCH_IKALA_NOPOOL) DCS_CHECK(ikala_trainer_new(time_context, F, batch, &t));
     else if (arch == DCS_ARCH_BACH10) DCS_CHECK(bach10_trainer_new(time_context, F, batch, &t));
     else if (arch == DCS_ARCH_DSD_ILD) DCS_CHECK(dsdild_trainer_new(time_context, F, batch, &t));
+    else if (arch == DCS_ARCH_BACH10_SI || arch == DCS_ARCH_BACH10_SI1)
+        DCS_CHECK(bach10si_trainer_new(arch, time_context, F, batch, &t));
     else
         DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d), the no-pool iKala graph (arch %d), "
-                 "the Bach10 graph (arch %d) and the stereo DSD graph (arch %d) train here", DCS_ARCH_DSD,
-                 DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10, DCS_ARCH_DSD_ILD);
+                 "the Bach10 graph (arch %d), the stereo DSD graph (arch %d) and the score-informed Bach10 graphs (arch %d, "
+                 "%d) train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10, DCS_ARCH_DSD_ILD,
+                 DCS_ARCH_BACH10_SI, DCS_ARCH_BACH10_SI1);
     // from here on every return frees t
     struct Guard {
         dcs_trainer* t;
@@ -413,9 +492,13 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     t->tc = time_context; t->F = F; t->B = batch;
     t->RF = (int64_t)batch * time_context * F;
     memcpy(t->hyp, hyper_h, sizeof(t->hyp));
-    for (int i = 0; i < nparams; ++i)
-        t->off[i + 1] = t->off[i] + t->shapes[i][0] * t->shapes[i][1] * t->shapes[i][2] * t->shapes[i][3];
-    t->P = t->off[nparams];
+    if (t->nstate == 0) {
+        t->nstate = nparams;
+        for (int i = 0; i < nparams; ++i)
+            t->state_size[i] = t->shapes[i][0] * t->shapes[i][1] * t->shapes[i][2] * t->shapes[i][3];
+    }
+    for (int i = 0; i < t->nstate; ++i) t->off[i + 1] = t->off[i] + t->state_size[i];
+    t->P = t->off[t->nstate];
     t->P4 = dcs_cdiv(t->P, 4);
 
     // one work buffer: the views, each rounded to 64 floats, then the f64 loss sums and out7
@@ -543,6 +626,54 @@ DCS_API int dcs_trainer_gather_channels(dcs_ctx* ctx, const float* data_d, const
     const int64_t n = (int64_t)batch * time_context * F;
     hipLaunchKernelGGL(gather_channels_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, ctx->stream, data_d,
                        files_d, windows_d, batch, time_context, F, cin, cout, scale_in, scale_out, inputs_d, targets_d);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_pack_score(const double* notes_h, int ninst, int n_notes, int width, int F, int* packed_h) {
+    if (!notes_h || !packed_h) DCS_FAIL(DCS_EINVAL, "dcs_trainer_pack_score: null argument");
+    if (ninst < 1 || ninst > 32 || n_notes < 0 || width < 5 || ((width - 3) & 1) || F < 1)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_pack_score: bad shape (ninst %d (1 .. 32), notes %d, width %d, F %d)", ninst, n_notes,
+                 width, F);
+    const int npairs = (width - 3) / 2, pw = 2 + 2 * npairs;
+    const double big = 2147483647.0;
+    for (int64_t i = 0; i < (int64_t)ninst * n_notes; ++i) {
+        const double* n = notes_h + i * width;
+        int* o = packed_h + i * pw;
+        memset(o, 0, pw * sizeof(int));
+        // filterSpec's test: midi > 0; the frame test is the kernel's (an empty frame range paints nothing)
+        if (!(n[2] > 0) || !(n[1] > 0)) continue;
+        o[0] = n[0] > 0 ? (int)std::min(n[0], big) : 0;
+        o[1] = (int)std::min(n[1], big);
+        for (int k = 0; k < npairs; ++k) {
+            const double fs = n[3 + 2 * k], fe = n[4 + 2 * k];
+            if (!(fe > 0)) continue;
+            const int64_t f0 = (int64_t)fs, f1 = (int64_t)fe;
+            // the reference's fancy bin index raises past F
+            if (f0 < 0 || f1 > F)
+                DCS_FAIL(DCS_ESHAPE, "dcs_trainer_pack_score: bin range [%lld, %lld) outside 0..%d", (long long)f0,
+                         (long long)f1, F);
+            if (f1 > f0) {
+                o[2 + 2 * k] = (int)f0;
+                o[3 + 2 * k] = (int)f1;
+            }
+        }
+    }
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_gather_score(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* notes_d,
+                                     const int64_t* note_files_d, const int* windows_d, int batch, int time_context, int F,
+                                     int ninst, int width, float scale, float* inputs_d, float* targets_d) {
+    if (!ctx || !data_d || !files_d || !notes_d || !note_files_d || !windows_d || !inputs_d || !targets_d)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score: null argument");
+    if (batch < 1 || batch > 65535 || time_context < 1 || F < 1 || ninst < 1 || ninst > 32 || width < 5 || ((width - 3) & 1))
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score: batch %d (1 .. 65535), time_context %d, F %d, ninst %d (1 .. 32), "
+                 "width %d (odd, from 5)", batch, time_context, F, ninst, width);
+    DCS_ON_DEVICE(ctx->device);
+    hipLaunchKernelGGL(gather_score_kernel, dim3((unsigned)time_context, (unsigned)batch), dim3(kThreads), 0, ctx->stream,
+                       data_d, files_d, notes_d, note_files_d, windows_d, time_context, F, ninst, (width - 3) / 2, scale,
+                       inputs_d, targets_d);
     DCS_HIP(hipGetLastError());
     return DCS_OK;
 }

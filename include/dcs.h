@@ -401,8 +401,8 @@ DCS_API int dcs_timing_query(dcs_ctx* ctx, int which, double* avg_ms, int64_t* l
  * (:66-123; trainCNNrwc.py and trainCNNSibelius.py train the same graph with the same loss): arch DCS_ARCH_BACH10,
  * time_context 2 .. 47 (conv2 is int(2 tc / 3) rows high; from 48 on dcs_model_create's bach10 graph has no column
  * convolution to run the result), F 30 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  Any other arch (DCS_ARCH_IKALA,
- * the pooled graph of separate_ikala.py, included: the reference never trains it; the score-informed graphs) is
- * DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
+ * the pooled graph of separate_ikala.py, included: the reference never trains it; the deep score-informed graph
+ * DCS_ARCH_BACH10_SI_1X1) is DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
  * order), copied into the trainer.  rand_d [batch][1][tc][F]: the uniform draw baked into the loss (trainCNN.py:174), copied.
  * hyper_h: eps, alpha, beta, beta_voc (:169-172) -- for iKala eps, alpha, beta_acc, beta_voc (ikala/trainCNN.py:152-155); for
  * Bach10 eps (1e-18, bach10/trainCNNbach10.py:160) and three ignored values -- then adadelta's learning_rate, rho, epsilon (lasagne defaults 1, 0.95, 1e-6).  Adadelta's accu / delta_accu start at zero
@@ -411,6 +411,20 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
                                const int64_t* shapes, int nparams, const float* rand_d, const double* hyper_h,
                                dcs_trainer** out);
 DCS_API int dcs_trainer_destroy(dcs_trainer* t);
+/* The score-informed Bach10 graph (examples/bach10_scoreinformed/trainCNNrwc.py: build_ca :134-193, train_fn / train_fn1
+ * :225-283; csrc/train_bach10si.hip): dcs_trainer_create with arch DCS_ARCH_BACH10_SI (17 arrays) or DCS_ARCH_BACH10_SI1
+ * (11 arrays, the single-branch form trainCNNrwc_samp.py:195-235 trains with the same loss, :275-321); time_context 2 .. 47
+ * (the largest value for which dcs_model_create runs the score-informed graph: its inference kernels are the Bach10 graph's),
+ * F 30 .. 2049, batch 1 .. 1024, else DCS_EINVAL.  rand_d [batch][1][tc][F]; hyper_h: eps (1e-18, :235), three ignored values,
+ * adadelta's three.  dcs_trainer_step takes inputs_d [batch][4][tc][F] (the mixture times the four harmonic masks,
+ * dcs_trainer_gather_score) and targets_d [batch][4][tc][F]; the loss reads prediction2[:, 0:4], the four channels of decoder
+ * branch 0, against the mixture x = ((x0 + x1) + x2) + x3: masks p_k / (p_1 + .. + p_4 + eps r), the loss |error1 + .. +
+ * error4|; out7 = (loss, error1 .. error4, 0, 0); the 0 / 0 NaN is kept.  dcs_trainer_forward writes p_d [batch][4][tc][F],
+ * the live channels prediction2[:, 0:4].
+ * Dead parameters: in the 17-array graph fc12, fc13, fc14 (arrays 10 .. 15) and bo[4:16] reach no loss term, so the
+ * reference's gradient for them is exactly zero and Adadelta from a zero state never moves them or their accumulators.  The
+ * trainer holds them once, outside the stepped state: dcs_trainer_get(which = 0) returns them bit-identical to what
+ * dcs_trainer_create was given, which = 1, 2, 3 return zeros for them. */
 /* The stereo (ILD) DSD100 graph (examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py: build_ca :66-113, train_fn_mse / train_fn1
  * :183-206, train_fn_ILD :210-228 and :268; csrc/train_dsdild.hip): dcs_trainer_create with arch DCS_ARCH_DSD_ILD,
  * time_context even in [4, 64], F 1 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  rand_d [2][batch][4][tc][F]: the
@@ -445,7 +459,7 @@ DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float*
 /* lasagne.layers.get_output(network2) (trainCNN.py:165) at the current parameters: p_d [batch][4][tc][F] (iKala
  * [batch][2][tc][F]), before masking */
 DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d);
-/* Copy one section of the trainer's state into 15 (iKala 13, Bach10 17) caller buffers in .pkl layout: which 0 = parameters
+/* Copy one section of the trainer's state into 15 (iKala 13, Bach10 17, score-informed 17 or 11) caller buffers in .pkl layout: which 0 = parameters
  * (get_all_param_values, trainCNN.py:59-64), 1 = the gradients of the last mode 1 / 2 step, 2 = adadelta accu,
  * 3 = adadelta delta_accu. */
 DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams);
@@ -468,6 +482,24 @@ DCS_API int dcs_trainer_gather_sources(dcs_ctx* ctx, const float* data_d, const 
 DCS_API int dcs_trainer_gather_channels(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d,
                                         int batch, int time_context, int F, int cin, int cout, float scale_in,
                                         float scale_out, float* inputs_d, float* targets_d);
+/* The score-informed feed (dataset.py LargeDatasetMask2: loadFile :383-488 with filterSpec :839-879, then
+ * trainCNNrwc.py:309-320), one launch per batch from data resident on the device.  data_d / files_d / windows_d as for
+ * dcs_trainer_gather_sources with nsrc = ninst: per file a [1 + ninst][T_i][F] block (Bach10: mixture, bassoon, clarinet,
+ * saxophone, violin).  notes_d: every file's packed note table (dcs_trainer_pack_score), note_files_d [n_files][2] int64 =
+ * (offset in ints, notes per instrument).  targets_d [batch][ninst][tc][F] = scale * source_j; inputs_d [batch][ninst][tc][F]
+ * = mask_j * (scale * mixture) with mask_j = filtered_j / sum_i filtered_i in float32, the instruments added in order,
+ * filtered = 1 on the note rectangles and 1e-18 elsewhere: the rectangle rule of dcs_score_masks_norm(.., start, start + tc,
+ * DCS_SCORE_NORM_SUM, ..).  Every product is rounded once to float32.  Zero slots (file < 0) and frames past T_i are zero in
+ * both outputs.  ninst 1 .. 32, width = 2 nharmonics + 3 (odd, from 5), else DCS_EINVAL.  The timbre-model branch of
+ * filterSpec is not part of the feed. */
+DCS_API int dcs_trainer_gather_score(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* notes_d,
+                                     const int64_t* note_files_d, const int* windows_d, int batch, int time_context, int F,
+                                     int ninst, int width, float scale, float* inputs_d, float* targets_d);
+/* One file's note table notes_h [ninst][n_notes][width] (first frame, end frame, MIDI number, then width - 3 values: first
+ * bin, end bin per harmonic; util.expandMidi) -> packed_h [ninst][n_notes][width - 1] ints for dcs_trainer_gather_score, on
+ * the host.  Notes with MIDI number <= 0 and bands with end bin <= 0 are dropped, as filterSpec drops them.  A band outside
+ * [0, F) is DCS_ESHAPE (the reference's bin index would raise for every window that holds the note). */
+DCS_API int dcs_trainer_pack_score(const double* notes_h, int ninst, int n_notes, int width, int F, int* packed_h);
 
 /* ------------------------------------------------------------------ memory-safety aid (tests/test_gpu_guard.py) */
 /* With DCS_WS_GUARD=<bytes> in the environment (read once per process) every scratch block libdcs allocates -- the

@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
-"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / dsd_ild, the iKala
-graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the stereo DSD graph (csrc/train_dsdild.hip;
---ild: its stage-2 loss), all on the shared core csrc/train_core.hip, against the same float32 graph, loss and Adadelta
-written in torch and run with autograd on the same GPU.  Prints one JSON line per batch size.
+"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / bach10_si / dsd_ild,
+the iKala graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the score-informed Bach10 graph
+(csrc/train_bach10si.hip; --branches 1: its 11-array layout) / the stereo DSD graph (csrc/train_dsdild.hip; --ild: its
+stage-2 loss), all on the shared core csrc/train_core.hip, against the same float32 graph, loss and Adadelta written in torch
+and run with autograd on the same GPU.  Prints one JSON line per batch size.
 
-    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10|dsd_ild] [--ild] [--batches 32 256] [--steps 50]
-                                  [--warmup 10] [--feat_size 513]
+    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10|bach10_si|dsd_ild] [--ild] [--branches 4|1]
+                                  [--batches 32 256] [--steps 50] [--warmup 10] [--feat_size 513]
 
-The Bach10 graph's working size is --feat_size 2049 (frame size 4096); its lines also carry the floor of a step from its
-shapes (``bach10_floor``): the bytes the dense matrices and Adadelta's state must move over the measured HBM rate, and the
-convolutions' multiply-adds over the f32 MFMA peak.
+The Bach10 graphs' working size is --feat_size 2049 (frame size 4096); their lines also carry the floor of a step from its
+shapes (``bach10_floor`` / ``bach10si_floor``): the bytes the dense matrices and Adadelta's state must move over the measured
+HBM rate, and the convolutions' multiply-adds over the f32 MFMA peak.
 
 ms/step is wall time over --steps steps of train_fn (forward, loss, gradients, Adadelta; no host synchronisation inside
 the timed loop) divided by the steps, after --warmup steps; windows/s = batch / (ms/step).  A kernel breakdown comes from
@@ -34,6 +35,9 @@ LAUNCHES_PER_STEP = 19
 LAUNCHES_PER_STEP_IKALA = 21
 # Bach10: the iKala list with four sources per batched launch (csrc/train_bach10.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_BACH10 = 21
+# score-informed Bach10: the Bach10 list with one decoder slot (csrc/train_bach10si.hip): 7 forward, loss + reduce, 6 backward,
+# 4 weight-gradient GEMMs, split-K reduce, Adadelta over the 11 stepped arrays
+LAUNCHES_PER_STEP_BACH10SI = 21
 # stereo DSD: 8 forward launches (F3 split-K GEMM + its sum, conv1^T once per input channel), loss + reduce (stage 2: the
 # per-bin sums and their means before them), 6 backward (B3 split-K + sum), 4 weight-gradient GEMMs, split-K reduce,
 # Adadelta (csrc/train_dsdild.hip, csrc/train_core.hip)
@@ -61,6 +65,76 @@ def bach10_floor(B, tc, F):
     flop = (1 + 4 + 5) * conv2 + (4 + 1) * conv2t + (1 + 4 + 4 + 5) * conv1 + 3 * 2 * B * 5 * d["flat"] * 256
     return dict(bytes=int(nbytes), memory_ms=round(nbytes / HBM_BYTES_PER_S * 1e3, 3), flop=int(flop),
                 compute_ms=round(flop / F32_MFMA_FLOP_PER_S * 1e3, 3))
+
+
+def bach10si_floor(B, tc, F):
+    """The same for one score-informed step (either layout: the dead arrays of the 17-array one are outside the step).
+    Memory: the two dense matrices Wfc and W_11 read twice and their gradients written once, Adadelta over the 11 stepped
+    arrays.  Compute: conv2 forward, backward and its weight gradient over 2 blocks; conv2^T forward and for da1; conv1 with
+    K = 4 channels x 30 taps forward, backward, transposed and its weight gradient over 2 blocks."""
+    from deepconvsep_amd.arch import ARCHS
+    d = ARCHS["bach10_si1"].dims(tc, F)
+    dense = 2 * d["flat"] * 256 * 4
+    state = 4 * sum(int(np.prod(s)) for s in ARCHS["bach10_si1"].param_shapes(tc, F))
+    nbytes = 3 * dense + 7 * state
+    conv2 = 2 * B * d["h2"] * d["w1"] * 30 * 30 * d["kh2"]
+    conv2t = 2 * B * tc * d["w1"] * 30 * 30 * d["kh2"]
+    conv1 = 2 * B * tc * d["w1"] * 30 * 4 * 30
+    flop = (1 + 1 + 2) * conv2 + (1 + 1) * conv2t + (1 + 1 + 1 + 2) * conv1 + 3 * 2 * B * 2 * d["flat"] * 256
+    return dict(bytes=int(nbytes), memory_ms=round(nbytes / HBM_BYTES_PER_S * 1e3, 3), flop=int(flop),
+                compute_ms=round(flop / F32_MFMA_FLOP_PER_S * 1e3, 3))
+
+
+def _si_inputs(B, tc, F):
+    rs = np.random.RandomState(0)
+    x = (0.3 * rs.uniform(0, 0.25, size=(B, 4, tc, F))).astype(np.float32)
+    y = (0.1 * rs.uniform(size=(B, 4, tc, F))).astype(np.float32)
+    r = rs.uniform(size=(B, 1, tc, F)).astype(np.float32)
+    return x, y, r
+
+
+def bench_hip_si(B, tc, F, steps, warmup, branches):
+    import torch
+    from deepconvsep_amd.score_training import ScoreTrainer, glorot_init
+    x, y, r = _si_inputs(B, tc, F)
+    t = ScoreTrainer(params=glorot_init(tc, F, 0, branches), branches=branches, batch_size=B, time_context=tc, feat_size=F,
+                     rand=r)
+    x, y = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    for _ in range(warmup):
+        t.run(x, y, 2)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        t.run(x, y, 2)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    t.close()
+    return ms
+
+
+def bench_torch_si(B, tc, F, steps, warmup, branches):
+    """float32 autograd of the same layout: with 17 arrays torch computes the three dead branches forward (autograd prunes
+    their backward), as the reference's compiled function would."""
+    import torch
+    import train_si_ref as ref
+    from deepconvsep_amd.score_training import glorot_init
+    x, y, r = (torch.from_numpy(a).cuda() for a in _si_inputs(B, tc, F))
+    P = [torch.from_numpy(p).cuda().requires_grad_(True) for p in glorot_init(tc, F, 0, branches)]
+    opt = torch.optim.Adadelta(P, lr=1.0, rho=0.95, eps=1e-6)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = ref.components(ref.forward(P, x), x, y, r)[0]
+        loss.backward()
+        opt.step()
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
 
 
 def _ild_inputs(B, tc, F):
@@ -158,7 +232,8 @@ def bench_torch(B, tc, F, steps, warmup, arch="dsd"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10", "dsd_ild"), default="dsd")
+    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10", "bach10_si", "dsd_ild"), default="dsd")
+    ap.add_argument("--branches", type=int, choices=(4, 1), default=4, help="bach10_si: the 17- or the 11-array layout")
     ap.add_argument("--ild", action="store_true", help="dsd_ild: the stage-2 loss (train_fn_ILD)")
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 256])
     ap.add_argument("--steps", type=int, default=50)
@@ -172,16 +247,21 @@ def main():
         if a.arch == "dsd_ild":
             ms = bench_hip_ild(B, a.time_context, a.feat_size, a.steps, a.warmup, a.ild)
             tms = bench_torch_ild(B, a.time_context, a.feat_size, a.steps, a.warmup, a.ild)
+        elif a.arch == "bach10_si":
+            ms = bench_hip_si(B, a.time_context, a.feat_size, a.steps, a.warmup, a.branches)
+            tms = bench_torch_si(B, a.time_context, a.feat_size, a.steps, a.warmup, a.branches)
         else:
             ms = bench_hip(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
             tms = bench_torch(B, a.time_context, a.feat_size, a.steps, a.warmup, a.arch)
         extra = {} if a.arch == "dsd" else dict(arch=a.arch)
         if a.arch == "dsd_ild":
             extra.update(ild=bool(a.ild))
-        launches = {"dsd": LAUNCHES_PER_STEP, "bach10": LAUNCHES_PER_STEP_BACH10,
+        if a.arch == "bach10_si":
+            extra.update(branches=a.branches)
+        launches = {"dsd": LAUNCHES_PER_STEP, "bach10": LAUNCHES_PER_STEP_BACH10, "bach10_si": LAUNCHES_PER_STEP_BACH10SI,
                     "dsd_ild": LAUNCHES_PER_STEP_ILD[bool(a.ild)]}.get(a.arch, LAUNCHES_PER_STEP_IKALA)
-        if a.arch == "bach10":
-            floor = bach10_floor(B, a.time_context, a.feat_size)
+        if a.arch in ("bach10", "bach10_si"):
+            floor = (bach10_floor if a.arch == "bach10" else bach10si_floor)(B, a.time_context, a.feat_size)
             extra.update(floor=floor, hip_over_floor=round(ms / max(floor["memory_ms"], floor["compute_ms"]), 2))
         print(json.dumps(dict(extra, batch=B, time_context=a.time_context, feat_size=a.feat_size, hip_ms_per_step=round(ms, 4),
                               hip_windows_per_s=round(B / ms * 1e3, 1), launches_per_step=launches,
