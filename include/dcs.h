@@ -124,6 +124,31 @@ DCS_API int dcs_stft_forward_f32_clips(dcs_stft* plan, const float* audio_d, int
 DCS_API int dcs_stft_forward_f64_clips(dcs_stft* plan, const double* audio_d, int64_t n_samples, int64_t n_clips, int64_t clip_stride,
                                double* mag_d, double* phase_d, int64_t ld, int64_t rows_out);
 
+/* The feature block of one augmented "virtual file", rendered inside the STFT's loader (csrc/fft_render.hip).  Replaces
+ * util.circular_shift (util.py:62-81), the time-domain mixing and the chunk slicing of the hiphop feature generators
+ * (examples/hiphopss/compute_features.py:55-85, augmentations/compute_features_cs_aug.py:98, :116-147,
+ * compute_features_instr_aug.py, compute_features_mix_aug.py:143-231) followed by compute_transform (transform.py:80-131):
+ * no rendered signal ever exists.  bank_d [bank_len]: mono source signals back to back.  tracks_h [S][4] int64 = (offset
+ * into the bank, length L_s, shift k_s in samples (any sign), output channel c_s in 1 .. S, each once), in the order the
+ * reference adds them into the mixture; gains_h [1 + S] = (mixture scale m, g_0 .. g_{S-1}).
+ *   r_s[n] = g_s * x_s[n - k_s] if 0 <= n - k_s < L_s else 0,   0 <= n < size
+ *   mix[n] = m * (((r_0 + r_1) + r_2) + ...)                     added in list order, no fused multiply-add
+ * chunks_h [n_chunks][2] = (a, Lc) with a + Lc <= size; samples outside [a, a + Lc) are zero, as the reference slices the
+ * chunk out before it transforms it.  out_d: per chunk one [1 + S][T_c][ld] block, back to back, T_c =
+ * dcs_frame_count(Lc, hop) (returned in frames_h [n_chunks]); channel 0 = compute_file(mix chunk), channel c_s =
+ * compute_file(r_s chunk); out_rows >= sum (1 + S) T_c.  ONE launch for all chunks.  _f64 takes a float64 bank and equals
+ * dcs_stft_forward_f64_clips on the host-rendered chunk bit for bit; _f32 takes a float32 bank.  S 1 .. 8, a track inside
+ * the bank, else DCS_EINVAL. */
+DCS_API int dcs_stft_forward_render_f64(dcs_stft* plan, const double* bank_d, int64_t bank_len, int S, const int64_t* tracks_h,
+                                const double* gains_h, int64_t size, const int64_t* chunks_h, int n_chunks, double* out_d,
+                                int64_t ld, int64_t out_rows, int64_t* frames_h);
+DCS_API int dcs_stft_forward_render_f32(dcs_stft* plan, const float* bank_d, int64_t bank_len, int S, const int64_t* tracks_h,
+                                const double* gains_h, int64_t size, const int64_t* chunks_h, int n_chunks, float* out_d,
+                                int64_t ld, int64_t out_rows, int64_t* frames_h);
+/* int64 per row of the device table of virtual files dcs_trainer_gather_render reads: (size, a, Lc, T) then S x (offset,
+ * L_s, k_s, c_s) */
+#define DCS_RENDER_ROW(S) (4 + 4 * (S))
+
 /* compute_inverse for n_src magnitude matrices sharing one phase:       transform.py:271-273, 337-396
  *   X = (mag / pre_div) * sqrt(N) * exp(j*phase) -> irfft -> window -> overlap-add -> / sum(w*w)
  * mag_d [n_src][n_frames, ld] (source stride src_stride elements), phase_d [n_frames, ld],
@@ -495,6 +520,20 @@ DCS_API int dcs_trainer_gather_channels(dcs_ctx* ctx, const float* data_d, const
 DCS_API int dcs_trainer_gather_score(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* notes_d,
                                      const int64_t* note_files_d, const int* windows_d, int batch, int time_context, int F,
                                      int ninst, int width, float scale, float* inputs_d, float* targets_d);
+/* The feed of the augmented trainers (examples/hiphopss/augmentations/trainCNN_{cs,instr,mix}_aug.py), in place of the
+ * compute_features_*_aug.py files read back by LargeDataset (dataset.py:383-488): the windows are transformed from source
+ * audio resident on the device, rendered by the rule of dcs_stft_forward_render.  bank_d [bank_len] float32.  files_d
+ * [n_files][DCS_RENDER_ROW(S)] int64: per virtual file -- what one .data file of the reference holds, i.e. one chunk of one
+ * variant -- (size, a, Lc, T = dcs_frame_count(Lc, hop)) then (offset, L_s, k_s, c_s) per track; gains_d [n_files][1 + S]
+ * float64 = (m, g_s).  windows_d [batch][2] int32 = (virtual file, first frame) with dcs_trainer_gather's zero rules: file
+ * < 0 (or >= n_files) is an all-zero window, frames past T are zero.  inputs_d [batch][1][tc][F] = scale * mag(mix),
+ * targets_d [batch][S][tc][F] = scale * mag(r_s) at channel c_s - 1, F = frame / 2 + 1; each product rounded once to
+ * float32.  One launch per batch, no intermediate audio or feature buffer.  The table lives on the device, so the kernel
+ * bounds it: samples outside the bank read as zero, a channel outside 1 .. S is not written.  S 1 .. 8, batch and
+ * time_context >= 1, else DCS_EINVAL. */
+DCS_API int dcs_trainer_gather_render(dcs_ctx* ctx, dcs_stft* plan, const float* bank_d, int64_t bank_len,
+                                      const int64_t* files_d, const double* gains_d, int n_files, const int* windows_d,
+                                      int batch, int time_context, int S, float scale, float* inputs_d, float* targets_d);
 /* One file's note table notes_h [ninst][n_notes][width] (first frame, end frame, MIDI number, then width - 3 values: first
  * bin, end bin per harmonic; util.expandMidi) -> packed_h [ninst][n_notes][width - 1] ints for dcs_trainer_gather_score, on
  * the host.  Notes with MIDI number <= 0 and bands with end bin <= 0 are dropped, as filterSpec drops them.  A band outside

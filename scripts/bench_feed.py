@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Feed benchmark of the augmented hiphop trainer: what one batch of training windows costs when it is cut from resident
+feature files (``dcs_trainer_gather``, the feed of ``FeatureWindows``), when it is rendered and transformed from resident
+source audio with the 14 circular-shift variants (``dcs_trainer_gather_render``, the feed of ``RenderedWindows``), and what
+the training step it feeds costs (``dcs_trainer_step``, mode 2).  Prints one JSON line.
+
+    python scripts/bench_feed.py [--batch 32] [--time_context 30] [--seconds 95] [--songs 2] [--steps 200] [--warmup 20]
+                                 [--repeats 5]
+
+The data: ``--songs`` seeded songs of ``--seconds`` at 44.1 kHz (four sources each), frame 1024 / hop 512, so F = 513; the cs
+variants of every song in 30 s chunks; windows='all', seeded permutation.  The resident files of the gather are the float64
+render of the same virtual files cast to float32 -- what compute_features.py --augment cs would have written -- so both
+feeds serve the same windows.  Each of the three is timed alone: ``--warmup`` calls, a synchronise, ``--steps`` calls on
+changing batches of the permutation with no host synchronisation inside, a synchronise; ms = wall time / steps, and the
+window is repeated ``--repeats`` times (median and spread are reported).  The window tables are uploaded before the timed
+window (the host's per-batch copy of a 32 x 2 int32 table is the same for both feeds).  A kernel breakdown comes from
+``rocprofv3 --kernel-trace --stats -- python scripts/bench_feed.py``, in a run of its own."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, n_args, steps, warmup, repeats, sync):
+    for i in range(warmup):
+        fn(i % n_args)
+    out = []
+    for _ in range(repeats):
+        sync()
+        t0 = time.perf_counter()
+        for i in range(steps):
+            fn(i % n_args)
+        sync()
+        out.append((time.perf_counter() - t0) * 1e3 / steps)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--time_context", type=int, default=30)
+    ap.add_argument("--overlap", type=int, default=25)
+    ap.add_argument("--seconds", type=float, default=95.0)
+    ap.add_argument("--songs", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    import torch
+    import deepconvsep_amd as dcs
+    from deepconvsep_amd import _lib, augment
+    from deepconvsep_amd.runtime import _ptr, default_context
+    from deepconvsep_amd.separation import blackmanharris
+    from deepconvsep_amd.synth import synth_audio
+    from deepconvsep_amd.training import Trainer, glorot_init
+    ctx = default_context()
+    sr, frame, hop, B, tc = 44100, 1024, 512, a.batch, a.time_context
+    F = frame // 2 + 1
+    signals, vfiles = {}, []
+    for s in range(a.songs):
+        ln = {}
+        for j, name in enumerate(augment.CHANNELS):
+            n = int(a.seconds * sr) + 1000 * j + 333 * s
+            signals[(s, name)] = synth_audio(n, seed=100 + 4 * s + j) * 0.25
+            ln[name] = n
+        vfiles += augment.virtual_files('cs', ln, sr=sr, song=s)
+    rw = augment.RenderedWindows(signals, vfiles, tc, a.overlap, 0.3, 'all', B, 0, ctx, frame, hop, blackmanharris)
+    rw._upload()
+    # the same windows from resident float32 feature blocks
+    tt = dcs.transformFFT(frameSize=frame, hopSize=hop, sampleRate=sr, window=blackmanharris)
+    bank64 = augment.Bank(signals, np.float64, ctx)
+    blocks, files, off = [], [], 0
+    for vf in vfiles:
+        for b in augment.render_features(tt, bank64, vf):
+            blocks.append(ctx.to_device(b, np.float32).reshape(-1))
+            files.append((off, b.shape[1]))
+            off += b.size
+    del bank64
+    with ctx.stream_scope():
+        data_d = torch.cat(blocks)
+        del blocks
+        files_d = torch.from_numpy(np.asarray(files, dtype=np.int64)).to(ctx.device)
+        perm = np.random.RandomState(0).permutation(rw.total)
+        n_batches = min(rw.iteration_size, 64)
+        wins = [torch.from_numpy(np.ascontiguousarray(rw.table[perm[i * B:(i + 1) * B]])).to(ctx.device) for i in range(n_batches)]
+        x = torch.empty((B, 1, tc, F), dtype=torch.float32, device=ctx.device)
+        t = torch.empty((B, 4, tc, F), dtype=torch.float32, device=ctx.device)
+        x2, t2 = torch.empty_like(x), torch.empty_like(t)
+
+        def gather(i):
+            _lib.check(ctx._lib.dcs_trainer_gather(ctx._h, _ptr(data_d), _ptr(files_d), _ptr(wins[i]), B, tc, F, 0.3, _ptr(x),
+                                                   _ptr(t)))
+
+        def render(i):
+            _lib.check(ctx._lib.dcs_trainer_gather_render(ctx._h, rw._plan._h, _ptr(rw._bank.tensor), rw._bank.length,
+                                                          _ptr(rw._rows_d), _ptr(rw._gains_d), len(rw.rows), _ptr(wins[i]), B, tc,
+                                                          4, 0.3, _ptr(x2), _ptr(t2)))
+        # the two feeds serve the same windows: largest difference over the batches, before anything is timed
+        err = 0.0
+        for i in range(min(n_batches, 8)):
+            gather(i)
+            render(i)
+            err = max(err, float((x - x2).abs().max()), float((t - t2).abs().max()))
+        trainer = Trainer(ctx, params=glorot_init('dsd', tc, F, 0), batch_size=B, time_context=tc, feat_size=F)
+
+        def step(i):
+            trainer.run(x, t, 2)
+        sync = ctx.synchronize
+        g = timed(gather, n_batches, a.steps, a.warmup, a.repeats, sync)
+        r = timed(render, n_batches, a.steps, a.warmup, a.repeats, sync)
+        s = timed(step, n_batches, a.steps, a.warmup, a.repeats, sync)
+    med = lambda v: float(np.median(v))  # noqa: E731
+    print(json.dumps(dict(
+        batch=B, time_context=tc, feat_size=F, songs=a.songs, seconds=a.seconds, virtual_files=len(rw.rows), windows=rw.total,
+        bank_mb=round(rw._bank.length * 4 / 1e6, 1), features_mb=round(off * 4 / 1e6, 1), frames_per_batch=B * tc * 5,
+        gather_ms=round(med(g), 4), gather_ms_min_max=[round(min(g), 4), round(max(g), 4)],
+        gather_render_ms=round(med(r), 4), gather_render_ms_min_max=[round(min(r), 4), round(max(r), 4)],
+        step_ms=round(med(s), 4), step_ms_min_max=[round(min(s), 4), round(max(s), 4)],
+        render_over_gather=round(med(r) / med(g), 2), render_over_step=round(med(r) / med(s), 3),
+        max_abs_difference_of_the_feeds=err, steps=a.steps, warmup=a.warmup, repeats=a.repeats)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
