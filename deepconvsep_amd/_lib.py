@@ -126,6 +126,10 @@ def load():
     proto("dcs_stft_forward_render_f64", i32, vp, vp, i64, i32, vp, vp, i64, vp, i32, vp, i64, i64, vp)
     proto("dcs_stft_forward_render_f32", i32, vp, vp, i64, i32, vp, vp, i64, vp, i32, vp, i64, i64, vp)
     proto("dcs_trainer_gather_render", i32, vp, vp, vp, i64, vp, vp, i32, vp, i32, i32, i32, f32, vp, vp)
+    proto("dcs_score_render_pack", i32, vp, vp, i32, i64, vp)
+    proto("dcs_stft_forward_score_render_f64", i32, vp, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp)
+    proto("dcs_stft_forward_score_render_f32", i32, vp, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp)
+    proto("dcs_trainer_gather_score_render", i32, vp, vp, vp, i64, vp, i64, vp, i32, vp, i32, i32, i32, f32, vp, vp)
     proto("dcs_trainer_set_rand", i32, vp, vp)
     proto("dcs_trainer_out_count", i32, vp, POINTER(i32))
     _lib = lib

@@ -1,5 +1,6 @@
-// The in-LDS complex FFT and the small helpers shared by the STFT kernels of fft.hip and fft_render.hip: one definition,
-// so that a frame transformed by either comes out bit for bit the same.  Internal linkage (device templates).
+// The in-LDS complex FFT and the small helpers shared by the STFT kernels of fft.hip, fft_render.hip and
+// fft_score_render.hip: one definition, so that a frame transformed by any of them comes out bit for bit the same.
+// Internal linkage (device templates).
 #pragma once
 #include "dcs_internal.h"
 
@@ -114,5 +115,28 @@ __device__ __forceinline__ float dcs_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double dcs_sqrt(double x) { return sqrt(x); }
 __device__ __forceinline__ void dcs_sincos(float a, float* s, float* c) { sincosf(a, s, c); }
 __device__ __forceinline__ void dcs_sincos(double a, double* s, double* c) { sincos(a, s, c); }
+
+// The tail of the render kernels (fft_render.hip, fft_score_render.hip): Z = the length-M complex transform of the frame
+// packed as (even, odd) samples; writes bins 0 .. M of the real transform as mag = |X| / sqrt(N) (SCALED: times `scale`)
+// and zeroes the row padding up to ld.  Every thread of the workgroup calls it.
+template <typename R, typename R2, bool SCALED>
+__device__ __forceinline__ void packed_real_mag_row(const R2* __restrict__ Z, const R2* __restrict__ tw, int M, int64_t ld,
+                                                    R sqrt_n, R scale, R* __restrict__ orow) {
+    const int tid = threadIdx.x;
+    for (int k = tid; k <= M; k += kThreads) {
+        const R2 zk = Z[k & (M - 1)];
+        const R2 zm = Z[(M - k) & (M - 1)];
+        // E = (zk + conj(zm))/2 ; O = -i (zk - conj(zm))/2 ; X = E + w^k O   (stft_forward_kernel, term for term)
+        const R er = R(0.5) * (zk.x + zm.x), ei = R(0.5) * (zk.y - zm.y);
+        const R orr = R(0.5) * (zk.y + zm.y), oi = R(-0.5) * (zk.x - zm.x);
+        const R2 w = tw[k];
+        const R xr = er + (w.x * orr - w.y * oi);
+        const R xi = ei + (w.x * oi + w.y * orr);
+        const R ax = dcs_sqrt(xr * xr + xi * xi);
+        const R mag = ax / sqrt_n;
+        orow[k] = SCALED ? scale * mag : mag;
+    }
+    for (int k = M + 1 + tid; k < ld; k += kThreads) orow[k] = R(0);   // row padding
+}
 
 }  // namespace

@@ -125,20 +125,7 @@ __global__ __launch_bounds__(kThreads) void stft_render_kernel(
     }
     __syncthreads();
     const R2* Z = fft_lds<R, R2, -1>(buf0, buf1, tw, M, log2m);
-    for (int k = tid; k <= M; k += kThreads) {
-        const R2 zk = Z[k & (M - 1)];
-        const R2 zm = Z[(M - k) & (M - 1)];
-        // E = (zk + conj(zm))/2 ; O = -i (zk - conj(zm))/2 ; X = E + w^k O   (stft_forward_kernel, term for term)
-        const R er = R(0.5) * (zk.x + zm.x), ei = R(0.5) * (zk.y - zm.y);
-        const R orr = R(0.5) * (zk.y + zm.y), oi = R(-0.5) * (zk.x - zm.x);
-        const R2 w = tw[k];
-        const R xr = er + (w.x * orr - w.y * oi);
-        const R xi = ei + (w.x * oi + w.y * orr);
-        const R ax = dcs_sqrt(xr * xr + xi * xi);
-        const R mag = ax / sqrt_n;
-        orow[k] = FEED ? scale * mag : mag;
-    }
-    for (int k = M + 1 + tid; k < ld; k += kThreads) orow[k] = R(0);   // row padding
+    packed_real_mag_row<R, R2, FEED>(Z, tw, M, ld, sqrt_n, scale, orow);
 }
 
 template <typename R, typename R2, bool FEED>

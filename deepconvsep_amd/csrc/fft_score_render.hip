@@ -1,0 +1,298 @@
+// Score-rendered forward STFT for gfx950: the RWC-sample training features of the Bach10 trainers, computed from a bank of
+// note samples resident on the device.
+//
+// Replaces the note-by-note synthesis of examples/bach10/compute_features_bach10rwc.py:112-139, the float64 feature files
+// it writes through compute_transform (:141; 318 MB per 45 s chunk and combination) and LargeDataset reading them back
+// (dataset.py:383-488).
+//
+// A track is assembled from many note samples, written in list order by assignment, so a later note overwrites an earlier
+// one where they overlap:
+//
+//   track_s[n] = bank[off_m + (n - b_m)]  for the LARGEST m of track s with b_m <= n < b_m + len_m, else 0   (0 <= n < size)
+//   mix[n]     = ((track_0[n] + track_1[n]) + track_2[n]) + ...       in list order, one addition each
+//
+// Note table (int64 rows (b, off, len, E), grouped per track in list order): b is non-decreasing within a track and E is
+// the running maximum of b + len over the track's notes so far (dcs_score_render_pack builds and checks it on the host).
+// With that order the note covering n is found from the last note with b <= n by walking back while E > n.  One workgroup
+// (256 threads) forms one windowed frame of one channel: it first resolves, once, the frame's candidate notes of every
+// track -- those with b < frame end and E > frame start, two binary searches by one thread per track, four integers per
+// track in LDS -- and a sample's lookup then stays inside that range.  The frame is transformed by the FFT body of
+// stft_forward_kernel (fft_lds.h) with the tail of stft_render_kernel (packed_real_mag_row): the float64 block equals the
+// existing kernel on host-rendered audio bit for bit.
+//
+// Descriptor of a virtual file (DCS_SCORE_RENDER_ROW(S) int64): size, T, then S x (first note, note count).  The file path
+// builds both tables on the host (validated there); the feed reads tables the caller keeps on the device, so the kernel
+// itself bounds every note index and every bank index: what lies outside reads as zero.
+#include "dcs_internal.h"
+#include "fft_lds.h"
+
+#include <vector>
+
+namespace {
+
+constexpr int kFileHead = 2;    // size, T
+constexpr int kMaxTracks = 8;
+
+// sample n of a track whose candidate notes are [lo, hi) of `notes`
+template <typename R>
+__device__ __forceinline__ R score_track(const R* __restrict__ bank, int64_t bank_len, const int64_t* __restrict__ notes, int lo,
+                                         int hi, int64_t n) {
+    int a = lo, z = hi;                     // a = one past the last note with b <= n
+    while (a < z) {
+        const int mid = (a + z) >> 1;
+        if (notes[4 * (int64_t)mid] <= n) a = mid + 1; else z = mid;
+    }
+    for (int m = a - 1; m >= lo; --m) {
+        const int64_t* r = notes + 4 * (int64_t)m;
+        const int64_t i = n - r[0];
+        if (i < r[2]) {                     // the latest note that covers n
+            const int64_t bi = r[1] + i;
+            return (i < 0 || bi < 0 || bi >= bank_len) ? R(0) : bank[bi];
+        }
+        if (r[3] <= n) break;               // no earlier note reaches n
+    }
+    return R(0);
+}
+
+// sample n (relative to the rendered signal) of channel j (0: the mixture, 1 + s: track s)
+template <typename R>
+__device__ __forceinline__ R score_sample(const R* __restrict__ bank, int64_t bank_len, const int64_t* __restrict__ notes,
+                                          const int* __restrict__ lo, const int* __restrict__ hi, int64_t size, int S, int j,
+                                          int64_t n) {
+#pragma clang fp contract(off)
+    if (n < 0 || n >= size) return R(0);
+    if (j > 0) return score_track<R>(bank, bank_len, notes, lo[j - 1], hi[j - 1], n);
+    R acc = score_track<R>(bank, bank_len, notes, lo[0], hi[0], n);
+    for (int s = 1; s < S; ++s) acc = acc + score_track<R>(bank, bank_len, notes, lo[s], hi[s], n);
+    return acc;
+}
+
+// FEED = false: one virtual file (row 0 of `files`), blockIdx.x = frame t, output row (j T + t) of out0 [1 + S][T][ld].
+// FEED = true: blockIdx.x = b * tc + t of window b = (file, first frame); out0 = inputs [B][1][tc][F], out1 = targets
+//   [B][S][tc][F], values times `scale`; zero rows for file < 0, file >= n_files and frames past T.
+// blockIdx.y = j: 0 the mixture, 1 + s track s.
+template <typename R, typename R2, bool FEED>
+__global__ __launch_bounds__(kThreads) void stft_score_render_kernel(
+    const R* __restrict__ bank, int64_t bank_len, const int64_t* __restrict__ notes, int n_notes,
+    const int64_t* __restrict__ files, int n_files, int S, const int* __restrict__ windows, int tc, R scale, R* __restrict__ out0,
+    R* __restrict__ out1, int64_t ld, const R* __restrict__ win, const R2* __restrict__ tw, int N, int hop, int log2m, R sqrt_n,
+    int tw_lds) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_lo[kMaxTracks], s_hi[kMaxTracks];
+    const int M = N >> 1;
+    const int tid = threadIdx.x;
+    const int j = blockIdx.y;
+    const int rs = kFileHead + 2 * S;
+    int64_t fi = 0, t = blockIdx.x;
+    bool live = true;
+    R* orow;
+    if (FEED) {
+        const int64_t b = blockIdx.x / tc;
+        const int tt = (int)(blockIdx.x - b * tc);
+        fi = windows[2 * b];
+        t = (int64_t)windows[2 * b + 1] + tt;
+        live = fi >= 0 && fi < n_files && t >= 0;
+        orow = j == 0 ? out0 + (b * tc + tt) * ld : out1 + (((b * S + j - 1) * tc) + tt) * ld;
+    }
+    const int64_t* row = files + (live ? fi : 0) * rs;
+    const int64_t size = live ? row[0] : 0;
+    const int64_t T = live ? row[1] : 0;
+    if (!FEED) orow = out0 + ((int64_t)j * T + t) * ld;
+    if (!live || t >= T) {
+        for (int k = tid; k < ld; k += kThreads) orow[k] = R(0);
+        return;
+    }
+    const int64_t base = t * (int64_t)hop - M;   // index of padded sample t * hop in the rendered signal
+    if (tid < S) {
+        // the frame's candidate notes of track tid: b < f1 and E > f0, for the frame's samples [f0, f1) inside [0, size)
+        const int64_t f0 = base > 0 ? base : 0;
+        const int64_t f1 = base + N < size ? base + N : size;
+        const int64_t first = row[kFileHead + 2 * tid], count = row[kFileHead + 2 * tid + 1];
+        int lo = 0, hi = 0;
+        if (f0 < f1 && first >= 0 && count > 0 && first <= (int64_t)n_notes - count) {
+            int a = (int)first, z = (int)(first + count);
+            while (a < z) {                 // first note with b >= f1
+                const int mid = (a + z) >> 1;
+                if (notes[4 * (int64_t)mid] < f1) a = mid + 1; else z = mid;
+            }
+            hi = a;
+            a = (int)first;
+            z = hi;
+            while (a < z) {                 // first note with E > f0
+                const int mid = (a + z) >> 1;
+                if (notes[4 * (int64_t)mid + 3] <= f0) a = mid + 1; else z = mid;
+            }
+            lo = a;
+        }
+        s_lo[tid] = lo;
+        s_hi[tid] = hi;
+    }
+    R2* buf0 = reinterpret_cast<R2*>(smem);
+    R2* buf1 = buf0 + M;
+    if (tw_lds) {   // twiddles staged in LDS with the frame, as stft_forward_kernel does
+        R2* twl = buf1 + M;
+        for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
+        tw = twl;
+    }
+    __syncthreads();
+    for (int m = tid; m < M; m += kThreads) {
+        const int64_t q = base + 2 * m;
+        const R x0 = score_sample<R>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q) * win[2 * m];
+        const R x1 = score_sample<R>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q + 1) * win[2 * m + 1];
+        buf0[m] = mk<R2, R>(x0, x1);
+    }
+    __syncthreads();
+    const R2* Z = fft_lds<R, R2, -1>(buf0, buf1, tw, M, log2m);
+    packed_real_mag_row<R, R2, FEED>(Z, tw, M, ld, sqrt_n, scale, orow);
+}
+
+template <typename R, typename R2, bool FEED>
+int launch_score_render(dcs_stft* p, const R* win, const R2* tw, const R* bank, int64_t bank_len, const int64_t* notes_d,
+                        int n_notes, const int64_t* files_d, int n_files, int S, const int* windows_d, int tc, R scale, R* out0,
+                        R* out1, int64_t ld, int64_t blocks) {
+    const int M = p->frame / 2;
+    size_t lds = (3 * (size_t)M + 1) * sizeof(R2);
+    const int tw_lds = lds <= 64 * 1024;
+    if (!tw_lds) lds = 2 * (size_t)M * sizeof(R2);   // float64 at N = 4096: the twiddles stay in global memory
+    auto kern = stft_score_render_kernel<R, R2, FEED>;
+    if (lds > 48 * 1024)
+        DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds));
+    DcsTimer tm(p->ctx, DCS_TAG_STFT);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)(1 + S)), dim3(kThreads), lds, p->ctx->stream, bank, bank_len,
+                       notes_d, n_notes, files_d, n_files, S, windows_d, tc, scale, out0, out1, ld, win, tw, p->frame, p->hop,
+                       p->log2m, (R)sqrt((double)p->frame), tw_lds);
+    tm.done();
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+int64_t sum_counts(const int64_t* counts_h, int n_tracks) {
+    int64_t n = 0;
+    for (int s = 0; s < n_tracks; ++s) {
+        if (counts_h[s] < 0 || counts_h[s] > 0x7fffffffLL - n) return -1;
+        n += counts_h[s];
+    }
+    return n;
+}
+
+template <typename R, typename R2>
+int score_render_file(dcs_stft* p, const R* win, const R2* tw, const R* bank_d, int64_t bank_len, int S, const int64_t* notes_h,
+                      const int64_t* counts_h, int64_t size, R* out_d, int64_t ld, int64_t out_rows, int64_t* frames_h) {
+    if (!p || !counts_h || (!bank_d && bank_len > 0))
+        DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: null argument");
+    if (S < 1 || S > kMaxTracks) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: %d tracks (1 .. 8)", S);
+    if (bank_len < 0 || size < 0)
+        DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: bank of %lld samples, size %lld", (long long)bank_len,
+                 (long long)size);
+    if (ld < p->frame / 2 + 1)
+        DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: ld %lld < bins %d", (long long)ld, p->frame / 2 + 1);
+    const int64_t n = sum_counts(counts_h, S);
+    if (n < 0) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: a negative note count, or more than 2^31 - 1 notes");
+    if (n > 0 && !notes_h) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: null note table");
+    const int rs = DCS_SCORE_RENDER_ROW(S);
+    // one block: the packed notes [n][4], then the file's descriptor [rs]
+    std::vector<int64_t> tab((size_t)n * 4 + rs);
+    DCS_CHECK(dcs_score_render_pack(notes_h, counts_h, S, bank_len, tab.data()));
+    const int64_t T = dcs_frame_count(size, p->hop);
+    int64_t* row = tab.data() + (size_t)n * 4;
+    row[0] = size;
+    row[1] = T;
+    int64_t first = 0;
+    for (int s = 0; s < S; ++s) {
+        row[kFileHead + 2 * s] = first;
+        row[kFileHead + 2 * s + 1] = counts_h[s];
+        first += counts_h[s];
+    }
+    if (frames_h) *frames_h = T;
+    if (!out_d) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: null output");
+    if (out_rows < (1 + S) * T)
+        DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: out_rows %lld < %lld", (long long)out_rows, (long long)((1 + S) * T));
+    if (T > 0x7fffffffLL) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: %lld frames in one launch", (long long)T);
+    DCS_ON_DEVICE(p->ctx->device);
+    void* tab_d = nullptr;
+    DCS_HIP(dcs_dev_alloc(&tab_d, tab.size() * sizeof(int64_t), "stft.score_render_table"));
+    int rc = DCS_OK;
+    if (hipMemcpy(tab_d, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
+        dcs_set_error("dcs_stft_forward_score_render: uploading the note table failed");
+        rc = DCS_EHIP;
+    }
+    const int64_t* notes_d = (const int64_t*)tab_d;
+    if (rc == DCS_OK)
+        rc = launch_score_render<R, R2, false>(p, win, tw, bank_d, bank_len, notes_d, (int)n, notes_d + (size_t)n * 4, 1, S,
+                                               nullptr, 1, R(1), out_d, nullptr, ld, T);
+    // the table is this call's own: wait for the launch, then give it back
+    if (hipStreamSynchronize(p->ctx->stream) != hipSuccess && rc == DCS_OK) {
+        dcs_set_error("dcs_stft_forward_score_render: the launch failed");
+        rc = DCS_EHIP;
+    }
+    dcs_dev_free(tab_d);
+    return rc;
+}
+
+}  // namespace
+
+DCS_API int dcs_score_render_pack(const int64_t* notes_h, const int64_t* counts_h, int n_tracks, int64_t bank_len,
+                                  int64_t* packed_h) {
+    if (!counts_h || n_tracks < 0) DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: null argument");
+    const int64_t n = sum_counts(counts_h, n_tracks);
+    if (n < 0) DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: a negative note count, or more than 2^31 - 1 notes");
+    if (n > 0 && (!notes_h || !packed_h)) DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: null note table");
+    if (bank_len < 0) DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: bank of %lld samples", (long long)bank_len);
+    int64_t m = 0;
+    for (int s = 0; s < n_tracks; ++s) {
+        int64_t prev = 0, E = 0;
+        for (int64_t i = 0; i < counts_h[s]; ++i, ++m) {
+            const int64_t b = notes_h[3 * m], off = notes_h[3 * m + 1], len = notes_h[3 * m + 2];
+            if (b < 0 || len < 0 || b > INT64_MAX - len)
+                DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: note %lld of track %d begins at %lld with %lld samples", (long long)i,
+                         s, (long long)b, (long long)len);
+            if (off < 0 || off > bank_len || len > bank_len - off)
+                DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: note %lld of track %d = [%lld, + %lld) reaches past the bank of %lld "
+                         "samples", (long long)i, s, (long long)off, (long long)len, (long long)bank_len);
+            if (b < prev)
+                DCS_FAIL(DCS_EINVAL, "dcs_score_render_pack: note %lld of track %d begins at %lld, before its predecessor at %lld "
+                         "(the notes of a track are ordered by their beginning)", (long long)i, s, (long long)b, (long long)prev);
+            prev = b;
+            if (b + len > E) E = b + len;
+            packed_h[4 * m] = b;
+            packed_h[4 * m + 1] = off;
+            packed_h[4 * m + 2] = len;
+            packed_h[4 * m + 3] = E;
+        }
+    }
+    return DCS_OK;
+}
+
+DCS_API int dcs_stft_forward_score_render_f64(dcs_stft* p, const double* bank_d, int64_t bank_len, int S, const int64_t* notes_h,
+                                              const int64_t* counts_h, int64_t size, double* out_d, int64_t ld, int64_t out_rows,
+                                              int64_t* frames_h) {
+    return score_render_file<double, double2>(p, p ? p->win_d : nullptr, p ? p->tw_d : nullptr, bank_d, bank_len, S, notes_h,
+                                              counts_h, size, out_d, ld, out_rows, frames_h);
+}
+
+DCS_API int dcs_stft_forward_score_render_f32(dcs_stft* p, const float* bank_d, int64_t bank_len, int S, const int64_t* notes_h,
+                                              const int64_t* counts_h, int64_t size, float* out_d, int64_t ld, int64_t out_rows,
+                                              int64_t* frames_h) {
+    return score_render_file<float, float2>(p, p ? p->win_f : nullptr, p ? p->tw_f : nullptr, bank_d, bank_len, S, notes_h,
+                                            counts_h, size, out_d, ld, out_rows, frames_h);
+}
+
+DCS_API int dcs_trainer_gather_score_render(dcs_ctx* ctx, dcs_stft* p, const float* bank_d, int64_t bank_len,
+                                            const int64_t* notes_d, int64_t n_notes, const int64_t* files_d, int n_files,
+                                            const int* windows_d, int batch, int time_context, int S, float scale,
+                                            float* inputs_d, float* targets_d) {
+    if (!ctx || !p || !bank_d || !files_d || !windows_d || !inputs_d || !targets_d || (!notes_d && n_notes > 0))
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_render: null argument");
+    if (p->ctx != ctx) DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_render: the plan belongs to another context");
+    if (batch < 1 || time_context < 1 || S < 1 || S > kMaxTracks || n_files < 1 || bank_len < 1 || n_notes < 0 ||
+        n_notes > 0x7fffffffLL)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_render: batch %d, time_context %d, S %d (1 .. 8), %d files, %lld notes, "
+                 "bank of %lld samples", batch, time_context, S, n_files, (long long)n_notes, (long long)bank_len);
+    if ((int64_t)batch * time_context > 0x7fffffffLL)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_render: %lld frames in one launch", (long long)batch * time_context);
+    DCS_ON_DEVICE(ctx->device);
+    return launch_score_render<float, float2, true>(p, p->win_f, p->tw_f, bank_d, bank_len, notes_d, (int)n_notes, files_d,
+                                                    n_files, S, windows_d, time_context, scale, inputs_d, targets_d,
+                                                    p->frame / 2 + 1, (int64_t)batch * time_context);
+}

@@ -5,6 +5,8 @@
                            [--model CNNbach10] [--batch_size 32] [--time_context 30] [--overlap 25] [--nepochs 20]
                            [--scale_factor 0.3] [--scale_factor_test 0.2] [--frame_size 4096] [--load] [--skip]
                            [--skip_sep] [--seed 0] [--windows reference|all]
+                           [--rwc <RWC dir> --render [--sample_size 400] [--chunk_size 45] [--original 1]
+                                                           [--sample_rate 44100]]
 
 Features come from compute_features.py (``<feature_path>/*.data``, default <db>/transforms/t3).  Per epoch the reference's six
 lines are printed and the model is saved as <output>/models/model_<NAME>.pkl (the format separate_bach10.py loads); the
@@ -16,6 +18,12 @@ per-epoch loss list is pickled as <output>/models/loss_<NAME>.data.  Then, unles
 The reference trains this one graph from three scripts -- trainCNNbach10.py, trainCNNrwc.py and trainCNNSibelius.py have the
 same build_ca and the same loss and differ only in where their features come from -- so --feature_path pointing at features
 made any other way (``[5, T, F]`` .data files: mixture, bassoon, clarinet, saxophone, violin) is the use of the other two.
+
+With --rwc PATH --render (the use of trainCNNrwc.py without its feature files) the windows are those of
+compute_features_rwc.py -- the scores of --dbs re-synthesised from the RWC note samples under PATH in --sample_size
+combinations per piece, chunks of --chunk_size seconds -- assembled and transformed per batch from the note bank resident on
+the device (``ScoreRenderedWindows``, csrc/fft_score_render.hip); no feature file is read or written, and --frame_size sets
+the transform.  Without these flags nothing changes.
 
 Differences from the reference: the window order of an epoch is RandomState(seed + epoch).permutation (the reference's
 shuffle is unseeded); --scale_factor and --scale_factor_test are floats (the reference's int() of them is a bug); --load,
@@ -35,6 +43,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
+from deepconvsep_amd import score_render  # noqa: E402
 from deepconvsep_amd.separation import Separator, blackmanharris, load_model, read_wav, write_wav  # noqa: E402
 from deepconvsep_amd.training import BACH10_COMPONENTS, FeatureWindows, Trainer  # noqa: E402
 
@@ -91,7 +100,17 @@ def main(argv=None):
     ap.add_argument("--skip_sep", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--windows", choices=("reference", "all"), default="reference")
+    ap.add_argument("--rwc", help="the rwc instrument sound path with mat and wav subfolders (with --render)")
+    ap.add_argument("--render", action="store_true", help="train on the scores of --dbs rendered from --rwc, without feature files")
+    ap.add_argument("--sample_size", type=int, default=400)
+    ap.add_argument("--chunk_size", type=float, default=45)
+    ap.add_argument("--original", type=int, default=1)
+    ap.add_argument("--sample_rate", type=int, default=44100, help="of the RWC recordings, with --render (for tests)")
     a = ap.parse_args(argv)
+    if a.render != (a.rwc is not None):
+        ap.error("--rwc PATH and --render go together")
+    if a.render and a.dbs is None:
+        ap.error("--render takes the scores from --dbs")
     db, output = a.db, a.output
     assert os.path.isdir(db), "Please input the directory for the Bach10 dataset with --db path_to_Bach10"
     assert a.dbs is None or os.path.isdir(a.dbs), \
@@ -104,10 +123,21 @@ def main(argv=None):
     params = load_model(model) if a.load else None
     F = a.frame_size // 2 + 1
     if not a.skip:
-        paths = sorted(glob.glob(os.path.join(feature_path, "*.data")))
-        if not paths:
-            raise SystemExit("no .data feature files under %s: run compute_features.py first" % feature_path)
-        data = FeatureWindows(paths, a.time_context, a.overlap, a.scale_factor, a.windows, a.batch_size, a.seed)
+        if a.render:
+            assert os.path.isdir(a.rwc), "Please input the directory for the RWC instrument sound with --rwc path_to_RWC"
+            bank = score_render.load_bank(a.rwc)
+            chunk = int(a.chunk_size) if a.chunk_size == int(a.chunk_size) else a.chunk_size
+            sfiles = [sf for _, _, v in score_render.dataset_files(a.dbs, bank, chunk, a.sample_size, bool(a.original), a.seed,
+                                                                      a.sample_rate) for sf in v]
+            if not sfiles:
+                raise SystemExit("no score under %s could be rendered from %s" % (a.dbs, a.rwc))
+            data = score_render.ScoreRenderedWindows(bank, sfiles, a.time_context, a.overlap, a.scale_factor, a.windows,
+                                                     a.batch_size, a.seed, None, a.frame_size, 512, blackmanharris)
+        else:
+            paths = sorted(glob.glob(os.path.join(feature_path, "*.data")))
+            if not paths:
+                raise SystemExit("no .data feature files under %s: run compute_features.py first" % feature_path)
+            data = FeatureWindows(paths, a.time_context, a.overlap, a.scale_factor, a.windows, a.batch_size, a.seed)
         if data.iteration_size == 0:
             raise SystemExit("%d windows are fewer than one batch of %d" % (data.total, a.batch_size))
         if data.F != F:

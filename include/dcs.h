@@ -149,6 +149,36 @@ DCS_API int dcs_stft_forward_render_f32(dcs_stft* plan, const float* bank_d, int
  * L_s, k_s, c_s) */
 #define DCS_RENDER_ROW(S) (4 + 4 * (S))
 
+/* The note table of the score renderer (csrc/fft_score_render.hip).  notes_h [sum counts_h][3] int64 = (b: first sample of
+ * the note in the rendered track, off: offset of its sample in the bank, len), grouped per track in the order the reference
+ * writes them (examples/bach10/compute_features_bach10rwc.py:125-134: each note is ASSIGNED into the track, so a later note
+ * overwrites an earlier one where they overlap); counts_h [n_tracks].  packed_h [sum counts_h][4] = (b, off, len, E), E the
+ * running maximum of b + len over the track's notes so far.  Host only, no device needed.  b >= 0, len >= 0, [off, off +
+ * len) inside the bank, b non-decreasing within a track (what lets the kernel find the covering note of a sample without
+ * searching the table), at most 2^31 - 1 notes, else DCS_EINVAL. */
+DCS_API int dcs_score_render_pack(const int64_t* notes_h, const int64_t* counts_h, int n_tracks, int64_t bank_len,
+                                  int64_t* packed_h);
+/* The feature block of one score-rendered virtual file: S tracks assembled note by note from a bank of instrument samples,
+ * their mixture, and the transform of each, in ONE launch and without the rendered audio ever existing.  Replaces
+ * compute_features_bach10rwc.py:112-139 (the tracks), :139 (the mixture, np.sum over the tracks = the sequential sum in
+ * list order) and :141 (compute_transform, transform.py:80-131).  bank_d [bank_len]; notes_h / counts_h [S] as for
+ * dcs_score_render_pack, which this call applies.
+ *   track_s[n] = bank[off_m + (n - b_m)] for the largest m of track s with b_m <= n < b_m + len_m, else 0   (0 <= n < size)
+ *   mix[n]     = ((track_0[n] + track_1[n]) + track_2[n]) + ...
+ * out_d [1 + S][T][ld], T = dcs_frame_count(size, hop) (returned in *frames_h if not NULL): channel 0 = compute_file(mix),
+ * channel 1 + s = compute_file(track_s); out_rows >= (1 + S) T.  _f64 takes a float64 bank and equals
+ * dcs_stft_forward_f64_clips on the host-rendered audio bit for bit; _f32 takes a float32 bank.  S 1 .. 8, ld >= bins, a
+ * valid note table, else DCS_EINVAL and nothing is launched. */
+DCS_API int dcs_stft_forward_score_render_f64(dcs_stft* plan, const double* bank_d, int64_t bank_len, int S,
+                                              const int64_t* notes_h, const int64_t* counts_h, int64_t size, double* out_d,
+                                              int64_t ld, int64_t out_rows, int64_t* frames_h);
+DCS_API int dcs_stft_forward_score_render_f32(dcs_stft* plan, const float* bank_d, int64_t bank_len, int S,
+                                              const int64_t* notes_h, const int64_t* counts_h, int64_t size, float* out_d,
+                                              int64_t ld, int64_t out_rows, int64_t* frames_h);
+/* int64 per row of the device table of virtual files dcs_trainer_gather_score_render reads: (size, T) then S x (first note,
+ * note count) */
+#define DCS_SCORE_RENDER_ROW(S) (2 + 2 * (S))
+
 /* compute_inverse for n_src magnitude matrices sharing one phase:       transform.py:271-273, 337-396
  *   X = (mag / pre_div) * sqrt(N) * exp(j*phase) -> irfft -> window -> overlap-add -> / sum(w*w)
  * mag_d [n_src][n_frames, ld] (source stride src_stride elements), phase_d [n_frames, ld],
@@ -534,6 +564,21 @@ DCS_API int dcs_trainer_gather_score(dcs_ctx* ctx, const float* data_d, const in
 DCS_API int dcs_trainer_gather_render(dcs_ctx* ctx, dcs_stft* plan, const float* bank_d, int64_t bank_len,
                                       const int64_t* files_d, const double* gains_d, int n_files, const int* windows_d,
                                       int batch, int time_context, int S, float scale, float* inputs_d, float* targets_d);
+/* The feed of the Bach10 trainers on RWC-sample data (examples/bach10/trainCNNrwc.py), in place of the
+ * compute_features_bach10rwc.py files (:112-141, one float64 file per combination and score chunk) read back by
+ * LargeDataset (dataset.py:383-488): the windows are transformed from a bank of note samples resident on the device, by the
+ * rule of dcs_stft_forward_score_render.  bank_d [bank_len] float32.  notes_d [n_notes][4] int64 as dcs_score_render_pack
+ * wrote it; files_d [n_files][DCS_SCORE_RENDER_ROW(S)] int64: per virtual file (size, T = dcs_frame_count(size, hop)) then
+ * (first note, note count) per track.  windows_d [batch][2] int32 = (virtual file, first frame) with dcs_trainer_gather's
+ * zero rules: file < 0 or >= n_files and frames past T give zero rows.  inputs_d [batch][1][tc][F] = scale * mag(mix),
+ * targets_d [batch][S][tc][F] = scale * mag(track_s), F = frame / 2 + 1, each product rounded once to float32.  One launch
+ * per batch.  The tables live on the device, so the kernel bounds them: a track whose notes lie outside the table is
+ * silent, samples outside the bank read as zero.  S 1 .. 8, batch, time_context, n_files and bank_len >= 1, else
+ * DCS_EINVAL. */
+DCS_API int dcs_trainer_gather_score_render(dcs_ctx* ctx, dcs_stft* plan, const float* bank_d, int64_t bank_len,
+                                            const int64_t* notes_d, int64_t n_notes, const int64_t* files_d, int n_files,
+                                            const int* windows_d, int batch, int time_context, int S, float scale,
+                                            float* inputs_d, float* targets_d);
 /* One file's note table notes_h [ninst][n_notes][width] (first frame, end frame, MIDI number, then width - 3 values: first
  * bin, end bin per harmonic; util.expandMidi) -> packed_h [ninst][n_notes][width - 1] ints for dcs_trainer_gather_score, on
  * the host.  Notes with MIDI number <= 0 and bands with end bin <= 0 are dropped, as filterSpec drops them.  A band outside

@@ -5,7 +5,14 @@ source audio with the 14 circular-shift variants (``dcs_trainer_gather_render``,
 the training step it feeds costs (``dcs_trainer_step``, mode 2).  Prints one JSON line.
 
     python scripts/bench_feed.py [--batch 32] [--time_context 30] [--seconds 95] [--songs 2] [--steps 200] [--warmup 20]
-                                 [--repeats 5]
+                                 [--repeats 5] [--source cs|score]
+
+``--source score`` measures the feed of the Bach10 RWC trainer instead (``dcs_trainer_gather_score_render``, the feed of
+``ScoreRenderedWindows``): frame 4096 / hop 512 (F = 2049), four tracks, ``--songs`` virtual files of ``--seconds`` (default
+30) assembled from a synthetic note bank (4 instruments x 24 notes of 2 s) by seeded scores of about two notes per second
+and track, consecutive notes overlapping by 0.2 s.  Against it: (a) ``dcs_trainer_gather`` on the float64 render of the same
+files cast to float32 and resident -- what the new feed replaces -- and (b) ``dcs_trainer_gather_render`` at the same shape
+on whole-signal tracks of the same length, which does the same FFT work without the note lookup.
 
 The data: ``--songs`` seeded songs of ``--seconds`` at 44.1 kHz (four sources each), frame 1024 / hop 512, so F = 513; the cs
 variants of every song in 30 s chunks; windows='all', seeded permutation.  The resident files of the gather are the float64
@@ -41,6 +48,96 @@ def timed(fn, n_args, steps, warmup, repeats, sync):
     return out
 
 
+def main_score(a):
+    import torch
+    import deepconvsep_amd as dcs
+    from deepconvsep_amd import _lib, augment, rwc, score_render
+    from deepconvsep_amd.runtime import _ptr, default_context
+    from deepconvsep_amd.separation import blackmanharris
+    from deepconvsep_amd.synth import synth_audio
+    ctx = default_context()
+    sr, frame, hop, B, tc, S = 44100, 4096, 512, a.batch, a.time_context, 4
+    F = frame // 2 + 1
+    seconds = 30.0 if a.seconds == 95.0 else a.seconds
+    size = int(seconds * sr)
+    bank = rwc.NoteBank.from_arrays({(i, p): synth_audio(2 * sr, seed=1000 + 24 * i + p, silence=False) * 0.25
+                                     for i in range(S) for p in range(24)}, sr=sr)
+    rs = np.random.RandomState(0)
+    sfiles, n_notes = [], 0
+    for f in range(a.songs):
+        tracks = []
+        for i in range(S):
+            b = np.sort((np.arange(0, seconds, 0.5) + rs.uniform(0, 0.2, int(np.ceil(seconds / 0.5)))) * sr).astype(np.int64)
+            b = b[b < size]
+            notes = []
+            for x in b:
+                e = bank.index[(i, int(rs.randint(24)))]
+                notes.append((int(x), e.offset, int(min(e.length, 0.7 * sr, size - x))))
+            tracks.append(tuple(notes))
+            n_notes += len(notes)
+        sfiles.append(score_render.ScoreFile("file_%d" % f, size, tuple(tracks)))
+    sw = score_render.ScoreRenderedWindows(bank, sfiles, tc, a.overlap, 0.3, 'all', B, 0, ctx, frame, hop, blackmanharris)
+    sw._upload()
+    # (b) whole-signal tracks of the same length: the same table of windows
+    signals = {(f, i): synth_audio(size, seed=2000 + S * f + i) * 0.25 for f in range(a.songs) for i in range(S)}
+    vfiles = [augment.VirtualFile(tuple(augment.Track((f, i), 0, 1.0, 1 + i) for i in range(S)), 1.0, size, ((0, size),),
+                                  ("whole_%d" % f,)) for f in range(a.songs)]
+    rw = augment.RenderedWindows(signals, vfiles, tc, a.overlap, 0.3, 'all', B, 0, ctx, frame, hop, blackmanharris)
+    rw._upload()
+    assert np.array_equal(rw.table, sw.table)
+    # (a) the same windows from resident float32 feature blocks
+    tt = dcs.transformFFT(frameSize=frame, hopSize=hop, sampleRate=sr, window=blackmanharris)
+    blocks, files, off = [], [], 0
+    for sf in sfiles:
+        b = score_render.render_score_features(tt, bank, sf)
+        blocks.append(ctx.to_device(b, np.float32).reshape(-1))
+        files.append((off, b.shape[1]))
+        off += b.size
+    with ctx.stream_scope():
+        data_d = torch.cat(blocks)
+        del blocks
+        files_d = torch.from_numpy(np.asarray(files, dtype=np.int64)).to(ctx.device)
+        perm = np.random.RandomState(0).permutation(sw.total)
+        n_batches = min(sw.iteration_size, 64)
+        wins = [torch.from_numpy(np.ascontiguousarray(sw.table[perm[i * B:(i + 1) * B]])).to(ctx.device) for i in range(n_batches)]
+        x = torch.empty((B, 1, tc, F), dtype=torch.float32, device=ctx.device)
+        t = torch.empty((B, S, tc, F), dtype=torch.float32, device=ctx.device)
+        x2, t2 = torch.empty_like(x), torch.empty_like(t)
+        x3, t3 = torch.empty_like(x), torch.empty_like(t)
+
+        def gather(i):
+            _lib.check(ctx._lib.dcs_trainer_gather(ctx._h, _ptr(data_d), _ptr(files_d), _ptr(wins[i]), B, tc, F, 0.3, _ptr(x),
+                                                   _ptr(t)))
+
+        def render(i):
+            _lib.check(ctx._lib.dcs_trainer_gather_render(ctx._h, rw._plan._h, _ptr(rw._bank.tensor), rw._bank.length,
+                                                          _ptr(rw._rows_d), _ptr(rw._gains_d), len(rw.rows), _ptr(wins[i]), B, tc,
+                                                          S, 0.3, _ptr(x2), _ptr(t2)))
+
+        def score(i):
+            _lib.check(ctx._lib.dcs_trainer_gather_score_render(
+                ctx._h, sw._plan._h, _ptr(sw._bank_d), bank.length, _ptr(sw._notes_d), len(sw.notes), _ptr(sw._rows_d),
+                len(sw.rows), _ptr(wins[i]), B, tc, S, 0.3, _ptr(x3), _ptr(t3)))
+        err = 0.0
+        for i in range(min(n_batches, 4)):
+            gather(i)
+            score(i)
+            err = max(err, float((x - x3).abs().max()), float((t - t3).abs().max()))
+        sync = ctx.synchronize
+        g = timed(gather, n_batches, a.steps, a.warmup, a.repeats, sync)
+        r = timed(render, n_batches, a.steps, a.warmup, a.repeats, sync)
+        c = timed(score, n_batches, a.steps, a.warmup, a.repeats, sync)
+    med = lambda v: float(np.median(v))  # noqa: E731
+    print(json.dumps(dict(
+        source="score", batch=B, time_context=tc, feat_size=F, files=a.songs, seconds=seconds, notes=n_notes, windows=sw.total,
+        bank_mb=round(bank.length * 4 / 1e6, 1), features_mb=round(off * 4 / 1e6, 1), frames_per_batch=B * tc * (1 + S),
+        gather_ms=round(med(g), 4), gather_ms_min_max=[round(min(g), 4), round(max(g), 4)],
+        gather_render_ms=round(med(r), 4), gather_render_ms_min_max=[round(min(r), 4), round(max(r), 4)],
+        gather_score_render_ms=round(med(c), 4), gather_score_render_ms_min_max=[round(min(c), 4), round(max(c), 4)],
+        score_over_gather=round(med(c) / med(g), 2), score_over_render=round(med(c) / med(r), 3),
+        max_abs_difference_of_the_feeds=err, steps=a.steps, warmup=a.warmup, repeats=a.repeats)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -51,7 +148,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--source", choices=("cs", "score"), default="cs")
     a = ap.parse_args()
+    if a.source == "score":
+        return main_score(a)
     import torch
     import deepconvsep_amd as dcs
     from deepconvsep_amd import _lib, augment
