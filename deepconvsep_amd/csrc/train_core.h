@@ -68,6 +68,9 @@ Gemm gemm0(int M, int N, int K);
 
 enum Tile { T128x32, T64x64, T32x32 };
 
+// the dense GEMMs with M = B rows: 64 x 64 tiles from 64 rows up
+inline Tile rows_tile(int M) { return M >= 64 ? T64x64 : T32x32; }
+
 // K split into slices of a multiple of kKT for a grid of about `target` workgroups, at most `cap` slices
 void pick_split(int64_t tiles, int64_t K, int* splits, int* kchunk, int64_t target, int64_t cap);
 

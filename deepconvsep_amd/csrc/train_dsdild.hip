@@ -287,9 +287,6 @@ struct IldMap {
     }
 };
 
-// the dense GEMMs with M = B rows: 64 x 64 tiles from 64 rows up
-Tile rows_tile(int M) { return M >= 64 ? T64x64 : T32x32; }
-
 struct IldTrainer : dcs_trainer {
     int kh = 0, h2 = 0, hp = 0;
     int64_t R = 0, Rh = 0, map = 0;

@@ -5,8 +5,8 @@ single-branch form of the same graph with the same loss) and the data feed of ``
 
 ``ScoreTrainer`` has the surface of :class:`deepconvsep_amd.training.Trainer`: four input channels (the mixture times the four
 harmonic masks), four targets, ``branches=4`` the 17-array ``.pkl`` layout ``'bach10_si'``, ``branches=1`` the 11-array layout
-``'bach10_si1'`` (csrc/train_bach10si.hip on the shared core csrc/train_core.hip).  Both train the same live computation: the
-loss reads ``prediction2[:, 0:4]``, the four channels of decoder branch 0.  The 17-array layout's ``fc12``, ``fc13``, ``fc14``
+``'bach10_si1'`` (csrc/train_bach10si.hip on the shared build_ca graph csrc/train_ca.hip and the core csrc/train_core.hip).  Both train the
+same live computation: the loss reads ``prediction2[:, 0:4]``, the four channels of decoder branch 0.  The 17-array layout's ``fc12``, ``fc13``, ``fc14``
 (arrays 10 .. 15) and ``bo[4:16]`` get an exactly zero gradient in the reference, so Adadelta never moves them: the trainer
 returns them as they were given, and zeros for their gradients and accumulators.  It is a class of its own because the graph
 differs from the mono ones in its input channels; ``training.TRAINABLE`` lists the mono graphs only.

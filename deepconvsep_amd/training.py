@@ -6,7 +6,7 @@ trainCNNSibelius.py train too), and the data feed of ``dataset.LargeDataset`` (d
 ``Trainer`` holds the parameters (15 for DSD, 13 for iKala, 17 for Bach10), Adadelta's state and the baked-in uniform draw on
 the device and runs ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the loss components) as HIP kernels
 (the shared core csrc/train_core.hip behind ``dcs_trainer_*``, the graphs in csrc/train_dsd.hip, csrc/train_ikala.hip and
-csrc/train_bach10.hip).
+csrc/train_bach10.hip, the last two descriptions of the shared build_ca graph csrc/train_ca.hip).
 ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files resident on the device and cuts the reference's windows
 from them.  There is no CPU fallback.
 """

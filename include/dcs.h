@@ -447,7 +447,8 @@ DCS_API int dcs_timing_query(dcs_ctx* ctx, int which, double* avg_ms, int64_t* l
 
 /* ------------------------------------------------------------------ training (csrc/train_core.hip; examples/dsd100/trainCNN.py:
  *                                                                     csrc/train_dsd.hip; examples/ikala/trainCNN.py: csrc/train_ikala.hip;
- *                                                                     examples/bach10/trainCNNbach10.py: csrc/train_bach10.hip) */
+ *                                                                     examples/bach10/trainCNNbach10.py: csrc/train_bach10.hip; the
+ *                                                                     last two on the shared build_ca graph csrc/train_ca.hip) */
 /* The train_fn / train_fn1 pair of train_auto (trainCNN.py:132-263) for the DSD graph build_ca (:66-130; also what
  * examples/hiphopss/trainCNN.py trains): arch DCS_ARCH_DSD, time_context even in [4, 64], F <= 2049, batch 1 .. 1024, else
  * DCS_EINVAL; 15 arrays.  Or the pair of examples/ikala/trainCNN.py:120-197 for the iKala graph (:66-118): arch
@@ -467,7 +468,7 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
                                dcs_trainer** out);
 DCS_API int dcs_trainer_destroy(dcs_trainer* t);
 /* The score-informed Bach10 graph (examples/bach10_scoreinformed/trainCNNrwc.py: build_ca :134-193, train_fn / train_fn1
- * :225-283; csrc/train_bach10si.hip): dcs_trainer_create with arch DCS_ARCH_BACH10_SI (17 arrays) or DCS_ARCH_BACH10_SI1
+ * :225-283; csrc/train_bach10si.hip on csrc/train_ca.hip): dcs_trainer_create with arch DCS_ARCH_BACH10_SI (17 arrays) or DCS_ARCH_BACH10_SI1
  * (11 arrays, the single-branch form trainCNNrwc_samp.py:195-235 trains with the same loss, :275-321); time_context 2 .. 47
  * (the largest value for which dcs_model_create runs the score-informed graph: its inference kernels are the Bach10 graph's),
  * F 30 .. 2049, batch 1 .. 1024, else DCS_EINVAL.  rand_d [batch][1][tc][F]; hyper_h: eps (1e-18, :235), three ignored values,

@@ -2,7 +2,8 @@
 """Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / bach10_si / dsd_ild,
 the iKala graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the score-informed Bach10 graph
 (csrc/train_bach10si.hip; --branches 1: its 11-array layout) / the stereo DSD graph (csrc/train_dsdild.hip; --ild: its
-stage-2 loss), all on the shared core csrc/train_core.hip, against the same float32 graph, loss and Adadelta written in torch
+stage-2 loss), all on the shared core csrc/train_core.hip (the iKala and the two Bach10 graphs through the shared build_ca graph
+csrc/train_ca.hip), against the same float32 graph, loss and Adadelta written in torch
 and run with autograd on the same GPU.  Prints one JSON line per batch size.
 
     python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10|bach10_si|dsd_ild] [--ild] [--branches 4|1]
@@ -31,12 +32,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # Adadelta (the graph's launches in csrc/train_dsd.hip, Adadelta in csrc/train_core.hip)
 LAUNCHES_PER_STEP = 19
 # iKala: 7 forward launches (F3 split-K GEMM + its sum), loss + reduce, 6 backward (B3 likewise), 4 weight-gradient GEMMs,
-# split-K reduce, Adadelta (csrc/train_ikala.hip, csrc/train_core.hip)
+# split-K reduce, Adadelta (the GEMMs in csrc/train_ca.hip, conv1^T and the loss in csrc/train_ikala.hip, Adadelta in
+# csrc/train_core.hip)
 LAUNCHES_PER_STEP_IKALA = 21
-# Bach10: the iKala list with four sources per batched launch (csrc/train_bach10.hip, csrc/train_core.hip)
+# Bach10: the iKala list with four sources per batched launch (csrc/train_ca.hip, csrc/train_bach10.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_BACH10 = 21
-# score-informed Bach10: the Bach10 list with one decoder slot (csrc/train_bach10si.hip): 7 forward, loss + reduce, 6 backward,
-# 4 weight-gradient GEMMs, split-K reduce, Adadelta over the 11 stepped arrays
+# score-informed Bach10: the Bach10 list with one decoder slot (csrc/train_ca.hip, csrc/train_bach10si.hip): 7 forward, loss +
+# reduce, 6 backward, 4 weight-gradient GEMMs, split-K reduce, Adadelta over the 11 stepped arrays
 LAUNCHES_PER_STEP_BACH10SI = 21
 # stereo DSD: 8 forward launches (F3 split-K GEMM + its sum, conv1^T once per input channel), loss + reduce (stage 2: the
 # per-bin sums and their means before them), 6 backward (B3 split-K + sum), 4 weight-gradient GEMMs, split-K reduce,

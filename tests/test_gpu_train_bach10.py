@@ -1,5 +1,5 @@
-"""Bach10 trainer on the MI355X (csrc/train_bach10.hip on csrc/train_core.hip) against the float64 autograd restatement
-tests/train_bach10_ref.py."""
+"""Bach10 trainer on the MI355X (csrc/train_bach10.hip on csrc/train_ca.hip and csrc/train_core.hip) against the float64
+autograd restatement tests/train_bach10_ref.py."""
 import os
 import pickle
 import subprocess

@@ -1,5 +1,5 @@
-"""The three HIP trainers (csrc/train_core.hip, train_dsd.hip, train_ikala.hip, train_bach10.hip) where a training run goes
-and the template of test_gpu_train*.py does not: exact zeros and ties at every site that carries Theano's conventions, the
+"""The three HIP trainers (csrc/train_core.hip, train_dsd.hip, train_ca.hip with train_ikala.hip and train_bach10.hip) where
+a training run goes and the template of test_gpu_train*.py does not: exact zeros and ties at every site that carries Theano's conventions, the
 ends of the accepted shape ranges and the split-K regimes behind them, non-default hyper-parameters, and Adadelta on a live
 state -- each against the float64 restatements, gradients by norm and by element (tests/train_edges.py).  The controls that
 show these cases can fail are in tests/test_train_edges_cpu.py."""

@@ -1,5 +1,5 @@
-"""iKala trainer on the MI355X (csrc/train_ikala.hip on csrc/train_core.hip) against the float64 autograd restatement
-tests/train_ikala_ref.py."""
+"""iKala trainer on the MI355X (csrc/train_ikala.hip on csrc/train_ca.hip and csrc/train_core.hip) against the float64
+autograd restatement tests/train_ikala_ref.py."""
 import os
 import pickle
 import subprocess

@@ -1,6 +1,6 @@
-"""Score-informed Bach10 trainer on the MI355X (csrc/train_bach10si.hip on csrc/train_core.hip) against the float64 autograd
-restatement tests/train_si_ref.py.  The tolerances are those of tests/test_gpu_train_bach10.py: the same arithmetic with one
-decoder slot."""
+"""Score-informed Bach10 trainer on the MI355X (csrc/train_bach10si.hip on csrc/train_ca.hip and csrc/train_core.hip) against
+the float64 autograd restatement tests/train_si_ref.py.  The tolerances are those of tests/test_gpu_train_bach10.py: the same
+arithmetic with one decoder slot."""
 import os
 import pickle
 import subprocess
