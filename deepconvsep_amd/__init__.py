@@ -15,9 +15,11 @@ from .stereo_training import StereoFeatureWindows, StereoTrainer
 from .score_training import ScoreFeatureWindows, ScoreTrainer
 from . import augment
 from .augment import RenderedWindows, render_features
+from .score_render import ScoreInformedRenderedWindows, render_score_informed_features
 
 __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "TILER_SCRIPT", "TransformFFT",
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
            "Separator", "blackmanharris", "generate_overlapadd", "load_model", "save_model", "overlapadd",
            "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "Trainer", "FeatureWindows", "glorot_init",
-           "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features"]
+           "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features",
+           "ScoreInformedRenderedWindows", "render_score_informed_features"]

@@ -130,6 +130,8 @@ def load():
     proto("dcs_stft_forward_score_render_f64", i32, vp, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp)
     proto("dcs_stft_forward_score_render_f32", i32, vp, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp)
     proto("dcs_trainer_gather_score_render", i32, vp, vp, vp, i64, vp, i64, vp, i32, vp, i32, i32, i32, f32, vp, vp)
+    proto("dcs_trainer_gather_score_informed_render", i32, vp, vp, vp, i64, vp, i64, vp, i32, vp, i64, vp, i32, vp, i32, i32,
+          i32, f32, vp, vp)
     proto("dcs_trainer_set_rand", i32, vp, vp)
     proto("dcs_trainer_out_count", i32, vp, POINTER(i32))
     _lib = lib

@@ -23,6 +23,10 @@
 // Descriptor of a virtual file (DCS_SCORE_RENDER_ROW(S) int64): size, T, then S x (first note, note count).  The file path
 // builds both tables on the host (validated there); the feed reads tables the caller keeps on the device, so the kernel
 // itself bounds every note index and every bank index: what lies outside reads as zero.
+//
+// The score-informed trainer's feed on the same data (examples/bach10_scoreinformed/compute_features_bach10rwc.py:96-163 read
+// back by LargeDatasetMask2) is stft_score_informed_kernel below: the render feed with train::gather_score_kernel's harmonic
+// masks applied to the mixture row in the same launch.
 #include "dcs_internal.h"
 #include "fft_lds.h"
 
@@ -167,6 +171,138 @@ int launch_score_render(dcs_stft* p, const R* win, const R2* tw, const R* bank, 
     return DCS_OK;
 }
 
+// ---- the score-informed feed: the windows of stft_score_render_kernel<float, float2, true> with train::gather_score_kernel's
+// harmonic masks (train_core.hip) applied to the mixture row while it is still in registers.
+
+// the frame's candidate notes of track s: b < f1 and E > f0 for the frame's samples [f0, f1) inside [0, size) -- the rule
+// of stft_score_render_kernel, restated here so that kernel's code stays as it is
+__device__ __forceinline__ void frame_candidates(const int64_t* __restrict__ notes, int n_notes, const int64_t* __restrict__ row,
+                                                 int s, int64_t base, int N, int64_t size, int* lo_out, int* hi_out) {
+    const int64_t f0 = base > 0 ? base : 0;
+    const int64_t f1 = base + N < size ? base + N : size;
+    const int64_t first = row[kFileHead + 2 * s], count = row[kFileHead + 2 * s + 1];
+    int lo = 0, hi = 0;
+    if (f0 < f1 && first >= 0 && count > 0 && first <= (int64_t)n_notes - count) {
+        int a = (int)first, z = (int)(first + count);
+        while (a < z) {                 // first note with b >= f1
+            const int mid = (a + z) >> 1;
+            if (notes[4 * (int64_t)mid] < f1) a = mid + 1; else z = mid;
+        }
+        hi = a;
+        a = (int)first;
+        z = hi;
+        while (a < z) {                 // first note with E > f0
+            const int mid = (a + z) >> 1;
+            if (notes[4 * (int64_t)mid + 3] <= f0) a = mid + 1; else z = mid;
+        }
+        lo = a;
+    }
+    *lo_out = lo;
+    *hi_out = hi;
+}
+
+// blockIdx.x = b * tc + t of window b = (file, first frame); blockIdx.y = j: 0 the mixture, 1 + s track s.
+// j > 0: targets [B][S][tc][F] row (b, j - 1, t) = scale * mag(track), as the render feed writes it.
+// j = 0: the workgroup marks, one bit per instrument, the bins of the mask notes that sound in frame fr = first frame + t
+//   (first <= fr < end; integer OR in LDS, in the buffer of the FFT's ping-pong pair that does not hold Z) and writes inputs
+//   [B][S][tc][F] rows (b, i, t) = (filtered_i / sum filtered) * x, x = scale * mag(mix).
+// masks: per file (mask_files[2 i] = offset in ints, mask_files[2 i + 1] = P) an int table [S][P][2 + 2 npairs] as
+//   dcs_trainer_pack_score writes it; a table that does not lie inside [0, mask_len) paints nothing.
+__global__ __launch_bounds__(kThreads) void stft_score_informed_kernel(
+    const float* __restrict__ bank, int64_t bank_len, const int64_t* __restrict__ notes, int n_notes,
+    const int64_t* __restrict__ files, int n_files, int S, const int* __restrict__ masks, int64_t mask_len,
+    const int64_t* __restrict__ mask_files, int npairs, const int* __restrict__ windows, int tc, float scale,
+    float* __restrict__ inputs, float* __restrict__ targets, const float* __restrict__ win, const float2* __restrict__ tw, int N,
+    int hop, int log2m, float sqrt_n, int tw_lds) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_lo[kMaxTracks], s_hi[kMaxTracks];
+    const int M = N >> 1;
+    const int F = M + 1;
+    const int tid = threadIdx.x;
+    const int j = blockIdx.y;
+    const int rs = kFileHead + 2 * S;
+    const int64_t b = blockIdx.x / tc;
+    const int tt = (int)(blockIdx.x - b * tc);
+    const int64_t fi = windows[2 * b];
+    const int64_t t = (int64_t)windows[2 * b + 1] + tt;
+    const bool live = fi >= 0 && fi < n_files && t >= 0;
+    const int64_t plane = (int64_t)tc * F;
+    float* irow = inputs + b * S * plane + (int64_t)tt * F;                 // row (b, 0, tt); instrument i at + i * plane
+    float* trow = targets + (b * S + (j > 0 ? j - 1 : 0)) * plane + (int64_t)tt * F;
+    const int64_t* row = files + (live ? fi : 0) * rs;
+    const int64_t size = live ? row[0] : 0;
+    const int64_t T = live ? row[1] : 0;
+    if (!live || t >= T) {
+        if (j > 0) {
+            for (int k = tid; k < F; k += kThreads) trow[k] = 0.f;
+        } else {
+            for (int i = 0; i < S; ++i)
+                for (int k = tid; k < F; k += kThreads) irow[i * plane + k] = 0.f;
+        }
+        return;
+    }
+    const int64_t base = t * (int64_t)hop - M;   // index of padded sample t * hop in the rendered signal
+    if (tid < S) frame_candidates(notes, n_notes, row, tid, base, N, size, &s_lo[tid], &s_hi[tid]);
+    float2* buf0 = reinterpret_cast<float2*>(smem);
+    float2* buf1 = buf0 + M;
+    if (tw_lds) {
+        float2* twl = buf1 + M;
+        for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
+        tw = twl;
+    }
+    __syncthreads();
+    for (int m = tid; m < M; m += kThreads) {
+        const int64_t q = base + 2 * m;
+        const float x0 = score_sample<float>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q) * win[2 * m];
+        const float x1 = score_sample<float>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q + 1) * win[2 * m + 1];
+        buf0[m] = mk<float2, float>(x0, x1);
+    }
+    __syncthreads();
+    const float2* Z = fft_lds<float, float2, -1>(buf0, buf1, tw, M, log2m);
+    if (j > 0) {
+        packed_real_mag_row<float, float2, true>(Z, tw, M, F, sqrt_n, scale, trow);
+        return;
+    }
+    // fft_lds ended with a barrier: the other buffer (8 M bytes) is free and takes the F bin flags
+    unsigned* on = reinterpret_cast<unsigned*>(Z == buf0 ? buf1 : buf0);
+    for (int k = tid; k < F; k += kThreads) on[k] = 0u;
+    const int pw = 2 + 2 * npairs;
+    int64_t moff = mask_files[2 * fi], P = mask_files[2 * fi + 1];
+    const int64_t per = (int64_t)S * pw;
+    if (moff < 0 || P < 0 || P > mask_len / per || moff > mask_len - P * per) P = 0;
+    const int* tab = masks + (P > 0 ? moff : 0);
+    // mag(mix) goes through the very loop that writes it into the file path's block (packed_real_mag_row<.., false>: the
+    // compiler contracts that loop's unrolled pairs and its remainder differently, so only the loop itself gives the block's
+    // bits), parked in instrument 0's output row: thread tid writes bins tid, tid + 256, .. there and reads back only those
+    packed_real_mag_row<float, float2, false>(Z, tw, M, F, sqrt_n, scale, irow);
+    __syncthreads();
+    for (int64_t i = tid; i < S * P; i += kThreads) {
+        const int* n = tab + i * pw;
+        if (t < n[0] || t >= n[1]) continue;
+        const unsigned bit = 1u << (int)(i / P);
+        for (int k = 0; k < npairs; ++k) {
+            const int f0 = max(n[2 + 2 * k], 0), f1 = min(n[3 + 2 * k], F);
+            for (int f = f0; f < f1; ++f) atomicOr(&on[f], bit);
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k <= M; k += kThreads) {
+        const float mag = irow[k];
+        // gather_score_kernel, operation for operation
+        const unsigned m = on[k];
+        float total = 0.f;
+        for (int i = 0; i < S; ++i) {
+            const float v = ((m >> i) & 1u) ? 1.0f : 1e-18f;
+            total = i == 0 ? v : total + v;
+        }
+        const float x = scale * mag;
+        for (int i = 0; i < S; ++i) {
+            const float v = (((m >> i) & 1u) ? 1.0f : 1e-18f) / total;
+            irow[i * plane + k] = v * x;
+        }
+    }
+}
+
 int64_t sum_counts(const int64_t* counts_h, int n_tracks) {
     int64_t n = 0;
     for (int s = 0; s < n_tracks; ++s) {
@@ -295,4 +431,43 @@ DCS_API int dcs_trainer_gather_score_render(dcs_ctx* ctx, dcs_stft* p, const flo
     return launch_score_render<float, float2, true>(p, p->win_f, p->tw_f, bank_d, bank_len, notes_d, (int)n_notes, files_d,
                                                     n_files, S, windows_d, time_context, scale, inputs_d, targets_d,
                                                     p->frame / 2 + 1, (int64_t)batch * time_context);
+}
+
+DCS_API int dcs_trainer_gather_score_informed_render(dcs_ctx* ctx, dcs_stft* p, const float* bank_d, int64_t bank_len,
+                                                     const int64_t* notes_d, int64_t n_notes, const int64_t* files_d,
+                                                     int n_files, const int* masks_d, int64_t mask_len,
+                                                     const int64_t* mask_files_d, int width, const int* windows_d, int batch,
+                                                     int time_context, int S, float scale, float* inputs_d, float* targets_d) {
+    if (!ctx || !p || !bank_d || !files_d || !masks_d || !mask_files_d || !windows_d || !inputs_d || !targets_d ||
+        (!notes_d && n_notes > 0))
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_informed_render: null argument");
+    if (p->ctx != ctx) DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_informed_render: the plan belongs to another context");
+    if (batch < 1 || time_context < 1 || S < 1 || S > kMaxTracks || n_files < 1 || bank_len < 1 || n_notes < 0 ||
+        n_notes > 0x7fffffffLL || mask_len < 0)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_informed_render: batch %d, time_context %d, S %d (1 .. 8), %d files, "
+                 "%lld notes, bank of %lld samples, %lld mask ints", batch, time_context, S, n_files, (long long)n_notes,
+                 (long long)bank_len, (long long)mask_len);
+    const int npairs = (width - 3) / 2;
+    // a packed mask note is (first frame, end frame) and npairs bands: width - 1 ints
+    if (width < 5 || 2 * npairs + 2 != width - 1)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_informed_render: width %d (odd, from 5)", width);
+    if ((int64_t)batch * time_context > 0x7fffffffLL)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_informed_render: %lld frames in one launch",
+                 (long long)batch * time_context);
+    DCS_ON_DEVICE(ctx->device);
+    const int M = p->frame / 2;
+    size_t lds = (3 * (size_t)M + 1) * sizeof(float2);
+    const int tw_lds = lds <= 64 * 1024;
+    if (!tw_lds) lds = 2 * (size_t)M * sizeof(float2);
+    auto kern = stft_score_informed_kernel;
+    if (lds > 48 * 1024)
+        DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DcsTimer tm(ctx, DCS_TAG_STFT);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)batch * time_context), (unsigned)(1 + S)), dim3(kThreads), lds, ctx->stream,
+                       bank_d, bank_len, notes_d, (int)n_notes, files_d, n_files, S, masks_d, mask_len, mask_files_d, npairs,
+                       windows_d, time_context, scale, inputs_d, targets_d, p->win_f, p->tw_f, p->frame, p->hop, p->log2m,
+                       (float)sqrt((double)p->frame), tw_lds);
+    tm.done();
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
 }

@@ -15,6 +15,10 @@ where they overlap, and ``getMidi`` returns ``begin - shift`` / ``end + shift``:
 The functions up to :func:`pack_tables` are pure host code.  :func:`render_score_features`
 (``dcs_stft_forward_score_render_*``) writes the reference's files or returns their contents; :class:`ScoreRenderedWindows`
 (``dcs_trainer_gather_score_render``) is ``FeatureWindows`` without files.  There is no CPU fallback.
+:func:`score_informed_files` is the score-informed generator (``examples/bach10_scoreinformed/compute_features_bach10rwc.py``:
+notes from ``expandMidi`` placed at frame x hop, two note tables per file); :func:`render_score_informed_features` writes its
+files and :class:`ScoreInformedRenderedWindows` (``dcs_trainer_gather_score_informed_render``) is ``ScoreFeatureWindows``
+without files, harmonic masks included.
 :func:`sibelius_files` covers ``compute_features_bach10sibelius.py``, whose rule -- whole recordings shifted and scaled --
 is the one :mod:`deepconvsep_amd.augment` already renders.
 """
@@ -169,6 +173,99 @@ def score_files(FilePath, piece, bank, combos, chunk_size=45, sr=44100, hop=512,
                 tracks.append(tuple(notes))
             if tracks is not None:
                 out.append(ScoreFile(file_name(piece, c, chnk), size, tuple(tracks)))
+    return out
+
+
+# a ScoreFile with the two note tables the score-informed generator writes next to it: float64 [S, nelem_g, 2 nharmonics + 3]
+ScoreInformedFile = collections.namedtuple('ScoreInformedFile', 'name size tracks melody_g melody_e')
+
+SI_NHARMONICS, SI_INTERVAL, SI_TUNING = 20, 50, 440          # bach10_scoreinformed/compute_features_bach10rwc.py:231-233
+
+
+def si_file_name(c, chnk):
+    """The stem of the score-informed generator's files below ``<feature_path>/<piece>/<style>/`` (bach10_scoreinformed/
+    compute_features_bach10rwc.py:156): ``<str(c) in base64, as for file_name>_<chunk>``; the files are ``<stem>__m_``,
+    ``<stem>__g_`` and ``<stem>__e_`` ``.data`` / ``.shape``."""
+    return base64.encodebytes(str(c).encode('ascii')).decode('ascii') + '_' + str(chnk)
+
+
+def score_informed_files(FilePath, bank, combos, chunk_size=45, sr=44100, hop=512, frame=4096, style_midi='_original',
+                         sources=SOURCES, instrument_ids=INSTRUMENT_IDS, dynamics=DYNAMICS, styles=STYLES,
+                         nharmonics=SI_NHARMONICS, interval=SI_INTERVAL, tuning_freq=SI_TUNING):
+    """The virtual files of one piece as the score-informed generator makes them (``Engine.__call__``,
+    bach10_scoreinformed/compute_features_bach10rwc.py:96-163): for every combination ``c`` and every chunk one
+    :class:`ScoreInformedFile`.  Chunks and ``size`` as in :func:`score_files`, except that the longest score is not
+    truncated to whole seconds (:105).  The notes come from ``score.expandMidi``, in frames: ``melody_g`` with the source's
+    shift on both sides, ``melody_e`` with the shift + 0.2 s and ``fermata`` = the shift + 0.5 s (:133-137), both ``[S,
+    nelem_g, 2 nharmonics + 3]`` with ``nelem_g`` the largest ``getMidiNum`` of the sources, at least 1 (:116-121).  Every
+    row of ``melody_g`` with a MIDI number > 0 is the segment ``bank.segment(key, (end frame - first frame) * hop / sr)``
+    placed by assignment at ``b = int(floor(first frame * hop))`` with ``len = min(segment length, size - b)`` (:140-150).
+    ``expandMidi`` keeps score order and its first frames are a monotonic function of the onsets, so ``b`` is non-decreasing
+    within a track and ``dcs_score_render_pack`` takes the notes as they are.
+
+    No file where the reference writes none: a note missing from the bank (GetOutOfLoop, :143-144); a source with fewer
+    than two notes selected in the chunk (``expandMidi`` returns None, :134 raises); a note at ``b > size`` of which more
+    than one sample would be left after the cut ``segment[:size - b]`` (the assignment into the empty slice raises, :148).
+    A note at ``b == size``, or past it with at most one sample left, is assigned into an empty slice and paints nothing:
+    the file is written without it.  GetOutOfLoop is caught per chunk (:162); the other two leave ``__call__``, so the later
+    chunks of that combination are not written either."""
+    from .score import expandMidi, getMidiNum
+    scores = [s + '_g' + style_midi for s in sources]
+    max_length = 0
+    for s in scores:
+        max_length = max(max_length, midi_length(s, FilePath))
+    if chunk_size > max_length:
+        chunk_size = max_length
+    out = []
+    if chunk_size <= 0:
+        return out
+    for c in combos:
+        c = np.array(c)
+        for chnk in range(int(np.floor(max_length / chunk_size))):
+            chunk_start, chunk_end = float(chunk_size * chnk), float((chnk + 1) * chunk_size)
+            nelem_g = 1
+            for s in scores:
+                nelem_g = max(getMidiNum(s, FilePath, chunk_start, chunk_end), nelem_g)
+            melody_g = np.zeros((len(scores), int(nelem_g), 2 * nharmonics + 3))
+            melody_e = np.zeros((len(scores), int(nelem_g), 2 * nharmonics + 3))
+            nframes = int(np.ceil(chunk_size * sr / np.double(hop))) + 2
+            size = int(chunk_size * sr - int(np.max(c[:, 0].astype(float)) * sr))
+            tracks, raised = [], False
+            for i, s in enumerate(scores):
+                g = expandMidi(s, FilePath, chunk_start, chunk_end, interval, tuning_freq, nharmonics, sr, hop, frame, c[i, 0],
+                               c[i, 0], nframes)
+                e = None if g is None else expandMidi(s, FilePath, chunk_start, chunk_end, interval, tuning_freq, nharmonics, sr,
+                                                      hop, frame, c[i, 0] + 0.2, c[i, 0] + 0.2, nframes, fermata=c[i, 0] + 0.5)
+                if g is None or e is None:
+                    tracks, raised = None, True
+                    break
+                melody_g[i, :g.shape[0], :] = g
+                melody_e[i, :e.shape[0], :] = e
+                notes = []
+                for m in range(int(nelem_g)):
+                    if not melody_g[i, m, 2] > 0:
+                        continue
+                    seg = bank.segment((instrument_ids[i], int(melody_g[i, m, 2]), dynamics[int(c[i, 1])], styles[int(c[i, 2])],
+                                        int(c[i, 3])), float(melody_g[i, m, 1] - melody_g[i, m, 0]) * hop / sr)
+                    if seg is None:
+                        notes = None
+                        break
+                    b, ln = int(np.floor(melody_g[i, m, 0] * hop)), max(seg[1], 0)
+                    if b >= size:
+                        if b > size and ln - (b - size) > 1:
+                            notes, raised = None, True
+                            break
+                        continue
+                    if min(ln, size - b) > 0:
+                        notes.append((b, seg[0], min(ln, size - b)))
+                if notes is None:
+                    tracks = None
+                    break
+                tracks.append(tuple(notes))
+            if tracks is not None:
+                out.append(ScoreInformedFile(si_file_name(c, chnk), size, tuple(tracks), melody_g, melody_e))
+            if raised:
+                break
     return out
 
 
@@ -345,6 +442,83 @@ class ScoreRenderedWindows(object):
             yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])
 
 
+def render_score_informed_features(tt, bank, sf, out_dir=None):
+    """What the score-informed generator writes for the virtual file ``sf`` (bach10_scoreinformed/
+    compute_features_bach10rwc.py:156-158): the ``[1 + S, T, F]`` float64 block of :func:`render_score_features` and the two
+    note tables.  Returns ``(block, melody_g, melody_e)``, or with ``out_dir`` writes ``<out_dir>/<name>__m_``, ``__g_`` and
+    ``__e_`` ``.data`` / ``.shape`` through ``tt.saveTensor`` -- the files ``ScoreFeatureWindows`` loads -- and returns the
+    path of the ``__m_.data`` file."""
+    g, e = np.ascontiguousarray(sf.melody_g, dtype=np.float64), np.ascontiguousarray(sf.melody_e, dtype=np.float64)
+    if out_dir is None:
+        return render_score_features(tt, bank, sf), g, e
+    path = render_score_features(tt, bank, sf, out_dir)
+    tt.saveTensor(g, '_' + tt.suffix + '_g_')
+    tt.saveTensor(e, '_' + tt.suffix + '_e_')
+    return path
+
+
+class ScoreInformedRenderedWindows(ScoreRenderedWindows):
+    """``ScoreFeatureWindows`` without feature files: the windows of the :class:`ScoreInformedFile` s ``sfiles``, harmonic
+    masks included, come per batch from the note bank in one launch (``dcs_trainer_gather_score_informed_render``).  The
+    bank, the packed render notes, the file descriptors and the mask tables of ``pitch_code`` (``'g'``: ``melody_g``,
+    ``'e'``: ``melody_e``, packed by ``dcs_trainer_pack_score``) stay on the device.  ``gather(rows)`` returns inputs and
+    targets, both ``[B, S, tc, F]``; window table, ``batches(epoch)``, ``total`` and ``iteration_size`` are those of
+    :class:`ScoreRenderedWindows`."""
+
+    def __init__(self, bank, sfiles, pitch_code='e', **kw):
+        if pitch_code not in ('g', 'e'):
+            raise ValueError("pitch_code must be 'g' or 'e'")
+        super(ScoreInformedRenderedWindows, self).__init__(bank, sfiles, **kw)
+        self.pitch_code = pitch_code
+        self.ninst = self.sources
+        tables = [np.asarray(sf.melody_g if pitch_code == 'g' else sf.melody_e, dtype=np.float64) for sf in self.sfiles]
+        widths = set(t.shape[2] for t in tables)
+        if len(widths) > 1:
+            raise ValueError("note tables disagree on their width")
+        self.width = widths.pop() if widths else 0
+        if tables and (self.width < 5 or self.width % 2 == 0):
+            raise ValueError("note table width %d (odd, from 5)" % self.width)
+        if any(t.shape[0] != self.sources for t in tables):
+            raise ValueError("a note table per track is needed")
+        self._tables = tables
+        self._masks_d = None
+
+    def _upload(self):
+        if self._masks_d is not None:
+            return
+        super(ScoreInformedRenderedWindows, self)._upload()
+        import torch
+        from .score_training import pack_notes as pack_masks
+        packed, mask_files, off = [], [], 0
+        for t in self._tables:
+            m = pack_masks(self.ctx._lib, t, self.F)
+            packed.append(m.ravel())
+            mask_files.append((off, t.shape[1]))
+            off += m.size
+        self.mask_len = off
+        with self.ctx.stream_scope():
+            self._mask_files_d = torch.from_numpy(np.asarray(mask_files, dtype=np.int64).reshape(-1, 2)).to(self.ctx.device)
+            self._masks_d = torch.from_numpy(np.concatenate(packed + [np.zeros(1, np.int32)])).to(self.ctx.device)
+
+    def gather(self, rows):
+        """Inputs ``[B, S, tc, F]`` = mask_j * (mult_factor * mixture) and targets ``[B, S, tc, F]`` (device tensors) of the
+        window-table rows ``rows``."""
+        self._upload()
+        import torch
+        from .runtime import _ptr
+        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
+        B = len(win)
+        with self.ctx.stream_scope():
+            win_d = torch.from_numpy(win).to(self.ctx.device)
+            x = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            t = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            _lib.check(self.ctx._lib.dcs_trainer_gather_score_informed_render(
+                self.ctx._h, self._plan._h, _ptr(self._bank_d), self.bank.length, _ptr(self._notes_d), len(self.notes),
+                _ptr(self._rows_d), len(self.rows), _ptr(self._masks_d), self.mask_len, _ptr(self._mask_files_d), self.width,
+                _ptr(win_d), B, self.tc, self.sources, self.mult, _ptr(x), _ptr(t)))
+        return x, t
+
+
 def load_bank(rwc_path, instrument_ids=INSTRUMENT_IDS, styles=STYLES, cases=CASES, dynamics=DYNAMICS):
     """The note bank of the generator's four instruments (:217-219)."""
     from .rwc import Instrument, NoteBank
@@ -366,4 +540,25 @@ def dataset_files(db, bank, chunk_size=45, sample_size=400, original=True, seed=
     for k, f in enumerate(pieces):
         combos = rwc_combinations(time_shifts, len(DYNAMICS), len(STYLES), CASES, len(SOURCES), sample_size, seed + k)
         out.append((f, style, score_files(os.path.join(db, f), f, bank, combos, chunk_size, sr, hop, style_midi)))
+    return out
+
+
+def si_dataset_files(db, bank, chunk_size=45., sample_size=400, original=True, seed=0, sr=44100, hop=512, frame=4096,
+                     pieces=None):
+    """The virtual files of a Bach10 Sibelius tree ``db`` as the score-informed generator's main program makes them
+    (bach10_scoreinformed/compute_features_bach10rwc.py:216-249): the styles, shifts and ``sample_size`` rule of
+    :func:`dataset_files`, the combinations of :func:`rwc_combinations` (one rule for both generators) drawn per piece from
+    ``seed`` + its position, the files of :func:`score_informed_files`.  Returns ``[(piece, style name, its files)]``; the
+    reference writes them below ``<feature_path>/<piece>/<style name>/``."""
+    if original:
+        style, style_midi, time_shifts = 'original', '_original', (0., 0.1, 0.2)
+    else:
+        style, style_midi, time_shifts = 'gt', '', (0.,)
+        sample_size = min(50, sample_size)
+    out = []
+    if pieces is None:
+        pieces = [f for f in sorted(os.listdir(db)) if os.path.isdir(os.path.join(db, f)) and f[0].isdigit()]
+    for k, f in enumerate(pieces):
+        combos = rwc_combinations(time_shifts, len(DYNAMICS), len(STYLES), CASES, len(SOURCES), sample_size, seed + k)
+        out.append((f, style, score_informed_files(os.path.join(db, f), bank, combos, chunk_size, sr, hop, frame, style_midi)))
     return out

@@ -7,6 +7,8 @@ block, :196-416).
                               [--batch_size 32] [--time_context 30] [--overlap 25] [--nepochs 40] [--scale_factor 0.3]
                               [--scale_factor_test 0.2] [--pitch_code e] [--branches 4|1] [--frame_size 4096] [--load]
                               [--skip] [--skip_sep] [--seed 0] [--windows reference|all]
+                              [--dbs <Bach10 Sibelius dir> --rwc <RWC dir> --render [--sample_size 400] [--chunk_size 45]
+                                                                                    [--original 1] [--sample_rate 44100]]
 
 Features and note tables come from compute_features.py (``<feature_path>/*_m_.data`` with their ``_<pitch_code>_`` tables,
 default <db>/transforms/t3).  The network's input is the mixture times the four harmonic masks of the score, cut for every
@@ -17,6 +19,12 @@ every piece <db>/<piece> is separated as :363-416 do: the mixture is the sum of 
 its ``_b`` score files and ``LargeDatasetMask2.filterSpec``, the soft masks are applied to the sum of the input channels
 (``Separator('bach10_si', ..., score_normalise='sum', score_mixture='sum')``), --scale_factor_test scales the magnitudes; the
 results go to <output>/output/<NAME>_gt/<piece>-<source>.wav.
+
+With --dbs DIR --rwc PATH --render (the reference's own use of this script, trainCNNrwc.py on the data of
+compute_features_bach10rwc.py, without its feature files) the windows are those of compute_features_rwc.py -- the scores of
+--dbs re-synthesised from the RWC note samples under PATH in --sample_size combinations per piece -- rendered, transformed and
+masked per batch on the device (``ScoreInformedRenderedWindows``, csrc/fft_score_render.hip); no feature file is read or
+written, --frame_size sets the transform and --pitch_code is e or g.
 
 --branches 1 trains the single-branch 11-array layout of trainCNNrwc_samp.py:195-235 (the same live computation and loss;
 the 17-array layout's other three branches are dead weight that no gradient reaches).
@@ -39,6 +47,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
+from deepconvsep_amd import score_render  # noqa: E402
 from deepconvsep_amd.score import melody_table  # noqa: E402
 from deepconvsep_amd.score_training import COMPONENTS, ScoreFeatureWindows, ScoreTrainer  # noqa: E402
 from deepconvsep_amd.separation import Separator, blackmanharris, load_model, read_wav, write_wav  # noqa: E402
@@ -88,7 +97,18 @@ def main(argv=None):
     ap.add_argument("--skip_sep", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--windows", choices=("reference", "all"), default="reference")
+    ap.add_argument("--dbs", help="the Bach10 Sibelius dataset path (with --render)")
+    ap.add_argument("--rwc", help="the rwc instrument sound path with mat and wav subfolders (with --render)")
+    ap.add_argument("--render", action="store_true", help="train on the scores of --dbs rendered from --rwc, without feature files")
+    ap.add_argument("--sample_size", type=int, default=400)
+    ap.add_argument("--chunk_size", type=float, default=45.0)
+    ap.add_argument("--original", type=int, default=1)
+    ap.add_argument("--sample_rate", type=int, default=44100, help="of the RWC recordings, with --render (for tests)")
     a = ap.parse_args(argv)
+    if a.render != (a.rwc is not None):
+        ap.error("--rwc PATH and --render go together")
+    if a.render and a.dbs is None:
+        ap.error("--render takes the scores from --dbs")
     db, output = a.db, a.output
     assert os.path.isdir(db), "Please input the directory for the Bach10 dataset with --db path_to_Bach10"
     assert os.path.isdir(output), "Please input the output directory --output path_to_output"
@@ -100,12 +120,25 @@ def main(argv=None):
     params = load_model(model) if a.load else None
     F = a.frame_size // 2 + 1
     if not a.skip:
-        assert os.path.isdir(feature_path), \
-            "Please input the directory where you stored the training features --feature_path path_to_features"
-        data = ScoreFeatureWindows([feature_path], a.pitch_code, a.time_context, a.overlap, a.scale_factor, a.windows,
-                                   a.batch_size, a.seed)
-        if not data.pairs:
-            raise SystemExit("no _m_.data feature files under %s: run compute_features.py first" % feature_path)
+        if a.render:
+            assert os.path.isdir(a.dbs), \
+                "Please input the directory for the Bach10 Sibelius dataset with --dbs path_to_Bach10Sibelius"
+            assert os.path.isdir(a.rwc), "Please input the directory for the RWC instrument sound with --rwc path_to_RWC"
+            bank = score_render.load_bank(a.rwc)
+            sfiles = [sf for _, _, v in score_render.si_dataset_files(a.dbs, bank, a.chunk_size, a.sample_size, bool(a.original),
+                                                                         a.seed, a.sample_rate, 512, a.frame_size) for sf in v]
+            if not sfiles:
+                raise SystemExit("no score under %s could be rendered from %s" % (a.dbs, a.rwc))
+            data = score_render.ScoreInformedRenderedWindows(
+                bank, sfiles, a.pitch_code, time_context=a.time_context, overlap=a.overlap, mult_factor=a.scale_factor,
+                windows=a.windows, batch_size=a.batch_size, seed=a.seed, frameSize=a.frame_size, hopSize=512)
+        else:
+            assert os.path.isdir(feature_path), \
+                "Please input the directory where you stored the training features --feature_path path_to_features"
+            data = ScoreFeatureWindows([feature_path], a.pitch_code, a.time_context, a.overlap, a.scale_factor, a.windows,
+                                       a.batch_size, a.seed)
+            if not data.pairs:
+                raise SystemExit("no _m_.data feature files under %s: run compute_features.py first" % feature_path)
         if data.iteration_size == 0:
             raise SystemExit("%d windows are fewer than one batch of %d" % (data.total, a.batch_size))
         if data.F != F:

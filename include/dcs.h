@@ -580,6 +580,27 @@ DCS_API int dcs_trainer_gather_score_render(dcs_ctx* ctx, dcs_stft* plan, const 
                                             const int64_t* notes_d, int64_t n_notes, const int64_t* files_d, int n_files,
                                             const int* windows_d, int batch, int time_context, int S, float scale,
                                             float* inputs_d, float* targets_d);
+/* The feed of the score-informed Bach10 trainer on RWC-sample data (examples/bach10_scoreinformed/trainCNNrwc.py), in place
+ * of the compute_features_bach10rwc.py files (:96-163: per combination and score chunk a float64 [5][T][F] block and two note
+ * tables) read back by LargeDatasetMask2: dcs_trainer_gather_score_render and dcs_trainer_gather_score in one launch per
+ * batch, with no intermediate audio or feature buffer.  ctx .. n_files, windows_d .. scale as for
+ * dcs_trainer_gather_score_render.  masks_d [mask_len] int32: every virtual file's mask table [S][P][width - 1] exactly as
+ * dcs_trainer_pack_score writes it (ninst = S); mask_files_d [n_files][2] int64 = (offset in ints, P); width = 2 nharmonics
+ * + 3.  targets_d [batch][S][tc][F] = scale * mag(track_s); inputs_d [batch][S][tc][F] = mask_j * (scale * mag(mix)), the
+ * arithmetic of dcs_trainer_gather_score operation for operation: filtered = 1 on the rectangles (a note paints frame fr of
+ * the virtual file when first <= fr < end) and 1e-18 elsewhere, the instruments added in order in float32, one division,
+ * one product.  Both outputs equal, bit for bit, dcs_trainer_gather_score on the blocks dcs_stft_forward_score_render_f32
+ * writes.  Zero rows (both outputs): file < 0, file >= n_files, frames past T.  The tables live on the device, so the
+ * kernel bounds them: a mask table that does not lie inside [0, mask_len) paints nothing (every mask is 1 / S up to the
+ * float32 sum), bins are clipped to [0, F), a track whose render notes lie outside the note table is silent, samples
+ * outside the bank read as zero.  DCS_EINVAL, launching nothing: a null argument, a plan of another context, S outside 1 ..
+ * 8, width even or below 5 (a packed note is 2 npairs + 2 = width - 1 ints), batch, time_context, n_files or bank_len
+ * below 1, mask_len or n_notes negative. */
+DCS_API int dcs_trainer_gather_score_informed_render(dcs_ctx* ctx, dcs_stft* plan, const float* bank_d, int64_t bank_len,
+                                                     const int64_t* notes_d, int64_t n_notes, const int64_t* files_d,
+                                                     int n_files, const int* masks_d, int64_t mask_len,
+                                                     const int64_t* mask_files_d, int width, const int* windows_d, int batch,
+                                                     int time_context, int S, float scale, float* inputs_d, float* targets_d);
 /* One file's note table notes_h [ninst][n_notes][width] (first frame, end frame, MIDI number, then width - 3 values: first
  * bin, end bin per harmonic; util.expandMidi) -> packed_h [ninst][n_notes][width - 1] ints for dcs_trainer_gather_score, on
  * the host.  Notes with MIDI number <= 0 and bands with end bin <= 0 are dropped, as filterSpec drops them.  A band outside
