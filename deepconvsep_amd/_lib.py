@@ -134,6 +134,7 @@ def load():
           i32, f32, vp, vp)
     proto("dcs_trainer_set_rand", i32, vp, vp)
     proto("dcs_trainer_out_count", i32, vp, POINTER(i32))
+    proto("dcs_trainer_rectify_codes", i32, vp, POINTER(vp), i32)
     _lib = lib
     return lib
 

@@ -150,6 +150,16 @@ class Deep1x1Arch(object):
         conv11 = 2 * self.nf * nb * self.nf * d['h6'] * d['w6']
         return enc + conv11 + nb * enc
 
+    def train_flops_per_tile(self, tc, F):
+        """Multiply-add FLOPs (2 per MAC) of one training step per window (csrc/train_deep1x1.hip): the live forward pass
+        (encoder, 200 rows of the 1x1 conv, one decoder branch); backward the decoder as six forward convolutions, the 1x1
+        conv transposed and the encoder transposed from conv6 down to conv2; the weight gradients, twice each convolution
+        (its encoder and its decoder use) and once the 1x1 conv."""
+        d = self.dims(tc, F)
+        per = [2 * l['cout'] * l['cin'] * l['kh'] * self.kw * l['ho'] * l['wo'] for l in d['layers']]
+        enc, conv11 = sum(per), 2 * self.nf * self.nf * d['h6'] * d['w6']
+        return (2 * enc + conv11) + (enc + conv11 + enc - per[0]) + (2 * enc + conv11)
+
 
 ARCHS['bach10_si1'] = Arch('bach10_si1', ARCH_BACH10_SI1, 4, (30, 30, 4), 0, (30, lambda tc: int(2 * tc / 3), 1), 256, [0], 4,
                            EPS_B, ['bassoon', 'clarinet', 'saxphone', 'violin'])

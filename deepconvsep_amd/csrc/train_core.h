@@ -21,7 +21,7 @@ constexpr int kThreads = 256;
 constexpr int kKT = 32;
 constexpr int kBig = 1 << 30;
 constexpr int kLossBlocks = 1024;
-constexpr int kMaxParams = 17;
+constexpr int kMaxParams = 22;
 
 // n / d for 0 <= n < 2^31 as (umulhi(n, m) + n) >> s (round-up magic numbers)
 struct FDiv {
@@ -247,6 +247,8 @@ struct dcs_trainer {
     virtual int loss(const float* x, const float* tgt, double* out7) = 0;
     virtual int backward() = 0;
     virtual int layout(float* flat, float* const* pkl, int to_internal) = 0;
+    // dcs_trainer_rectify_codes: the graphs that keep their rectifier codes copy them out
+    virtual int codes(float* const* out_d, int n);
 
     float* param(int i) { return state + off[i]; }
     float* grad() { return state + 4 * P4; }

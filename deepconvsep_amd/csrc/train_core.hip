@@ -436,6 +436,11 @@ int dcs_trainer::finish(const float* part, int splits, int N, const float* bias,
     return DCS_OK;
 }
 
+int dcs_trainer::codes(float* const*, int) {
+    DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_rectify_codes: this graph keeps pre-activations, not codes (only arch %d has them)",
+             DCS_ARCH_BACH10_SI_1X1);
+}
+
 int dcs_trainer::reduce(const Reduce& r) {
     const int64_t most = std::max(r.count[0], r.count[1]);
     hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)dcs_cdiv(most, kThreads), 2), dim3(kThreads), 0, ctx->stream, r);
@@ -450,6 +455,7 @@ int ikala_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int bach10_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int dsdild_trainer_new(int time_context, int F, int batch, dcs_trainer** out);
 int bach10si_trainer_new(int arch, int time_context, int F, int batch, dcs_trainer** out);
+int deep1x1_trainer_new(int time_context, int F, int batch, const int64_t* shapes, int nparams, dcs_trainer** out);
 
 extern "C" {
 
@@ -465,11 +471,13 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     else if (arch == DCS_ARCH_DSD_ILD) DCS_CHECK(dsdild_trainer_new(time_context, F, batch, &t));
     else if (arch == DCS_ARCH_BACH10_SI || arch == DCS_ARCH_BACH10_SI1)
         DCS_CHECK(bach10si_trainer_new(arch, time_context, F, batch, &t));
+    else if (arch == DCS_ARCH_BACH10_SI_1X1)
+        DCS_CHECK(deep1x1_trainer_new(time_context, F, batch, shapes, nparams, &t));
     else
         DCS_FAIL(DCS_EUNSUPPORTED, "dcs_trainer_create: only the DSD graph (arch %d), the no-pool iKala graph (arch %d), "
                  "the Bach10 graph (arch %d), the stereo DSD graph (arch %d) and the score-informed Bach10 graphs (arch %d, "
-                 "%d) train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10, DCS_ARCH_DSD_ILD,
-                 DCS_ARCH_BACH10_SI, DCS_ARCH_BACH10_SI1);
+                 "%d, %d) train here", DCS_ARCH_DSD, DCS_ARCH_IKALA_NOPOOL, DCS_ARCH_BACH10, DCS_ARCH_DSD_ILD,
+                 DCS_ARCH_BACH10_SI, DCS_ARCH_BACH10_SI1, DCS_ARCH_BACH10_SI_1X1);
     // from here on every return frees t
     struct Guard {
         dcs_trainer* t;
@@ -592,6 +600,14 @@ DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int 
         if (!out_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: buffer %d is null", i);
     DCS_ON_DEVICE(t->ctx->device);
     return t->layout(t->state + which * 4 * t->P4, out_d, 0);
+}
+
+DCS_API int dcs_trainer_rectify_codes(dcs_trainer* t, float* const* out_d, int n) {
+    if (!t || !out_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_rectify_codes: null argument");
+    for (int i = 0; i < n; ++i)
+        if (!out_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_rectify_codes: buffer %d is null", i);
+    DCS_ON_DEVICE(t->ctx->device);
+    return t->codes(out_d, n);
 }
 
 DCS_API int dcs_trainer_gather(dcs_ctx* ctx, const float* data_d, const int64_t* files_d, const int* windows_d, int batch,

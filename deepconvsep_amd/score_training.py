@@ -11,6 +11,10 @@ same live computation: the loss reads ``prediction2[:, 0:4]``, the four channels
 returns them as they were given, and zeros for their gradients and accumulators.  It is a class of its own because the graph
 differs from the mono ones in its input channels; ``training.TRAINABLE`` lists the mono graphs only.
 
+``function='build_ca_1x1'`` trains the deep graph of trainCNNrwc.py:66-132 instead (csrc/train_deep1x1.hip): 22 arrays, the
+``.pkl`` layout ``'bach10_si_1x1'`` that ``arch.resolve`` tells apart, with ``branches`` 4 (the whole graph) or 1 .. 3 (the
+live-only layouts).  Its loss reads branch 0 too: rows 200 .. 799 of the 1x1 layer and ``fb[4:16]`` are dead in the same sense.
+
 ``ScoreFeatureWindows`` keeps the ``[5, T, F]`` feature files and their note tables resident on the device and cuts the
 reference's windows, masks included, in one launch per batch.  There is no CPU fallback.
 """
@@ -31,23 +35,35 @@ COMPONENTS = BACH10_COMPONENTS           # trainCNNrwc.py:336-339
 SI_EPS = BACH10_EPS                      # trainCNNrwc.py:235
 
 
-def arch_name(branches):
+FUNCTIONS = ('build_ca', 'build_ca_1x1')     # trainCNNrwc.py --function
+
+
+def arch_name(branches, function='build_ca'):
+    if function not in FUNCTIONS:
+        raise ValueError("function must be one of %r, got %r" % (FUNCTIONS, function))
+    if function == 'build_ca_1x1':
+        if branches not in (1, 2, 3, 4):
+            raise ValueError("branches must be 4 (the whole graph) or 1 .. 3 (live-only layouts), got %r" % (branches,))
+        return 'bach10_si_1x1'
     if branches not in (1, 4):
         raise ValueError("branches must be 4 (the 17-array layout) or 1 (the 11-array layout), got %r" % (branches,))
     return 'bach10_si' if branches == 4 else 'bach10_si1'
 
 
-def param_shapes(tc, F, branches=4):
-    """The .pkl shapes of build_ca: 17 arrays (trainCNNrwc.py:134-193) or, ``branches=1``, 11 (trainCNNrwc_samp.py:195-235)."""
+def param_shapes(tc, F, branches=4, function='build_ca'):
+    """The .pkl shapes of build_ca: 17 arrays (trainCNNrwc.py:134-193) or, ``branches=1``, 11 (trainCNNrwc_samp.py:195-235);
+    of build_ca_1x1: 22 arrays (:66-132), the 1x1 layer and the final bias cut to ``branches`` branches."""
+    if arch_name(branches, function) == 'bach10_si_1x1':
+        return [tuple(s) for s in ARCHS['bach10_si_1x1'].param_shapes(tc, F, branches=branches)]
     return [tuple(s) for s in ARCHS[arch_name(branches)].param_shapes(tc, F)]
 
 
-def glorot_init(tc=30, F=2049, seed=0, branches=4):
+def glorot_init(tc=30, F=2049, seed=0, branches=4, function='build_ca'):
     """Lasagne's defaults for build_ca: every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) * sqrt(2 / ((n1 + n2) *
     receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32."""
     rs = np.random.RandomState(seed)
     out = []
-    for shp in param_shapes(tc, F, branches):
+    for shp in param_shapes(tc, F, branches, function):
         if len(shp) == 1:
             out.append(np.zeros(shp, dtype=np.float32))
             continue
@@ -65,16 +81,19 @@ class ScoreTrainer(object):
     the reference's compiled graph."""
 
     def __init__(self, ctx=None, params=None, branches=4, batch_size=32, time_context=30, feat_size=2049, seed=0, rand=None,
-                 eps=SI_EPS, learning_rate=LEARNING_RATE, rho=RHO, epsilon=ADA_EPSILON):
+                 eps=SI_EPS, learning_rate=LEARNING_RATE, rho=RHO, epsilon=ADA_EPSILON, function='build_ca'):
+        self.branches = int(branches)
+        self.function = function
+        self.arch = arch_name(self.branches, function)
+        if self.arch == 'bach10_si_1x1':
+            ARCHS[self.arch].dims(int(time_context), int(feat_size))   # ValueError below time_context 19 / feat_size 253
         torch = require_gpu()
         self.ctx = ctx if ctx is not None else default_context()
-        self.branches = int(branches)
-        self.arch = arch_name(self.branches)
         self.C, self.S = CHANNELS, N_SOURCES
         self.B, self.tc, self.F = int(batch_size), int(time_context), int(feat_size)
         self.rand_shape = (self.B, 1, self.tc, self.F)
         if params is None:
-            params = glorot_init(self.tc, self.F, seed, self.branches)
+            params = glorot_init(self.tc, self.F, seed, self.branches, function)
         params = [np.asarray(p, dtype=np.float32) for p in params]
         if rand is None:
             rand = np.random.RandomState(seed).uniform(size=self.rand_shape)
@@ -177,6 +196,21 @@ class ScoreTrainer(object):
         p = torch.empty(shape, dtype=torch.float32, device=self.ctx.device)
         _lib.check(self.ctx._lib.dcs_trainer_forward(self._h, _ptr(x), _ptr(p)))
         return p
+
+    @_on_ctx_stream
+    def rectify_codes(self):
+        """``build_ca_1x1`` only: r'(pre) of the last step's seven rectified layers (conv1 .. conv6, the live rows of the 1x1
+        layer) as float32 arrays ``[B, C, H, W]`` of 0 / 0.5 / 1 (0.5: a pre-activation of exactly 0)."""
+        torch = require_gpu()
+        if self.arch != 'bach10_si_1x1':
+            raise NotImplementedError("rectify_codes: only the build_ca_1x1 trainer keeps its rectifier codes")
+        a = ARCHS[self.arch]
+        d = a.dims(self.tc, self.F)
+        shapes = [(self.B, l['cout'], l['ho'], l['wo']) for l in d['layers']] + [(self.B, a.nf, d['h6'], d['w6'])]
+        outs = [torch.empty(s, dtype=torch.float32, device=self.ctx.device) for s in shapes]
+        ptrs = (c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        _lib.check(self.ctx._lib.dcs_trainer_rectify_codes(self._h, ptrs, len(outs)))
+        return [o.cpu().numpy() for o in outs]
 
     def save_model(self, path):
         """trainCNNrwc.py:59-64: the pickled list ``Separator('bach10_si', ...)`` and

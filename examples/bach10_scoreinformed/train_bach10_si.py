@@ -6,7 +6,7 @@ block, :196-416).
     python train_bach10_si.py --db <Bach10 Sources dir> --output <dir> [--feature_path P] [--model CNNrwc_se1]
                               [--batch_size 32] [--time_context 30] [--overlap 25] [--nepochs 40] [--scale_factor 0.3]
                               [--scale_factor_test 0.2] [--pitch_code e] [--branches 4|1] [--frame_size 4096] [--load]
-                              [--skip] [--skip_sep] [--seed 0] [--windows reference|all]
+                              [--skip] [--skip_sep] [--seed 0] [--windows reference|all] [--function build_ca|build_ca_1x1]
                               [--dbs <Bach10 Sibelius dir> --rwc <RWC dir> --render [--sample_size 400] [--chunk_size 45]
                                                                                     [--original 1] [--sample_rate 44100]]
 
@@ -28,6 +28,11 @@ written, --frame_size sets the transform and --pitch_code is e or g.
 
 --branches 1 trains the single-branch 11-array layout of trainCNNrwc_samp.py:195-235 (the same live computation and loss;
 the 17-array layout's other three branches are dead weight that no gradient reaches).
+
+--function build_ca_1x1 trains the deep graph of trainCNNrwc.py:66-132 (six strided convolutions, a 1x1 convolution and
+their InverseLayers; 22 arrays) with the same loss and feeds; as in the reference (:630-639) any other value means build_ca,
+and the 1x1 choice appends ``_x`` to the model name before the style suffix: model_<NAME>_x_gt.pkl.  It needs --time_context
+>= 19 and --frame_size >= 504; --branches 1 writes its live-only layout.
 
 Differences from the reference: the window order of an epoch is RandomState(seed + epoch).permutation (the reference's shuffle
 is unseeded); --scale_factor and --scale_factor_test are floats (the reference's int() of them is a bug); --load, --skip and
@@ -77,6 +82,16 @@ def separate_all(params, db, pieces, outdir, scale_factor, tc, overlap, batch_si
             write_wav(os.path.join(outdir, f + '-' + s + '.wav'), out[i][:len(audio)], sampleRate)
 
 
+def network_function(value):
+    """trainCNNrwc.py:627-631: ``build_ca_1x1`` if asked for by name, ``build_ca`` for anything else."""
+    return 'build_ca_1x1' if value == 'build_ca_1x1' else 'build_ca'
+
+
+def model_name(model, function):
+    """trainCNNrwc.py:633-639: the 1x1 graph's models carry ``_x``, then the ``gt`` style suffix."""
+    return model + ('_x' if function == 'build_ca_1x1' else '') + '_gt'
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--db", required=True, help="the Bach10 dataset path (its Sources directory)")
@@ -104,7 +119,9 @@ def main(argv=None):
     ap.add_argument("--chunk_size", type=float, default=45.0)
     ap.add_argument("--original", type=int, default=1)
     ap.add_argument("--sample_rate", type=int, default=44100, help="of the RWC recordings, with --render (for tests)")
+    ap.add_argument("--function", default="build_ca", help="build_ca (default) or build_ca_1x1; anything else is build_ca")
     a = ap.parse_args(argv)
+    function = network_function(a.function)
     if a.render != (a.rwc is not None):
         ap.error("--rwc PATH and --render go together")
     if a.render and a.dbs is None:
@@ -114,7 +131,7 @@ def main(argv=None):
     assert os.path.isdir(output), "Please input the output directory --output path_to_output"
     feature_path = a.feature_path or os.path.join(db, 'transforms', 't3')
     pieces = [f for f in sorted(os.listdir(db)) if os.path.isdir(os.path.join(db, f)) and f[0].isdigit()]
-    name = a.model + '_gt'                                                                         # :633-639
+    name = model_name(a.model, function)
     os.makedirs(os.path.join(output, 'models'), exist_ok=True)
     model = os.path.join(output, 'models', "model_" + name + ".pkl")
     params = load_model(model) if a.load else None
@@ -143,11 +160,12 @@ def main(argv=None):
             raise SystemExit("%d windows are fewer than one batch of %d" % (data.total, a.batch_size))
         if data.F != F:
             raise SystemExit("the features have %d bins, --frame_size %d gives %d" % (data.F, a.frame_size, F))
-        if params is not None and len(params) != (17 if a.branches == 4 else 11):
-            raise SystemExit("%s holds %d arrays, --branches %d trains %d" % (model, len(params), a.branches,
-                                                                              17 if a.branches == 4 else 11))
+        narrays = 22 if function == 'build_ca_1x1' else (17 if a.branches == 4 else 11)
+        if params is not None and len(params) != narrays:
+            raise SystemExit("%s holds %d arrays, --function %s --branches %d trains %d" % (model, len(params), function,
+                                                                                            a.branches, narrays))
         trainer = ScoreTrainer(params=params, branches=a.branches, batch_size=a.batch_size, time_context=a.time_context,
-                               feat_size=data.F, seed=a.seed)
+                               feat_size=data.F, seed=a.seed, function=function)
         losser = []
         min_loss = 1e14                                                                            # :288
         for epoch in range(a.nepochs):

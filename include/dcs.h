@@ -68,7 +68,8 @@ enum { DCS_ARCH_DSD = 0, DCS_ARCH_IKALA = 1, DCS_ARCH_BACH10 = 2, DCS_ARCH_BACH1
                                      time_context >= 19 and F >= 253.  dcs_model_forward / _forward_masked, dcs_model_set_score_semantics
                                      and dcs_separate_scoreinformed take it (tie_mode is ignored: no pooling); the f16 switch, the
                                      one-batch stages and the single-channel / batch / ragged / stereo / spectra paths are
-                                     DCS_EUNSUPPORTED.  f32 MFMA throughout (csrc/deep1x1.hip) */ };
+                                     DCS_EUNSUPPORTED.  f32 MFMA throughout (csrc/deep1x1.hip); trained by
+                                     csrc/train_deep1x1.hip */ };
 /* soft-mask epsilon convention: A = separate_dsd.py:258-266, B = separate_bach10.py:251-259 */
 enum { DCS_EPS_A = 0, DCS_EPS_B = 1 };
 /* max-pool gradient tie routing: ALL = Theano 0.9 CPU MaxPoolGrad, FIRST = cuDNN */
@@ -456,9 +457,9 @@ DCS_API int dcs_timing_query(dcs_ctx* ctx, int which, double* avg_ms, int64_t* l
  * batch 1 .. 1024, else DCS_EINVAL; 13 arrays.  Or the pair of examples/bach10/trainCNNbach10.py:126-206 for the Bach10 graph
  * (:66-123; trainCNNrwc.py and trainCNNSibelius.py train the same graph with the same loss): arch DCS_ARCH_BACH10,
  * time_context 2 .. 47 (conv2 is int(2 tc / 3) rows high; from 48 on dcs_model_create's bach10 graph has no column
- * convolution to run the result), F 30 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  Any other arch (DCS_ARCH_IKALA,
- * the pooled graph of separate_ikala.py, included: the reference never trains it; the deep score-informed graph
- * DCS_ARCH_BACH10_SI_1X1) is DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
+ * convolution to run the result), F 30 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  The stereo, the score-informed
+ * and the deep score-informed graphs are described below.  Any other arch (DCS_ARCH_IKALA, the pooled graph of
+ * separate_ikala.py, included: the reference never trains it) is DCS_EUNSUPPORTED.  params_d / shapes / nparams as for dcs_model_create (.pkl
  * order), copied into the trainer.  rand_d [batch][1][tc][F]: the uniform draw baked into the loss (trainCNN.py:174), copied.
  * hyper_h: eps, alpha, beta, beta_voc (:169-172) -- for iKala eps, alpha, beta_acc, beta_voc (ikala/trainCNN.py:152-155); for
  * Bach10 eps (1e-18, bach10/trainCNNbach10.py:160) and three ignored values -- then adadelta's learning_rate, rho, epsilon (lasagne defaults 1, 0.95, 1e-6).  Adadelta's accu / delta_accu start at zero
@@ -481,6 +482,23 @@ DCS_API int dcs_trainer_destroy(dcs_trainer* t);
  * reference's gradient for them is exactly zero and Adadelta from a zero state never moves them or their accumulators.  The
  * trainer holds them once, outside the stepped state: dcs_trainer_get(which = 0) returns them bit-identical to what
  * dcs_trainer_create was given, which = 1, 2, 3 return zeros for them. */
+/* The deep score-informed graph build_ca_1x1 (examples/bach10_scoreinformed/trainCNNrwc.py:66-132, --function build_ca_1x1;
+ * csrc/train_deep1x1.hip): dcs_trainer_create with arch DCS_ARCH_BACH10_SI_1X1, 22 arrays in .pkl order: the whole graph
+ * (the 1x1 layer [800][200][1][1], its two biases [800], the final bias [16]) or a live-only layout of k = 1 .. 3 branches
+ * ([200 k][200][1][1], [200 k], [200 k], [4 k]).  time_context 19 .. 1024, F 253 .. 2049 (below 19 / 253 a convolution has no
+ * output), batch 1 .. 1024, and 2 batch time_context ((F - 5) / 2 + 1) < 2^30: the K of conv1's weight gradient, the largest
+ * index a GEMM of the step forms, stays in the 30 bits its index arithmetic has; anything else is DCS_EINVAL.  rand_d, hyper_h,
+ * inputs_d, targets_d, out7, the loss (it reads prediction2[:, 0:4]: branch 0, rows 0 .. 199 of the 1x1 layer), the kept NaN
+ * and dcs_trainer_forward are those of DCS_ARCH_BACH10_SI above.  Dead parameters: rows 200 .. of the 1x1 layer's W, b and
+ * BiasLayer.b and the final bias from entry 4 on reach no loss term; they are held once outside the stepped state,
+ * dcs_trainer_get(which = 0) returns them bit-identical to what create was given, which = 1, 2, 3 zeros.
+ *
+ * dcs_trainer_rectify_codes: r'(pre) of the seven rectified layers (conv1 .. conv6, the live 200 rows of the 1x1 layer) at the
+ * last dcs_trainer_step / dcs_trainer_forward, as floats 0 / 0.5 / 1 (0.5: a pre-activation of exactly 0) into n = 7 device
+ * buffers [batch][C_l][H_l][W_l].  These codes are what the step's gradient was computed with (the InverseLayers multiply
+ * by them), so a float64 check of the gradient evaluates its graph at them.  DCS_EUNSUPPORTED for every other graph (they
+ * keep pre-activations), DCS_ESHAPE for n != 7. */
+DCS_API int dcs_trainer_rectify_codes(dcs_trainer* t, float* const* out_d, int n);
 /* The stereo (ILD) DSD100 graph (examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py: build_ca :66-113, train_fn_mse / train_fn1
  * :183-206, train_fn_ILD :210-228 and :268; csrc/train_dsdild.hip): dcs_trainer_create with arch DCS_ARCH_DSD_ILD,
  * time_context even in [4, 64], F 1 .. 2049, batch 1 .. 1024, else DCS_EINVAL; 17 arrays.  rand_d [2][batch][4][tc][F]: the
@@ -515,7 +533,7 @@ DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float*
 /* lasagne.layers.get_output(network2) (trainCNN.py:165) at the current parameters: p_d [batch][4][tc][F] (iKala
  * [batch][2][tc][F]), before masking */
 DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d);
-/* Copy one section of the trainer's state into 15 (iKala 13, Bach10 17, score-informed 17 or 11) caller buffers in .pkl layout: which 0 = parameters
+/* Copy one section of the trainer's state into 15 (iKala 13, Bach10 17, score-informed 17 or 11, deep score-informed 22) caller buffers in .pkl layout: which 0 = parameters
  * (get_all_param_values, trainCNN.py:59-64), 1 = the gradients of the last mode 1 / 2 step, 2 = adadelta accu,
  * 3 = adadelta delta_accu. */
 DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams);

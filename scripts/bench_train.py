@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / bach10_si / dsd_ild,
-the iKala graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the score-informed Bach10 graph
-(csrc/train_bach10si.hip; --branches 1: its 11-array layout) / the stereo DSD graph (csrc/train_dsdild.hip; --ild: its
-stage-2 loss), all on the shared core csrc/train_core.hip (the iKala and the two Bach10 graphs through the shared build_ca graph
+"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / bach10_si / dsd_ild /
+bach10_si_1x1, the iKala graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the score-informed Bach10
+graph (csrc/train_bach10si.hip; --branches 1: its 11-array layout) / the stereo DSD graph (csrc/train_dsdild.hip; --ild: its
+stage-2 loss) / the deep score-informed graph build_ca_1x1 (csrc/train_deep1x1.hip; its line carries the step's FLOPs from
+``Deep1x1Arch.train_flops_per_tile`` and the TFLOP/s they make), all on the shared core csrc/train_core.hip (the iKala and the two Bach10 graphs through the shared build_ca graph
 csrc/train_ca.hip), against the same float32 graph, loss and Adadelta written in torch
 and run with autograd on the same GPU.  Prints one JSON line per batch size.
 
-    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10|bach10_si|dsd_ild] [--ild] [--branches 4|1]
+    python scripts/bench_train.py [--arch dsd|ikala_nopool|bach10|bach10_si|dsd_ild|bach10_si_1x1] [--ild] [--branches 4|1]
                                   [--batches 32 256] [--steps 50] [--warmup 10] [--feat_size 513]
 
 The Bach10 graphs' working size is --feat_size 2049 (frame size 4096); their lines also carry the floor of a step from its
@@ -44,6 +45,10 @@ LAUNCHES_PER_STEP_BACH10SI = 21
 # per-bin sums and their means before them), 6 backward (B3 split-K + sum), 4 weight-gradient GEMMs, split-K reduce,
 # Adadelta (csrc/train_dsdild.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_ILD = {False: 22, True: 24}
+# build_ca_1x1 (csrc/train_deep1x1.hip): forward 7 weight packs, the input transpose, 7 convolutions, 6 x (2 transposed
+# launches + the code product) = 33; loss + reduce; backward the dq transpose, 6 convolutions, the 1x1 product and its code
+# product, 5 x 2 transposed launches, 6 code products = 25; 7 weight-gradient GEMMs and their 7 reduces; Adadelta
+LAUNCHES_PER_STEP_DEEP1X1 = 75
 # MI355X: HBM3E as a float4 copy reaches it (8 TB/s spec) and the f32 MFMA peak (v_mfma_f32_16x16x4_f32)
 HBM_BYTES_PER_S = 6.29e12
 F32_MFMA_FLOP_PER_S = 157.3e12
@@ -127,6 +132,56 @@ def bench_torch_si(B, tc, F, steps, warmup, branches):
     def step():
         opt.zero_grad(set_to_none=True)
         loss = ref.components(ref.forward(P, x), x, y, r)[0]
+        loss.backward()
+        opt.step()
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def bench_hip_deep(B, tc, F, steps, warmup, branches):
+    import torch
+    from deepconvsep_amd.score_training import ScoreTrainer
+    from deepconvsep_amd.synth import synth_params
+    x, y, r = _si_inputs(B, tc, F)
+    params = synth_params('bach10_si_1x1', tc, F, seed=0)
+    if branches < 4:
+        import train_deep1x1_ref as ref
+        params = ref.live(params)
+    t = ScoreTrainer(params=params, branches=branches, batch_size=B, time_context=tc, feat_size=F, rand=r, function='build_ca_1x1')
+    x, y = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    for _ in range(warmup):
+        t.run(x, y, 2)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        t.run(x, y, 2)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    t.close()
+    return ms
+
+
+def bench_torch_deep(B, tc, F, steps, warmup, branches):
+    """float32 autograd of tests/train_deep1x1_ref.graph (the live branch; the dead rows of the 1x1 layer forward only)."""
+    import torch
+    import train_deep1x1_ref as ref
+    import train_ref
+    from deepconvsep_amd.synth import synth_params
+    x, y, r = (torch.from_numpy(a).cuda() for a in _si_inputs(B, tc, F))
+    params = synth_params('bach10_si_1x1', tc, F, seed=0)
+    P = [torch.from_numpy(np.asarray(p, np.float32)).cuda().requires_grad_(True) for p in (params if branches == 4 else ref.live(params))]
+    opt = torch.optim.Adadelta(P, lr=1.0, rho=0.95, eps=1e-6)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        q, _, _ = ref.graph(P, x)
+        loss = ref.components(train_ref.rectify(q), x, y, r)[0]
         loss.backward()
         opt.step()
     for _ in range(warmup):
@@ -234,7 +289,8 @@ def bench_torch(B, tc, F, steps, warmup, arch="dsd"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10", "bach10_si", "dsd_ild"), default="dsd")
+    ap.add_argument("--arch", choices=("dsd", "ikala_nopool", "bach10", "bach10_si", "dsd_ild", "bach10_si_1x1"),
+                    default="dsd")
     ap.add_argument("--branches", type=int, choices=(4, 1), default=4, help="bach10_si: the 17- or the 11-array layout")
     ap.add_argument("--ild", action="store_true", help="dsd_ild: the stage-2 loss (train_fn_ILD)")
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 256])
@@ -249,6 +305,9 @@ def main():
         if a.arch == "dsd_ild":
             ms = bench_hip_ild(B, a.time_context, a.feat_size, a.steps, a.warmup, a.ild)
             tms = bench_torch_ild(B, a.time_context, a.feat_size, a.steps, a.warmup, a.ild)
+        elif a.arch == "bach10_si_1x1":
+            ms = bench_hip_deep(B, a.time_context, a.feat_size, a.steps, a.warmup, a.branches)
+            tms = bench_torch_deep(B, a.time_context, a.feat_size, a.steps, a.warmup, a.branches)
         elif a.arch == "bach10_si":
             ms = bench_hip_si(B, a.time_context, a.feat_size, a.steps, a.warmup, a.branches)
             tms = bench_torch_si(B, a.time_context, a.feat_size, a.steps, a.warmup, a.branches)
@@ -258,9 +317,13 @@ def main():
         extra = {} if a.arch == "dsd" else dict(arch=a.arch)
         if a.arch == "dsd_ild":
             extra.update(ild=bool(a.ild))
-        if a.arch == "bach10_si":
+        if a.arch in ("bach10_si", "bach10_si_1x1"):
             extra.update(branches=a.branches)
-        launches = {"dsd": LAUNCHES_PER_STEP, "bach10": LAUNCHES_PER_STEP_BACH10, "bach10_si": LAUNCHES_PER_STEP_BACH10SI,
+        if a.arch == "bach10_si_1x1":
+            from deepconvsep_amd.arch import ARCHS
+            flop = B * ARCHS["bach10_si_1x1"].train_flops_per_tile(a.time_context, a.feat_size)
+            extra.update(step_flop=int(flop), hip_tflops=round(flop / ms * 1e-9, 2), torch_tflops=round(flop / tms * 1e-9, 2))
+        launches = {"dsd": LAUNCHES_PER_STEP, "bach10_si_1x1": LAUNCHES_PER_STEP_DEEP1X1, "bach10": LAUNCHES_PER_STEP_BACH10, "bach10_si": LAUNCHES_PER_STEP_BACH10SI,
                     "dsd_ild": LAUNCHES_PER_STEP_ILD[bool(a.ild)]}.get(a.arch, LAUNCHES_PER_STEP_IKALA)
         if a.arch in ("bach10", "bach10_si"):
             floor = (bach10_floor if a.arch == "bach10" else bach10si_floor)(B, a.time_context, a.feat_size)
