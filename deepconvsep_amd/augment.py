@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from .runtime import StftPlan, _ptr, default_context
-from .training import all_slots, reference_slots
+from .training import WindowFeed
 
 CHANNELS = ('vocals', 'bass', 'drums', 'other')       # channels 1 .. 4 of a feature file (0 is the mixture)
 # the order in which each script adds the sources into its mixture (compute_features.py:85, compute_features_cs_aug.py:120,
@@ -262,7 +262,7 @@ def render_audio(signals, vf):
     return out
 
 
-class RenderedWindows(object):
+class RenderedWindows(WindowFeed):
     """``FeatureWindows`` without feature files: the training windows of the virtual files ``vfiles`` are transformed per
     batch from ``signals`` (key -> mono signal, uploaded once as float32) by ``dcs_trainer_gather_render``.
 
@@ -272,10 +272,8 @@ class RenderedWindows(object):
 
     def __init__(self, signals, vfiles, time_context=30, overlap=25, mult_factor=0.3, windows='reference', batch_size=32,
                  seed=0, ctx=None, frameSize=1024, hopSize=512, window=None):
-        if windows not in ('reference', 'all'):
-            raise ValueError("windows must be 'reference' or 'all'")
-        self.tc, self.overlap, self.mult, self.batch_size, self.seed = int(time_context), int(overlap), float(mult_factor), \
-            int(batch_size), int(seed)
+        WindowFeed.__init__(self, windows, time_context, overlap, batch_size, seed, ctx)
+        self.mult = float(mult_factor)
         self.frame, self.hop, self._window = int(frameSize), int(hopSize), window
         self.vfiles = list(vfiles)
         counts = set(len(vf.tracks) for vf in self.vfiles)
@@ -292,14 +290,7 @@ class RenderedWindows(object):
         self.rows, self.gains = table_rows(self.vfiles, self.index, self.hop)
         self.names = [n for vf in self.vfiles for n in vf.names]
         self.F = self.frame // 2 + 1
-        slots = reference_slots if windows == 'reference' else all_slots
-        table = []
-        for i, r in enumerate(self.rows):
-            table += [(i if s is not None else -1, s if s is not None else 0) for s in slots(int(r[3]), self.tc, self.overlap)]
-        self.table = np.asarray(table, dtype=np.int32).reshape(-1, 2)
-        self.total = len(self.table)
-        self.iteration_size = self.total // self.batch_size
-        self._ctx = ctx
+        self._set_table(r[3] for r in self.rows)
         self._bank = None
 
     def _upload(self):
@@ -307,7 +298,7 @@ class RenderedWindows(object):
             return
         import torch
         from .separation import blackmanharris
-        self.ctx = self._ctx if self._ctx is not None else default_context()
+        self._open()
         self._bank = Bank(self._signals, np.float32, self.ctx)
         self._signals = None
         win = self._window if self._window is not None else blackmanharris
@@ -319,22 +310,12 @@ class RenderedWindows(object):
     def gather(self, rows):
         """Inputs ``[B, 1, tc, F]`` and targets ``[B, sources, tc, F]`` (device tensors) of the window-table rows ``rows``."""
         self._upload()
-        import torch
-        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
-        B = len(win)
         with self.ctx.stream_scope():
-            win_d = torch.from_numpy(win).to(self.ctx.device)
-            x = torch.empty((B, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            t = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            win_d, B, x, t = self._batch(rows, 1, self.sources)
             _lib.check(self.ctx._lib.dcs_trainer_gather_render(
                 self.ctx._h, self._plan._h, _ptr(self._bank.tensor), self._bank.length, _ptr(self._rows_d),
                 _ptr(self._gains_d), len(self.rows), _ptr(win_d), B, self.tc, self.sources, self.mult, _ptr(x), _ptr(t)))
         return x, t
-
-    def batches(self, epoch=0):
-        perm = np.random.RandomState(self.seed + epoch).permutation(self.total)
-        for b in range(self.iteration_size):
-            yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])
 
 
 def _mono(path):

@@ -33,7 +33,7 @@ import numpy as np
 from . import _lib
 from .augment import Track, VirtualFile, shift_samples
 from .score import _score_path, _select, read_score, str2midi
-from .training import all_slots, reference_slots
+from .training import WindowFeed
 
 SOURCES = ('bassoon', 'clarinet', 'saxophone', 'violin')      # the score files <source>_g<style>.txt, in track order
 INSTRUMENT_IDS = (30, 31, 27, 15)                             # their RWC instrument numbers (:215)
@@ -369,7 +369,7 @@ def render_score_features(tt, bank, sf, out_dir=None):
     return tt.out_path.replace('.data', '_' + tt.suffix + '_m_.data')
 
 
-class ScoreRenderedWindows(object):
+class ScoreRenderedWindows(WindowFeed):
     """``FeatureWindows`` without feature files: the training windows of the virtual files ``sfiles`` are assembled and
     transformed per batch from the note bank (uploaded once as float32, with the note and file tables) by
     ``dcs_trainer_gather_score_render``.
@@ -380,10 +380,8 @@ class ScoreRenderedWindows(object):
 
     def __init__(self, bank, sfiles, time_context=30, overlap=25, mult_factor=0.3, windows='reference', batch_size=32, seed=0,
                  ctx=None, frameSize=4096, hopSize=512, window=None):
-        if windows not in ('reference', 'all'):
-            raise ValueError("windows must be 'reference' or 'all'")
-        self.tc, self.overlap, self.mult, self.batch_size, self.seed = int(time_context), int(overlap), float(mult_factor), \
-            int(batch_size), int(seed)
+        WindowFeed.__init__(self, windows, time_context, overlap, batch_size, seed, ctx)
+        self.mult = float(mult_factor)
         self.frame, self.hop, self._window = int(frameSize), int(hopSize), window
         self.sfiles = list(sfiles)
         counts = set(len(sf.tracks) for sf in self.sfiles)
@@ -396,23 +394,16 @@ class ScoreRenderedWindows(object):
         self.notes, self.rows = pack_tables(self.sfiles, bank.length, self.hop)
         self.names = [sf.name for sf in self.sfiles]
         self.F = self.frame // 2 + 1
-        slots = reference_slots if windows == 'reference' else all_slots
-        table = []
-        for i, r in enumerate(self.rows):
-            table += [(i if s is not None else -1, s if s is not None else 0) for s in slots(int(r[1]), self.tc, self.overlap)]
-        self.table = np.asarray(table, dtype=np.int32).reshape(-1, 2)
-        self.total = len(self.table)
-        self.iteration_size = self.total // self.batch_size
-        self._ctx = ctx
+        self._set_table(r[1] for r in self.rows)
         self._bank_d = None
 
     def _upload(self):
         if self._bank_d is not None:
             return
         import torch
-        from .runtime import StftPlan, default_context
+        from .runtime import StftPlan
         from .separation import blackmanharris
-        self.ctx = self._ctx if self._ctx is not None else default_context()
+        self._open()
         self._bank_d = self.bank.device(np.float32, self.ctx)
         win = self._window if self._window is not None else blackmanharris
         self._plan = StftPlan(self.ctx, self.frame, self.hop, win(self.frame) if callable(win) else win)
@@ -423,23 +414,13 @@ class ScoreRenderedWindows(object):
     def gather(self, rows):
         """Inputs ``[B, 1, tc, F]`` and targets ``[B, sources, tc, F]`` (device tensors) of the window-table rows ``rows``."""
         self._upload()
-        import torch
         from .runtime import _ptr
-        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
-        B = len(win)
         with self.ctx.stream_scope():
-            win_d = torch.from_numpy(win).to(self.ctx.device)
-            x = torch.empty((B, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            t = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            win_d, B, x, t = self._batch(rows, 1, self.sources)
             _lib.check(self.ctx._lib.dcs_trainer_gather_score_render(
                 self.ctx._h, self._plan._h, _ptr(self._bank_d), self.bank.length, _ptr(self._notes_d), len(self.notes),
                 _ptr(self._rows_d), len(self.rows), _ptr(win_d), B, self.tc, self.sources, self.mult, _ptr(x), _ptr(t)))
         return x, t
-
-    def batches(self, epoch=0):
-        perm = np.random.RandomState(self.seed + epoch).permutation(self.total)
-        for b in range(self.iteration_size):
-            yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])
 
 
 def render_score_informed_features(tt, bank, sf, out_dir=None):
@@ -504,14 +485,9 @@ class ScoreInformedRenderedWindows(ScoreRenderedWindows):
         """Inputs ``[B, S, tc, F]`` = mask_j * (mult_factor * mixture) and targets ``[B, S, tc, F]`` (device tensors) of the
         window-table rows ``rows``."""
         self._upload()
-        import torch
         from .runtime import _ptr
-        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
-        B = len(win)
         with self.ctx.stream_scope():
-            win_d = torch.from_numpy(win).to(self.ctx.device)
-            x = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            t = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            win_d, B, x, t = self._batch(rows, self.sources, self.sources)
             _lib.check(self.ctx._lib.dcs_trainer_gather_score_informed_render(
                 self.ctx._h, self._plan._h, _ptr(self._bank_d), self.bank.length, _ptr(self._notes_d), len(self.notes),
                 _ptr(self._rows_d), len(self.rows), _ptr(self._masks_d), self.mask_len, _ptr(self._mask_files_d), self.width,

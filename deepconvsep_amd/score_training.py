@@ -8,26 +8,28 @@ harmonic masks), four targets, ``branches=4`` the 17-array ``.pkl`` layout ``'ba
 ``'bach10_si1'`` (csrc/train_bach10si.hip on the shared build_ca graph csrc/train_ca.hip and the core csrc/train_core.hip).  Both train the
 same live computation: the loss reads ``prediction2[:, 0:4]``, the four channels of decoder branch 0.  The 17-array layout's ``fc12``, ``fc13``, ``fc14``
 (arrays 10 .. 15) and ``bo[4:16]`` get an exactly zero gradient in the reference, so Adadelta never moves them: the trainer
-returns them as they were given, and zeros for their gradients and accumulators.  It is a class of its own because the graph
-differs from the mono ones in its input channels; ``training.TRAINABLE`` lists the mono graphs only.
+returns them as they were given, and zeros for their gradients and accumulators.  The handle itself is
+:class:`deepconvsep_amd.training.TrainerHandle`; the class adds the choice of layout (``arch_name``) and ``rectify_codes``.
+``training.TRAINABLE`` lists the mono graphs only.
 
 ``function='build_ca_1x1'`` trains the deep graph of trainCNNrwc.py:66-132 instead (csrc/train_deep1x1.hip): 22 arrays, the
 ``.pkl`` layout ``'bach10_si_1x1'`` that ``arch.resolve`` tells apart, with ``branches`` 4 (the whole graph) or 1 .. 3 (the
 live-only layouts).  Its loss reads branch 0 too: rows 200 .. 799 of the 1x1 layer and ``fb[4:16]`` are dead in the same sense.
 
 ``ScoreFeatureWindows`` keeps the ``[5, T, F]`` feature files and their note tables resident on the device and cuts the
-reference's windows, masks included, in one launch per batch.  There is no CPU fallback.
+reference's windows, masks included, in one launch per batch (slot table and epoch order:
+:class:`deepconvsep_amd.training.WindowFeed`).  There is no CPU fallback.
 """
 import os
-from ctypes import byref, c_double, c_int64, c_void_p
+from ctypes import c_void_p
 
 import numpy as np
 
 from . import _lib
 from .arch import ARCHS
-from .runtime import _on_ctx_stream, _ptr, default_context, require_gpu
-from .separation import save_model as _save_model
-from .training import ADA_EPSILON, BACH10_COMPONENTS, BACH10_EPS, LEARNING_RATE, RHO, all_slots, reference_slots
+from .runtime import _on_ctx_stream, _ptr, require_gpu
+from .training import (ADA_EPSILON, BACH10_COMPONENTS, BACH10_EPS, LEARNING_RATE, RHO, TrainerHandle, WindowFeed,
+                       glorot_arrays, listed_files)
 from .transform import read_shape_file
 
 CHANNELS, N_SOURCES = 4, 4
@@ -61,24 +63,17 @@ def param_shapes(tc, F, branches=4, function='build_ca'):
 def glorot_init(tc=30, F=2049, seed=0, branches=4, function='build_ca'):
     """Lasagne's defaults for build_ca: every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) * sqrt(2 / ((n1 + n2) *
     receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32."""
-    rs = np.random.RandomState(seed)
-    out = []
-    for shp in param_shapes(tc, F, branches, function):
-        if len(shp) == 1:
-            out.append(np.zeros(shp, dtype=np.float32))
-            continue
-        rf = int(np.prod(shp[2:])) if len(shp) > 2 else 1
-        a = np.sqrt(3.0) * np.sqrt(2.0 / ((shp[0] + shp[1]) * rf))
-        out.append(rs.uniform(-a, a, size=shp).astype(np.float32))
-    return out
+    return glorot_arrays(param_shapes(tc, F, branches, function), seed)
 
 
-class ScoreTrainer(object):
+class ScoreTrainer(TrainerHandle):
     """``train_fn`` / ``train_fn1`` of trainCNNrwc.py:281-283, resident on one GPU.
 
     ``params``: the 17 (``branches=4``) or 11 (``branches=1``) arrays in .pkl order, default :func:`glorot_init`.  ``rand``:
     the uniform draw of :246 ``[batch, 1, tc, F]``; default ``RandomState(seed).uniform``.  The batch size is fixed, as in
-    the reference's compiled graph."""
+    the reference's compiled graph.  ``forward`` returns ``get_output(network2)[:, 0:4]`` (:244-251), the live channels;
+    ``save_model`` (:59-64) writes the list ``Separator('bach10_si', ...)`` and
+    examples/bach10_scoreinformed/separate_bach10.py load (17 arrays, or 11: resolved to ``'bach10_si1'``)."""
 
     def __init__(self, ctx=None, params=None, branches=4, batch_size=32, time_context=30, feat_size=2049, seed=0, rand=None,
                  eps=SI_EPS, learning_rate=LEARNING_RATE, rho=RHO, epsilon=ADA_EPSILON, function='build_ca'):
@@ -87,115 +82,17 @@ class ScoreTrainer(object):
         self.arch = arch_name(self.branches, function)
         if self.arch == 'bach10_si_1x1':
             ARCHS[self.arch].dims(int(time_context), int(feat_size))   # ValueError below time_context 19 / feat_size 253
-        torch = require_gpu()
-        self.ctx = ctx if ctx is not None else default_context()
         self.C, self.S = CHANNELS, N_SOURCES
-        self.B, self.tc, self.F = int(batch_size), int(time_context), int(feat_size)
-        self.rand_shape = (self.B, 1, self.tc, self.F)
-        if params is None:
-            params = glorot_init(self.tc, self.F, seed, self.branches, function)
-        params = [np.asarray(p, dtype=np.float32) for p in params]
-        if rand is None:
-            rand = np.random.RandomState(seed).uniform(size=self.rand_shape)
-        rand = np.asarray(rand)
-        if rand.shape != self.rand_shape:
-            raise ValueError("rand has shape %r, the trainer takes %r" % (rand.shape, self.rand_shape))
-        self.shapes = [tuple(p.shape) for p in params]
-        with self.ctx.stream_scope():
-            dev = [self.ctx.to_device(p, np.float32) for p in params]
-            rand_d = self.ctx.to_device(rand, np.float32)
-            self._out7 = torch.zeros(7, dtype=torch.float64, device=self.ctx.device)
-        n = len(dev)
-        ptrs = (c_void_p * n)(*[p.data_ptr() for p in dev])
-        shapes = (c_int64 * (4 * n))()
-        for i, p in enumerate(params):
-            if p.ndim > 4:
-                raise ValueError("mismatch: parameter %d has %d axes" % (i, p.ndim))
-            shp = list(p.shape) + [1] * (4 - p.ndim)
-            for k in range(4):
-                shapes[4 * i + k] = shp[k]
-        hyper = (c_double * 7)(eps, 0.0, 0.0, 0.0, learning_rate, rho, epsilon)
-        h = c_void_p()
-        _lib.check(self.ctx._lib.dcs_trainer_create(self.ctx._h, ARCHS[self.arch].code, self.tc, self.F, self.B, ptrs, shapes,
-                                                    n, _ptr(rand_d), hyper, byref(h)))
-        self._h = h
-        self._keep = (dev, rand_d)   # released after create's copies have run (stream order)
+        TrainerHandle.__init__(self, ctx, self.arch, self.C, self.S, batch_size, time_context, feat_size,
+                               (int(batch_size), 1, int(time_context), int(feat_size)), params, rand, seed,
+                               (eps, 0.0, 0.0, 0.0, learning_rate, rho, epsilon))
 
-    def _io(self, inputs, targets):
-        torch = require_gpu()
-        x = inputs if isinstance(inputs, torch.Tensor) else self.ctx.to_device(inputs, np.float32)
-        t = targets if isinstance(targets, torch.Tensor) else self.ctx.to_device(targets, np.float32)
-        x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        t = t.to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        want_x, want_t = (self.B, self.C, self.tc, self.F), (self.B, self.S, self.tc, self.F)
-        if tuple(x.shape) != want_x or tuple(t.shape) != want_t:
-            raise ValueError("inputs %r / targets %r, the trainer takes %r / %r" % (tuple(x.shape), tuple(t.shape), want_x,
-                                                                                     want_t))
-        return x, t
-
-    @_on_ctx_stream
-    def run(self, inputs, targets, mode):
-        """``dcs_trainer_step``; returns the device tensor of (loss, error1 .. error4, 0, 0) before any update."""
-        x, t = self._io(inputs, targets)
-        _lib.check(self.ctx._lib.dcs_trainer_step(self._h, _ptr(x), _ptr(t), int(mode), _ptr(self._out7)))
-        self._last_io = (x, t)
-        return self._out7
-
-    def step(self, inputs, targets):
-        """``train_fn`` (trainCNNrwc.py:281): the loss at the current parameters, then one Adadelta update."""
-        return float(self.ctx.to_host(self.run(inputs, targets, 2))[0])
+    def _default_params(self, seed):
+        return glorot_init(self.tc, self.F, seed, self.branches, self.function)
 
     def losses(self, inputs, targets):
         """``train_fn1`` (trainCNNrwc.py:283): error1 .. error4 (bassoon, clarinet, saxophone, violin)."""
         return [float(v) for v in self.ctx.to_host(self.run(inputs, targets, 0))[1:1 + self.S]]
-
-    def loss_and_gradients(self, inputs, targets):
-        """Testing aid: the seven outputs and the gradients of the loss (one per parameter; exact zeros for the dead
-        parameters of the 17-array layout), no update."""
-        out = self.ctx.to_host(self.run(inputs, targets, 1)).copy()
-        return out, self.gradients()
-
-    @_on_ctx_stream
-    def set_rand(self, rand):
-        """Replace the draw (``[batch, 1, tc, F]``, an ndarray or a device tensor) in stream order."""
-        torch = require_gpu()
-        r = rand if isinstance(rand, torch.Tensor) else self.ctx.to_device(np.asarray(rand), np.float32)
-        if tuple(r.shape) != self.rand_shape:
-            raise ValueError("rand has shape %r, the trainer takes %r" % (tuple(r.shape), self.rand_shape))
-        r = r.to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        _lib.check(self.ctx._lib.dcs_trainer_set_rand(self._h, _ptr(r)))
-        self._rand_keep = r
-
-    @_on_ctx_stream
-    def _get(self, which):
-        torch = require_gpu()
-        outs = [torch.empty(s, dtype=torch.float32, device=self.ctx.device) for s in self.shapes]
-        ptrs = (c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-        _lib.check(self.ctx._lib.dcs_trainer_get(self._h, int(which), ptrs, len(outs)))
-        return [o.cpu().numpy() for o in outs]
-
-    def params(self):
-        """``lasagne.layers.get_all_param_values``: float32 arrays in .pkl order."""
-        return self._get(0)
-
-    def gradients(self):
-        """Gradients of the last step (testing aid), .pkl order."""
-        return self._get(1)
-
-    def adadelta_state(self):
-        """(accu, delta_accu) of lasagne.updates.adadelta, .pkl order."""
-        return self._get(2), self._get(3)
-
-    @_on_ctx_stream
-    def forward(self, inputs):
-        """``lasagne.layers.get_output(network2)[:, 0:4]`` (trainCNNrwc.py:244-251): the live channels ``[B, 4, tc, F]``
-        before masking (device tensor)."""
-        torch = require_gpu()
-        shape = (self.B, self.S, self.tc, self.F)
-        x, _ = self._io(inputs, torch.zeros(shape, dtype=torch.float32, device=self.ctx.device))
-        p = torch.empty(shape, dtype=torch.float32, device=self.ctx.device)
-        _lib.check(self.ctx._lib.dcs_trainer_forward(self._h, _ptr(x), _ptr(p)))
-        return p
 
     @_on_ctx_stream
     def rectify_codes(self):
@@ -212,35 +109,13 @@ class ScoreTrainer(object):
         _lib.check(self.ctx._lib.dcs_trainer_rectify_codes(self._h, ptrs, len(outs)))
         return [o.cpu().numpy() for o in outs]
 
-    def save_model(self, path):
-        """trainCNNrwc.py:59-64: the pickled list ``Separator('bach10_si', ...)`` and
-        examples/bach10_scoreinformed/separate_bach10.py load (17 arrays, or 11: resolved to ``'bach10_si1'``)."""
-        _save_model(path, self.params())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx._lib.dcs_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def score_pairs(paths, pitch_code='e'):
     """The ``(features, note table)`` file pairs of ``LargeDataset`` (dataset.py:617-619 and loadPitch :361-364): every file
     of ``paths`` (files or directories) that ends in ``_m_.data``, with ``_m_`` replaced by ``_<pitch_code>_`` for its note
     table; sorted."""
-    files = []
-    for p in paths:
-        if os.path.isdir(p):
-            files += [os.path.join(p, f) for f in os.listdir(p)]
-        else:
-            files.append(p)
     pairs = []
-    for f in sorted(files):
+    for f in sorted(listed_files(paths)):
         if not f.endswith('_m_.data'):
             continue
         d, name = os.path.split(f)
@@ -263,7 +138,7 @@ def pack_notes(lib, notes, F):
     return out
 
 
-class ScoreFeatureWindows(object):
+class ScoreFeatureWindows(WindowFeed):
     """The training data of ``LargeDatasetMask2`` (dataset.py:819-879) resident on the device.
 
     ``paths``: feature directories or ``*_m_.data`` files, float64 ``[5, T, F]`` (mixture, bassoon, clarinet, saxophone,
@@ -277,22 +152,18 @@ class ScoreFeatureWindows(object):
 
     def __init__(self, paths, pitch_code='e', time_context=30, overlap=25, mult_factor=0.3, windows='reference',
                  batch_size=32, seed=0, ctx=None):
-        if windows not in ('reference', 'all'):
-            raise ValueError("windows must be 'reference' or 'all'")
-        self.tc, self.overlap, self.mult, self.batch_size, self.seed = int(time_context), int(overlap), float(mult_factor), \
-            int(batch_size), int(seed)
+        WindowFeed.__init__(self, windows, time_context, overlap, batch_size, seed, ctx)
+        self.mult = float(mult_factor)
         self.pitch_code = pitch_code
         self.pairs = score_pairs([paths] if isinstance(paths, str) else list(paths), pitch_code)
-        slots = reference_slots if windows == 'reference' else all_slots
-        self.shapes, self.note_shapes, table = [], [], []
-        for i, (p, q) in enumerate(self.pairs):
+        self.shapes, self.note_shapes = [], []
+        for p, q in self.pairs:
             shp = read_shape_file(p.replace('.data', '.shape'))
             nshp = read_shape_file(q.replace('.data', '.shape'))
             if len(shp) != 3 or len(nshp) != 3 or shp[0] != 1 + nshp[0]:
                 raise ValueError("%s: shapes %r / %r, expected (1 + ninst, T, F) / (ninst, P, W)" % (p, shp, nshp))
             self.shapes.append(tuple(shp))
             self.note_shapes.append(tuple(nshp))
-            table += [(i if s is not None else -1, s if s is not None else 0) for s in slots(shp[1], self.tc, self.overlap)]
         for k, what in ((0, "channels"), (2, "F")):
             if len(set(s[k] for s in self.shapes)) > 1:
                 raise ValueError("feature files disagree on %s" % what)
@@ -303,15 +174,12 @@ class ScoreFeatureWindows(object):
         if self.shapes and (not 1 <= self.ninst <= 32 or self.width < 5 or self.width % 2 == 0):
             raise ValueError("ninst %d (1 .. 32), note table width %d (odd, from 5)" % (self.ninst, self.width))
         self.F = self.shapes[0][2] if self.shapes else 0
-        self.table = np.asarray(table, dtype=np.int32).reshape(-1, 2)
-        self.total = len(self.table)
-        self.iteration_size = self.total // self.batch_size
-        self._ctx = ctx
+        self._set_table(s[1] for s in self.shapes)
 
     def _upload(self):
         if getattr(self, "_data", None) is not None:
             return
-        self.ctx = self._ctx if self._ctx is not None else default_context()
+        self._open()
         blocks, files, off = [], [], 0
         packed, note_files, noff = [], [], 0
         for (p, q), shp, nshp in zip(self.pairs, self.shapes, self.note_shapes):
@@ -333,20 +201,10 @@ class ScoreFeatureWindows(object):
     def gather(self, rows):
         """Inputs ``[B, ninst, tc, F]`` and targets ``[B, ninst, tc, F]`` (device tensors) of the window-table rows ``rows``."""
         self._upload()
-        import torch
-        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
-        B = len(win)
         with self.ctx.stream_scope():
-            win_d = torch.from_numpy(win).to(self.ctx.device)
-            x = torch.empty((B, self.ninst, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            t = torch.empty((B, self.ninst, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            win_d, B, x, t = self._batch(rows, self.ninst, self.ninst)
             _lib.check(self.ctx._lib.dcs_trainer_gather_score(self.ctx._h, _ptr(self._data), _ptr(self._files),
                                                               _ptr(self._notes), _ptr(self._note_files), _ptr(win_d), B,
                                                               self.tc, self.F, self.ninst, self.width, self.mult, _ptr(x),
                                                               _ptr(t)))
         return x, t
-
-    def batches(self, epoch=0):
-        perm = np.random.RandomState(self.seed + epoch).permutation(self.total)
-        for b in range(self.iteration_size):
-            yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])

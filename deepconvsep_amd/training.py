@@ -3,15 +3,19 @@
 ``'ikala_nopool'``) and for the Bach10 graph (examples/bach10/trainCNNbach10.py:126-254, the graph trainCNNrwc.py and
 trainCNNSibelius.py train too), and the data feed of ``dataset.LargeDataset`` (dataset.py:383-602).
 
-``Trainer`` holds the parameters (15 for DSD, 13 for iKala, 17 for Bach10), Adadelta's state and the baked-in uniform draw on
-the device and runs ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the loss components) as HIP kernels
-(the shared core csrc/train_core.hip behind ``dcs_trainer_*``, the graphs in csrc/train_dsd.hip, csrc/train_ikala.hip and
-csrc/train_bach10.hip, the last two descriptions of the shared build_ca graph csrc/train_ca.hip).
+``TrainerHandle`` is the one Python handle on ``dcs_trainer_*`` (the shared core csrc/train_core.hip): upload of the
+parameters and the baked-in draw, Adadelta's state, ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the
+loss components) as HIP kernels.  ``Trainer`` describes the three mono graphs to it (15 parameters for DSD, 13 for iKala, 17
+for Bach10: csrc/train_dsd.hip, csrc/train_ikala.hip and csrc/train_bach10.hip, the last two descriptions of the shared
+build_ca graph csrc/train_ca.hip); ``stereo_training.StereoTrainer`` and ``score_training.ScoreTrainer`` describe theirs.
+``WindowFeed`` is what the window feeds share: the slot table, the seeded epoch order and the lazily opened context.
 ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files resident on the device and cuts the reference's windows
-from them.  There is no CPU fallback.
+from them; the feeds of stereo_training, score_training, augment and score_render derive from the same base.
+:func:`glorot_arrays` is Lasagne's initialisation for any of the layouts.  There is no CPU fallback.
 """
 import math
-from ctypes import byref, c_double, c_int64, c_void_p
+import os
+from ctypes import byref, c_double, c_int, c_int64, c_void_p
 
 import numpy as np
 
@@ -54,12 +58,13 @@ def param_shapes(arch, tc, F):
     return shapes + [(4,)]
 
 
-def glorot_init(arch='dsd', tc=30, F=513, seed=0):
-    """Lasagne's defaults for build_ca (any of the trainers): every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
-    sqrt(2 / ((n1 + n2) * receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32."""
+def glorot_arrays(shapes, seed):
+    """Lasagne's defaults for a list of parameter shapes: every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
+    sqrt(2 / ((n1 + n2) * receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32,
+    drawn from one ``RandomState(seed)`` in parameter order."""
     rs = np.random.RandomState(seed)
     out = []
-    for shp in param_shapes(arch, tc, F):
+    for shp in shapes:
         if len(shp) == 1:
             out.append(np.zeros(shp, dtype=np.float32))
             continue
@@ -69,7 +74,159 @@ def glorot_init(arch='dsd', tc=30, F=513, seed=0):
     return out
 
 
-class Trainer(object):
+def glorot_init(arch='dsd', tc=30, F=513, seed=0):
+    """Lasagne's defaults for build_ca (any of the trainers): every W ``GlorotUniform(gain=1)`` -- uniform in +-sqrt(3) *
+    sqrt(2 / ((n1 + n2) * receptive field)) with (n1, n2) the first two axes -- and every bias ``Constant(0)``; float32."""
+    return glorot_arrays(param_shapes(arch, tc, F), seed)
+
+
+class TrainerHandle(object):
+    """One ``dcs_trainer`` handle: what ``Trainer``, ``stereo_training.StereoTrainer`` and ``score_training.ScoreTrainer``
+    share.  The parameters, Adadelta's state and the baked-in draw live on the device; the batch size is fixed, as in the
+    reference's compiled graph.
+
+    A subclass describes its graph to ``__init__`` -- the arch name, input and output channels, the draw's shape and the
+    seven ``hyper`` values of ``dcs_trainer_create`` -- and supplies ``_default_params(seed)`` and, where the draw is not
+    uniform, ``_default_rand(seed)``; both are only called once a GPU is known to be there.  ``params``: float32 arrays in
+    .pkl order, at most four axes each."""
+
+    def __init__(self, ctx, arch, channels_in, channels_out, batch_size, time_context, feat_size, rand_shape, params, rand,
+                 seed, hyper, code=None):
+        torch = require_gpu()
+        self.ctx = ctx if ctx is not None else default_context()
+        self.arch = arch
+        self.B, self.tc, self.F = int(batch_size), int(time_context), int(feat_size)
+        self.rand_shape = tuple(rand_shape)
+        self._x_shape = (self.B, channels_in, self.tc, self.F)
+        self._t_shape = (self.B, channels_out, self.tc, self.F)
+        if params is None:
+            params = self._default_params(seed)
+        params = [np.asarray(p, dtype=np.float32) for p in params]
+        if rand is None:
+            rand = self._default_rand(seed)
+        rand = np.asarray(rand)
+        if rand.shape != self.rand_shape:
+            raise ValueError("rand has shape %r, the trainer takes %r" % (rand.shape, self.rand_shape))
+        self.shapes = [tuple(p.shape) for p in params]
+        n = len(params)
+        shapes = (c_int64 * (4 * n))()
+        for i, p in enumerate(params):
+            if p.ndim > 4:
+                raise ValueError("mismatch: parameter %d has %d axes" % (i, p.ndim))
+            shp = list(p.shape) + [1] * (4 - p.ndim)
+            for k in range(4):
+                shapes[4 * i + k] = shp[k]
+        with self.ctx.stream_scope():
+            dev = [self.ctx.to_device(p, np.float32) for p in params]
+            rand_d = self.ctx.to_device(rand, np.float32)
+        ptrs = (c_void_p * n)(*[p.data_ptr() for p in dev])
+        h = c_void_p()
+        _lib.check(self.ctx._lib.dcs_trainer_create(self.ctx._h, ARCHS[arch].code if code is None else code, self.tc, self.F,
+                                                    self.B, ptrs, shapes, n, _ptr(rand_d), (c_double * 7)(*hyper), byref(h)))
+        self._h = h
+        count = c_int()
+        _lib.check(self.ctx._lib.dcs_trainer_out_count(self._h, byref(count)))
+        with self.ctx.stream_scope():
+            self._out = torch.zeros(count.value, dtype=torch.float64, device=self.ctx.device)
+        self._keep = (dev, rand_d)   # released after create's copies have run (stream order)
+
+    def _default_rand(self, seed):
+        return np.random.RandomState(seed).uniform(size=self.rand_shape)
+
+    def _io(self, inputs, targets=None):
+        """``inputs`` (and ``targets``, where given) as contiguous float32 device tensors of the trainer's shapes."""
+        torch = require_gpu()
+        x = inputs if isinstance(inputs, torch.Tensor) else self.ctx.to_device(inputs, np.float32)
+        x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        if targets is None:
+            if tuple(x.shape) != self._x_shape:
+                raise ValueError("inputs %r, the trainer takes %r" % (tuple(x.shape), self._x_shape))
+            return x, None
+        t = targets if isinstance(targets, torch.Tensor) else self.ctx.to_device(targets, np.float32)
+        t = t.to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        if tuple(x.shape) != self._x_shape or tuple(t.shape) != self._t_shape:
+            raise ValueError("inputs %r / targets %r, the trainer takes %r / %r" % (tuple(x.shape), tuple(t.shape),
+                                                                                     self._x_shape, self._t_shape))
+        return x, t
+
+    @_on_ctx_stream
+    def run(self, inputs, targets, mode):
+        """``dcs_trainer_step``; returns the device tensor of ``dcs_trainer_out_count`` doubles (loss, components, zeros)
+        before any update."""
+        x, t = self._io(inputs, targets)
+        _lib.check(self.ctx._lib.dcs_trainer_step(self._h, _ptr(x), _ptr(t), int(mode), _ptr(self._out)))
+        self._last_io = (x, t)
+        return self._out
+
+    def step(self, inputs, targets):
+        """``train_fn``: the loss at the current parameters, then one Adadelta update."""
+        return float(self.ctx.to_host(self.run(inputs, targets, 2))[0])
+
+    def loss_and_gradients(self, inputs, targets):
+        """Testing aid: the outputs of ``run`` and the gradients of the loss (one per parameter; exact zeros for parameters
+        the loss does not reach) at the current parameters, no update."""
+        out = self.ctx.to_host(self.run(inputs, targets, 1)).copy()
+        return out, self.gradients()
+
+    @_on_ctx_stream
+    def set_rand(self, rand):
+        """Replace the draw (``rand_shape``, an ndarray or a device tensor) in stream order."""
+        torch = require_gpu()
+        r = rand if isinstance(rand, torch.Tensor) else self.ctx.to_device(np.asarray(rand), np.float32)
+        if tuple(r.shape) != self.rand_shape:
+            raise ValueError("rand has shape %r, the trainer takes %r" % (tuple(r.shape), self.rand_shape))
+        r = r.to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        _lib.check(self.ctx._lib.dcs_trainer_set_rand(self._h, _ptr(r)))
+        self._rand_keep = r
+
+    @_on_ctx_stream
+    def _get(self, which):
+        torch = require_gpu()
+        outs = [torch.empty(s, dtype=torch.float32, device=self.ctx.device) for s in self.shapes]
+        ptrs = (c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        _lib.check(self.ctx._lib.dcs_trainer_get(self._h, int(which), ptrs, len(outs)))
+        return [o.cpu().numpy() for o in outs]
+
+    def params(self):
+        """``lasagne.layers.get_all_param_values``: float32 arrays in .pkl order."""
+        return self._get(0)
+
+    def gradients(self):
+        """Gradients of the last step (testing aid), .pkl order."""
+        return self._get(1)
+
+    def adadelta_state(self):
+        """(accu, delta_accu) of lasagne.updates.adadelta, .pkl order."""
+        return self._get(2), self._get(3)
+
+    @_on_ctx_stream
+    def forward(self, inputs):
+        """``lasagne.layers.get_output`` of the network: the output channels ``[B, channels_out, tc, F]`` before masking
+        (device tensor)."""
+        torch = require_gpu()
+        x, _ = self._io(inputs)
+        p = torch.empty(self._t_shape, dtype=torch.float32, device=self.ctx.device)
+        _lib.check(self.ctx._lib.dcs_trainer_forward(self._h, _ptr(x), _ptr(p)))
+        return p
+
+    def save_model(self, path):
+        """The reference's ``save_model``: the pickled parameter list that ``Network(arch, ...)``, ``Separator(arch, ...)``
+        and the separate_*.py scripts load (``arch.resolve`` tells the layouts apart by their shapes)."""
+        _save_model(path, self.params())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.dcs_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Trainer(TrainerHandle):
     """``train_fn`` / ``train_fn1`` of trainCNN.py:262-263 for the DSD graph, resident on one GPU; ``arch='ikala_nopool'``:
     the same pair of examples/ikala/trainCNN.py:195-197 for the iKala graph; ``arch='bach10'``: that of
     examples/bach10/trainCNNbach10.py:204-206 for the Bach10 graph.
@@ -84,10 +241,6 @@ class Trainer(object):
     def __init__(self, ctx=None, arch='dsd', params=None, batch_size=32, time_context=30, feat_size=513, seed=0,
                  rand=None, eps=EPS, alpha=ALPHA, beta=BETA, beta_voc=BETA_VOC, learning_rate=LEARNING_RATE, rho=RHO,
                  epsilon=ADA_EPSILON):
-        torch = require_gpu()
-        self.ctx = ctx if ctx is not None else default_context()
-        self.arch = arch
-        self.S = n_sources(arch)
         if arch == 'ikala_nopool':
             eps = IKALA_EPS if eps is EPS else eps
             alpha = IKALA_ALPHA if alpha is ALPHA else alpha
@@ -95,57 +248,15 @@ class Trainer(object):
             beta_voc = IKALA_BETA_VOC if beta_voc is BETA_VOC else beta_voc
         elif arch == 'bach10':
             eps = BACH10_EPS if eps is EPS else eps
-        self.B, self.tc, self.F = int(batch_size), int(time_context), int(feat_size)
-        if params is None:
-            params = glorot_init(arch, self.tc, self.F, seed)
-        params = [np.asarray(p, dtype=np.float32) for p in params]
-        if rand is None:
-            rand = np.random.RandomState(seed).uniform(size=(self.B, 1, self.tc, self.F))
-        rand = np.asarray(rand)
-        if rand.shape != (self.B, 1, self.tc, self.F):
-            raise ValueError("rand has shape %r, the trainer takes %r" % (rand.shape, (self.B, 1, self.tc, self.F)))
-        self.shapes = [tuple(p.shape) for p in params]
-        code = ARCHS[arch].code if arch in ARCHS else -1
-        with self.ctx.stream_scope():
-            dev = [self.ctx.to_device(p, np.float32) for p in params]
-            rand_d = self.ctx.to_device(rand, np.float32)
-            self._out7 = torch.zeros(7, dtype=torch.float64, device=self.ctx.device)
-        n = len(dev)
-        ptrs = (c_void_p * n)(*[p.data_ptr() for p in dev])
-        shapes = (c_int64 * (4 * n))()
-        for i, p in enumerate(params):
-            shp = list(p.shape) + [1] * (4 - p.ndim)
-            for k in range(4):
-                shapes[4 * i + k] = shp[k]
-        hyper = (c_double * 7)(eps, alpha, beta, beta_voc, learning_rate, rho, epsilon)
-        h = c_void_p()
-        _lib.check(self.ctx._lib.dcs_trainer_create(self.ctx._h, code, self.tc, self.F, self.B, ptrs, shapes, n,
-                                                    _ptr(rand_d), hyper, byref(h)))
-        self._h = h
-        self._keep = (dev, rand_d)   # released after create's copies have run (stream order)
+        self.S = n_sources(arch)
+        # an arch without a code goes to the library as -1: dcs_trainer_create refuses what it cannot train
+        TrainerHandle.__init__(self, ctx, arch, 1, self.S, batch_size, time_context, feat_size,
+                               (int(batch_size), 1, int(time_context), int(feat_size)), params, rand, seed,
+                               (eps, alpha, beta, beta_voc, learning_rate, rho, epsilon),
+                               code=ARCHS[arch].code if arch in ARCHS else -1)
 
-    def _io(self, inputs, targets):
-        torch = require_gpu()
-        x = inputs if isinstance(inputs, torch.Tensor) else self.ctx.to_device(inputs, np.float32)
-        t = targets if isinstance(targets, torch.Tensor) else self.ctx.to_device(targets, np.float32)
-        x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        t = t.to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        if tuple(x.shape) != (self.B, 1, self.tc, self.F) or tuple(t.shape) != (self.B, self.S, self.tc, self.F):
-            raise ValueError("inputs %r / targets %r, the trainer takes (%d, 1, %d, %d) / (%d, %d, %d, %d)"
-                             % (tuple(x.shape), tuple(t.shape), self.B, self.tc, self.F, self.B, self.S, self.tc, self.F))
-        return x, t
-
-    @_on_ctx_stream
-    def run(self, inputs, targets, mode):
-        """``dcs_trainer_step``; returns the device tensor of (loss, components, zeros to 7) before any update."""
-        x, t = self._io(inputs, targets)
-        _lib.check(self.ctx._lib.dcs_trainer_step(self._h, _ptr(x), _ptr(t), int(mode), _ptr(self._out7)))
-        self._last_io = (x, t)
-        return self._out7
-
-    def step(self, inputs, targets):
-        """``train_fn`` (trainCNN.py:262): the loss at the current parameters, then one Adadelta update."""
-        return float(self.ctx.to_host(self.run(inputs, targets, 2))[0])
+    def _default_params(self, seed):
+        return glorot_init(self.arch, self.tc, self.F, seed)
 
     def losses(self, inputs, targets):
         """``train_fn1`` (trainCNN.py:263): vocals, bass, drums, negative, alpha, negative_voc at the current parameters;
@@ -153,58 +264,6 @@ class Trainer(object):
         (bach10/trainCNNbach10.py:206): error1 .. error4 (bassoon, clarinet, saxophone, violin)."""
         n = {'dsd': len(COMPONENTS), 'bach10': len(BACH10_COMPONENTS)}.get(self.arch, len(IKALA_COMPONENTS))
         return [float(v) for v in self.ctx.to_host(self.run(inputs, targets, 0))[1:1 + n]]
-
-    def loss_and_gradients(self, inputs, targets):
-        """Testing aid: loss and the gradients of |E| (one per parameter) at the current parameters, no update."""
-        out = self.ctx.to_host(self.run(inputs, targets, 1)).copy()
-        return out, self.gradients()
-
-    @_on_ctx_stream
-    def _get(self, which):
-        torch = require_gpu()
-        outs = [torch.empty(s, dtype=torch.float32, device=self.ctx.device) for s in self.shapes]
-        ptrs = (c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-        _lib.check(self.ctx._lib.dcs_trainer_get(self._h, int(which), ptrs, len(outs)))
-        return [o.cpu().numpy() for o in outs]
-
-    def params(self):
-        """``lasagne.layers.get_all_param_values`` (trainCNN.py:60): float32 arrays in .pkl order."""
-        return self._get(0)
-
-    def gradients(self):
-        """Gradients of the last step (testing aid), .pkl order."""
-        return self._get(1)
-
-    def adadelta_state(self):
-        """(accu, delta_accu) of lasagne.updates.adadelta, .pkl order."""
-        return self._get(2), self._get(3)
-
-    @_on_ctx_stream
-    def forward(self, inputs):
-        """``lasagne.layers.get_output(network2)``: ``[B, 4, tc, F]`` (iKala ``[B, 2, tc, F]``) before masking (device
-        tensor)."""
-        torch = require_gpu()
-        x, _ = self._io(inputs, torch.zeros((self.B, self.S, self.tc, self.F), dtype=torch.float32, device=self.ctx.device))
-        p = torch.empty((self.B, self.S, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-        _lib.check(self.ctx._lib.dcs_trainer_forward(self._h, _ptr(x), _ptr(p)))
-        return p
-
-    def save_model(self, path):
-        """trainCNN.py:59-64: the pickled list ``Network('dsd', ...)`` and separate_dsd.py load (iKala: ``Network('ikala',
-        ...)``, ``Separator('ikala', ...)`` and separate_ikala.py, which resolve it to the no-pool graph; Bach10:
-        ``Network('bach10', ...)``, ``Separator('bach10', ...)`` and separate_bach10.py)."""
-        _save_model(path, self.params())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx._lib.dcs_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def reference_slots(T, tc, overlap):
@@ -229,7 +288,63 @@ def all_slots(T, tc, overlap):
     return list(range(0, T - tc + 1, tc - overlap))
 
 
-class FeatureWindows(object):
+def listed_files(paths):
+    """``paths`` (files or directories) as a list of files: a directory stands for the files in it."""
+    files = []
+    for p in paths:
+        if os.path.isdir(p):
+            files += [os.path.join(p, f) for f in os.listdir(p)]
+        else:
+            files.append(p)
+    return files
+
+
+class WindowFeed(object):
+    """What the window feeds share: the slot table over a list of files (real or virtual), the seeded epoch order and the
+    context that is only opened when the first batch is cut.
+
+    A subclass validates its files, hands their frame counts to :meth:`_set_table`, uploads its data in ``_upload`` (which
+    starts with :meth:`_open`) and cuts a batch in ``gather(rows)`` with one library call on the tensors of
+    :meth:`_batch`."""
+
+    def __init__(self, windows, time_context, overlap, batch_size, seed, ctx):
+        if windows not in ('reference', 'all'):
+            raise ValueError("windows must be 'reference' or 'all'")
+        self._slots = reference_slots if windows == 'reference' else all_slots
+        self.tc, self.overlap, self.batch_size, self.seed = int(time_context), int(overlap), int(batch_size), int(seed)
+        self._ctx = ctx
+
+    def _set_table(self, frames):
+        """``table`` [total, 2] int32 = (file, window start) of every slot of files of ``frames`` frames each; file -1: a
+        slot the reference never fills (an all-zero window)."""
+        table = []
+        for i, T in enumerate(frames):
+            table += [(i if s is not None else -1, s if s is not None else 0) for s in self._slots(int(T), self.tc, self.overlap)]
+        self.table = np.asarray(table, dtype=np.int32).reshape(-1, 2)
+        self.total = len(self.table)
+        self.iteration_size = self.total // self.batch_size
+
+    def _open(self):
+        self.ctx = self._ctx if self._ctx is not None else default_context()
+
+    def _batch(self, rows, channels_in, channels_out):
+        """Inside ``ctx.stream_scope()``: the table rows ``rows`` on the device, their count B, and uninitialised inputs
+        ``[B, channels_in, tc, F]`` and targets ``[B, channels_out, tc, F]``."""
+        import torch
+        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
+        B = len(win)
+        win_d = torch.from_numpy(win).to(self.ctx.device)
+        x = torch.empty((B, channels_in, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+        t = torch.empty((B, channels_out, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+        return win_d, B, x, t
+
+    def batches(self, epoch=0):
+        perm = np.random.RandomState(self.seed + epoch).permutation(self.total)
+        for b in range(self.iteration_size):
+            yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])
+
+
+class FeatureWindows(WindowFeed):
     """The training data of ``LargeDataset`` (dataset.py) resident on the device.
 
     ``paths``: ``.data`` files of float64 ``[1 + sources, T, F]`` (each with its ``.shape``): by default ``[5, T, F]``
@@ -241,34 +356,27 @@ class FeatureWindows(object):
 
     def __init__(self, paths, time_context=30, overlap=25, mult_factor=0.3, windows='reference', batch_size=32, seed=0,
                  ctx=None, sources=4):
-        if windows not in ('reference', 'all'):
-            raise ValueError("windows must be 'reference' or 'all'")
+        WindowFeed.__init__(self, windows, time_context, overlap, batch_size, seed, ctx)
         self.sources = int(sources)
         if not 1 <= self.sources <= 8:
             raise ValueError("sources must be 1 .. 8, got %r" % (sources,))
-        self.tc, self.overlap, self.mult, self.batch_size, self.seed = int(time_context), int(overlap), float(mult_factor), \
-            int(batch_size), int(seed)
+        self.mult = float(mult_factor)
         self.paths = list(paths)
-        slots = reference_slots if windows == 'reference' else all_slots
-        self.shapes, table = [], []
-        for i, p in enumerate(self.paths):
+        self.shapes = []
+        for p in self.paths:
             shp = read_shape_file(p.replace('.data', '.shape'))
             if len(shp) != 3 or shp[0] != 1 + self.sources:
                 raise ValueError("%s: shape %r, expected (%d, T, F)" % (p, shp, 1 + self.sources))
             self.shapes.append(shp)
-            table += [(i if s is not None else -1, s if s is not None else 0) for s in slots(shp[1], self.tc, self.overlap)]
         if len(set(s[2] for s in self.shapes)) > 1:
             raise ValueError("feature files disagree on F: %r" % sorted(set(s[2] for s in self.shapes)))
         self.F = self.shapes[0][2] if self.shapes else 0
-        self.table = np.asarray(table, dtype=np.int32).reshape(-1, 2)
-        self.total = len(self.table)
-        self.iteration_size = self.total // self.batch_size
-        self._ctx = ctx
+        self._set_table(s[1] for s in self.shapes)
 
     def _upload(self):
         if getattr(self, "_data", None) is not None:
             return
-        self.ctx = self._ctx if self._ctx is not None else default_context()
+        self._open()
         blocks, files, off = [], [], 0
         for p, shp in zip(self.paths, self.shapes):
             a = np.fromfile(p, dtype=np.float64).reshape(shp).astype(np.float32)
@@ -283,13 +391,8 @@ class FeatureWindows(object):
     def gather(self, rows):
         """Inputs ``[B, 1, tc, F]`` and targets ``[B, sources, tc, F]`` (device tensors) of the window-table rows ``rows``."""
         self._upload()
-        import torch
-        win = np.ascontiguousarray(self.table[np.asarray(rows, dtype=np.int64)])
-        B = len(win)
         with self.ctx.stream_scope():
-            win_d = torch.from_numpy(win).to(self.ctx.device)
-            x = torch.empty((B, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
-            t = torch.empty((B, self.sources, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+            win_d, B, x, t = self._batch(rows, 1, self.sources)
             if self.sources == 4:
                 _lib.check(self.ctx._lib.dcs_trainer_gather(self.ctx._h, _ptr(self._data), _ptr(self._files), _ptr(win_d), B,
                                                             self.tc, self.F, self.mult, _ptr(x), _ptr(t)))
@@ -298,8 +401,3 @@ class FeatureWindows(object):
                                                                     _ptr(win_d), B, self.tc, self.F, self.sources,
                                                                     self.mult, _ptr(x), _ptr(t)))
         return x, t
-
-    def batches(self, epoch=0):
-        perm = np.random.RandomState(self.seed + epoch).permutation(self.total)
-        for b in range(self.iteration_size):
-            yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])
