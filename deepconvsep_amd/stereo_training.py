@@ -4,10 +4,10 @@ examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py (:117-289) and the data feed of `
 
 ``StereoTrainer`` has the surface of :class:`deepconvsep_amd.training.Trainer` for arch ``'dsd_ild'``: 17 parameters, two
 input channels, eight output channels (channel ``2 s + c``: source s in input channel c), the stage-1 loss of
-``train_fn_mse`` / ``train_fn1`` and, with ``ild=True``, the stage-2 loss of ``train_fn_ILD`` (csrc/train_dsdild.hip on the
-shared core csrc/train_core.hip).  The handle itself is :class:`deepconvsep_amd.training.TrainerHandle`; the class adds what
-only this graph knows: its channels, its two draws and the ``ild`` flag of its second loss.  ``training.TRAINABLE`` lists the
-mono graphs only.
+``train_fn_mse`` / ``train_fn1`` and, with ``ild=True``, the stage-2 loss of ``train_fn_ILD`` (csrc/train_dsdild.hip on
+csrc/train_dsd_graph.hip and the shared core csrc/train_core.hip).  The handle itself is
+:class:`deepconvsep_amd.training.TrainerHandle`; the class adds what only this graph knows: its channels, its two draws and
+the ``ild`` flag of its second loss.  ``training.TRAINABLE`` lists the mono graphs only.
 
 The draws: the reference's ``rand_num`` / ``rand_num2`` are ``RandomStreams(128).normal(std=0.1)`` and are redrawn by Theano
 on every call.  The trainer holds one pair ``[2, B, 4, tc, F]`` until :meth:`StereoTrainer.set_rand` replaces it (the

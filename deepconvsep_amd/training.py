@@ -6,8 +6,9 @@ trainCNNSibelius.py train too), and the data feed of ``dataset.LargeDataset`` (d
 ``TrainerHandle`` is the one Python handle on ``dcs_trainer_*`` (the shared core csrc/train_core.hip): upload of the
 parameters and the baked-in draw, Adadelta's state, ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the
 loss components) as HIP kernels.  ``Trainer`` describes the three mono graphs to it (15 parameters for DSD, 13 for iKala, 17
-for Bach10: csrc/train_dsd.hip, csrc/train_ikala.hip and csrc/train_bach10.hip, the last two descriptions of the shared
-build_ca graph csrc/train_ca.hip); ``stereo_training.StereoTrainer`` and ``score_training.ScoreTrainer`` describe theirs.
+for Bach10: csrc/train_dsd.hip, a description of the full-width graph csrc/train_dsd_graph.hip, and csrc/train_ikala.hip and
+csrc/train_bach10.hip, descriptions of the shared build_ca graph csrc/train_ca.hip); ``stereo_training.StereoTrainer`` and
+``score_training.ScoreTrainer`` describe theirs.
 ``WindowFeed`` is what the window feeds share: the slot table, the seeded epoch order and the lazily opened context.
 ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files resident on the device and cuts the reference's windows
 from them; the feeds of stereo_training, score_training, augment and score_render derive from the same base.

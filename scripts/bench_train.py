@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip) or, with --arch ikala_nopool / bach10 / bach10_si / dsd_ild /
+"""Training-step benchmark of the DSD graph (csrc/train_dsd.hip on csrc/train_dsd_graph.hip) or, with --arch ikala_nopool / bach10 / bach10_si / dsd_ild /
 bach10_si_1x1, the iKala graph (csrc/train_ikala.hip) / the Bach10 graph (csrc/train_bach10.hip) / the score-informed Bach10
-graph (csrc/train_bach10si.hip; --branches 1: its 11-array layout) / the stereo DSD graph (csrc/train_dsdild.hip; --ild: its
+graph (csrc/train_bach10si.hip; --branches 1: its 11-array layout) / the stereo DSD graph (csrc/train_dsdild.hip on csrc/train_dsd_graph.hip; --ild: its
 stage-2 loss) / the deep score-informed graph build_ca_1x1 (csrc/train_deep1x1.hip; its line carries the step's FLOPs from
 ``Deep1x1Arch.train_flops_per_tile`` and the TFLOP/s they make), all on the shared core csrc/train_core.hip (the iKala and the two Bach10 graphs through the shared build_ca graph
 csrc/train_ca.hip), against the same float32 graph, loss and Adadelta written in torch
@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 # kernels per train_fn step: 6 forward GEMMs, loss + reduce, 5 backward GEMMs, 4 weight-gradient GEMMs, split-K reduce,
-# Adadelta (the graph's launches in csrc/train_dsd.hip, Adadelta in csrc/train_core.hip)
+# Adadelta (the graph's launches in csrc/train_dsd_graph.hip, the loss in csrc/train_dsd.hip, Adadelta in csrc/train_core.hip)
 LAUNCHES_PER_STEP = 19
 # iKala: 7 forward launches (F3 split-K GEMM + its sum), loss + reduce, 6 backward (B3 likewise), 4 weight-gradient GEMMs,
 # split-K reduce, Adadelta (the GEMMs in csrc/train_ca.hip, conv1^T and the loss in csrc/train_ikala.hip, Adadelta in
@@ -43,7 +43,7 @@ LAUNCHES_PER_STEP_BACH10 = 21
 LAUNCHES_PER_STEP_BACH10SI = 21
 # stereo DSD: 8 forward launches (F3 split-K GEMM + its sum, conv1^T once per input channel), loss + reduce (stage 2: the
 # per-bin sums and their means before them), 6 backward (B3 split-K + sum), 4 weight-gradient GEMMs, split-K reduce,
-# Adadelta (csrc/train_dsdild.hip, csrc/train_core.hip)
+# Adadelta (csrc/train_dsd_graph.hip, the loss in csrc/train_dsdild.hip, csrc/train_core.hip)
 LAUNCHES_PER_STEP_ILD = {False: 22, True: 24}
 # build_ca_1x1 (csrc/train_deep1x1.hip): forward 7 weight packs, the input transpose, 7 convolutions, 6 x (2 transposed
 # launches + the code product) = 33; loss + reduce; backward the dq transpose, 6 convolutions, the 1x1 product and its code

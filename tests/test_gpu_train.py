@@ -1,4 +1,5 @@
-"""DSD trainer on the MI355X (csrc/train_dsd.hip on csrc/train_core.hip) against the float64 autograd restatement tests/train_ref.py."""
+"""DSD trainer on the MI355X (csrc/train_dsd.hip on csrc/train_dsd_graph.hip and csrc/train_core.hip) against the float64
+autograd restatement tests/train_ref.py."""
 import os
 import subprocess
 import sys

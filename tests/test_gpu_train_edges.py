@@ -1,4 +1,4 @@
-"""The three HIP trainers (csrc/train_core.hip, train_dsd.hip, train_ca.hip with train_ikala.hip and train_bach10.hip) where
+"""The three HIP trainers (csrc/train_core.hip, train_dsd.hip on train_dsd_graph.hip, train_ca.hip with train_ikala.hip and train_bach10.hip) where
 a training run goes and the template of test_gpu_train*.py does not: exact zeros and ties at every site that carries Theano's conventions, the
 ends of the accepted shape ranges and the split-K regimes behind them, non-default hyper-parameters, and Adadelta on a live
 state -- each against the float64 restatements, gradients by norm and by element (tests/train_edges.py).  The controls that

@@ -1,4 +1,4 @@
-"""Stereo (ILD) DSD100 trainer on the MI355X (csrc/train_dsdild.hip on csrc/train_core.hip, StereoTrainer and
+"""Stereo (ILD) DSD100 trainer on the MI355X (csrc/train_dsdild.hip on csrc/train_dsd_graph.hip and csrc/train_core.hip, StereoTrainer and
 StereoFeatureWindows) against the float64 autograd restatement tests/train_ild_ref.py."""
 import os
 import pickle
