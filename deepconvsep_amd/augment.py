@@ -25,8 +25,8 @@ from ctypes import POINTER, c_double, c_int64
 import numpy as np
 
 from . import _lib
-from .runtime import StftPlan, _ptr, default_context
-from .training import WindowFeed
+from .runtime import StftPlan, _ptr, default_context  # noqa: F401  (StftPlan, WindowFeed: importable from here as before)
+from .training import RenderedFeed, WindowFeed  # noqa: F401
 
 CHANNELS = ('vocals', 'bass', 'drums', 'other')       # channels 1 .. 4 of a feature file (0 is the mixture)
 # the order in which each script adds the sources into its mixture (compute_features.py:85, compute_features_cs_aug.py:120,
@@ -190,48 +190,41 @@ def table_rows(vfiles, index, hop):
     return np.asarray(rows, dtype=np.int64), np.asarray(gains, dtype=np.float64)
 
 
+def bank_index(signals):
+    """Key -> ``(offset, length)`` of the signals laid back to back in the order of ``signals``, and the total length."""
+    index, off = {}, 0
+    for k, x in signals.items():
+        index[k] = (off, len(x))
+        off += len(x)
+    return index, off
+
+
 class Bank(object):
     """Mono source signals back to back on the device: ``signals`` maps a key (song, source name) to a 1-D array; ``index``
     maps the key to ``(offset, length)``.  Uploaded once, as ``dtype``."""
 
     def __init__(self, signals, dtype=np.float32, ctx=None):
         self.ctx = ctx if ctx is not None else default_context()
-        self.index, off = {}, 0
-        for k, x in signals.items():
-            self.index[k] = (off, len(x))
-            off += len(x)
-        self.length = off
-        flat = np.concatenate([np.asarray(x, dtype=dtype).ravel() for x in signals.values()]) if off else np.zeros(1, dtype)
+        self.index, self.length = bank_index(signals)
+        flat = np.concatenate([np.asarray(x, dtype=dtype).ravel() for x in signals.values()]) if self.length \
+            else np.zeros(1, dtype)
         self.tensor = self.ctx.to_device(flat, dtype)
 
 
-def render_features(tt, bank, vf, out_dir=None):
-    """The feature blocks of the virtual file ``vf``, all chunks in one launch (``dcs_stft_forward_render_f64`` / ``_f32``
-    after ``tt.precision``, the bank's dtype): a list ``[chunk] -> [1 + S, T, F]`` float64, or with ``out_dir`` the files
-    ``<out_dir>/<name>__m_.data`` / ``.shape`` through ``tt.saveTensor`` (what ``tt.compute_transform(audio, path,
-    phase=False)`` writes for the host-rendered chunk) and the list of paths.  ``tt``: a ``transformFFT``."""
+def render_blocks(tt, entry, S, frames, names, out_dir, call):
+    """What the feature renderers share.  ``call(fn, plan, out, rows)`` runs ``fn`` = the library's ``entry`` + ``_f64`` /
+    ``_f32`` (after ``tt.precision``) into ``out``, a device tensor of ``rows`` = (1 + S) * sum(frames) rows of ``plan.bins``,
+    and returns its code.  Returns the blocks ``[1 + S, T, F]`` float64 of ``frames``, or with ``out_dir`` writes block i as
+    ``<out_dir>/<names[i]>__m_.data`` / ``.shape`` through ``tt.saveTensor`` and returns the paths of the ``.data`` files."""
     import torch
     plan = tt._get_plan()
     ctx = plan.ctx
     f64 = tt.precision == 'float64'
-    if bank.tensor.dtype != (torch.float64 if f64 else torch.float32):
-        raise ValueError("the bank holds %s, the transform computes in %s" % (bank.tensor.dtype, tt.precision))
-    S = len(vf.tracks)
-    tracks = np.asarray([list(bank.index[t.signal]) + [t.k, t.c] for t in vf.tracks], dtype=np.int64)
-    gains = np.asarray([vf.m] + [t.g for t in vf.tracks], dtype=np.float64)
-    chunks = np.asarray(vf.chunks, dtype=np.int64).reshape(-1, 2)
-    n = len(chunks)
-    frames = [_lib.frame_count(int(Lc), plan.hop) for _, Lc in chunks]
     rows = (1 + S) * sum(frames)
-    got = (c_int64 * max(n, 1))()
     with ctx.stream_scope():
-        out = torch.empty((max(rows, 1), plan.bins), dtype=bank.tensor.dtype, device=ctx.device)
-        fn = ctx._lib.dcs_stft_forward_render_f64 if f64 else ctx._lib.dcs_stft_forward_render_f32
-        _lib.check(fn(plan._h, _ptr(bank.tensor), bank.length, S, tracks.ctypes.data_as(POINTER(c_int64)),
-                      gains.ctypes.data_as(POINTER(c_double)), int(vf.size), chunks.ctypes.data_as(POINTER(c_int64)), n,
-                      _ptr(out), plan.bins, rows, got))
+        out = torch.empty((max(rows, 1), plan.bins), dtype=torch.float64 if f64 else torch.float32, device=ctx.device)
+        _lib.check(call(getattr(ctx._lib, entry + ('_f64' if f64 else '_f32')), plan, out, rows))
         host = out.double().cpu().numpy()
-    assert list(got)[:n] == frames
     blocks, at = [], 0
     for T in frames:
         blocks.append(host[at:at + (1 + S) * T].reshape(1 + S, T, plan.bins))
@@ -240,11 +233,34 @@ def render_features(tt, bank, vf, out_dir=None):
         return blocks
     os.makedirs(out_dir, exist_ok=True)
     paths = []
-    for name, b in zip(vf.names, blocks):
+    for name, b in zip(names, blocks):
         tt.out_path = os.path.join(out_dir, name + '.data')
         tt.saveTensor(np.ascontiguousarray(b), '_' + tt.suffix + '_m_')
         paths.append(tt.out_path.replace('.data', '_' + tt.suffix + '_m_.data'))
     return paths
+
+
+def render_features(tt, bank, vf, out_dir=None):
+    """The feature blocks of the virtual file ``vf``, all chunks in one launch (``dcs_stft_forward_render_f64`` / ``_f32``
+    after ``tt.precision``, the bank's dtype): a list ``[chunk] -> [1 + S, T, F]`` float64, or with ``out_dir`` the files
+    ``<out_dir>/<name>__m_.data`` / ``.shape`` through ``tt.saveTensor`` (what ``tt.compute_transform(audio, path,
+    phase=False)`` writes for the host-rendered chunk) and the list of paths.  ``tt``: a ``transformFFT``."""
+    import torch
+    if bank.tensor.dtype != (torch.float64 if tt.precision == 'float64' else torch.float32):
+        raise ValueError("the bank holds %s, the transform computes in %s" % (bank.tensor.dtype, tt.precision))
+    S = len(vf.tracks)
+    tracks = np.asarray([list(bank.index[t.signal]) + [t.k, t.c] for t in vf.tracks], dtype=np.int64)
+    gains = np.asarray([vf.m] + [t.g for t in vf.tracks], dtype=np.float64)
+    chunks = np.asarray(vf.chunks, dtype=np.int64).reshape(-1, 2)
+    n = len(chunks)
+    frames = [_lib.frame_count(int(Lc), tt.hopSize) for _, Lc in chunks]
+    got = (c_int64 * max(n, 1))()
+    out = render_blocks(tt, 'dcs_stft_forward_render', S, frames, vf.names, out_dir, lambda fn, plan, out, rows: fn(
+        plan._h, _ptr(bank.tensor), bank.length, S, tracks.ctypes.data_as(POINTER(c_int64)),
+        gains.ctypes.data_as(POINTER(c_double)), int(vf.size), chunks.ctypes.data_as(POINTER(c_int64)), n, _ptr(out), plan.bins,
+        rows, got))
+    assert list(got)[:n] == frames
+    return out
 
 
 def render_audio(signals, vf):
@@ -262,7 +278,7 @@ def render_audio(signals, vf):
     return out
 
 
-class RenderedWindows(WindowFeed):
+class RenderedWindows(RenderedFeed):
     """``FeatureWindows`` without feature files: the training windows of the virtual files ``vfiles`` are transformed per
     batch from ``signals`` (key -> mono signal, uploaded once as float32) by ``dcs_trainer_gather_render``.
 
@@ -272,24 +288,13 @@ class RenderedWindows(WindowFeed):
 
     def __init__(self, signals, vfiles, time_context=30, overlap=25, mult_factor=0.3, windows='reference', batch_size=32,
                  seed=0, ctx=None, frameSize=1024, hopSize=512, window=None):
-        WindowFeed.__init__(self, windows, time_context, overlap, batch_size, seed, ctx)
-        self.mult = float(mult_factor)
-        self.frame, self.hop, self._window = int(frameSize), int(hopSize), window
         self.vfiles = list(vfiles)
-        counts = set(len(vf.tracks) for vf in self.vfiles)
-        if len(counts) != 1:
-            raise ValueError("virtual files disagree on the number of tracks: %r" % sorted(counts))
-        self.sources = counts.pop()
-        if not 1 <= self.sources <= 8:
-            raise ValueError("1 .. 8 tracks per virtual file, got %d" % self.sources)
+        RenderedFeed.__init__(self, self.vfiles, mult_factor, frameSize, hopSize, window, windows, time_context, overlap,
+                              batch_size, seed, ctx)
         self._signals = signals
-        self.index, off = {}, 0
-        for k, x in signals.items():
-            self.index[k] = (off, len(x))
-            off += len(x)
+        self.index = bank_index(signals)[0]
         self.rows, self.gains = table_rows(self.vfiles, self.index, self.hop)
         self.names = [n for vf in self.vfiles for n in vf.names]
-        self.F = self.frame // 2 + 1
         self._set_table(r[3] for r in self.rows)
         self._bank = None
 
@@ -297,12 +302,9 @@ class RenderedWindows(WindowFeed):
         if self._bank is not None:
             return
         import torch
-        from .separation import blackmanharris
         self._open()
         self._bank = Bank(self._signals, np.float32, self.ctx)
         self._signals = None
-        win = self._window if self._window is not None else blackmanharris
-        self._plan = StftPlan(self.ctx, self.frame, self.hop, win(self.frame) if callable(win) else win)
         with self.ctx.stream_scope():
             self._rows_d = torch.from_numpy(self.rows).to(self.ctx.device)
             self._gains_d = torch.from_numpy(self.gains).to(self.ctx.device)

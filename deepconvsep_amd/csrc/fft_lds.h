@@ -1,5 +1,6 @@
 // The in-LDS complex FFT and the small helpers shared by the STFT kernels of fft.hip, fft_render.hip and
 // fft_score_render.hip: one definition, so that a frame transformed by any of them comes out bit for bit the same.
+// What only the render kernels share -- the frame around fft_lds, their launch -- is fft_frame.h, on top of this header.
 // Internal linkage (device templates).
 #pragma once
 #include "dcs_internal.h"

@@ -9,7 +9,9 @@
 // STFT's LOADER: one workgroup (256 threads) forms one windowed frame of one channel straight from the bank through three
 // nested bounds -- chunk [a, a + Lc), rendered length `size`, source length L_s -- and transforms it with the FFT body of
 // stft_forward_kernel (fft_lds.h: fft_lds, the packed real transform, mag = |X| / sqrt(N)).  Neither the rendered audio nor
-// (for the feed) the feature block ever exists in memory.
+// (for the feed) the feature block ever exists in memory.  This file holds the sample source (render_sample), the mapping
+// of a workgroup to its frame and output row, and the entry points' checks; the frame itself, the feed's window decode, the
+// launch and the life of the file path's own table are fft_frame.h, shared with fft_score_render.hip.
 //
 //   r_s[n] = g_s * x_s[n - k_s] if 0 <= n - k_s < L_s else 0 ;  mix[n] = m * (((r_0 + r_1) + r_2) + ...)
 //
@@ -22,9 +24,7 @@
 // (1 + S float64): m, g_0 .. g_{S-1}.  The file path builds one descriptor per chunk on the host (validated there); the
 // feed reads a table the caller keeps on the device, so the kernel itself bounds every bank index and output channel.
 #include "dcs_internal.h"
-#include "fft_lds.h"
-
-#include <vector>
+#include "fft_frame.h"
 
 namespace {
 
@@ -70,25 +70,20 @@ __global__ __launch_bounds__(kThreads) void stft_render_kernel(
     int log2m, R sqrt_n, int tw_lds) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int M = N >> 1;
-    const int tid = threadIdx.x;
     const int j = blockIdx.y;
     const int rs = kHead + 4 * S;
-    int64_t fi, t;
-    R* orow = nullptr;
-    bool live;
+    FeedWindow w = {};
     if (FEED) {
-        const int64_t b = blockIdx.x / tc;
-        const int tt = (int)(blockIdx.x - b * tc);
-        fi = windows[2 * b];
-        t = (int64_t)windows[2 * b + 1] + tt;
-        live = fi >= 0 && fi < n_files && t >= 0;
+        w = feed_window(windows, tc, n_files);
     } else {
         const int64_t g = blockIdx.x;
-        fi = 0;
-        while (fi + 1 < n_files && first[fi + 1] <= g) ++fi;
-        t = g - first[fi];
-        live = true;
+        w.fi = 0;
+        while (w.fi + 1 < n_files && first[w.fi + 1] <= g) ++w.fi;
+        w.t = g - first[w.fi];
+        w.live = true;
     }
+    const int64_t fi = w.fi, t = w.t;
+    const bool live = w.live;
     const int64_t* row = files + (live ? fi : 0) * rs;
     const double* gains = gains_all + (live ? fi : 0) * (1 + S);
     const int64_t T = live ? row[3] : 0;
@@ -98,55 +93,15 @@ __global__ __launch_bounds__(kThreads) void stft_render_kernel(
         ch = live ? (int)row[kHead + 4 * (j - 1) + 3] : j;
         if (ch < 1 || ch > S) return;
     }
-    if (FEED) {
-        const int64_t b = blockIdx.x / tc;
-        const int tt = (int)(blockIdx.x - b * tc);
-        orow = ch == 0 ? out0 + (b * tc + tt) * ld : out1 + (((b * S + ch - 1) * tc) + tt) * ld;
-    } else {
-        orow = out0 + ((1 + S) * first[fi] + (int64_t)ch * T + t) * ld;
-    }
-    if (!live || t >= T) {
-        for (int k = tid; k < ld; k += kThreads) orow[k] = R(0);
-        return;
-    }
-    R2* buf0 = reinterpret_cast<R2*>(smem);
-    R2* buf1 = buf0 + M;
-    if (tw_lds) {   // twiddles staged in LDS with the frame, as stft_forward_kernel does
-        R2* twl = buf1 + M;
-        for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
-        tw = twl;
-    }
+    R* orow = !FEED    ? out0 + ((1 + S) * first[fi] + (int64_t)ch * T + t) * ld
+              : ch == 0 ? out0 + (w.b * tc + w.tt) * ld
+                        : out1 + (((w.b * S + ch - 1) * tc) + w.tt) * ld;
+    if (!live || t >= T) return zero_row(orow, ld);
     const int64_t base = t * (int64_t)hop - M;   // chunk-relative index of padded sample t * hop
-    for (int m = tid; m < M; m += kThreads) {
-        const int64_t q = base + 2 * m;
-        const R x0 = render_sample<R>(bank, bank_len, row, gains, S, j, q) * win[2 * m];
-        const R x1 = render_sample<R>(bank, bank_len, row, gains, S, j, q + 1) * win[2 * m + 1];
-        buf0[m] = mk<R2, R>(x0, x1);
-    }
-    __syncthreads();
-    const R2* Z = fft_lds<R, R2, -1>(buf0, buf1, tw, M, log2m);
+    const R2* Z = render_frame<R, R2, false>(smem, win, tw, tw_lds, M, log2m, base, [&](int64_t q) {
+        return render_sample<R>(bank, bank_len, row, gains, S, j, q);
+    });
     packed_real_mag_row<R, R2, FEED>(Z, tw, M, ld, sqrt_n, scale, orow);
-}
-
-template <typename R, typename R2, bool FEED>
-int launch_render(dcs_stft* p, const R* win, const R2* tw, const R* bank, int64_t bank_len, const int64_t* files_d,
-                  const double* gains_d, int n_files, int S, const int64_t* first_d, const int* windows_d, int tc, R scale,
-                  R* out0, R* out1, int64_t ld, int64_t blocks) {
-    const int M = p->frame / 2;
-    size_t lds = (3 * (size_t)M + 1) * sizeof(R2);
-    const int tw_lds = lds <= 64 * 1024;
-    if (!tw_lds) lds = 2 * (size_t)M * sizeof(R2);
-    auto kern = stft_render_kernel<R, R2, FEED>;
-    if (lds > 48 * 1024)
-        DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-    DcsTimer tm(p->ctx, DCS_TAG_STFT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)(1 + S)), dim3(kThreads), lds, p->ctx->stream, bank, bank_len,
-                       files_d, gains_d, n_files, S, first_d, windows_d, tc, scale, out0, out1, ld, win, tw, p->frame, p->hop,
-                       p->log2m, (R)sqrt((double)p->frame), tw_lds);
-    tm.done();
-    DCS_HIP(hipGetLastError());
-    return DCS_OK;
 }
 
 template <typename R, typename R2>
@@ -198,25 +153,12 @@ int render_file(dcs_stft* p, const R* win, const R2* tw, const R* bank_d, int64_
         DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_render: out_rows %lld < %lld", (long long)out_rows, (long long)((1 + S) * total));
     if (total > 0x7fffffffLL) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_render: %lld frames in one launch", (long long)total);
     DCS_ON_DEVICE(p->ctx->device);
-    void* tab_d = nullptr;
-    DCS_HIP(dcs_dev_alloc(&tab_d, tab.size() * sizeof(int64_t), "stft.render_table"));
-    int rc = DCS_OK;
-    if (hipMemcpy(tab_d, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
-        dcs_set_error("dcs_stft_forward_render: uploading the chunk table failed");
-        rc = DCS_EHIP;
-    }
-    const int64_t* files_d = (const int64_t*)tab_d;
-    const int64_t* first_d = files_d + (size_t)n_chunks * rs;
-    if (rc == DCS_OK)
-        rc = launch_render<R, R2, false>(p, win, tw, bank_d, bank_len, files_d, (const double*)(first_d + n_chunks + 1), n_chunks,
-                                         S, first_d, nullptr, 1, R(1), out_d, nullptr, ld, total);
-    // the table is this call's own: wait for the launch, then give it back
-    if (hipStreamSynchronize(p->ctx->stream) != hipSuccess && rc == DCS_OK) {
-        dcs_set_error("dcs_stft_forward_render: the launch failed");
-        rc = DCS_EHIP;
-    }
-    dcs_dev_free(tab_d);
-    return rc;
+    return with_own_table(p, tab, "stft.render_table", "dcs_stft_forward_render", "chunk", [&](const int64_t* files_d) {
+        const int64_t* first_d = files_d + (size_t)n_chunks * rs;
+        return launch_frames(p, stft_render_kernel<R, R2, false>, total, S, win, tw, bank_d, bank_len, files_d,
+                             (const double*)(first_d + n_chunks + 1), n_chunks, S, first_d, (const int*)nullptr, 1, R(1), out_d,
+                             (R*)nullptr, ld);
+    });
 }
 
 }  // namespace
@@ -247,7 +189,7 @@ DCS_API int dcs_trainer_gather_render(dcs_ctx* ctx, dcs_stft* p, const float* ba
     if ((int64_t)batch * time_context > 0x7fffffffLL)
         DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_render: %lld frames in one launch", (long long)batch * time_context);
     DCS_ON_DEVICE(ctx->device);
-    return launch_render<float, float2, true>(p, p->win_f, p->tw_f, bank_d, bank_len, files_d, gains_d, n_files, S, nullptr,
-                                              windows_d, time_context, scale, inputs_d, targets_d, p->frame / 2 + 1,
-                                              (int64_t)batch * time_context);
+    return launch_frames(p, stft_render_kernel<float, float2, true>, (int64_t)batch * time_context, S, p->win_f, p->tw_f, bank_d,
+                         bank_len, files_d, gains_d, n_files, S, (const int64_t*)nullptr, windows_d, time_context, scale,
+                         inputs_d, targets_d, (int64_t)(p->frame / 2 + 1));
 }

@@ -16,8 +16,9 @@
 // With that order the note covering n is found from the last note with b <= n by walking back while E > n.  One workgroup
 // (256 threads) forms one windowed frame of one channel: it first resolves, once, the frame's candidate notes of every
 // track -- those with b < frame end and E > frame start, two binary searches by one thread per track, four integers per
-// track in LDS -- and a sample's lookup then stays inside that range.  The frame is transformed by the FFT body of
-// stft_forward_kernel (fft_lds.h) with the tail of stft_render_kernel (packed_real_mag_row): the float64 block equals the
+// track in LDS (frame_candidates, the prepare step) -- and a sample's lookup (score_sample, the sample source) then stays
+// inside that range.  The frame is formed and transformed by render_frame (fft_frame.h, shared with stft_render_kernel: the
+// FFT body of stft_forward_kernel) and ends in that kernel's tail (packed_real_mag_row): the float64 block equals the
 // existing kernel on host-rendered audio bit for bit.
 //
 // Descriptor of a virtual file (DCS_SCORE_RENDER_ROW(S) int64): size, T, then S x (first note, note count).  The file path
@@ -26,11 +27,9 @@
 //
 // The score-informed trainer's feed on the same data (examples/bach10_scoreinformed/compute_features_bach10rwc.py:96-163 read
 // back by LargeDatasetMask2) is stft_score_informed_kernel below: the render feed with train::gather_score_kernel's harmonic
-// masks applied to the mixture row in the same launch.
+// masks applied to the mixture row in the same launch -- the same prepare step and sample source, and a tail of its own.
 #include "dcs_internal.h"
-#include "fft_lds.h"
-
-#include <vector>
+#include "fft_frame.h"
 
 namespace {
 
@@ -71,111 +70,7 @@ __device__ __forceinline__ R score_sample(const R* __restrict__ bank, int64_t ba
     return acc;
 }
 
-// FEED = false: one virtual file (row 0 of `files`), blockIdx.x = frame t, output row (j T + t) of out0 [1 + S][T][ld].
-// FEED = true: blockIdx.x = b * tc + t of window b = (file, first frame); out0 = inputs [B][1][tc][F], out1 = targets
-//   [B][S][tc][F], values times `scale`; zero rows for file < 0, file >= n_files and frames past T.
-// blockIdx.y = j: 0 the mixture, 1 + s track s.
-template <typename R, typename R2, bool FEED>
-__global__ __launch_bounds__(kThreads) void stft_score_render_kernel(
-    const R* __restrict__ bank, int64_t bank_len, const int64_t* __restrict__ notes, int n_notes,
-    const int64_t* __restrict__ files, int n_files, int S, const int* __restrict__ windows, int tc, R scale, R* __restrict__ out0,
-    R* __restrict__ out1, int64_t ld, const R* __restrict__ win, const R2* __restrict__ tw, int N, int hop, int log2m, R sqrt_n,
-    int tw_lds) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_lo[kMaxTracks], s_hi[kMaxTracks];
-    const int M = N >> 1;
-    const int tid = threadIdx.x;
-    const int j = blockIdx.y;
-    const int rs = kFileHead + 2 * S;
-    int64_t fi = 0, t = blockIdx.x;
-    bool live = true;
-    R* orow;
-    if (FEED) {
-        const int64_t b = blockIdx.x / tc;
-        const int tt = (int)(blockIdx.x - b * tc);
-        fi = windows[2 * b];
-        t = (int64_t)windows[2 * b + 1] + tt;
-        live = fi >= 0 && fi < n_files && t >= 0;
-        orow = j == 0 ? out0 + (b * tc + tt) * ld : out1 + (((b * S + j - 1) * tc) + tt) * ld;
-    }
-    const int64_t* row = files + (live ? fi : 0) * rs;
-    const int64_t size = live ? row[0] : 0;
-    const int64_t T = live ? row[1] : 0;
-    if (!FEED) orow = out0 + ((int64_t)j * T + t) * ld;
-    if (!live || t >= T) {
-        for (int k = tid; k < ld; k += kThreads) orow[k] = R(0);
-        return;
-    }
-    const int64_t base = t * (int64_t)hop - M;   // index of padded sample t * hop in the rendered signal
-    if (tid < S) {
-        // the frame's candidate notes of track tid: b < f1 and E > f0, for the frame's samples [f0, f1) inside [0, size)
-        const int64_t f0 = base > 0 ? base : 0;
-        const int64_t f1 = base + N < size ? base + N : size;
-        const int64_t first = row[kFileHead + 2 * tid], count = row[kFileHead + 2 * tid + 1];
-        int lo = 0, hi = 0;
-        if (f0 < f1 && first >= 0 && count > 0 && first <= (int64_t)n_notes - count) {
-            int a = (int)first, z = (int)(first + count);
-            while (a < z) {                 // first note with b >= f1
-                const int mid = (a + z) >> 1;
-                if (notes[4 * (int64_t)mid] < f1) a = mid + 1; else z = mid;
-            }
-            hi = a;
-            a = (int)first;
-            z = hi;
-            while (a < z) {                 // first note with E > f0
-                const int mid = (a + z) >> 1;
-                if (notes[4 * (int64_t)mid + 3] <= f0) a = mid + 1; else z = mid;
-            }
-            lo = a;
-        }
-        s_lo[tid] = lo;
-        s_hi[tid] = hi;
-    }
-    R2* buf0 = reinterpret_cast<R2*>(smem);
-    R2* buf1 = buf0 + M;
-    if (tw_lds) {   // twiddles staged in LDS with the frame, as stft_forward_kernel does
-        R2* twl = buf1 + M;
-        for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
-        tw = twl;
-    }
-    __syncthreads();
-    for (int m = tid; m < M; m += kThreads) {
-        const int64_t q = base + 2 * m;
-        const R x0 = score_sample<R>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q) * win[2 * m];
-        const R x1 = score_sample<R>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q + 1) * win[2 * m + 1];
-        buf0[m] = mk<R2, R>(x0, x1);
-    }
-    __syncthreads();
-    const R2* Z = fft_lds<R, R2, -1>(buf0, buf1, tw, M, log2m);
-    packed_real_mag_row<R, R2, FEED>(Z, tw, M, ld, sqrt_n, scale, orow);
-}
-
-template <typename R, typename R2, bool FEED>
-int launch_score_render(dcs_stft* p, const R* win, const R2* tw, const R* bank, int64_t bank_len, const int64_t* notes_d,
-                        int n_notes, const int64_t* files_d, int n_files, int S, const int* windows_d, int tc, R scale, R* out0,
-                        R* out1, int64_t ld, int64_t blocks) {
-    const int M = p->frame / 2;
-    size_t lds = (3 * (size_t)M + 1) * sizeof(R2);
-    const int tw_lds = lds <= 64 * 1024;
-    if (!tw_lds) lds = 2 * (size_t)M * sizeof(R2);   // float64 at N = 4096: the twiddles stay in global memory
-    auto kern = stft_score_render_kernel<R, R2, FEED>;
-    if (lds > 48 * 1024)
-        DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-    DcsTimer tm(p->ctx, DCS_TAG_STFT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)(1 + S)), dim3(kThreads), lds, p->ctx->stream, bank, bank_len,
-                       notes_d, n_notes, files_d, n_files, S, windows_d, tc, scale, out0, out1, ld, win, tw, p->frame, p->hop,
-                       p->log2m, (R)sqrt((double)p->frame), tw_lds);
-    tm.done();
-    DCS_HIP(hipGetLastError());
-    return DCS_OK;
-}
-
-// ---- the score-informed feed: the windows of stft_score_render_kernel<float, float2, true> with train::gather_score_kernel's
-// harmonic masks (train_core.hip) applied to the mixture row while it is still in registers.
-
-// the frame's candidate notes of track s: b < f1 and E > f0 for the frame's samples [f0, f1) inside [0, size) -- the rule
-// of stft_score_render_kernel, restated here so that kernel's code stays as it is
+// the frame's candidate notes [lo, hi) of track s: b < f1 and E > f0 for the frame's samples [f0, f1) inside [0, size)
 __device__ __forceinline__ void frame_candidates(const int64_t* __restrict__ notes, int n_notes, const int64_t* __restrict__ row,
                                                  int s, int64_t base, int N, int64_t size, int* lo_out, int* hi_out) {
     const int64_t f0 = base > 0 ? base : 0;
@@ -201,6 +96,44 @@ __device__ __forceinline__ void frame_candidates(const int64_t* __restrict__ not
     *hi_out = hi;
 }
 
+// FEED = false: one virtual file (row 0 of `files`), blockIdx.x = frame t, output row (j T + t) of out0 [1 + S][T][ld].
+// FEED = true: blockIdx.x = b * tc + t of window b = (file, first frame); out0 = inputs [B][1][tc][F], out1 = targets
+//   [B][S][tc][F], values times `scale`; zero rows for file < 0, file >= n_files and frames past T.
+// blockIdx.y = j: 0 the mixture, 1 + s track s.
+template <typename R, typename R2, bool FEED>
+__global__ __launch_bounds__(kThreads) void stft_score_render_kernel(
+    const R* __restrict__ bank, int64_t bank_len, const int64_t* __restrict__ notes, int n_notes,
+    const int64_t* __restrict__ files, int n_files, int S, const int* __restrict__ windows, int tc, R scale, R* __restrict__ out0,
+    R* __restrict__ out1, int64_t ld, const R* __restrict__ win, const R2* __restrict__ tw, int N, int hop, int log2m, R sqrt_n,
+    int tw_lds) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_lo[kMaxTracks], s_hi[kMaxTracks];
+    const int M = N >> 1;
+    const int tid = threadIdx.x;
+    const int j = blockIdx.y;
+    FeedWindow w = {0, 0, blockIdx.x, 0, true};
+    R* orow;
+    if (FEED) {
+        w = feed_window(windows, tc, n_files);
+        orow = j == 0 ? out0 + (w.b * tc + w.tt) * ld : out1 + (((w.b * S + j - 1) * tc) + w.tt) * ld;
+    }
+    const int64_t t = w.t;
+    const int64_t* row = files + (w.live ? w.fi : 0) * (kFileHead + 2 * S);
+    const int64_t size = w.live ? row[0] : 0;
+    const int64_t T = w.live ? row[1] : 0;
+    if (!FEED) orow = out0 + ((int64_t)j * T + t) * ld;
+    if (!w.live || t >= T) return zero_row(orow, ld);
+    const int64_t base = t * (int64_t)hop - M;   // index of padded sample t * hop in the rendered signal
+    if (tid < S) frame_candidates(notes, n_notes, row, tid, base, N, size, &s_lo[tid], &s_hi[tid]);
+    const R2* Z = render_frame<R, R2, true>(smem, win, tw, tw_lds, M, log2m, base, [&](int64_t q) {
+        return score_sample<R>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q);
+    });
+    packed_real_mag_row<R, R2, FEED>(Z, tw, M, ld, sqrt_n, scale, orow);
+}
+
+// ---- the score-informed feed: the windows of stft_score_render_kernel<float, float2, true> with train::gather_score_kernel's
+// harmonic masks (train_core.hip) applied to the mixture row while it is still in registers.
+
 // blockIdx.x = b * tc + t of window b = (file, first frame); blockIdx.y = j: 0 the mixture, 1 + s track s.
 // j > 0: targets [B][S][tc][F] row (b, j - 1, t) = scale * mag(track), as the render feed writes it.
 // j = 0: the workgroup marks, one bit per instrument, the bins of the mask notes that sound in frame fr = first frame + t
@@ -220,6 +153,8 @@ __global__ __launch_bounds__(kThreads) void stft_score_informed_kernel(
     const int F = M + 1;
     const int tid = threadIdx.x;
     const int j = blockIdx.y;
+    // own window decode and zero rows, not feed_window / zero_row: with those the compiler moves this kernel's row addresses
+    // into its tails and a batch took 0.9 % longer; the rule is feed_window's
     const int rs = kFileHead + 2 * S;
     const int64_t b = blockIdx.x / tc;
     const int tt = (int)(blockIdx.x - b * tc);
@@ -243,28 +178,16 @@ __global__ __launch_bounds__(kThreads) void stft_score_informed_kernel(
     }
     const int64_t base = t * (int64_t)hop - M;   // index of padded sample t * hop in the rendered signal
     if (tid < S) frame_candidates(notes, n_notes, row, tid, base, N, size, &s_lo[tid], &s_hi[tid]);
-    float2* buf0 = reinterpret_cast<float2*>(smem);
-    float2* buf1 = buf0 + M;
-    if (tw_lds) {
-        float2* twl = buf1 + M;
-        for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
-        tw = twl;
-    }
-    __syncthreads();
-    for (int m = tid; m < M; m += kThreads) {
-        const int64_t q = base + 2 * m;
-        const float x0 = score_sample<float>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q) * win[2 * m];
-        const float x1 = score_sample<float>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q + 1) * win[2 * m + 1];
-        buf0[m] = mk<float2, float>(x0, x1);
-    }
-    __syncthreads();
-    const float2* Z = fft_lds<float, float2, -1>(buf0, buf1, tw, M, log2m);
+    const float2* Z = render_frame<float, float2, true>(smem, win, tw, tw_lds, M, log2m, base, [&](int64_t q) {
+        return score_sample<float>(bank, bank_len, notes, s_lo, s_hi, size, S, j, q);
+    });
     if (j > 0) {
         packed_real_mag_row<float, float2, true>(Z, tw, M, F, sqrt_n, scale, trow);
         return;
     }
     // fft_lds ended with a barrier: the other buffer (8 M bytes) is free and takes the F bin flags
-    unsigned* on = reinterpret_cast<unsigned*>(Z == buf0 ? buf1 : buf0);
+    float2* buf0 = reinterpret_cast<float2*>(smem);
+    unsigned* on = reinterpret_cast<unsigned*>(Z == buf0 ? buf0 + M : buf0);
     for (int k = tid; k < F; k += kThreads) on[k] = 0u;
     const int pw = 2 + 2 * npairs;
     int64_t moff = mask_files[2 * fi], P = mask_files[2 * fi + 1];
@@ -346,24 +269,10 @@ int score_render_file(dcs_stft* p, const R* win, const R2* tw, const R* bank_d, 
         DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: out_rows %lld < %lld", (long long)out_rows, (long long)((1 + S) * T));
     if (T > 0x7fffffffLL) DCS_FAIL(DCS_EINVAL, "dcs_stft_forward_score_render: %lld frames in one launch", (long long)T);
     DCS_ON_DEVICE(p->ctx->device);
-    void* tab_d = nullptr;
-    DCS_HIP(dcs_dev_alloc(&tab_d, tab.size() * sizeof(int64_t), "stft.score_render_table"));
-    int rc = DCS_OK;
-    if (hipMemcpy(tab_d, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
-        dcs_set_error("dcs_stft_forward_score_render: uploading the note table failed");
-        rc = DCS_EHIP;
-    }
-    const int64_t* notes_d = (const int64_t*)tab_d;
-    if (rc == DCS_OK)
-        rc = launch_score_render<R, R2, false>(p, win, tw, bank_d, bank_len, notes_d, (int)n, notes_d + (size_t)n * 4, 1, S,
-                                               nullptr, 1, R(1), out_d, nullptr, ld, T);
-    // the table is this call's own: wait for the launch, then give it back
-    if (hipStreamSynchronize(p->ctx->stream) != hipSuccess && rc == DCS_OK) {
-        dcs_set_error("dcs_stft_forward_score_render: the launch failed");
-        rc = DCS_EHIP;
-    }
-    dcs_dev_free(tab_d);
-    return rc;
+    return with_own_table(p, tab, "stft.score_render_table", "dcs_stft_forward_score_render", "note", [&](const int64_t* notes_d) {
+        return launch_frames(p, stft_score_render_kernel<R, R2, false>, T, S, win, tw, bank_d, bank_len, notes_d, (int)n,
+                             notes_d + (size_t)n * 4, 1, S, (const int*)nullptr, 1, R(1), out_d, (R*)nullptr, ld);
+    });
 }
 
 }  // namespace
@@ -428,9 +337,9 @@ DCS_API int dcs_trainer_gather_score_render(dcs_ctx* ctx, dcs_stft* p, const flo
     if ((int64_t)batch * time_context > 0x7fffffffLL)
         DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_render: %lld frames in one launch", (long long)batch * time_context);
     DCS_ON_DEVICE(ctx->device);
-    return launch_score_render<float, float2, true>(p, p->win_f, p->tw_f, bank_d, bank_len, notes_d, (int)n_notes, files_d,
-                                                    n_files, S, windows_d, time_context, scale, inputs_d, targets_d,
-                                                    p->frame / 2 + 1, (int64_t)batch * time_context);
+    return launch_frames(p, stft_score_render_kernel<float, float2, true>, (int64_t)batch * time_context, S, p->win_f, p->tw_f,
+                         bank_d, bank_len, notes_d, (int)n_notes, files_d, n_files, S, windows_d, time_context, scale, inputs_d,
+                         targets_d, (int64_t)(p->frame / 2 + 1));
 }
 
 DCS_API int dcs_trainer_gather_score_informed_render(dcs_ctx* ctx, dcs_stft* p, const float* bank_d, int64_t bank_len,
@@ -455,19 +364,7 @@ DCS_API int dcs_trainer_gather_score_informed_render(dcs_ctx* ctx, dcs_stft* p, 
         DCS_FAIL(DCS_EINVAL, "dcs_trainer_gather_score_informed_render: %lld frames in one launch",
                  (long long)batch * time_context);
     DCS_ON_DEVICE(ctx->device);
-    const int M = p->frame / 2;
-    size_t lds = (3 * (size_t)M + 1) * sizeof(float2);
-    const int tw_lds = lds <= 64 * 1024;
-    if (!tw_lds) lds = 2 * (size_t)M * sizeof(float2);
-    auto kern = stft_score_informed_kernel;
-    if (lds > 48 * 1024)
-        DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DcsTimer tm(ctx, DCS_TAG_STFT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)batch * time_context), (unsigned)(1 + S)), dim3(kThreads), lds, ctx->stream,
-                       bank_d, bank_len, notes_d, (int)n_notes, files_d, n_files, S, masks_d, mask_len, mask_files_d, npairs,
-                       windows_d, time_context, scale, inputs_d, targets_d, p->win_f, p->tw_f, p->frame, p->hop, p->log2m,
-                       (float)sqrt((double)p->frame), tw_lds);
-    tm.done();
-    DCS_HIP(hipGetLastError());
-    return DCS_OK;
+    return launch_frames(p, stft_score_informed_kernel, (int64_t)batch * time_context, S, p->win_f, p->tw_f, bank_d, bank_len,
+                         notes_d, (int)n_notes, files_d, n_files, S, masks_d, mask_len, mask_files_d, npairs, windows_d,
+                         time_context, scale, inputs_d, targets_d);
 }

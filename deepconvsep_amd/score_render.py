@@ -31,9 +31,10 @@ from ctypes import POINTER, c_int64
 import numpy as np
 
 from . import _lib
-from .augment import Track, VirtualFile, shift_samples
+from .augment import Track, VirtualFile, render_blocks, shift_samples
 from .score import _score_path, _select, read_score, str2midi
-from .training import WindowFeed
+from .runtime import _ptr
+from .training import RenderedFeed, WindowFeed  # noqa: F401  (importable from here as before)
 
 SOURCES = ('bassoon', 'clarinet', 'saxophone', 'violin')      # the score files <source>_g<style>.txt, in track order
 INSTRUMENT_IDS = (30, 31, 27, 15)                             # their RWC instrument numbers (:215)
@@ -343,33 +344,20 @@ def render_score_features(tt, bank, sf, out_dir=None):
     ``tt.precision``): ``[1 + S, T, F]`` float64, or with ``out_dir`` the files ``<out_dir>/<name>__m_.data`` / ``.shape``
     through ``tt.saveTensor`` -- what ``tt.compute_transform(audio, path, phase=False)`` writes for the host-rendered
     audio -- and the path of the ``.data`` file.  ``tt``: a ``transformFFT``; ``bank``: a ``NoteBank``."""
-    import torch
-    from .runtime import _ptr
-    plan = tt._get_plan()
-    ctx = plan.ctx
-    f64 = tt.precision == 'float64'
-    bank_t = bank.device(np.float64 if f64 else np.float32, ctx)
+    bank_t = bank.device(np.float64 if tt.precision == 'float64' else np.float32, tt._get_plan().ctx)
     S = len(sf.tracks)
     counts = np.asarray([len(t) for t in sf.tracks], dtype=np.int64)
     notes = np.asarray([n for t in sf.tracks for n in t], dtype=np.int64).reshape(-1, 3)
-    T = _lib.frame_count(sf.size, plan.hop)
+    T = _lib.frame_count(sf.size, tt.hopSize)
     got = c_int64(0)
-    with ctx.stream_scope():
-        out = torch.empty(((1 + S) * T, plan.bins), dtype=bank_t.dtype, device=ctx.device)
-        fn = ctx._lib.dcs_stft_forward_score_render_f64 if f64 else ctx._lib.dcs_stft_forward_score_render_f32
-        _lib.check(fn(plan._h, _ptr(bank_t), bank.length, S, notes.ctypes.data, counts.ctypes.data, int(sf.size), _ptr(out),
-                      plan.bins, (1 + S) * T, POINTER(c_int64)(got)))
-        block = out.double().cpu().numpy().reshape(1 + S, T, plan.bins)
+    out = render_blocks(tt, 'dcs_stft_forward_score_render', S, [T], [sf.name], out_dir, lambda fn, plan, out, rows: fn(
+        plan._h, _ptr(bank_t), bank.length, S, notes.ctypes.data, counts.ctypes.data, int(sf.size), _ptr(out), plan.bins, rows,
+        POINTER(c_int64)(got)))
     assert got.value == T
-    if out_dir is None:
-        return block
-    os.makedirs(out_dir, exist_ok=True)
-    tt.out_path = os.path.join(out_dir, sf.name + '.data')
-    tt.saveTensor(np.ascontiguousarray(block), '_' + tt.suffix + '_m_')
-    return tt.out_path.replace('.data', '_' + tt.suffix + '_m_.data')
+    return out[0]
 
 
-class ScoreRenderedWindows(WindowFeed):
+class ScoreRenderedWindows(RenderedFeed):
     """``FeatureWindows`` without feature files: the training windows of the virtual files ``sfiles`` are assembled and
     transformed per batch from the note bank (uploaded once as float32, with the note and file tables) by
     ``dcs_trainer_gather_score_render``.
@@ -380,20 +368,12 @@ class ScoreRenderedWindows(WindowFeed):
 
     def __init__(self, bank, sfiles, time_context=30, overlap=25, mult_factor=0.3, windows='reference', batch_size=32, seed=0,
                  ctx=None, frameSize=4096, hopSize=512, window=None):
-        WindowFeed.__init__(self, windows, time_context, overlap, batch_size, seed, ctx)
-        self.mult = float(mult_factor)
-        self.frame, self.hop, self._window = int(frameSize), int(hopSize), window
         self.sfiles = list(sfiles)
-        counts = set(len(sf.tracks) for sf in self.sfiles)
-        if len(counts) != 1:
-            raise ValueError("virtual files disagree on the number of tracks: %r" % sorted(counts))
-        self.sources = counts.pop()
-        if not 1 <= self.sources <= 8:
-            raise ValueError("1 .. 8 tracks per virtual file, got %d" % self.sources)
+        RenderedFeed.__init__(self, self.sfiles, mult_factor, frameSize, hopSize, window, windows, time_context, overlap,
+                              batch_size, seed, ctx)
         self.bank = bank
         self.notes, self.rows = pack_tables(self.sfiles, bank.length, self.hop)
         self.names = [sf.name for sf in self.sfiles]
-        self.F = self.frame // 2 + 1
         self._set_table(r[1] for r in self.rows)
         self._bank_d = None
 
@@ -401,12 +381,8 @@ class ScoreRenderedWindows(WindowFeed):
         if self._bank_d is not None:
             return
         import torch
-        from .runtime import StftPlan
-        from .separation import blackmanharris
         self._open()
         self._bank_d = self.bank.device(np.float32, self.ctx)
-        win = self._window if self._window is not None else blackmanharris
-        self._plan = StftPlan(self.ctx, self.frame, self.hop, win(self.frame) if callable(win) else win)
         with self.ctx.stream_scope():
             self._notes_d = torch.from_numpy(self.notes if len(self.notes) else np.zeros((1, 4), np.int64)).to(self.ctx.device)
             self._rows_d = torch.from_numpy(self.rows).to(self.ctx.device)
@@ -414,7 +390,6 @@ class ScoreRenderedWindows(WindowFeed):
     def gather(self, rows):
         """Inputs ``[B, 1, tc, F]`` and targets ``[B, sources, tc, F]`` (device tensors) of the window-table rows ``rows``."""
         self._upload()
-        from .runtime import _ptr
         with self.ctx.stream_scope():
             win_d, B, x, t = self._batch(rows, 1, self.sources)
             _lib.check(self.ctx._lib.dcs_trainer_gather_score_render(
@@ -485,7 +460,6 @@ class ScoreInformedRenderedWindows(ScoreRenderedWindows):
         """Inputs ``[B, S, tc, F]`` = mask_j * (mult_factor * mixture) and targets ``[B, S, tc, F]`` (device tensors) of the
         window-table rows ``rows``."""
         self._upload()
-        from .runtime import _ptr
         with self.ctx.stream_scope():
             win_d, B, x, t = self._batch(rows, self.sources, self.sources)
             _lib.check(self.ctx._lib.dcs_trainer_gather_score_informed_render(
@@ -501,22 +475,28 @@ def load_bank(rwc_path, instrument_ids=INSTRUMENT_IDS, styles=STYLES, cases=CASE
     return NoteBank.from_instruments([Instrument(rwc_path, i, list(styles), list(cases), list(dynamics)) for i in instrument_ids])
 
 
-def dataset_files(db, bank, chunk_size=45, sample_size=400, original=True, seed=0, sr=44100, hop=512):
-    """The virtual files of a Bach10 Sibelius tree ``db`` (``<piece>/<source>_g<style>.txt``) as the generator's main
-    program makes them (:202-231): ``--original`` 1: the original scores, time shifts 0, 0.1, 0.2; 0: the ground-truth
-    aligned scores, no shifts, at most 50 combinations.  Every piece draws its combinations from ``seed`` + its position.
-    Returns ``[(piece, style name, its ScoreFiles)]``."""
+def _dataset_opening(db, original, sample_size, seed, pieces=None):
+    """What the two generators' main programs open with: ``(style name, style_midi, [(piece, its combinations)])``.
+    ``--original`` 1: the original scores, time shifts 0, 0.1, 0.2; 0: the ground-truth aligned scores, no shifts, at most 50
+    combinations.  Every piece (a directory of ``db`` that begins with a digit) draws its combinations from ``seed`` + its
+    position."""
     if original:
         style, style_midi, time_shifts = 'original', '_original', (0., 0.1, 0.2)
     else:
         style, style_midi, time_shifts = 'gt', '', (0.,)
         sample_size = min(50, sample_size)
-    out = []
-    pieces = [f for f in sorted(os.listdir(db)) if os.path.isdir(os.path.join(db, f)) and f[0].isdigit()]
-    for k, f in enumerate(pieces):
-        combos = rwc_combinations(time_shifts, len(DYNAMICS), len(STYLES), CASES, len(SOURCES), sample_size, seed + k)
-        out.append((f, style, score_files(os.path.join(db, f), f, bank, combos, chunk_size, sr, hop, style_midi)))
-    return out
+    if pieces is None:
+        pieces = [f for f in sorted(os.listdir(db)) if os.path.isdir(os.path.join(db, f)) and f[0].isdigit()]
+    return style, style_midi, [(f, rwc_combinations(time_shifts, len(DYNAMICS), len(STYLES), CASES, len(SOURCES), sample_size,
+                                                    seed + k)) for k, f in enumerate(pieces)]
+
+
+def dataset_files(db, bank, chunk_size=45, sample_size=400, original=True, seed=0, sr=44100, hop=512):
+    """The virtual files of a Bach10 Sibelius tree ``db`` (``<piece>/<source>_g<style>.txt``) as the generator's main
+    program makes them (:202-231; ``original`` and ``sample_size``: :func:`_dataset_opening`).  Returns ``[(piece, style
+    name, its ScoreFiles)]``."""
+    style, style_midi, pieces = _dataset_opening(db, original, sample_size, seed)
+    return [(f, style, score_files(os.path.join(db, f), f, bank, combos, chunk_size, sr, hop, style_midi)) for f, combos in pieces]
 
 
 def si_dataset_files(db, bank, chunk_size=45., sample_size=400, original=True, seed=0, sr=44100, hop=512, frame=4096,
@@ -526,15 +506,6 @@ def si_dataset_files(db, bank, chunk_size=45., sample_size=400, original=True, s
     :func:`dataset_files`, the combinations of :func:`rwc_combinations` (one rule for both generators) drawn per piece from
     ``seed`` + its position, the files of :func:`score_informed_files`.  Returns ``[(piece, style name, its files)]``; the
     reference writes them below ``<feature_path>/<piece>/<style name>/``."""
-    if original:
-        style, style_midi, time_shifts = 'original', '_original', (0., 0.1, 0.2)
-    else:
-        style, style_midi, time_shifts = 'gt', '', (0.,)
-        sample_size = min(50, sample_size)
-    out = []
-    if pieces is None:
-        pieces = [f for f in sorted(os.listdir(db)) if os.path.isdir(os.path.join(db, f)) and f[0].isdigit()]
-    for k, f in enumerate(pieces):
-        combos = rwc_combinations(time_shifts, len(DYNAMICS), len(STYLES), CASES, len(SOURCES), sample_size, seed + k)
-        out.append((f, style, score_informed_files(os.path.join(db, f), bank, combos, chunk_size, sr, hop, frame, style_midi)))
-    return out
+    style, style_midi, pieces = _dataset_opening(db, original, sample_size, seed, pieces)
+    return [(f, style, score_informed_files(os.path.join(db, f), bank, combos, chunk_size, sr, hop, frame, style_midi))
+            for f, combos in pieces]

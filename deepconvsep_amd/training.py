@@ -9,7 +9,8 @@ loss components) as HIP kernels.  ``Trainer`` describes the three mono graphs to
 for Bach10: csrc/train_dsd.hip, a description of the full-width graph csrc/train_dsd_graph.hip, and csrc/train_ikala.hip and
 csrc/train_bach10.hip, descriptions of the shared build_ca graph csrc/train_ca.hip); ``stereo_training.StereoTrainer`` and
 ``score_training.ScoreTrainer`` describe theirs.
-``WindowFeed`` is what the window feeds share: the slot table, the seeded epoch order and the lazily opened context.
+``WindowFeed`` is what the window feeds share: the slot table, the seeded epoch order and the lazily opened context;
+``RenderedFeed`` adds what the feeds of augment and score_render share, which transform their windows per batch.
 ``FeatureWindows`` keeps the ``.data`` / ``.shape`` feature files resident on the device and cuts the reference's windows
 from them; the feeds of stereo_training, score_training, augment and score_render derive from the same base.
 :func:`glorot_arrays` is Lasagne's initialisation for any of the layouts.  There is no CPU fallback.
@@ -22,8 +23,8 @@ import numpy as np
 
 from . import _lib
 from .arch import ARCHS
-from .runtime import _on_ctx_stream, _ptr, default_context, require_gpu
-from .separation import save_model as _save_model
+from .runtime import StftPlan, _on_ctx_stream, _ptr, default_context, require_gpu
+from .separation import blackmanharris, save_model as _save_model
 from .transform import read_shape_file
 
 # trainCNN.py:167-170 and lasagne.updates.adadelta's defaults
@@ -343,6 +344,29 @@ class WindowFeed(object):
         perm = np.random.RandomState(self.seed + epoch).permutation(self.total)
         for b in range(self.iteration_size):
             yield self.gather(perm[b * self.batch_size:(b + 1) * self.batch_size])
+
+
+class RenderedFeed(WindowFeed):
+    """What the feeds share that render and transform their windows per batch (``augment.RenderedWindows``,
+    ``score_render.ScoreRenderedWindows``): the scale, the track count ``sources`` of the virtual files ``files``, ``F``, and
+    the ``StftPlan``, made with the context (``window``: an array or a function of the frame size, default blackmanharris)."""
+
+    def __init__(self, files, mult_factor, frameSize, hopSize, window, *feed):
+        WindowFeed.__init__(self, *feed)
+        self.mult = float(mult_factor)
+        self.frame, self.hop, self._window = int(frameSize), int(hopSize), window
+        counts = set(len(f.tracks) for f in files)
+        if len(counts) != 1:
+            raise ValueError("virtual files disagree on the number of tracks: %r" % sorted(counts))
+        self.sources = counts.pop()
+        if not 1 <= self.sources <= 8:
+            raise ValueError("1 .. 8 tracks per virtual file, got %d" % self.sources)
+        self.F = self.frame // 2 + 1
+
+    def _open(self):
+        WindowFeed._open(self)
+        win = self._window if self._window is not None else blackmanharris
+        self._plan = StftPlan(self.ctx, self.frame, self.hop, win(self.frame) if callable(win) else win)
 
 
 class FeatureWindows(WindowFeed):

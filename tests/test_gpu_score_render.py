@@ -247,9 +247,11 @@ def _feed_case(ctx, blocks64, frame, hop, tc, batch, scale, guard=0):
     return T, win, (x, t), (xr, tr)
 
 
-@pytest.mark.parametrize("batch", [1, 32])
-@pytest.mark.parametrize("scale", [1.0, 0.3])
-@pytest.mark.parametrize("frame,hop,tc", [(1024, 512, 4), (256, 64, 8)])
+# every (frame, hop, tc) x scale x batch of the first two shapes, and the frame of 4096 once: above 48 KiB of LDS the launch
+# raises the kernel's dynamic shared-memory limit first
+@pytest.mark.parametrize("frame,hop,tc,scale,batch",
+                         [(f, h, tc, s, b) for f, h, tc in [(1024, 512, 4), (256, 64, 8)] for s in [1.0, 0.3] for b in [1, 32]]
+                         + [(4096, 512, 3, 0.3, 2)])
 def test_gather_score_render_against_gather_on_the_float64_blocks(ctx, blocks64, frame, hop, tc, scale, batch):
     T, win, (x, t), (xr, tr) = _feed_case(ctx, blocks64, frame, hop, tc, batch, scale)
     ex, et = float(np.max(np.abs(x - xr))), float(np.max(np.abs(t - tr)))
