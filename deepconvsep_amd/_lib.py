@@ -135,6 +135,10 @@ def load():
     proto("dcs_trainer_set_rand", i32, vp, vp)
     proto("dcs_trainer_out_count", i32, vp, POINTER(i32))
     proto("dcs_trainer_rectify_codes", i32, vp, POINTER(vp), i32)
+    proto("dcs_trainer_set", i32, vp, i32, POINTER(vp), i32)
+    proto("dcs_trainer_set_optimizer", i32, vp, i32, POINTER(c_double))
+    proto("dcs_trainer_get_optimizer", i32, vp, POINTER(i32), POINTER(c_double), POINTER(i64))
+    proto("dcs_trainer_set_steps", i32, vp, i64)
     _lib = lib
     return lib
 

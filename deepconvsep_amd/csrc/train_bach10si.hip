@@ -77,6 +77,8 @@ struct SiTrainer : CaTrainer {
         DCS_CHECK(CaTrainer::layout(flat_d, live, to_internal));
         if (!full) return DCS_OK;
         const int which = (int)((flat_d - state) / (4 * P4));
+        // dcs_trainer_set on an optimiser slot: `dead` holds parameters, not accumulators, and stays as it is
+        if (to_internal && which != 0) return DCS_OK;
         const int64_t wsz = kHidden * flat;
         int64_t at = 0;
         for (int i = 10; i <= 16; ++i) {

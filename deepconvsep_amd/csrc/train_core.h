@@ -232,8 +232,12 @@ struct dcs_trainer {
     int64_t RF = 0, P = 0, P4 = 0;
     int64_t shapes[train::kMaxParams][4] = {{0}};   // .pkl shapes
     double hyp[7] = {0};
+    int opt_kind = 0;            // the update of mode 2: 0 Adadelta (lr, rho, epsilon), 1 Adam (lr, beta1, beta2, epsilon)
+    double opt[4] = {0};         // its hyper-parameters; at create hyp[4 .. 6]
+    int64_t steps = 0;           // updates since the optimiser was set (Adam's t - 1), host side
     int64_t off[train::kMaxParams + 1] = {0};
-    float* state = nullptr;      // [4][4 P4]: params, grads, accu, delta_accu; sections padded to four floats, pad zero
+    float* state = nullptr;      // [4][4 P4]: params, grads, accu, delta_accu (Adam: m, v); sections padded to four floats,
+                                 // pad zero
     float* work = nullptr;
     double* lpart = nullptr;     // [kLossBlocks][loss_sums]
     double* out7 = nullptr;      // when the caller passes none
@@ -246,6 +250,8 @@ struct dcs_trainer {
     virtual int forward(const float* x) = 0;
     virtual int loss(const float* x, const float* tgt, double* out7) = 0;
     virtual int backward() = 0;
+    // flat: one of the four slots of state.  A graph that holds parameters outside the state reads and writes them for slot 0
+    // alone: for the other slots they are zeros on the way out and ignored on the way in.
     virtual int layout(float* flat, float* const* pkl, int to_internal) = 0;
     // dcs_trainer_rectify_codes: the graphs that keep their rectifier codes copy them out
     virtual int codes(float* const* out_d, int n);

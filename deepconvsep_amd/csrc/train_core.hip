@@ -1,7 +1,9 @@
-// The training core (train_core.h): the f32-MFMA GEMM template and its split-K helpers, Adadelta, rectify, the window
-// gather, and the dcs_trainer_* entry points.  One step on the ctx stream is forward, loss, backward (the graph's) and the
-// Adadelta update, with no host synchronisation and no float atomics: two runs give bit-identical weights.
+// The training core (train_core.h): the f32-MFMA GEMM template and its split-K helpers, Adadelta and Adam, rectify, the
+// window gather, and the dcs_trainer_* entry points.  One step on the ctx stream is forward, loss, backward (the graph's) and
+// the selected update, with no host synchronisation and no float atomics: two runs give bit-identical weights.
 #include "train_core.h"
+
+#include <cmath>
 
 using namespace train;
 
@@ -244,6 +246,32 @@ __global__ __launch_bounds__(kThreads) void adadelta_kernel(float4* __restrict__
     state[i] = p;
     state[2 * P4 + i] = acc;
     state[3 * P4 + i] = del;
+}
+
+// lasagne.updates.adam (lasagne/updates.py adam): m' = beta1 m + (1 - beta1) g, v' = beta2 v + (1 - beta2) g^2,
+// p -= a_t m' / (sqrt(v') + eps) with a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) from the host (eps is outside the bias
+// correction).  m sits in adadelta_kernel's accu slot and v in its delta_accu slot; omb1 = 1 - beta1 and omb2 = 1 - beta2
+// come rounded from double (1.f - 0.999f is 1.3e-5 off 0.001).  g = m = v = 0 gives a step of exactly 0.
+__global__ __launch_bounds__(kThreads) void adam_kernel(float4* __restrict__ state, int64_t P4, float a_t, float beta1,
+                                                        float omb1, float beta2, float omb2, float eps) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= P4) return;
+    const float4 g = state[P4 + i];
+    float4 p = state[i], m = state[2 * P4 + i], v = state[3 * P4 + i];
+    float* pp = &p.x;
+    float* pm = &m.x;
+    float* pv = &v.x;
+    const float* pg = &g.x;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const float gi = pg[l];
+        pm[l] = beta1 * pm[l] + omb1 * gi;
+        pv[l] = beta2 * pv[l] + omb2 * gi * gi;
+        pp[l] = pp[l] - a_t * pm[l] / (sqrtf(pv[l]) + eps);
+    }
+    state[i] = p;
+    state[2 * P4 + i] = m;
+    state[3 * P4 + i] = v;
 }
 
 __global__ __launch_bounds__(kThreads) void relu_kernel(const float* __restrict__ q, float* __restrict__ p, int64_t n) {
@@ -500,6 +528,7 @@ DCS_API int dcs_trainer_create(dcs_ctx* ctx, int arch, int time_context, int F, 
     t->tc = time_context; t->F = F; t->B = batch;
     t->RF = (int64_t)batch * time_context * F;
     memcpy(t->hyp, hyper_h, sizeof(t->hyp));
+    for (int i = 0; i < 3; ++i) t->opt[i] = hyper_h[4 + i];   // the initial optimiser: Adadelta
     if (t->nstate == 0) {
         t->nstate = nparams;
         for (int i = 0; i < nparams; ++i)
@@ -562,9 +591,62 @@ DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float*
     if (mode == 0) return DCS_OK;
     DCS_CHECK(t->backward());
     if (mode == 1) return DCS_OK;
-    hipLaunchKernelGGL(adadelta_kernel, dim3((unsigned)dcs_cdiv(t->P4, kThreads)), dim3(kThreads), 0, t->ctx->stream,
-                       (float4*)t->state, t->P4, (float)t->hyp[4], (float)t->hyp[5], (float)t->hyp[6]);
+    const dim3 grid((unsigned)dcs_cdiv(t->P4, kThreads));
+    const double* o = t->opt;
+    if (t->opt_kind == DCS_OPT_ADAM) {
+        // lasagne/updates.py adam: t = t_prev + 1 and a_t, in double on the host (the count never leaves it)
+        const double n = (double)(t->steps + 1);
+        const double a_t = o[0] * sqrt(1.0 - pow(o[2], n)) / (1.0 - pow(o[1], n));
+        hipLaunchKernelGGL(adam_kernel, grid, dim3(kThreads), 0, t->ctx->stream, (float4*)t->state, t->P4, (float)a_t,
+                           (float)o[1], (float)(1.0 - o[1]), (float)o[2], (float)(1.0 - o[2]), (float)o[3]);
+    } else {
+        hipLaunchKernelGGL(adadelta_kernel, grid, dim3(kThreads), 0, t->ctx->stream, (float4*)t->state, t->P4, (float)o[0],
+                           (float)o[1], (float)o[2]);
+    }
     DCS_HIP(hipGetLastError());
+    ++t->steps;
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_set_optimizer(dcs_trainer* t, int kind, const double* hyper_h) {
+    if (!t || !hyper_h) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: null argument");
+    if (kind != DCS_OPT_ADADELTA && kind != DCS_OPT_ADAM)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: kind %d (%d adadelta, %d adam)", kind, DCS_OPT_ADADELTA, DCS_OPT_ADAM);
+    const double* h = hyper_h;
+    auto unit = [](double v) { return v >= 0.0 && v < 1.0; };   // false for a NaN
+    if (!std::isfinite(h[0]) || h[0] < 0.0)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: learning rate %g (finite, not negative)", h[0]);
+    if (kind == DCS_OPT_ADADELTA) {
+        if (!unit(h[1])) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: adadelta rho %g (in [0, 1))", h[1]);
+        if (!(h[2] > 0.0) || !std::isfinite(h[2]))
+            DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: adadelta epsilon %g (finite, above 0)", h[2]);
+    } else {
+        if (!unit(h[1]) || !unit(h[2]))
+            DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: adam beta1 %g, beta2 %g (each in [0, 1))", h[1], h[2]);
+        if (!(h[3] > 0.0) || !std::isfinite(h[3]))
+            DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_optimizer: adam epsilon %g (finite, above 0)", h[3]);
+    }
+    DCS_ON_DEVICE(t->ctx->device);
+    // the two accumulator slots are adjacent
+    DCS_HIP(hipMemsetAsync(t->state + 8 * t->P4, 0, 8 * t->P4 * sizeof(float), t->ctx->stream));
+    t->opt_kind = kind;
+    for (int i = 0; i < 4; ++i) t->opt[i] = (kind == DCS_OPT_ADADELTA && i == 3) ? 0.0 : h[i];
+    t->steps = 0;
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_get_optimizer(dcs_trainer* t, int* kind, double* hyper_h, int64_t* steps) {
+    if (!t || !kind || !hyper_h || !steps) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get_optimizer: null argument");
+    *kind = t->opt_kind;
+    memcpy(hyper_h, t->opt, sizeof(t->opt));
+    *steps = t->steps;
+    return DCS_OK;
+}
+
+DCS_API int dcs_trainer_set_steps(dcs_trainer* t, int64_t steps) {
+    if (!t) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_steps: null argument");
+    if (steps < 0) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set_steps: %lld steps", (long long)steps);
+    t->steps = steps;
     return DCS_OK;
 }
 
@@ -600,6 +682,19 @@ DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int 
         if (!out_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_get: buffer %d is null", i);
     DCS_ON_DEVICE(t->ctx->device);
     return t->layout(t->state + which * 4 * t->P4, out_d, 0);
+}
+
+DCS_API int dcs_trainer_set(dcs_trainer* t, int which, const float* const* in_d, int nparams) {
+    if (!t || !in_d) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set: null argument");
+    if (which != 0 && which != 2 && which != 3)
+        DCS_FAIL(DCS_EINVAL, "dcs_trainer_set: which %d (0 params, 2 accu / m, 3 delta_accu / v; the gradients are not set)",
+                 which);
+    if (nparams != t->nparams)
+        DCS_FAIL(DCS_ESHAPE, "mismatch: got %d values to set %d parameters", nparams, t->nparams);
+    for (int i = 0; i < nparams; ++i)
+        if (!in_d[i]) DCS_FAIL(DCS_EINVAL, "dcs_trainer_set: buffer %d is null", i);
+    DCS_ON_DEVICE(t->ctx->device);
+    return t->layout(t->state + which * 4 * t->P4, (float* const*)in_d, 1);
 }
 
 DCS_API int dcs_trainer_rectify_codes(dcs_trainer* t, float* const* out_d, int n) {

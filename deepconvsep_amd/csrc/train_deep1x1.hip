@@ -333,6 +333,8 @@ struct Deep1x1Trainer : dcs_trainer {
         DCS_CHECK(run_layout(flat_d, pkl, to_internal, map));
         if (ndead == 0) return DCS_OK;
         const int which = (int)((flat_d - state) / (4 * P4));
+        // dcs_trainer_set on an optimiser slot: `dead` holds parameters, not accumulators, and stays as it is
+        if (to_internal && which != 0) return DCS_OK;
         int64_t at = 0;
         for (int i = 3 * kL; i < kNparams; ++i) {
             float* p = pkl[i] + state_size[i];

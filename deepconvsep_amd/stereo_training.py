@@ -72,7 +72,7 @@ class StereoTrainer(TrainerHandle):
 
     def step(self, inputs, targets, ild=False):
         """``train_fn_mse`` (:204), with ``ild`` ``train_fn_ILD`` (:268): the loss at the current parameters, then one
-        Adadelta update."""
+        step of the selected update (Adadelta unless ``set_optimizer`` chose another)."""
         return float(self.ctx.to_host(self.run(inputs, targets, 2, ild))[0])
 
     def losses(self, inputs, targets):

@@ -4,8 +4,10 @@
 trainCNNSibelius.py train too), and the data feed of ``dataset.LargeDataset`` (dataset.py:383-602).
 
 ``TrainerHandle`` is the one Python handle on ``dcs_trainer_*`` (the shared core csrc/train_core.hip): upload of the
-parameters and the baked-in draw, Adadelta's state, ``train_fn`` (forward, loss, gradients, Adadelta) and ``train_fn1`` (the
-loss components) as HIP kernels.  ``Trainer`` describes the three mono graphs to it (15 parameters for DSD, 13 for iKala, 17
+parameters and the baked-in draw, the optimiser's state, ``train_fn`` (forward, loss, gradients, and Adadelta or -- after
+``set_optimizer('adam')`` -- Adam) and ``train_fn1`` (the loss components) as HIP kernels; ``set_params``,
+``optimizer_state`` / ``load_optimizer_state`` and ``save_checkpoint`` / ``load_checkpoint`` rewrite and resume a live
+trainer.  ``Trainer`` describes the three mono graphs to it (15 parameters for DSD, 13 for iKala, 17
 for Bach10: csrc/train_dsd.hip, a description of the full-width graph csrc/train_dsd_graph.hip, and csrc/train_ikala.hip and
 csrc/train_bach10.hip, descriptions of the shared build_ca graph csrc/train_ca.hip); ``stereo_training.StereoTrainer`` and
 ``score_training.ScoreTrainer`` describe theirs.
@@ -17,6 +19,7 @@ from them; the feeds of stereo_training, score_training, augment and score_rende
 """
 import math
 import os
+import pickle
 from ctypes import byref, c_double, c_int, c_int64, c_void_p
 
 import numpy as np
@@ -30,6 +33,9 @@ from .transform import read_shape_file
 # trainCNN.py:167-170 and lasagne.updates.adadelta's defaults
 EPS, ALPHA, BETA, BETA_VOC = 1e-8, 0.001, 0.01, 0.03
 LEARNING_RATE, RHO, ADA_EPSILON = 1.0, 0.95, 1e-6
+# dcs_trainer_set_optimizer: kind -> (DCS_OPT_* code, the names of hyper_h, lasagne.updates' defaults)
+OPTIMIZERS = {'adadelta': (0, ('learning_rate', 'rho', 'epsilon'), (LEARNING_RATE, RHO, ADA_EPSILON)),
+              'adam': (1, ('learning_rate', 'beta1', 'beta2', 'epsilon'), (1e-3, 0.9, 0.999, 1e-8))}
 COMPONENTS = ("vocals", "bass", "drums", "negative", "alpha", "negative_voc")
 # examples/ikala/trainCNN.py:152-155; train_fn1's four components (:197)
 IKALA_EPS, IKALA_ALPHA, IKALA_BETA_ACC, IKALA_BETA_VOC = 1e-8, 0.9, 0.005, 0.02
@@ -84,7 +90,7 @@ def glorot_init(arch='dsd', tc=30, F=513, seed=0):
 
 class TrainerHandle(object):
     """One ``dcs_trainer`` handle: what ``Trainer``, ``stereo_training.StereoTrainer`` and ``score_training.ScoreTrainer``
-    share.  The parameters, Adadelta's state and the baked-in draw live on the device; the batch size is fixed, as in the
+    share.  The parameters, the optimiser's state and the baked-in draw live on the device; the batch size is fixed, as in the
     reference's compiled graph.
 
     A subclass describes its graph to ``__init__`` -- the arch name, input and output channels, the draw's shape and the
@@ -161,7 +167,8 @@ class TrainerHandle(object):
         return self._out
 
     def step(self, inputs, targets):
-        """``train_fn``: the loss at the current parameters, then one Adadelta update."""
+        """``train_fn``: the loss at the current parameters, then one step of the selected update (Adadelta unless
+        :meth:`set_optimizer` chose another)."""
         return float(self.ctx.to_host(self.run(inputs, targets, 2))[0])
 
     def loss_and_gradients(self, inputs, targets):
@@ -200,6 +207,91 @@ class TrainerHandle(object):
     def adadelta_state(self):
         """(accu, delta_accu) of lasagne.updates.adadelta, .pkl order."""
         return self._get(2), self._get(3)
+
+    @_on_ctx_stream
+    def _set(self, which, arrays):
+        """``dcs_trainer_set``: ``arrays`` in .pkl order with the trainer's shapes into the parameters (0) or one of the two
+        accumulators (2, 3), in stream order."""
+        arrays = [np.asarray(a, dtype=np.float32) for a in arrays]
+        if len(arrays) == len(self.shapes):    # a wrong count goes to the library, which words it; the shapes only Python knows
+            self._check_shapes(arrays)
+        dev = [self.ctx.to_device(a, np.float32) for a in arrays]
+        ptrs = (c_void_p * max(len(dev), 1))(*[d.data_ptr() for d in dev])
+        _lib.check(self.ctx._lib.dcs_trainer_set(self._h, int(which), ptrs, len(dev)))
+        self._set_keep = dev   # released after the copies have run (stream order)
+
+    def _check_shapes(self, arrays):
+        """``ValueError`` in the library's "mismatch: ..." wording unless ``arrays`` has the trainer's count and shapes."""
+        if len(arrays) != len(self.shapes):
+            raise ValueError("mismatch: got %d values to set %d parameters" % (len(arrays), len(self.shapes)))
+        for i, (a, want) in enumerate(zip(arrays, self.shapes)):
+            if tuple(np.shape(a)) != want:
+                raise ValueError("mismatch: parameter %d has shape %r but value to set has shape %r"
+                                 % (i, want, tuple(np.shape(a))))
+
+    def set_params(self, params):
+        """``lasagne.layers.set_all_param_values`` on the live trainer: the optimiser's state and step count stay."""
+        self._set(0, params)
+
+    def set_optimizer(self, kind='adadelta', **hyper):
+        """Select the update of :meth:`step`, as calling ``lasagne.updates.adadelta`` / ``lasagne.updates.adam`` again does:
+        fresh (zero) accumulators and step count.  ``hyper``: ``learning_rate``, ``rho``, ``epsilon`` for ``'adadelta'``
+        (Lasagne's 1, 0.95, 1e-6), ``learning_rate``, ``beta1``, ``beta2``, ``epsilon`` for ``'adam'`` (1e-3, 0.9, 0.999,
+        1e-8)."""
+        if kind not in OPTIMIZERS:
+            raise ValueError("optimizer %r: one of %r" % (kind, sorted(OPTIMIZERS)))
+        code, names, defaults = OPTIMIZERS[kind]
+        unknown = sorted(set(hyper) - set(names))
+        if unknown:
+            raise TypeError("set_optimizer(%r) takes %r, not %r" % (kind, names, unknown))
+        vals = [float(hyper.get(n, d)) for n, d in zip(names, defaults)]
+        self._set_optimizer(code, vals)
+
+    def _set_optimizer(self, code, vals):
+        vals = list(vals) + [0.0] * (4 - len(vals))
+        _lib.check(self.ctx._lib.dcs_trainer_set_optimizer(self._h, int(code), (c_double * 4)(*vals)))
+
+    def optimizer_state(self):
+        """The selected update and its state: ``kind``, ``hyper`` (a dict by name), ``steps`` (updates since it was selected;
+        Adam's t) and the two accumulators ``slots`` = (accu, delta_accu) or (m, v), each in .pkl order."""
+        kind, vals, steps = c_int(), (c_double * 4)(), c_int64()
+        _lib.check(self.ctx._lib.dcs_trainer_get_optimizer(self._h, byref(kind), vals, byref(steps)))
+        name = [k for k, v in OPTIMIZERS.items() if v[0] == kind.value][0]
+        return {'kind': name, 'hyper': dict(zip(OPTIMIZERS[name][1], list(vals))), 'steps': int(steps.value),
+                'slots': (self._get(2), self._get(3))}
+
+    def load_optimizer_state(self, d):
+        """Put back what :meth:`optimizer_state` returned (of a trainer with the same shapes): the update, its
+        hyper-parameters, both accumulators and the step count."""
+        slots = d['slots']
+        if len(slots) != 2:
+            raise ValueError("mismatch: an optimiser state holds two slots, got %d" % len(slots))
+        if int(d['steps']) < 0:
+            raise ValueError("load_optimizer_state: %d steps" % int(d['steps']))
+        for arrays in slots:      # before the optimiser is replaced
+            self._check_shapes(arrays)
+        self.set_optimizer(d['kind'], **d['hyper'])
+        self._set(2, slots[0])
+        self._set(3, slots[1])
+        _lib.check(self.ctx._lib.dcs_trainer_set_steps(self._h, int(d['steps'])))
+
+    def save_checkpoint(self, path):
+        """The parameters and :meth:`optimizer_state` in one protocol-2 pickle: what :meth:`load_checkpoint` resumes
+        from, bit for bit.  (:meth:`save_model` writes the parameter list alone, the reference's format.)"""
+        with open(path, 'wb') as f:
+            pickle.dump({'params': self.params(), 'optimizer': self.optimizer_state()}, f, protocol=2)
+
+    def load_checkpoint(self, path):
+        """Resume from :meth:`save_checkpoint`'s file; the shapes must be the trainer's (``ValueError`` "mismatch: ...")."""
+        with open(path, 'rb') as f:
+            d = pickle.load(f)
+        if not isinstance(d, dict) or 'params' not in d or 'optimizer' not in d:
+            raise ValueError("%s is not a trainer checkpoint (a parameter list goes to set_params)" % path)
+        # every shape is checked before anything is written
+        for arrays in (d['params'],) + tuple(d['optimizer']['slots']):
+            self._check_shapes(arrays)
+        self.set_params(d['params'])
+        self.load_optimizer_state(d['optimizer'])
 
     @_on_ctx_stream
     def forward(self, inputs):

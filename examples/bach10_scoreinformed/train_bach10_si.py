@@ -6,7 +6,8 @@ block, :196-416).
     python train_bach10_si.py --db <Bach10 Sources dir> --output <dir> [--feature_path P] [--model CNNrwc_se1]
                               [--batch_size 32] [--time_context 30] [--overlap 25] [--nepochs 40] [--scale_factor 0.3]
                               [--scale_factor_test 0.2] [--pitch_code e] [--branches 4|1] [--frame_size 4096] [--load]
-                              [--skip] [--skip_sep] [--seed 0] [--windows reference|all] [--function build_ca|build_ca_1x1]
+                              [--skip] [--skip_sep] [--second_pass] [--seed 0] [--windows reference|all]
+                              [--function build_ca|build_ca_1x1]
                               [--dbs <Bach10 Sibelius dir> --rwc <RWC dir> --render [--sample_size 400] [--chunk_size 45]
                                                                                     [--original 1] [--sample_rate 44100]]
 
@@ -29,6 +30,12 @@ written, --frame_size sets the transform and --pitch_code is e or g.
 --branches 1 trains the single-branch 11-array layout of trainCNNrwc_samp.py:195-235 (the same live computation and loss;
 the 17-array layout's other three branches are dead weight that no gradient reaches).
 
+--second_pass ports :346-354: after the --nepochs Adadelta epochs, if the last epoch's loss is above the best one the best
+model is loaded back into the live trainer (``set_params``), the optimiser becomes ``lasagne.updates.adam`` with its defaults
+(``set_optimizer('adam')``, csrc/train_core.hip's adam_kernel) and int(ceil(nepochs / 5)) more epochs run, printed as "Epoch k
+of n2", with the same save-on-improvement rule; the loss list and the best loss carry over, and epoch k of the second pass
+cuts the windows of ``batches(nepochs + k)``.  It is a property of the loop alone: every --function, --branches and feed takes it.
+
 --function build_ca_1x1 trains the deep graph of trainCNNrwc.py:66-132 (six strided convolutions, a 1x1 convolution and
 their InverseLayers; 22 arrays) with the same loss and feeds; as in the reference (:630-639) any other value means build_ca,
 and the 1x1 choice appends ``_x`` to the model name before the style suffix: model_<NAME>_x_gt.pkl.  It needs --time_context
@@ -37,12 +44,16 @@ and the 1x1 choice appends ``_x`` to the model name before the style suffix: mod
 Differences from the reference: the window order of an epoch is RandomState(seed + epoch).permutation (the reference's shuffle
 is unseeded); --scale_factor and --scale_factor_test are floats (the reference's int() of them is a bug); --load, --skip and
 --skip_sep are flags; --pitch_code, --branches, --windows and --frame_size are new (the reference's transform is fixed at 4096,
-2049 bins; --frame_size must match the features'); the second pass with Adam (:346-354) is not ported -- no trainer here
-ports it, and :351 as written raises a TypeError (set_all_param_values takes no learning_rate); the Sibelius loop of the
-reference is commented out there (:418-) and absent here; features are read from one flat directory rather than from
+2049 bins; --frame_size must match the features'); the second pass with Adam (:346-354) runs only with --second_pass, and
+its reload of the best model is the evident intent of :349-351, which as written raises in Lasagne (set_all_param_values
+reads ``learning_rate=0.0001`` as a parameter tag) -- so Adam runs at lasagne.updates.adam's own learning rate 1e-3, as :353
+builds it; with --nepochs 0 no second pass runs (the reference fails on ``losser[-1]``), and after the second pass the
+reference's loop would reach :349-351 once more, while here the separation uses the network as it stands; the Sibelius loop
+of the reference is commented out there (:418-) and absent here; features are read from one flat directory rather than from
 <feature_path>/<piece>/gt.
 """
 import argparse
+import math
 import os
 import pickle
 import sys
@@ -92,6 +103,12 @@ def model_name(model, function):
     return model + ('_x' if function == 'build_ca_1x1' else '') + '_gt'
 
 
+def second_pass_epochs(nepochs):
+    """trainCNNrwc.py:347: the second pass runs ``int(np.ceil(float(num_epochs) / 5.))`` epochs; none after no first pass
+    (the reference would fail on ``losser[-1]``, :349)."""
+    return int(math.ceil(nepochs / 5.)) if nepochs > 0 else 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--db", required=True, help="the Bach10 dataset path (its Sources directory)")
@@ -110,6 +127,7 @@ def main(argv=None):
     ap.add_argument("--load", action="store_true", help="resume from the saved model")
     ap.add_argument("--skip", action="store_true", help="skip training")
     ap.add_argument("--skip_sep", action="store_true")
+    ap.add_argument("--second_pass", action="store_true", help="then ceil(nepochs / 5) more epochs with Adam (:346-354)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--windows", choices=("reference", "all"), default="reference")
     ap.add_argument("--dbs", help="the Bach10 Sibelius dataset path (with --render)")
@@ -167,23 +185,34 @@ def main(argv=None):
         trainer = ScoreTrainer(params=params, branches=a.branches, batch_size=a.batch_size, time_context=a.time_context,
                                feat_size=data.F, seed=a.seed, function=function)
         losser = []
-        min_loss = 1e14                                                                            # :288
-        for epoch in range(a.nepochs):
-            start_time = time.time()
-            err = 0.0
-            comp = np.zeros(4)
-            for inputs, targets in data.batches(epoch):
-                err += trainer.step(inputs, targets)                 # train_fn (:325)
-                comp += np.asarray(trainer.losses(inputs, targets))  # train_fn1 (:326)
-            n = data.iteration_size
-            print("Epoch {} of {} took {:.3f}s".format(epoch + 1, a.nepochs, time.time() - start_time))
-            print("  training loss:\t\t{:.6f}".format(err / n))
-            for k, source in enumerate(COMPONENTS):
-                print("  training loss for {}:\t\t{:.6f}".format(source, comp[k] / n))
-            losser.append(err / n)
-            if err / n < min_loss:                                                                 # :342-344
-                min_loss = err / n
-                trainer.save_model(model)
+        min_loss = [1e14]                                                                          # :288
+
+        def run_epochs(count, first):
+            """``count`` epochs of :295-344; epoch k cuts the windows of ``data.batches(first + k)``."""
+            for epoch in range(count):
+                start_time = time.time()
+                err = 0.0
+                comp = np.zeros(4)
+                for inputs, targets in data.batches(first + epoch):
+                    err += trainer.step(inputs, targets)                 # train_fn (:325)
+                    comp += np.asarray(trainer.losses(inputs, targets))  # train_fn1 (:326)
+                n = data.iteration_size
+                print("Epoch {} of {} took {:.3f}s".format(epoch + 1, count, time.time() - start_time))
+                print("  training loss:\t\t{:.6f}".format(err / n))
+                for k, source in enumerate(COMPONENTS):
+                    print("  training loss for {}:\t\t{:.6f}".format(source, comp[k] / n))
+                losser.append(err / n)
+                if err / n < min_loss[0]:                                                          # :342-344
+                    min_loss[0] = err / n
+                    trainer.save_model(model)
+
+        run_epochs(a.nepochs, 0)
+        n2 = second_pass_epochs(a.nepochs) if a.second_pass else 0
+        if n2:                                                                                     # :346-354
+            if losser[-1] > min_loss[0]:
+                trainer.set_params(load_model(model))
+            trainer.set_optimizer('adam')
+            run_epochs(n2, a.nepochs)
         with open(os.path.join(output, 'models', "loss_" + name + ".data"), 'wb') as f:
             pickle.dump(losser, f, protocol=2)
         params = trainer.params()                                    # the separation uses the network as it stands (:357)

@@ -37,8 +37,9 @@ from deepconvsep_amd.separation import Separator, load_model, read_wav, write_wa
 from deepconvsep_amd.stereo_training import RAND_STD, SOURCES, StereoFeatureWindows, StereoTrainer  # noqa: E402
 
 
-def separate_all(params, db, outdir, scale_factor, tc, overlap, batch_size):
-    """trainCNN_ILD_DSD100.py:291-341 with the fused stereo separation path."""
+def separate_all(params, db, outdir, scale_factor, tc, overlap, batch_size, mix_type='mixture'):
+    """trainCNN_ILD_DSD100.py:291-341 with the fused stereo separation path; ``mix_type``: the file of each song that is
+    separated, <mix_type>.wav (trainCNN_ILD_DSD100_3stages.py:543-546 and :335: 'binaural' for the binaural mixtures)."""
     sep = Separator('dsd_ild', params, scale_factor, tc, overlap, batch_size, 513, 1024, 512, np.hanning)
     for sub in ('Dev', 'Test'):
         d = os.path.join(db, 'Mixtures', sub)
@@ -47,7 +48,7 @@ def separate_all(params, db, outdir, scale_factor, tc, overlap, batch_size):
         for song in sorted(os.listdir(d)):
             if song.startswith('.'):
                 continue
-            sampleRate, audio = read_wav(os.path.join(d, song, 'mixture.wav'))
+            sampleRate, audio = read_wav(os.path.join(d, song, mix_type + '.wav'))
             assert sampleRate == 44100, "Sample rate needs to be 44100"
             if audio.ndim == 1:
                 audio = np.repeat(audio[:, None], 2, axis=1)

@@ -83,6 +83,8 @@ enum { DCS_SCORE_NORM_MAX = 0, DCS_SCORE_NORM_SUM = 1 };
 enum { DCS_MIX_CH0 = 0, DCS_MIX_SUM = 1 };
 /* tiler: SCRIPT = separate_dsd.py:114-135 (drops the tail), LIBRARY = util.py:220-248 (zero pads) */
 enum { DCS_TILER_SCRIPT = 0, DCS_TILER_LIBRARY = 1 };
+/* the update of a trainer (dcs_trainer_set_optimizer): lasagne.updates.adadelta or lasagne.updates.adam */
+enum { DCS_OPT_ADADELTA = 0, DCS_OPT_ADAM = 1 };
 
 /* ------------------------------------------------------------------ library / context */
 DCS_API int dcs_version(void);
@@ -523,7 +525,7 @@ DCS_API int dcs_trainer_set_rand(dcs_trainer* t, const float* rand_d);
 /* One step on inputs_d [batch][1][tc][F] and targets_d [batch][4][tc][F] (iKala: [batch][2][tc][F], voice then
  * accompaniment; Bach10: bassoon, clarinet, saxophone, violin) (trainCNN.py:243-263), no host synchronisation: mode 0 = train_fn1 (:263): forward, loss and components;
  * 1 also the gradients of |E|, one per parameter (Theano conventions: rectify'(0) = 0.5, abs'(0) = 0); 2 = train_fn (:262):
- * also the adadelta update (:223).  out7_d (device, nullable): 7 doubles, all at the parameters BEFORE this step's update:
+ * also the update: adadelta (:223) unless dcs_trainer_set_optimizer selected another.  out7_d (device, nullable): 7 doubles, all at the parameters BEFORE this step's update:
  * DSD the loss |E| then vocals, bass, drums, negative, alpha, negative_voc (:217, :263); iKala the loss |E| with E =
  * vocals_error + acc_error - negative_error_voc, then vocals_error, acc_error, negative_error_voc, negative_error_acc
  * (ikala/trainCNN.py:189, :197), then two zeros; Bach10 the loss |error1 + error2 + error3 + error4|, then the four errors
@@ -535,8 +537,34 @@ DCS_API int dcs_trainer_step(dcs_trainer* t, const float* inputs_d, const float*
 DCS_API int dcs_trainer_forward(dcs_trainer* t, const float* inputs_d, float* p_d);
 /* Copy one section of the trainer's state into 15 (iKala 13, Bach10 17, score-informed 17 or 11, deep score-informed 22) caller buffers in .pkl layout: which 0 = parameters
  * (get_all_param_values, trainCNN.py:59-64), 1 = the gradients of the last mode 1 / 2 step, 2 = adadelta accu,
- * 3 = adadelta delta_accu. */
+ * 3 = adadelta delta_accu; under DCS_OPT_ADAM 2 = m, 3 = v. */
 DCS_API int dcs_trainer_get(dcs_trainer* t, int which, float* const* out_d, int nparams);
+/* The inverse of dcs_trainer_get, in stream order: lasagne.layers.set_all_param_values on the live network
+ * (examples/bach10_scoreinformed/trainCNNrwc.py:349-351 reloads the best model before its second pass;
+ * examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100_3stages.py:266-267 and :298-299 load a saved model between its stages) for
+ * which = 0, and the same for the two accumulators of the selected update, which = 2 (adadelta accu, adam m) and 3 (adadelta
+ * delta_accu, adam v).  in_d: nparams device arrays in .pkl order with the trainer's shapes, copied.  which = 1 (the
+ * gradients, rewritten by every step) or anything else is DCS_EINVAL; a wrong nparams is DCS_ESHAPE ("mismatch: ...").
+ * Nothing else changes: which = 0 keeps both accumulators and the step count.  Dead parameters (the score-informed graphs above)
+ * are taken from which = 0 alone; for which = 2 and 3 their arrays are ignored and stay zero. */
+DCS_API int dcs_trainer_set(dcs_trainer* t, int which, const float* const* in_d, int nparams);
+/* Select the update that dcs_trainer_step mode 2 applies, which is what calling lasagne.updates.adadelta / lasagne.updates.adam
+ * again does in the reference (trainCNNrwc.py:353 builds adam for the second pass; trainCNN_ILD_DSD100_3stages.py:269 rebuilds
+ * adadelta for the ILD stage): kind DCS_OPT_ADADELTA with hyper_h = (learning_rate, rho, epsilon, unused; lasagne's defaults
+ * 1, 0.95, 1e-6) or DCS_OPT_ADAM with hyper_h = (learning_rate, beta1, beta2, epsilon; 1e-3, 0.9, 0.999, 1e-8).  Both
+ * accumulators (which = 2 and 3 of dcs_trainer_get) and the step count become zero, in stream order.  A trainer starts as
+ * DCS_OPT_ADADELTA with hyper_h[4 .. 6] of dcs_trainer_create.  Adam is lasagne's: with t the step count after this step,
+ * a_t = learning_rate sqrt(1 - beta2^t) / (1 - beta1^t) (computed on the host in double), m' = beta1 m + (1 - beta1) g,
+ * v' = beta2 v + (1 - beta2) g^2, p' = p - a_t m' / (sqrt(v') + epsilon): epsilon outside the bias correction.  Where g, m
+ * and v are zero the step is exactly zero.  DCS_EINVAL: an unknown kind, a learning rate that is negative or not finite,
+ * rho or a beta outside [0, 1), epsilon <= 0 or not finite; the trainer is unchanged then. */
+DCS_API int dcs_trainer_set_optimizer(dcs_trainer* t, int kind, const double* hyper_h);
+/* The selected update: its kind, its four hyper-parameters as dcs_trainer_set_optimizer takes them, and the number of mode-2
+ * steps since it was selected (Adam's t before the next step). */
+DCS_API int dcs_trainer_get_optimizer(dcs_trainer* t, int* kind, double* hyper_h, int64_t* steps);
+/* Set the step count (>= 0, else DCS_EINVAL): with dcs_trainer_set of both accumulators, the exact resume of a run (Adam's
+ * a_t depends on it; lasagne/updates.py adam keeps t as a shared variable next to m and v). */
+DCS_API int dcs_trainer_set_steps(dcs_trainer* t, int64_t steps);
 /* LargeDataset's windows (dataset.py:383-488) from feature files resident on the device: data_d holds every file's
  * [5][T_i][F] float32 block (mixture, vocals, bass, drums, other), files_d [n_files][2] int64 = (element offset, T_i),
  * windows_d [batch][2] int32 = (file, first frame); file < 0 is an all-zero window (initOutput, :509-516), frames past T_i are
