@@ -15,7 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dcs.h")
 DCS_OK, DCS_EINVAL, DCS_EUNSUPPORTED, DCS_EHIP, DCS_ENOMEM, DCS_ESHAPE = 0, -1, -2, -3, -4, -5
 
 TAGS = dict(stft=0, conv1=1, conv2=2, fc=3, fc1x=4, deconv2=5, final=6, istft=7, ola=8, tile=9, pool=10, unpool=11,
-            mask=12, score=13, decoder=14)
+            mask=12, score=13, decoder=14, mwf=17)
 
 
 class DcsError(RuntimeError):
@@ -112,6 +112,8 @@ def load():
     proto("dcs_debug_check_guards", i32, vp, POINTER(i64))
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
+    proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)
+    proto("dcs_mwf_frames_per_block", i32)
     proto("dcs_trainer_create", i32, vp, i32, i32, i32, i32, POINTER(vp), POINTER(i64), i32, vp, POINTER(c_double),
           POINTER(vp))
     proto("dcs_trainer_destroy", i32, vp)

@@ -149,6 +149,7 @@ struct dcs_ctx {
     std::vector<float> ola_rise_h;
     DcsUploadRing score_ring;  // note rectangles and floor values of dcs_score_masks
     DcsBuffer bss_ws;          // dcs_bss_energies / dcs_bss_lagcorr: segment sums, lag correlations, Gram matrices
+    DcsBuffer mwf_ws;          // dcs_mwf_f32: v [J][T][F] float32 and the two sets of per-chunk sums
 };
 
 // RAII-ish helper: records a start event on construction and a stop event in done().

@@ -97,16 +97,42 @@ class Context(object):
         _lib.check(self._lib.dcs_debug_check_guards(self._h, byref(n)))
         return n.value
 
+    # -- multichannel Wiener filter ----------------------------------------------------------------
+    def mwf(self, mag, phase, src, niter, pre_div=1.0, eps=1e-10):
+        """``dcs_mwf_f32``: ``niter`` EM iterations of the multichannel Wiener filter (time-invariant full-rank spatial
+        covariances) on float32 device tensors.  ``mag``, ``phase`` ``[2, T, F]`` (the mixture), ``src`` ``[2, J, T, F]``
+        (per-channel source magnitudes, divided by ``pre_div`` before use) -> (magnitudes, phases), both ``[2, J, T, F]``.
+        ``niter=0`` returns ``src / pre_div`` and the mixture's phases."""
+        torch = _torch()
+        if mag.dim() != 3 or src.dim() != 4 or mag.shape[0] != 2 or src.shape[0] != 2 or tuple(phase.shape) != tuple(mag.shape) \
+                or tuple(src.shape[2:]) != tuple(mag.shape[1:]):
+            raise ValueError("mwf expects mag, phase [2, T, F] and src [2, J, T, F], got %r, %r, %r"
+                             % (tuple(mag.shape), tuple(phase.shape), tuple(src.shape)))
+        if any(t.dtype != torch.float32 or t.device != self.device for t in (mag, phase, src)):
+            raise ValueError("mwf expects float32 tensors on %s" % (self.device,))
+        with self.stream_scope():
+            mag, phase, src = mag.contiguous(), phase.contiguous(), src.contiguous()
+            J, T, F = (int(x) for x in src.shape[1:])
+            out_mag = torch.empty((2, J, T, F), dtype=torch.float32, device=src.device)
+            out_phase = torch.empty((2, J, T, F), dtype=torch.float32, device=src.device)
+            _lib.check(self._lib.dcs_mwf_f32(self._h, _ptr(mag), _ptr(phase), T * F, _ptr(src), J * T * F, T * F, F, T, F, J,
+                                             int(niter), float(pre_div), float(eps), _ptr(out_mag), _ptr(out_phase)))
+        return out_mag, out_phase
+
     # -- kernel timing (bench.py) ---------------------------------------------------------------
     def timing_stride(self, stride):
         _lib.check(self._lib.dcs_timing_stride(self._h, int(stride)))
 
     def timing(self, tags):
-        """Bracket the kernels of the named tags (``_lib.TAGS`` keys; ``'all'``; ``None`` = off) with HIP events."""
+        """Bracket the kernels of the named tags (``_lib.TAGS`` keys; ``'all'``; ``None`` = off) with HIP events.  ``'all'``
+        is every tag ``_lib.TAGS`` names: not ``DCS_TAG_BSS_CORR`` / ``DCS_TAG_BSS_CHOL`` (15, 16), which
+        ``scripts/bench_bsseval.py`` enables by number."""
         if not tags:
             mask = 0
         elif tags == 'all':
-            mask = (1 << len(_lib.TAGS)) - 1
+            mask = 0
+            for t in _lib.TAGS.values():
+                mask |= 1 << t
         else:
             mask = 0
             for t in tags:
@@ -198,9 +224,9 @@ class StftPlan(object):
         return mag, ph
 
     @_on_ctx_stream
-    def inverse(self, mag_t, phase_t, n_out=None, pre_div=1.0):
+    def inverse(self, mag_t, phase_t, n_out=None, pre_div=1.0, out=None):
         """mag_t ``[S, T, ld]`` or ``[T, ld]``, phase_t ``[T, ld]`` (same ld).  Returns ``[S, n_out]``
-        (or ``[n_out]``)."""
+        (or ``[n_out]``), written into ``out`` (contiguous ``[S, n_out]``, same dtype) when given."""
         torch = _torch()
         squeeze = mag_t.dim() == 2
         if squeeze:
@@ -212,7 +238,10 @@ class StftPlan(object):
         phase_t = phase_t.contiguous()
         full = _lib.inverse_length(T, self.hop, self.frame)
         n_out = full if n_out is None else min(int(n_out), full)
-        out = torch.empty((S, n_out), dtype=mag_t.dtype, device=mag_t.device)
+        if out is None:
+            out = torch.empty((S, n_out), dtype=mag_t.dtype, device=mag_t.device)
+        elif tuple(out.shape) != (S, n_out) or out.dtype != mag_t.dtype or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %r tensor of the magnitudes' dtype" % ((S, n_out),))
         if mag_t.dtype == torch.float64:
             _lib.check(self.ctx._lib.dcs_stft_inverse_f64(self._h, _ptr(mag_t), T * ld, _ptr(phase_t), ld, T, S,
                                                           float(pre_div), _ptr(out), n_out))
@@ -408,21 +437,26 @@ class Network(object):
         return out
 
     @_on_ctx_stream
-    def separate_stereo(self, plan, audio_t, overlap, tiler=TILER_LIBRARY, scale=0.3, want_spectra=False):
+    def separate_stereo(self, plan, audio_t, overlap, tiler=TILER_LIBRARY, scale=0.3, want_spectra=False, want_pcm=True):
         """Stereo (ILD) graph: ``[2, L]`` float32 device tensor (rows contiguous) -> PCM ``[2, S, L]`` (and, with
-        ``want_spectra``, the cross-faded scaled magnitudes ``[2, S, T, F]``)."""
+        ``want_spectra``, the cross-faded scaled magnitudes ``[2, S, T, F]``; ``want_pcm=False``: the spectra alone, no
+        iSTFT runs)."""
         torch = _torch()
         if audio_t.dim() != 2 or audio_t.shape[0] != 2 or audio_t.stride(1) != 1:
             raise ValueError("separate_stereo expects a [2, samples] tensor with contiguous rows")
         L = int(audio_t.shape[1])
         T = _lib.frame_count(L, plan.hop)
-        out = torch.empty((2, self.S, L), dtype=torch.float32, device=audio_t.device)
+        if not want_pcm and not want_spectra:
+            raise ValueError("separate_stereo: neither PCM nor spectra requested")
+        out = torch.empty((2, self.S, L), dtype=torch.float32, device=audio_t.device) if want_pcm else None
         sep = torch.empty((2, self.S, T, self.F), dtype=torch.float32, device=audio_t.device) if want_spectra else None
         nt, nf = c_int64(), c_int64()
         _lib.check(self.ctx._lib.dcs_separate_stereo(self._h, plan._h, _ptr(audio_t), L, int(audio_t.stride(0)),
                                                      int(overlap), int(tiler), float(scale), _ptr(out),
                                                      _ptr(sep) if sep is not None else None, self.F, byref(nt), byref(nf)))
         self.last_tiles, self.last_frames = nt.value, nf.value
+        if not want_pcm:
+            return sep
         return (out, sep) if want_spectra else out
 
     @_on_ctx_stream
@@ -470,6 +504,11 @@ def tile(ctx, mag_t, time_context, overlap, tiler, scale=1.0):
             _lib.check(ctx._lib.dcs_tile(ctx._h, _ptr(mag_t), T * F, F, C, T, F, int(time_context), int(overlap),
                                          int(tiler), float(scale), _ptr(tiles), n))
     return tiles, n
+
+
+def mwf(ctx, mag_t, phase_t, src_t, niter, pre_div=1.0, eps=1e-10):
+    """:meth:`Context.mwf`: the multichannel Wiener filter the reference left unfinished (util.py:633-719) on the device."""
+    return ctx.mwf(mag_t, phase_t, src_t, niter, pre_div, eps)
 
 
 def pcm_to_int16(ctx, pcm_t, out=None):

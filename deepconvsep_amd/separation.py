@@ -457,12 +457,34 @@ class Separator(object):
 
 
     @_on_ctx_stream
-    def separate_stereo(self, audio):
+    def separate_stereo(self, audio, mwf_iters=0):
         """The "Separating" block of the stereo trainer (examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py:291-325):
-        ``audio [L, 2]`` -> ``sep_audio [L, S, 2]`` (one stereo signal per source, :299,316)."""
+        ``audio [L, 2]`` -> ``sep_audio [L, S, 2]`` (one stereo signal per source, :299,316).
+        ``mwf_iters > 0``: the per-channel estimates go through that many iterations of the multichannel Wiener filter
+        (``dcs_mwf_f32``) before the inverse transform, each (channel, source) then with its own phase."""
         a = self.ctx.to_device(np.ascontiguousarray(np.asarray(audio).T), np.float32)          # [2, L]
-        pcm = self.net.separate_stereo(self.plan, a, self.overlap, TILER_LIBRARY, self.scale_factor)
+        if not mwf_iters:
+            pcm = self.net.separate_stereo(self.plan, a, self.overlap, TILER_LIBRARY, self.scale_factor)
+        else:
+            pcm = self.separate_stereo_mwf_device(a, int(mwf_iters))
         return np.ascontiguousarray(self.ctx.to_host(pcm).astype(np.float64).transpose(2, 1, 0))   # [L, S, 2]
+
+    @_on_ctx_stream
+    def separate_stereo_mwf_device(self, a, mwf_iters):
+        """``a [2, L]`` float32 on the device -> float32 PCM ``[2, S, L]``: two-channel STFT, the network's per-channel
+        magnitudes, the Wiener filter (``pre_div = scale_factor``), one inverse transform per (channel, source)."""
+        import torch
+        L = int(a.shape[1])
+        mag, ph = self.plan.forward_clips(a, phase=True)                                        # [2, T, F]
+        sep = self.net.separate_stereo(self.plan, a, self.overlap, TILER_LIBRARY, self.scale_factor, want_spectra=True,
+                                       want_pcm=False)                                          # [2, S, T, F], x scale_factor
+        out_mag, out_ph = self.ctx.mwf(mag, ph, sep, mwf_iters, pre_div=self.scale_factor)
+        S = int(sep.shape[1])
+        pcm = torch.empty((2, S, L), dtype=torch.float32, device=a.device)
+        for c in range(2):
+            for j in range(S):
+                self.plan.inverse(out_mag[c, j], out_ph[c, j], n_out=L, out=pcm[c, j:j + 1])
+        return pcm
 
     @_on_ctx_stream
     def separate_scoreinformed(self, audio, melody, timbre_model_path=None):

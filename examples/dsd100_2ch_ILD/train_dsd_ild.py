@@ -5,6 +5,7 @@ examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py.
     python train_dsd_ild.py --db <DSD100 root> --output <dir> [--feature_path F] [--model NAME] [--batch_size 32]
                             [--time_context 30] [--overlap 25] [--nepochs 30] [--scale_factor 0.3]
                             [--scale_factor_test 0.3] [--load] [--skip] [--skip_sep] [--seed 0] [--windows reference|all]
+                            [--mwf N]
 
 Features come from compute_features.py (``<feature_path>/*_in_m_.data`` / ``*_out_m_.data``, default
 <db>/transforms/feature_folder).
@@ -14,6 +15,8 @@ Stage 1 (mse) runs --nepochs epochs of train_fn_mse + train_fn1, prints the refe
 trainer loaded from the _noILD model -- the reference rebuilds ``adadelta`` there, which gives fresh accumulators -- and saves
 <output>/models/model_<NAME>.pkl.  The loss list (both stages) is pickled as <output>/models/loss_<NAME>.data.  Then, unless
 --skip_sep, Mixtures/{Dev,Test} are separated into <output>/output/<NAME>/Sources/<sub>/<song>/<source>.wav, stereo files.
+--mwf N (default 0: the reference's block) puts N iterations of the multichannel Wiener filter between the network and the
+inverse transform (the filter util.py:633-719 left unfinished; ``Separator.separate_stereo(audio, mwf_iters=N)``).
 
 --load starts stage 1 from model_<NAME>_noILD.pkl if it is there, else from model_<NAME>.pkl; --skip trains nothing and
 separates with model_<NAME>.pkl.
@@ -37,7 +40,7 @@ from deepconvsep_amd.separation import Separator, load_model, read_wav, write_wa
 from deepconvsep_amd.stereo_training import RAND_STD, SOURCES, StereoFeatureWindows, StereoTrainer  # noqa: E402
 
 
-def separate_all(params, db, outdir, scale_factor, tc, overlap, batch_size, mix_type='mixture'):
+def separate_all(params, db, outdir, scale_factor, tc, overlap, batch_size, mix_type='mixture', mwf_iters=0):
     """trainCNN_ILD_DSD100.py:291-341 with the fused stereo separation path; ``mix_type``: the file of each song that is
     separated, <mix_type>.wav (trainCNN_ILD_DSD100_3stages.py:543-546 and :335: 'binaural' for the binaural mixtures)."""
     sep = Separator('dsd_ild', params, scale_factor, tc, overlap, batch_size, 513, 1024, 512, np.hanning)
@@ -52,7 +55,7 @@ def separate_all(params, db, outdir, scale_factor, tc, overlap, batch_size, mix_
             assert sampleRate == 44100, "Sample rate needs to be 44100"
             if audio.ndim == 1:
                 audio = np.repeat(audio[:, None], 2, axis=1)
-            out = sep.separate_stereo(audio[:, :2])                       # [L, S, 2]
+            out = sep.separate_stereo(audio[:, :2], mwf_iters=mwf_iters)  # [L, S, 2]
             dirout = os.path.join(outdir, 'Sources', sub, song)
             os.makedirs(dirout, exist_ok=True)
             for i, s in enumerate(SOURCES):
@@ -76,6 +79,7 @@ def main(argv=None):
     ap.add_argument("--skip_sep", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--windows", choices=("reference", "all"), default="reference")
+    ap.add_argument("--mwf", type=int, default=0, help="iterations of the multichannel Wiener filter when separating")
     a = ap.parse_args(argv)
     db, output = a.db, a.output
     assert os.path.isdir(db), "Please input the directory for the DSD100 dataset with --db path_to_DSD100"
@@ -156,7 +160,7 @@ def main(argv=None):
     if not a.skip_sep:
         print("Separating")
         separate_all(params, db, os.path.join(output, 'output', a.model), a.scale_factor_test, a.time_context, a.overlap,
-                     a.batch_size)
+                     a.batch_size, mwf_iters=a.mwf)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100_3stages.py.
                                     [--time_context 30] [--overlap 25] [--nepochs_mse 30] [--nepochs_ILD 10]
                                     [--scale_factor 0.3] [--scale_factor_test 0.3] [--load] [--skip_train_mse]
                                     [--skip_train_ILD] [--binaural] [--skip_sep] [--seed 0] [--windows reference|all]
+                                    [--mwf N]
 
 Features come from compute_features.py (``<feature_path>/*_in_m_.data`` / ``*_out_m_.data``, default
 <db>/transforms/feature_folder).  Without --load the model's name is <NAME>_mseEp=<nepochs_mse or 0>_ILDEp=<nepochs_ILD or 0>
@@ -21,7 +22,8 @@ whose updates hold the accumulators stage 1 ended with.  So does this script: on
 ``optimizer_state()`` is kept on the host across stage 2 and put back (``load_optimizer_state``) before stage 3.
 The loss list (stages 1 and 2) is pickled as <output>/models/loss_<name>.data.  Then, unless --skip_sep, mixture.wav
 (--binaural: binaural.wav, :543-546) of every song under Mixtures/{Dev,Test} is separated with the network as it stands into
-<output>/output/<name>/Sources/<sub>/<song>/<source>.wav, stereo files.
+<output>/output/<name>/Sources/<sub>/<song>/<source>.wav, stereo files; --mwf N (default 0: the reference's block) runs N
+iterations of the multichannel Wiener filter between the network and the inverse transform.
 
 Differences from the reference: the two normal draws of the loss are replaced before every step from a device generator
 seeded with --seed (Theano's RandomStreams(128) stream is not reproduced); the window order of an epoch is RandomState(seed
@@ -82,6 +84,7 @@ def main(argv=None):
     ap.add_argument("--skip_sep", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--windows", choices=("reference", "all"), default="reference")
+    ap.add_argument("--mwf", type=int, default=0, help="iterations of the multichannel Wiener filter when separating")
     a = ap.parse_args(argv)
     db, output = a.db, a.output
     assert os.path.isdir(db), "Please input the directory for the DSD100 dataset with --db path_to_DSD100"
@@ -181,7 +184,7 @@ def main(argv=None):
     if not a.skip_sep:
         print("Separating")
         separate_all(params, db, os.path.join(output, 'output', name), a.scale_factor_test, a.time_context, a.overlap,
-                     a.batch_size, mix_type='binaural' if a.binaural else 'mixture')
+                     a.batch_size, mix_type='binaural' if a.binaural else 'mixture', mwf_iters=a.mwf)
 
 
 if __name__ == "__main__":

@@ -431,6 +431,33 @@ DCS_API int dcs_bss_energies(dcs_ctx* ctx, const double* ref_d, const double* es
 DCS_API int dcs_bss_lagcorr(dcs_ctx* ctx, const double* ref_d, const double* est_d, int n_ref, int n_est, int64_t n_samples,
                             int flen, double* out_d);
 
+/* ------------------------------------------------------------------ multichannel Wiener filter (csrc/mwf.hip) */
+/* The filter the reference's authors were transcribing behind their stereo network and never ran: util.py:633-719 mwf(spec,
+ * mixture, niter=10) quotes the MATLAB of Duong / Vincent / Gribonval's EM for full-rank spatial covariances (:647-682), stops
+ * at a pdb.set_trace() (:718) and its update line (:719) has inconsistent dimensions.  What runs here is that EM with gamma1 =
+ * 0 (no temporal prior) and a time-invariant spatial covariance R_j[f], for I = 2 channels and J sources:
+ *   X[c,t,f] = mag[c,t,f] e^{i phase[c,t,f]},   A[c,j,t,f] = src[c,j,t,f] / pre_div  (float32 division)
+ *   init:   y_j[t,f] = (A[0,j] e^{i phase[0]}, A[1,j] e^{i phase[1]}),  C_j = y_j y_j^H,  v_j = tr(C_j) / 2
+ *   niter times:
+ *     M:    R_j[f] = sum_t C_j[t,f] / (sum_t v_j[t,f] + eps)
+ *     E:    Cx = sum_j v_j R_j + eps I,  W_j = v_j R_j Cx^{-1},  y_j = W_j x,
+ *           C_j = y_j y_j^H + (I - W_j) v_j R_j,  v_j = Re tr(C_j) / 2
+ *   out:    |y_j[c]|, angle(y_j[c]) (0 where y is 0), float32
+ * niter = 0 returns src / pre_div and the mixture's phases.  mag_d / phase_d [2][n_frames, ld] (channel stride ch_stride);
+ * src_d, out_mag_d, out_phase_d [2][J][n_frames, ld] (strides src_ch_stride, src_stride, in elements, shared by all three);
+ * columns F .. ld-1 of the outputs are not written.  pre_div: the scale_factor the stereo path's magnitudes carry (as in
+ * dcs_stft_inverse_f32).  The 2x2 algebra, the phasors and the sums over t are float64, what is kept between passes (v_j
+ * [J][n_frames][F]) float32 in the context's scratch; one launch per pass, niter + 1 launches, no atomics: the same bits every
+ * run.  DCS_EINVAL for J outside 1 .. 8, niter outside 0 .. 100, F < 1, ld < F, pre_div <= 0, eps <= 0 (or below DBL_MIN:
+ * the inverse of an empty bin's Cx = eps I must be finite; any normal eps keeps zero rows at zero) or a NULL pointer;
+ * n_frames == 0 does nothing.  Enqueued on the ctx stream. */
+DCS_API int dcs_mwf_f32(dcs_ctx* ctx, const float* mag_d, const float* phase_d, int64_t ch_stride, const float* src_d,
+                        int64_t src_ch_stride, int64_t src_stride, int64_t ld, int64_t n_frames, int F, int J, int niter,
+                        float pre_div, double eps, float* out_mag_d, float* out_phase_d);
+/* frames of one chunk of dcs_mwf_f32: a workgroup sums over one chunk, or over every 32nd one past 32 chunks, and the next
+ * pass adds up min(ceil(n_frames / this), 32) sets of sums */
+DCS_API int dcs_mwf_frames_per_block(void);
+
 /* ------------------------------------------------------------------ timing aid for bench.py */
 /* Average duration (ms) of the kernels tagged `which` since the last reset, measured with HIP events
  * on the ctx stream.  tag_mask bit t enables the tag t (two event records per tagged launch);
@@ -441,7 +468,8 @@ enum { DCS_TAG_STFT = 0, DCS_TAG_CONV1 = 1, DCS_TAG_CONV2 = 2, DCS_TAG_FC = 3, D
        DCS_TAG_DECODER = 14 /* transposed conv2 + transposed conv1 in one kernel (Bach10 graph, f16 switch) */,
        DCS_TAG_BSS_CORR = 15 /* dcs_bss_energies / dcs_bss_lagcorr: lag correlations, one bracket per window group */,
        DCS_TAG_BSS_CHOL = 16 /* dcs_bss_energies: Gram assembly, partial Cholesky, energies, one bracket per window group */,
-       DCS_TAG_COUNT = 17 };
+       DCS_TAG_MWF = 17 /* dcs_mwf_f32: one bracket per pass */,
+       DCS_TAG_COUNT = 18 };
 DCS_API int dcs_timing_enable(dcs_ctx* ctx, unsigned tag_mask);
 /* bracket only every stride-th launch of an enabled tag (an event pair costs ~6 us of stream time each side) */
 DCS_API int dcs_timing_stride(dcs_ctx* ctx, int stride);
