@@ -110,6 +110,9 @@ def load():
     proto("dcs_timing_reset", i32, vp)
     proto("dcs_timing_query", i32, vp, i32, POINTER(c_double), POINTER(i64))
     proto("dcs_debug_check_guards", i32, vp, POINTER(i64))
+    proto("dcs_debug_stft_forward_f32", i32, vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, i32, vp)
+    proto("dcs_debug_stft_inverse_unit_f32", i32, vp, vp, i64, vp, i64, i64, i64, i32, i64, f32, vp, i64, vp, i64)
+    proto("dcs_debug_stft_last_kernel", i32, vp, POINTER(i32), POINTER(i32), POINTER(i64))
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)

@@ -506,6 +506,89 @@ extern "C" int dcs_stft_inverse_f64(dcs_stft* p, const double* mag_d, int64_t sr
                                    dcs_launch_stft_inverse_f64);
 }
 
+// ------------------------------------------------------------------------------- test aids for the transform kernels
+// the device clip table on the host, checked against the rows / samples the caller's arguments describe
+static int debug_clip_table(dcs_stft* p, const int64_t* clip_tab_d, int64_t n_clips, std::vector<int64_t>* tab) {
+    tab->resize((size_t)n_clips * kDcsClipTab);
+    DCS_HIP(hipStreamSynchronize(p->ctx->stream));
+    DCS_HIP(hipMemcpy(tab->data(), clip_tab_d, tab->size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    int compact = 0;
+    for (int64_t c = 0; c < n_clips; ++c) compact += (*tab)[c * kDcsClipTab + 3] >= 0;
+    if (compact != 0 && compact != n_clips) DCS_FAIL(DCS_EINVAL, "clip table: row offsets in some clips only");
+    return DCS_OK;
+}
+
+extern "C" int dcs_debug_stft_forward_f32(dcs_stft* p, const float* audio_d, int64_t n, int64_t audio_stride, int64_t n_clips,
+                                          float* mag_d, float* phase_d, float* unit_d, int64_t ld, int64_t rows_out,
+                                          int interleave, const int64_t* clip_tab_d) {
+    int64_t T = 0;
+    if (rows_out < 0) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_forward: negative size");
+    if (!audio_d) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_forward: null argument");
+    DCS_CHECK(forward_clips_check(p, audio_d, n, n_clips, audio_stride, mag_d, ld, rows_out, &T));
+    if (n_clips == 0) return DCS_OK;
+    if (clip_tab_d && interleave) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_forward: a clip table with interleaved rows");
+    DCS_ON_DEVICE(p->ctx->device);
+    if (clip_tab_d) {
+        std::vector<int64_t> tab;
+        DCS_CHECK(debug_clip_table(p, clip_tab_d, n_clips, &tab));
+        for (int64_t c = 0; c < n_clips; ++c) {
+            const int64_t* e = &tab[c * kDcsClipTab];
+            if (e[0] < 0 || e[0] > n || e[1] != dcs_frame_count(e[0], p->hop) || e[1] > rows_out)
+                DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_forward: clip %lld of the table: %lld samples, %lld frames", (long long)c,
+                         (long long)e[0], (long long)e[1]);
+            if (e[3] >= 0 && (e[5] < e[1] || e[5] > rows_out || e[3] > rows_out * n_clips - e[5]))
+                DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_forward: clip %lld of the table: rows [%lld, +%lld) of %lld", (long long)c,
+                         (long long)e[3], (long long)e[5], (long long)(rows_out * n_clips));
+        }
+    }
+    return dcs_launch_stft_forward_f32_clips(p, audio_d, n, audio_stride, n_clips, mag_d, phase_d,
+                                             reinterpret_cast<float2*>(unit_d), ld, rows_out, T, interleave != 0, clip_tab_d);
+}
+
+extern "C" int dcs_debug_stft_inverse_unit_f32(dcs_stft* p, const float* mag_d, int64_t src_stride, const float* unit_d,
+                                               int64_t unit_clip_stride, int64_t ld, int64_t T, int n_src, int64_t n_clips,
+                                               float pre_div, float* audio_d, int64_t n_out, const int64_t* clip_tab_d,
+                                               int64_t out_stride) {
+    if (!p || !mag_d || !unit_d || !audio_d) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: null argument");
+    if (T < 0 || n_src < 0 || n_clips < 0 || n_out < 0 || out_stride < 0)
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: negative size");
+    if (ld < p->frame / 2 + 1) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: ld < bins");
+    if (!(pre_div != 0.f) || !std::isfinite(pre_div)) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: pre_div");
+    if (out_stride != 0 && out_stride < n_out) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: out_stride < n_out");
+    if (T > 0x7fffffffLL / ld) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: %lld frames", (long long)T);
+    if (n_clips > 1 && unit_clip_stride < T * ld) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: unit_clip_stride < n_frames * ld");
+    if (n_src * n_clips > 1 && src_stride < T * ld) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: src_stride < n_frames * ld");
+    if (n_src * n_clips > 0x7fffLL) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: %lld sources", (long long)(n_src * n_clips));
+    if (T == 0 || n_src == 0 || n_clips == 0 || n_out == 0) return DCS_OK;
+    if (n_out > dcs_inverse_length(T, p->hop, p->frame))
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: n_out %lld exceeds %lld", (long long)n_out,
+                 (long long)dcs_inverse_length(T, p->hop, p->frame));
+    DCS_ON_DEVICE(p->ctx->device);
+    if (clip_tab_d) {
+        if (!dcs_stft_inverse_is_wave(p))
+            DCS_FAIL(DCS_EUNSUPPORTED, "clips of different lengths need the wave iSTFT kernel (frameSize 1024 / 2048 / 4096, hop | frameSize)");
+        std::vector<int64_t> tab;
+        DCS_CHECK(debug_clip_table(p, clip_tab_d, n_clips, &tab));
+        const int64_t unit_rows = ((n_clips - 1) * unit_clip_stride) / ld + T;   // what the strides describe
+        for (int64_t c = 0; c < n_clips; ++c) {
+            const int64_t* e = &tab[c * kDcsClipTab];
+            if (e[0] < 0 || e[0] > n_out || e[1] < 0 || e[1] > T || (e[3] >= 0 && e[3] > unit_rows - e[1]))
+                DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_inverse_unit: clip %lld of the table: %lld samples, %lld frames at row %lld",
+                         (long long)c, (long long)e[0], (long long)e[1], (long long)e[3]);
+        }
+    }
+    return dcs_launch_stft_inverse_f32_clips(p, mag_d, src_stride, reinterpret_cast<const float2*>(unit_d), unit_clip_stride, ld,
+                                             T, n_src, n_clips, pre_div, audio_d, n_out, clip_tab_d, out_stride);
+}
+
+extern "C" int dcs_debug_stft_last_kernel(const dcs_stft* p, int* forward, int* inverse, int64_t* param) {
+    if (!p) DCS_FAIL(DCS_EINVAL, "dcs_debug_stft_last_kernel: null plan");
+    if (forward) *forward = p->last_fwd;
+    if (inverse) *inverse = p->last_inv;
+    if (param) *param = p->last_param;
+    return DCS_OK;
+}
+
 // ------------------------------------------------------------------------------- tiling
 extern "C" int dcs_tile(dcs_ctx* ctx, const float* mag_d, int64_t ch_stride, int64_t ld, int C, int64_t T, int F,
                         int tc, int ov, int tiler, float scale, float* tiles_d, int64_t n_tiles) {

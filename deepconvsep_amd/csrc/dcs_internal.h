@@ -179,6 +179,10 @@ struct dcs_stft {
     double2* tw_d = nullptr;
     float* wsq_f = nullptr;     // [N] window*window in float32 (normaliser terms)
     double* wsq_d = nullptr;
+    // which kernel the last forward / inverse launch of this plan took (DCS_STFT_FWD_* / DCS_STFT_INV_*, 0 = none yet) and
+    // the C / Cs / LC its launcher chose (0 where there is none): dcs_debug_stft_last_kernel, a test aid -- one store per launch
+    int last_fwd = 0, last_inv = 0;
+    int64_t last_param = 0;
 };
 
 // launchers implemented in fft.hip
@@ -205,6 +209,8 @@ int dcs_launch_stft_inverse_f32(dcs_stft* p, const float* mag, int64_t src_strid
 int dcs_launch_stft_inverse_f64(dcs_stft* p, const double* mag, int64_t src_stride, const double* phase,
                                 const double2* unit, int64_t ld, int64_t T, int n_src, double pre_div, double* audio,
                                 int64_t n_out);
+// whether the float32 inverse of this plan goes to the wave kernels of fft_wave.hip (they alone take a clip table)
+bool dcs_stft_inverse_is_wave(const dcs_stft* p);
 
 // ---------------------------------------------------------------------------------- clips of different lengths in one launch
 // Device table of kDcsClipTab int64 per clip (separate_impl, net.hip): {samples, frames, tiles, row offset, tile offset, rows}.

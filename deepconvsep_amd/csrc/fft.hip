@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void istft_fused_kernel(
     const R* __restrict__ mag, int64_t src_stride, const R* __restrict__ phase, const R2* __restrict__ unit,
     int64_t ld, const R* __restrict__ win, const R* __restrict__ wsq, const R2* __restrict__ tw,
     R* __restrict__ audio, int64_t n_out, int N, int hop, int log2m, int64_t T, int C, R pre_div, R sqrt_n,
-    int tw_lds) {
+    int tw_lds, int64_t out_stride) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int M = N >> 1;
     const int tid = threadIdx.x;
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void istft_fused_kernel(
         R norm = R(0);
         for (int64_t n = f_lo; n <= f_hi; ++n) norm += wsq[p - n * hop];
         if (norm == R(0)) norm = R(1);
-        audio[(int64_t)s * n_out + m] = acc[q] / norm;
+        audio[(int64_t)s * out_stride + m] = acc[q] / norm;
     }
 #undef DCS_ROWS_LOAD
 }
@@ -227,30 +227,31 @@ int launch_forward(dcs_stft* p, const R* win, const R2* tw, const R* audio, int6
                        audio_stride, interleave ? n_clips : (int64_t)0);
     tm.done();
     DCS_HIP(hipGetLastError());
+    p->last_fwd = DCS_STFT_FWD_BLOCK;
     return DCS_OK;
 }
 
 template <typename R, typename R2, bool UNIT, int PF>
 int launch_inverse_pf(dcs_stft* p, const dim3& grid, size_t lds, const R* win, const R2* tw, const R* wsq, const R* mag,
                       int64_t src_stride, const R* phase, const R2* unit, int64_t ld, int64_t T, R pre_div, R* audio,
-                      int64_t n_out, int C, int tw_lds) {
+                      int64_t n_out, int C, int tw_lds, int64_t out_stride) {
     auto kern = istft_fused_kernel<R, R2, UNIT, PF>;
     if (lds > 48 * 1024)
         DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, p->ctx->stream, mag, src_stride, phase, unit, ld, win, wsq, tw,
-                       audio, n_out, p->frame, p->hop, p->log2m, T, C, pre_div, (R)sqrt((double)p->frame), tw_lds);
+                       audio, n_out, p->frame, p->hop, p->log2m, T, C, pre_div, (R)sqrt((double)p->frame), tw_lds, out_stride);
     return DCS_OK;
 }
 
 template <typename R, typename R2, bool UNIT>
 int launch_inverse_unit(dcs_stft* p, const dim3& grid, size_t lds, const R* win, const R2* tw, const R* wsq,
                         const R* mag, int64_t src_stride, const R* phase, const R2* unit, int64_t ld, int64_t T,
-                        R pre_div, R* audio, int64_t n_out, int C, int tw_lds) {
+                        R pre_div, R* audio, int64_t n_out, int C, int tw_lds, int64_t out_stride) {
     const int need = (p->frame / 2 + 1 + kThreads - 1) / kThreads;
 #define DCS_PF(PF_)                                                                                                  \
     return launch_inverse_pf<R, R2, UNIT, PF_>(p, grid, lds, win, tw, wsq, mag, src_stride, phase, unit, ld, T, pre_div, \
-                                               audio, n_out, C, tw_lds)
+                                               audio, n_out, C, tw_lds, out_stride)
     if (need <= 3) DCS_PF(3);
     if (need <= 5) DCS_PF(5);
     if (need <= 9) DCS_PF(9);
@@ -261,8 +262,9 @@ int launch_inverse_unit(dcs_stft* p, const dim3& grid, size_t lds, const R* win,
 template <typename R, typename R2>
 int launch_inverse(dcs_stft* p, const R* win, const R2* tw, const R* wsq, const R* mag, int64_t src_stride,
                    const R* phase, const R2* unit, int64_t ld, int64_t T, int n_src, R pre_div, R* audio,
-                   int64_t n_out) {
+                   int64_t n_out, int64_t out_stride = 0 /* elements between the sources' outputs; 0: n_out */) {
     if (T <= 0 || n_src <= 0 || n_out <= 0) return DCS_OK;
+    if (out_stride <= 0) out_stride = n_out;
     const int N = p->frame, hop = p->hop;
     const int M = N / 2;
     const int64_t hops = (n_out + N / 2 + hop - 1) / hop;  // padded positions [0, n_out + N/2)
@@ -287,13 +289,15 @@ int launch_inverse(dcs_stft* p, const R* win, const R2* tw, const R* wsq, const 
     int rc;
     if (unit)
         rc = launch_inverse_unit<R, R2, true>(p, grid, lds, win, tw, wsq, mag, src_stride, phase, unit, ld, T, pre_div,
-                                              audio, n_out, (int)C, tw_lds);
+                                              audio, n_out, (int)C, tw_lds, out_stride);
     else
         rc = launch_inverse_unit<R, R2, false>(p, grid, lds, win, tw, wsq, mag, src_stride, phase, unit, ld, T, pre_div,
-                                               audio, n_out, (int)C, tw_lds);
+                                               audio, n_out, (int)C, tw_lds, out_stride);
     tm.done();
     DCS_CHECK(rc);
     DCS_HIP(hipGetLastError());
+    p->last_inv = DCS_STFT_INV_BLOCK;
+    p->last_param = C;
     return DCS_OK;
 }
 
@@ -356,11 +360,14 @@ int dcs_launch_stft_inverse_f32_clips(dcs_stft* p, const float* mag, int64_t src
     if (T <= 0 || n_src <= 0 || n_out <= 0 || n_clips <= 0) return DCS_OK;
     if (clip_tab && (!dcs_fft_wave_inverse_supported(p) || !unit))
         DCS_FAIL(DCS_EUNSUPPORTED, "clips of different lengths need the wave iSTFT kernel (frameSize 1024 / 2048 / 4096, hop | frameSize)");
-    if (!dcs_fft_wave_inverse_supported(p) || !unit) {
+    if (!unit) DCS_FAIL(DCS_EINVAL, "istft of stacked clips: no phasors");
+    if (!dcs_fft_wave_inverse_supported(p)) {
+        // the block-level kernel, clip by clip (out_stride: the pitch of the sources' outputs, as in the wave kernels)
+        const int64_t os = out_stride > 0 ? out_stride : n_out;
         for (int64_t c = 0; c < n_clips; ++c)
-            DCS_CHECK(dcs_launch_stft_inverse_f32(p, mag + c * n_src * src_stride, src_stride, nullptr,
-                                                  unit ? unit + c * unit_clip_stride : nullptr, ld, T, n_src, pre_div,
-                                                  audio + c * n_src * n_out, n_out));
+            DCS_CHECK((launch_inverse<float, float2>(p, p->win_f, p->tw_f, p->wsq_f, mag + c * n_src * src_stride, src_stride,
+                                                     nullptr, unit + c * unit_clip_stride, ld, T, n_src, pre_div,
+                                                     audio + c * n_src * os, n_out, os)));
         return DCS_OK;
     }
     DcsTimer tm(p->ctx, DCS_TAG_ISTFT);
@@ -377,3 +384,4 @@ int dcs_launch_stft_inverse_f64(dcs_stft* p, const double* mag, int64_t src_stri
     return launch_inverse<double, double2>(p, p->win_d, p->tw_d, p->wsq_d, mag, src_stride, phase, unit, ld, T, n_src,
                                            pre_div, audio, n_out);
 }
+bool dcs_stft_inverse_is_wave(const dcs_stft* p) { return dcs_fft_wave_inverse_supported(p); }

@@ -1270,6 +1270,7 @@ int launch_fwd(dcs_stft* p, const float* audio, int64_t L, int64_t audio_stride,
     hipLaunchKernelGGL(kern, dim3((unsigned)dcs_cdiv(rows_all, fpw)), dim3(64 * fpw), lds, p->ctx->stream, audio, L,
                        p->win_f, p->tw_f, mag, phase, unit, ld, p->hop, T, rows_out, n_clips, audio_stride,
                        (float)sqrt((double)p->frame), interleave ? 1 : 0, clip_tab);
+    p->last_fwd = fpw == 4 ? DCS_STFT_FWD_WAVE4 : DCS_STFT_FWD_WAVE1;
     return DCS_OK;
 }
 
@@ -1354,6 +1355,8 @@ int launch_inv(dcs_stft* p, const float* mag, int64_t src_stride, const float* p
                     }
                     if (R_ == 4) DCS_CHAIN(4) else DCS_CHAIN(2)
 #undef DCS_CHAIN
+                    p->last_inv = DCS_STFT_INV_CHAIN;
+                    p->last_param = LC;
                     return DCS_OK;
                 }
             }
@@ -1369,6 +1372,8 @@ int launch_inv(dcs_stft* p, const float* mag, int64_t src_stride, const float* p
             }
             if (stage) {
                 if (R_ == 4) DCS_SEQ_STAGE(4) else DCS_SEQ_STAGE(2)
+                p->last_inv = DCS_STFT_INV_SEQ_STAGED;
+                p->last_param = Cs;
                 return DCS_OK;
             }
 #undef DCS_SEQ_STAGE
@@ -1386,6 +1391,8 @@ int launch_inv(dcs_stft* p, const float* mag, int64_t src_stride, const float* p
             if (unit) { if (R_ == 4) DCS_SEQ(true, 4) else DCS_SEQ(true, 2) }
             else { if (R_ == 4) DCS_SEQ(false, 4) else DCS_SEQ(false, 2) }
 #undef DCS_SEQ
+            p->last_inv = DCS_STFT_INV_SEQ;
+            p->last_param = Cs;
             return DCS_OK;
         }
     }
@@ -1413,6 +1420,8 @@ int launch_inv(dcs_stft* p, const float* mag, int64_t src_stride, const float* p
     }
     if (unit) DCS_GO(true) else DCS_GO(false)
 #undef DCS_GO
+    p->last_inv = DCS_STFT_INV_RING;
+    p->last_param = C;
     return DCS_OK;
 }
 

@@ -689,6 +689,48 @@ DCS_API int dcs_trainer_pack_score(const double* notes_h, int ninst, int n_notes
  * No reference counterpart (the reference is NumPy / Theano); n_blocks_out (nullable) = guarded blocks alive. */
 DCS_API int dcs_debug_check_guards(dcs_ctx* ctx, int64_t* n_blocks_out);
 
+/* Test aids for the transform kernels (tests/test_gpu_stft_kernels.py); no reference counterpart.  The two launchers below
+ * are the ones dcs_separate* use internally -- the forward one writes unit phasors X / |X| ((1, 0) where X == 0) next to the
+ * magnitudes, the inverse one reads them instead of an angle -- reached here with every argument checked first: DCS_EINVAL
+ * and no launch for a null pointer, a negative count, ld < frame / 2 + 1, a stride shorter than what it strides over, or a
+ * clip table that points outside the buffers as these arguments describe them.  The table is on the device and is read back
+ * (one stream synchronisation per call: these are no production entry points).
+ *
+ * forward: n_clips signals of n_samples each, signal c at audio_d + c * audio_stride.  T = dcs_frame_count(n_samples, hop);
+ * mag_d / phase_d (nullable) / unit_d (nullable, (re, im) pairs) hold n_clips * rows_out rows of ld values, rows_out >= T,
+ * clip c at row c * rows_out -- or, with interleave != 0, row t * n_clips + c.  Rows past a clip's frames and columns past
+ * frame / 2 are written as magnitude 0, phase 0, phasor (1, 0).  clip_tab_d (nullable; frameSize 1024 / 2048 / 4096 only,
+ * else DCS_EUNSUPPORTED; not with interleave): per clip six int64 {samples, frames, tiles, row offset, tile offset, rows}
+ * with samples <= n_samples and frames = dcs_frame_count(samples, hop) <= rows_out.  Row offset < 0 in every clip: the
+ * pitch above applies.  Otherwise in every clip: clip c owns rows [row offset, row offset + rows) of the buffers, frames <=
+ * rows <= rows_out, inside the n_clips * rows_out rows. */
+DCS_API int dcs_debug_stft_forward_f32(dcs_stft* plan, const float* audio_d, int64_t n_samples, int64_t audio_stride,
+                                       int64_t n_clips, float* mag_d, float* phase_d, float* unit_d, int64_t ld,
+                                       int64_t rows_out, int interleave, const int64_t* clip_tab_d);
+/* inverse: n_clips clips of n_src sources each.  Source s of clip c reads the magnitudes at mag_d + (c * n_src + s) *
+ * src_stride ([n_frames, ld]) and the clip's phasors at unit_d + c * unit_clip_stride ([n_frames, ld] pairs), and writes
+ * n_out <= dcs_inverse_length(n_frames, hop, frame) samples at audio_d + (c * n_src + s) * out_stride (out_stride 0: n_out;
+ * samples [n_out, out_stride) are not written).  X = (mag / pre_div) * sqrt(frame) * unit; imaginary parts at bins 0 and
+ * frame / 2 are ignored.  clip_tab_d (nullable; needs frameSize 1024 / 2048 / 4096 and an even hop that divides it, else
+ * DCS_EUNSUPPORTED): clip c has samples <= n_out samples and frames <= n_frames frames; with row offsets >= 0 its phasor
+ * rows start at row `row offset` of unit_d instead and must end inside the rows the strides describe. */
+DCS_API int dcs_debug_stft_inverse_unit_f32(dcs_stft* plan, const float* mag_d, int64_t src_stride, const float* unit_d,
+                                            int64_t unit_clip_stride, int64_t ld, int64_t n_frames, int n_src,
+                                            int64_t n_clips, float pre_div, float* audio_d, int64_t n_out,
+                                            const int64_t* clip_tab_d, int64_t out_stride);
+/* Which kernel the plan's last forward / last inverse launch ran (any entry point, dcs_separate* included; 0 = none yet),
+ * and in *param the number of hop-blocks per workgroup (block, ring), per wave (seq) or of frames per wave (chain) that the
+ * inverse launcher chose.  Host-side bookkeeping, one store per launch.  Every pointer is nullable. */
+#define DCS_STFT_FWD_BLOCK 1      /* one workgroup per frame (any frameSize, float64) */
+#define DCS_STFT_FWD_WAVE1 2      /* one wave per frame, one frame per workgroup */
+#define DCS_STFT_FWD_WAVE4 3      /* one wave per frame, four frames per workgroup */
+#define DCS_STFT_INV_BLOCK 1      /* accumulator in LDS, one workgroup per run of hops (any size, float64) */
+#define DCS_STFT_INV_RING 2       /* four waves, ring of hop-blocks in LDS */
+#define DCS_STFT_INV_SEQ 3        /* one wave per run of hop-blocks, blocks in registers */
+#define DCS_STFT_INV_SEQ_STAGED 4 /* the same with the spectra brought in through LDS */
+#define DCS_STFT_INV_CHAIN 5      /* eight waves walk consecutive runs of frames and meet at seams */
+DCS_API int dcs_debug_stft_last_kernel(const dcs_stft* plan, int* forward, int* inverse, int64_t* param);
+
 #ifdef __cplusplus
 }
 #endif
