@@ -119,6 +119,17 @@ class Context(object):
                                              int(niter), float(pre_div), float(eps), _ptr(out_mag), _ptr(out_phase)))
         return out_mag, out_phase
 
+    # -- sample-rate conversion ----------------------------------------------------------------------
+    def resampler(self, fi, fo, **design):
+        """The :class:`deepconvsep_amd.resample.Resampler` of ``fi -> fo`` Hz (``design``: ``zero_crossings``, ``beta``,
+        ``rolloff``), made on first use and kept with the context."""
+        from .resample import Resampler
+        key = (int(fi), int(fo)) + tuple(sorted(design.items()))
+        cache = self.__dict__.setdefault("_resamplers", {})
+        if key not in cache:
+            cache[key] = Resampler(self, fi, fo, **design)
+        return cache[key]
+
     # -- kernel timing (bench.py) ---------------------------------------------------------------
     def timing_stride(self, stride):
         _lib.check(self._lib.dcs_timing_stride(self._h, int(stride)))
@@ -149,6 +160,8 @@ class Context(object):
 
     def close(self):
         if getattr(self, "_h", None):
+            for rs in self.__dict__.pop("_resamplers", {}).values():
+                rs.close()
             self._lib.dcs_destroy(self._h)
             self._h = None
 

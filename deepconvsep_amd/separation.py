@@ -20,6 +20,7 @@ import scipy.io.wavfile
 
 from . import _lib
 from .arch import ARCHS, TIE_ALL, TILER_LIBRARY, TILER_SCRIPT
+from .resample import TARGET_RATE, out_length as resampled_length, ratio as rate_ratio
 from .runtime import Network, StftPlan, _on_ctx_stream, default_context, overlap_add, pcm16_to_float, pcm_to_int16, tile
 
 
@@ -208,11 +209,24 @@ class Separator(object):
         if (score_normalise, score_mixture) != ('max', 'ch0'):
             self.net.set_score_semantics(score_normalise, score_mixture)
 
+    def _at_model_rate(self, a, sample_rate, run):
+        """``a`` ``[L]`` or ``[C, L]`` float32 on the device at ``sample_rate`` Hz -> ``run(a at 44 100 Hz)`` (PCM
+        ``[..., L']``) -> its signals back at ``sample_rate``, ``[rows, L]``: one conversion in front, ONE behind for all
+        the signals, cropped to the input's length (``dcs_resample_f32``); nothing leaves the device in between."""
+        L = int(a.shape[-1])
+        pcm = run(self.ctx.resampler(sample_rate, TARGET_RATE)(a))
+        back = self.ctx.resampler(TARGET_RATE, sample_rate)(pcm.reshape(-1, int(pcm.shape[-1])))
+        return back[:, :L]
+
     @_on_ctx_stream
-    def separate(self, audio):
-        """Fused device path: float audio ``[L]`` -> float64 ``[S, L]``."""
+    def separate(self, audio, sample_rate=TARGET_RATE):
+        """Fused device path: float audio ``[L]`` -> float64 ``[S, L]``.  ``sample_rate`` other than 44 100: the audio is
+        converted to 44 100 Hz on the device, separated, and the sources converted back (:meth:`_at_model_rate`)."""
         a = self.ctx.to_device(np.asarray(audio), np.float32)
-        pcm = self.net.separate(self.plan, a, self.overlap, self.tiler, self.scale_factor, None, self.tie_mode)
+
+        def run(a):
+            return self.net.separate(self.plan, a, self.overlap, self.tiler, self.scale_factor, None, self.tie_mode)
+        pcm = run(a) if int(sample_rate) == TARGET_RATE else self._at_model_rate(a, sample_rate, run)
         return self.ctx.to_host(pcm).astype(np.float64)
 
     def separate_many(self, audios, max_group=16, max_ratio=None, on_error='raise'):
@@ -457,17 +471,25 @@ class Separator(object):
 
 
     @_on_ctx_stream
-    def separate_stereo(self, audio, mwf_iters=0):
+    def separate_stereo(self, audio, mwf_iters=0, sample_rate=TARGET_RATE):
         """The "Separating" block of the stereo trainer (examples/dsd100_2ch_ILD/trainCNN_ILD_DSD100.py:291-325):
         ``audio [L, 2]`` -> ``sep_audio [L, S, 2]`` (one stereo signal per source, :299,316).
         ``mwf_iters > 0``: the per-channel estimates go through that many iterations of the multichannel Wiener filter
-        (``dcs_mwf_f32``) before the inverse transform, each (channel, source) then with its own phase."""
+        (``dcs_mwf_f32``) before the inverse transform, each (channel, source) then with its own phase.
+        ``sample_rate`` other than 44 100: both channels are converted to 44 100 Hz on the device and the 2 S separated
+        signals back in one call (:meth:`_at_model_rate`)."""
         a = self.ctx.to_device(np.ascontiguousarray(np.asarray(audio).T), np.float32)          # [2, L]
-        if not mwf_iters:
-            pcm = self.net.separate_stereo(self.plan, a, self.overlap, TILER_LIBRARY, self.scale_factor)
+
+        def run(a):
+            if not mwf_iters:
+                return self.net.separate_stereo(self.plan, a, self.overlap, TILER_LIBRARY, self.scale_factor)
+            return self.separate_stereo_mwf_device(a, int(mwf_iters))
+        if int(sample_rate) == TARGET_RATE:
+            pcm = self.ctx.to_host(run(a))
         else:
-            pcm = self.separate_stereo_mwf_device(a, int(mwf_iters))
-        return np.ascontiguousarray(self.ctx.to_host(pcm).astype(np.float64).transpose(2, 1, 0))   # [L, S, 2]
+            pcm = self.ctx.to_host(self._at_model_rate(a, sample_rate, run))                   # [2 S, L]
+            pcm = pcm.reshape(2, -1, pcm.shape[-1])
+        return np.ascontiguousarray(pcm.astype(np.float64).transpose(2, 1, 0))                  # [L, S, 2]
 
     @_on_ctx_stream
     def separate_stereo_mwf_device(self, a, mwf_iters):
@@ -487,20 +509,29 @@ class Separator(object):
         return pcm
 
     @_on_ctx_stream
-    def separate_scoreinformed(self, audio, melody, timbre_model_path=None):
+    def separate_scoreinformed(self, audio, melody, timbre_model_path=None, sample_rate=TARGET_RATE):
         """Score-informed separation (examples/bach10_scoreinformed/separate_bach10.py:497-541), stage by stage on the
         device: STFT -> x scale -> harmonic masks of the score x spectrogram (``dcs_score_masks``) -> library tiler
         with one input channel per instrument (``util.generate_overlapadd``, :531) -> network (masks from the first
         ``S`` output channels, mixture = input channel 0, :473-486) -> overlapadd_multi -> iSTFT.
         ``melody``: note tables ``[instruments, notes, 2*nharmonics+3]`` (``score.melody_table``).
         ``timbre_model_path``: the pickled harmonic templates of ``filterSpec(..., timbre_model_path)`` -- the masks are then
-        the template-weighted ones (host, ``score.timbre_masks``) and the path runs stage by stage."""
+        the template-weighted ones (host, ``score.timbre_masks``) and the path runs stage by stage.
+        ``sample_rate`` other than 44 100: the audio is converted to 44 100 Hz on the device and the sources back
+        (:meth:`_at_model_rate`); ``melody`` is then the table of the CONVERTED signal's frames
+        (``resample.out_length(L, *resample.ratio(sample_rate, 44100))`` samples at 44 100 Hz -- note files are in seconds)."""
         a = self.ctx.to_device(np.asarray(audio), np.float32)
         if timbre_model_path is not None:
             from .score import load_timbre_model
-            pcm = self._separate_scoreinformed_staged(a, melody, load_timbre_model(timbre_model_path))
-            return self.ctx.to_host(pcm).astype(np.float64)
-        return self.ctx.to_host(self.separate_scoreinformed_device(a, melody)).astype(np.float64)
+            harmonics = load_timbre_model(timbre_model_path)
+
+            def run(a):
+                return self._separate_scoreinformed_staged(a, melody, harmonics)
+        else:
+            def run(a):
+                return self.separate_scoreinformed_device(a, melody)
+        pcm = run(a) if int(sample_rate) == TARGET_RATE else self._at_model_rate(a, sample_rate, run)
+        return self.ctx.to_host(pcm).astype(np.float64)
 
     def separate_scoreinformed_device(self, a, melody, staged=False):
         """:meth:`separate_scoreinformed` on a float32 device tensor ``[L]``; returns the float32 PCM ``[S, L]`` on the
@@ -570,10 +601,12 @@ def output_paths(arch_name, filein, outdir):
 
 def train_auto(arch_name, filein, outdir, model, scale_factor=0.3, time_context=30, overlap=20, batch_size=32,
                input_size=513, frameSize=None, hopSize=None, window=None, fused=True, device=None, score_normalise='max',
-               score_mixture='ch0'):
+               score_mixture='ch0', resample=False):
     """``train_auto`` of the separate scripts: wav in, one wav per source out.  ``score_normalise`` / ``score_mixture``
     (score-informed only): ``('sum', 'sum')`` = what the trainer's own separation block computes
-    (bach10_scoreinformed/trainCNNrwc.py:360-416), for models that trainer wrote; the default is the separate script's."""
+    (bach10_scoreinformed/trainCNNrwc.py:360-416), for models that trainer wrote; the default is the separate script's.
+    ``resample=True``: a file at another rate than 44 100 Hz, which the scripts refuse, is converted on the device,
+    separated and written at ITS OWN rate (``Separator.separate(..., sample_rate=)``)."""
     d_frame, d_hop, d_win, _, _ = _SCRIPT_DEFAULTS[arch_name]
     frameSize = d_frame if frameSize is None else frameSize
     hopSize = d_hop if hopSize is None else hopSize
@@ -583,14 +616,18 @@ def train_auto(arch_name, filein, outdir, model, scale_factor=0.3, time_context=
                     hopSize, window, tiler='library' if arch_name == 'bach10_si' else 'script', device=device,
                     score_normalise=score_normalise, score_mixture=score_mixture)
     sampleRate, audioObj = read_wav(filein)
-    if sampleRate == 44100:
+    if sampleRate == 44100 or resample:
         audio = to_mono(audioObj, arch_name)
         if arch_name == 'bach10_si':
             from .score import melody_table
-            nframes = int(np.ceil(len(audio) / np.double(hopSize))) + 2     # :500
-            melody = melody_table(SI_SCORE_FILES, os.path.dirname(filein), nframes, sampleRate, hopSize, frameSize,
+            # the frames of the signal the network sees: the file's own samples, or as many as they are at 44 100 Hz
+            n44 = len(audio) if sampleRate == 44100 else resampled_length(len(audio), *rate_ratio(sampleRate, TARGET_RATE))
+            nframes = int(np.ceil(n44 / np.double(hopSize))) + 2     # :500
+            melody = melody_table(SI_SCORE_FILES, os.path.dirname(filein), nframes, TARGET_RATE, hopSize, frameSize,
                                   **SI_SCORE_PARAMS)
-            pcm = sep.separate_scoreinformed(audio, melody)
+            pcm = sep.separate_scoreinformed(audio, melody, sample_rate=sampleRate)
+        elif sampleRate != 44100:
+            pcm = sep.separate(audio, sample_rate=sampleRate)
         else:
             pcm = sep.separate(audio) if fused else sep.separate_stepwise(audio)
         for path, audio_out in zip(output_paths(arch_name, filein, outdir), pcm):

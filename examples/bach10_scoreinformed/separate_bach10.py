@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's examples/bach10_scoreinformed/separate_bach10.py, running on MI355X.
 
-    python separate_bach10.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl>
+    python separate_bach10.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl> [--trainer-semantics] [--resample]
 
 The four score files ``bassoon_b.txt, clarinet_b.txt, saxophone_b.txt, violin_b.txt`` (lines ``onset,offset,note``)
 are read from the directory of the input wav, as in the reference (:455, :516).  Same hard-coded hyper-parameters
@@ -15,7 +15,8 @@ trainCNNrwc.py ``--function build_ca_1x1`` (:66-132, ``model_*_x_*.pkl``); the g
 One extra long option, ``--trainer-semantics``: harmonic masks divided by their sum over the instruments
 (``LargeDatasetMask2.filterSpec``, dataset.py:862) and soft masks applied to the sum of the four input channels
 (trainCNNrwc.py:258-263) -- what the TRAINER's own separation block computes and what its models were trained on; without it
-the script's semantics (own maximum, :195; input channel 0, :485).
+the script's semantics (own maximum, :195; input channel 0, :485).  And ``--resample``: a file that is not at 44 100 Hz is
+converted on the device, separated and written at its own rate (the score files are in seconds and apply as they are).
 """
 import getopt
 import os
@@ -28,26 +29,28 @@ from deepconvsep_amd.separation import generate_overlapadd, load_model, overlapa
 from deepconvsep_amd.separation import train_auto as _train_auto  # noqa: E402
 from deepconvsep_amd.transform import compute_file, compute_inverse  # noqa: E402,F401
 
-USAGE = 'python separate_bach10.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl>'
+USAGE = 'python separate_bach10.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl> [--trainer-semantics] [--resample]'
 
 
 def train_auto(filein, outdir, model, scale_factor=0.3, time_context=30, overlap=20, batch_size=32, input_size=2049,
-               frameSize=4096, hopSize=512, trainer_semantics=False):
+               frameSize=4096, hopSize=512, trainer_semantics=False, resample=False):
     sem = ('sum', 'sum') if trainer_semantics else ('max', 'ch0')
     return _train_auto('bach10_si', filein, outdir, model, scale_factor, time_context, overlap, batch_size, input_size,
-                       frameSize, hopSize, score_normalise=sem[0], score_mixture=sem[1])
+                       frameSize, hopSize, score_normalise=sem[0], score_mixture=sem[1], resample=resample)
 
 
 def main(argv):
     try:
-        opts, args = getopt.getopt(argv, "hi:o:m:", ["ifile=", "odir=", "mfile=", "trainer-semantics"])
+        opts, args = getopt.getopt(argv, "hi:o:m:", ["ifile=", "odir=", "mfile=", "trainer-semantics", "resample"])
     except getopt.GetoptError:
         print(USAGE)
         sys.exit(2)
-    trainer = False
+    trainer = resample = False
     for opt, arg in opts:
         if opt == '--trainer-semantics':
             trainer = True
+        elif opt == '--resample':
+            resample = True
         elif opt == '-h':
             print(USAGE)
             sys.exit()
@@ -57,7 +60,7 @@ def main(argv):
             outdir = arg
         elif opt in ("-m", "--mfile"):
             model = arg
-    train_auto(inputfile, outdir, model, 0.3, 30, 25, 32, 2049, 4096, 512, trainer_semantics=trainer)
+    train_auto(inputfile, outdir, model, 0.3, 30, 25, 32, 2049, 4096, 512, trainer_semantics=trainer, resample=resample)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's examples/ikala/separate_ikala.py, running on MI355X.
 
-    python separate_ikala.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl>
+    python separate_ikala.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl> [--resample]
 
 Same options, hard-coded hyper-parameters and output file names as the
 reference's main() (examples/ikala/separate_ikala.py); the work is done by
@@ -19,18 +19,19 @@ from deepconvsep_amd.separation import (generate_overlapadd, load_model, overlap
 from deepconvsep_amd.separation import train_auto as _train_auto  # noqa: E402
 from deepconvsep_amd.transform import compute_file, compute_inverse  # noqa: E402,F401
 
-USAGE = 'python separate_ikala.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl>'
+USAGE = 'python separate_ikala.py -i <inputfile> -o <outputdir> -m <path_to_model.pkl> [--resample]'
 
 
 def train_auto(filein, outdir, model, scale_factor=0.3, time_context=30, overlap=20, batch_size=32, input_size=513,
-               frameSize=None, hopSize=None):
+               frameSize=None, hopSize=None, resample=False):
     return _train_auto('ikala', filein, outdir, model, scale_factor, time_context, overlap, batch_size, input_size,
-                       frameSize, hopSize)
+                       frameSize, hopSize, resample=resample)
 
 
 def main(argv):
+    resample = False
     try:
-        opts, args = getopt.getopt(argv, "hi:o:m:", ["ifile=", "odir=", "mfile="])
+        opts, args = getopt.getopt(argv, "hi:o:m:", ["ifile=", "odir=", "mfile=", "resample"])
     except getopt.GetoptError:
         print(USAGE)
         sys.exit(2)
@@ -44,7 +45,9 @@ def main(argv):
             outdir = arg
         elif opt in ("-m", "--mfile"):
             model = arg
-    train_auto(inputfile, outdir, model, 0.3, 30, 20, 32, 513)
+        elif opt == "--resample":
+            resample = True
+    train_auto(inputfile, outdir, model, 0.3, 30, 20, 32, 513, resample=resample)
 
 
 if __name__ == "__main__":

@@ -19,6 +19,8 @@ header ``scipy.io.wavfile.write`` would produce -- the output files are byte-ide
 sample format takes the float path (``read_wav`` / ``to_mono`` / ``separate_many`` / ``write_wav``) file by file.
 While the GPU separates group i the workers read group i+1 and write group i-1, and the main thread does not wait for
 the device either: a group is enqueued (``separate_many_pcm16(..., wait=False)``) and collected one iteration later.
+``--resample``: a file that is not at 44 100 Hz, which is otherwise skipped with the scripts' message, takes the float path
+alone through ``Separator.separate(..., sample_rate=rate)`` -- converted on the device, separated, written at its own rate.
 """
 import argparse
 import os
@@ -38,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--float-path", action="store_true",
                     help="force the float path of the single-file scripts (read_wav / to_mono on the host, float32 upload, "
                          "float64 download, scipy writes) also for 16-bit PCM files")
+    ap.add_argument("--resample", action="store_true",
+                    help="separate files that are not at 44100 Hz too (converted on the device, one by one, written at their "
+                         "own rate) instead of skipping them")
     ap.add_argument("--stats", action="store_true",
                     help="print one JSON line at the end: files, seconds from model-ready to the last wav written, ms per file")
     ap.add_argument("files", nargs="+")
@@ -74,7 +79,7 @@ def main(argv=None):
         """The scripts' own read (scipy) + mix-down: (path, rate, mono float signal | None | the exception)."""
         try:
             sr, audio = sp.read_wav(path)
-            return path, sr, (sp.to_mono(audio, args.arch) if sr == 44100 else None)
+            return path, sr, (sp.to_mono(audio, args.arch) if sr == 44100 or args.resample else None)
         except Exception as exc:      # a file that cannot be read or mixed down fails alone (the notebook: one process per file)
             return path, None, exc
 
@@ -105,7 +110,7 @@ def main(argv=None):
         def classify(path, sr, audio):
             if isinstance(audio, Exception):
                 failed.append((path, audio))
-            elif sr != 44100 or audio is None:
+            elif audio is None:
                 print("Sample rate is not 44100")          # separate_dsd.py:313
             else:
                 slow.append((path, sr, audio))
@@ -119,6 +124,8 @@ def main(argv=None):
                 failed.append((path, got))
             elif got is None:                                # not plain 16-bit PCM: the scripts' float path for this file
                 classify(*read_float(path))
+            elif got[0] != 44100 and args.resample:           # one by one on the float path, at its own rate
+                classify(*read_float(path))
             elif got[0] != 44100:
                 print("Sample rate is not 44100")
             else:
@@ -126,6 +133,21 @@ def main(argv=None):
                 t = arena[offs[j]:offs[j] + 2 * frames * ch].view(torch.int16)
                 fast.append((path, sr, t if ch == 1 else t.view(frames, ch)))
         return fast, slow
+
+    def separate_slow(slow):
+        """Float-path files: those at 44 100 Hz share launches, the others (--resample) go one by one."""
+        res = [None] * len(slow)
+        at44 = [k for k, (_, sr, _) in enumerate(slow) if sr == 44100]
+        if at44:
+            for k, pcm in zip(at44, sep.separate_many([slow[k][2] for k in at44], on_error='return')):
+                res[k] = pcm
+        for k, (_, sr, audio) in enumerate(slow):
+            if sr != 44100:
+                try:
+                    res[k] = sep.separate(audio, sample_rate=sr)
+                except Exception as exc:
+                    res[k] = exc
+        return res
 
     def out_dir(path):
         return os.path.join(args.odir, os.path.splitext(os.path.basename(path))[0])
@@ -192,7 +214,7 @@ def main(argv=None):
             t0 = now()
             h16 = (sep.separate_many_pcm16([a for _, _, a in fast], max_group=max(16, G), on_error='return', wait=False)
                    if fast else None)
-            resf = sep.separate_many([a for _, _, a in slow], on_error='return') if slow else []
+            resf = separate_slow(slow)
             t_stage["enqueue"] += now() - t0
             # the arena of chunk ci + 1 was last used by chunk ci - 2, collected in the previous iteration
             t0 = now()

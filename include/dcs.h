@@ -458,6 +458,33 @@ DCS_API int dcs_mwf_f32(dcs_ctx* ctx, const float* mag_d, const float* phase_d, 
  * pass adds up min(ceil(n_frames / this), 32) sets of sums */
 DCS_API int dcs_mwf_frames_per_block(void);
 
+/* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
+/* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is
+ * the rate change in front of the STFT and behind the iSTFT that lets every other file through.  For up / down = fo / fi in
+ * lowest terms and a filter h[t], t = -half .. half, on the grid of rate up * fi (designed on the host in float64,
+ * deepconvsep_amd/resample.py: Kaiser-windowed sinc, cut-off rolloff * min(fi, fo) / 2):
+ *   y[m] = sum_n x[n] h[m down - n up],   0 <= n < n_in,  |m down - n up| <= half,   m = 0 .. ceil(n_in up / down) - 1
+ * (scipy.signal.resample_poly(x, up, down, window=h / up)): x is zero outside [0, n_in), the filter is centred, no delay. */
+typedef struct dcs_resampler dcs_resampler;
+/* ceil(n_samples * up / down); -1 for n_samples < 0, up < 1, down < 1 or a product past int64 */
+DCS_API int64_t dcs_resample_length(int64_t n_samples, int up, int down);
+/* taps_h: the 2 half + 1 values of h (host, float64).  They are stored as float32, one row per phase p = (m down) mod up
+ * holding that phase's taps h[p + j up] in the order the kernel adds them (ascending n).  DCS_EINVAL for up < 1, down < 1,
+ * half < 0 (checked before anything else) or a NULL pointer.  DCS_EUNSUPPORTED for what the plan cannot hold: up or down above
+ * 2^20; a table of up x round_up(2 half / up + 1, 4) float32 above 1 MiB (32 zero crossings at rolloff 0.95 need 43 KB for
+ * 160/147, 44 KB for 147/160, 85 KB for 147/320, 117 KB for 441/320, 441/160 and 441/80); 256 consecutive outputs reaching over more than 64 KiB of input
+ * (256 down / up + 2 half / up samples).  Synchronous (two small uploads). */
+DCS_API int dcs_resample_plan(dcs_ctx* ctx, int up, int down, const double* taps_h, int64_t half, dcs_resampler** out);
+DCS_API int dcs_resample_plan_destroy(dcs_resampler* r);
+/* n_clips signals of n_in float32 samples, signal k at in_d + k in_stride, -> dcs_resample_length(n_in, up, down) samples each
+ * at out_d + k out_stride (strides in elements, at least the lengths when n_clips > 1), ONE launch.  Nothing outside [in_d + k
+ * in_stride, + n_in) is read and nothing outside the outputs written.  Float32 arithmetic: every output is one fmaf chain over
+ * its taps in ascending n -- the order depends on (up, down, half) only, so a batched call, a single one and a longer signal
+ * with the same samples under the window give the same bits.  n_in == 0 or n_clips == 0 does nothing.  Enqueued on the ctx
+ * stream of the plan. */
+DCS_API int dcs_resample_f32(dcs_resampler* r, const float* in_d, int64_t n_in, int64_t n_clips, int64_t in_stride,
+                             float* out_d, int64_t out_stride);
+
 /* ------------------------------------------------------------------ timing aid for bench.py */
 /* Average duration (ms) of the kernels tagged `which` since the last reset, measured with HIP events
  * on the ctx stream.  tag_mask bit t enables the tag t (two event records per tagged launch);
