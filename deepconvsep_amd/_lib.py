@@ -113,6 +113,13 @@ def load():
     proto("dcs_debug_stft_forward_f32", i32, vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, i32, vp)
     proto("dcs_debug_stft_inverse_unit_f32", i32, vp, vp, i64, vp, i64, i64, i64, i32, i64, f32, vp, i64, vp, i64)
     proto("dcs_debug_stft_last_kernel", i32, vp, POINTER(i32), POINTER(i32), POINTER(i64))
+    proto("dcs_debug_gemm", i32, vp, i32, vp)
+    proto("dcs_debug_gemm_f16_skinny", i32, vp, vp, i64, i64, i32, i32, i32, i32, POINTER(vp), i64, POINTER(vp), i64, POINTER(vp),
+          i64, i64, vp, i64)
+    proto("dcs_debug_gemm_f16_longk", i32, vp, vp, i64, i64, i32, i32, i32, vp, i64, i32, vp, i64, vp, i64, i64, i32, i32)
+    proto("dcs_debug_gemm_bytes", i64, i32, i32, i32)
+    proto("dcs_debug_gemm_pack", i32, vp, i32, vp, i64, i32, i64, i32, POINTER(i64), vp, i64)
+    proto("dcs_debug_gemm_last_kernel", i32, vp, POINTER(i32), POINTER(i64))
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)

@@ -150,6 +150,14 @@ struct dcs_ctx {
     DcsUploadRing score_ring;  // note rectangles and floor values of dcs_score_masks
     DcsBuffer bss_ws;          // dcs_bss_energies / dcs_bss_lagcorr: segment sums, lag correlations, Gram matrices
     DcsBuffer mwf_ws;          // dcs_mwf_f32: v [J][T][F] float32 and the two sets of per-chunk sums
+    // which kernel the last GEMM launch took (DCS_GEMM_K_*, 0 = none yet) and {ksplit, kchunk, row blocks of 16 per workgroup, Aq used}
+    // (0 where there is none): dcs_debug_gemm_last_kernel, a test aid -- one host store per launch
+    int last_gemm = 0;
+    int64_t last_gemm_param[4] = {0, 0, 0, 0};
+    void note_gemm(int code, int64_t ksplit = 0, int64_t kchunk = 0, int64_t rbt = 0, int64_t aq = 0) {
+        last_gemm = code;
+        last_gemm_param[0] = ksplit; last_gemm_param[1] = kchunk; last_gemm_param[2] = rbt; last_gemm_param[3] = aq;
+    }
 };
 
 // RAII-ish helper: records a start event on construction and a stop event in done().
@@ -283,6 +291,8 @@ void dcs_launch_gemm_longk_reduce(dcs_ctx* ctx, const DcsGemm& q, int ksplit);  
 // A [M][K] f32 (lda) -> bf16 x 3 planes for DcsGemm::Aq: [(K + 31) / 32][3][rows_pad][4] 16-byte pieces, rows >= M and k >= K zero
 size_t dcs_gemm_aq_bytes(int K, int rows_pad);
 int dcs_gemm_split_a(dcs_ctx* ctx, const float* A_d, int64_t lda, int64_t M, int K, int rows_pad, void* Aq_d);
+// DcsGemm::Bfrag on the host: B [K rows][ldb] -> out [n_cols / 16][dcs_bfrag_chunks(K)][64 lanes][4] floats, the chunks past K zero
+void dcs_gemm_pack_bfrag(const float* B, int K, int ldb, int n_cols, float* out);
 
 int dcs_score_masks_scaled(dcs_ctx* ctx, const float* mag_d, int64_t ld, int64_t n_frames, int F, const double* notes_h,
                            int ninst, int n_notes, int width, int64_t start, int64_t stop, float mag_scale, float* out_d,

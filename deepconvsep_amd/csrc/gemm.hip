@@ -332,6 +332,8 @@ __global__ __launch_bounds__(kThreads) void gemm_ksplit_reduce_kernel(const DcsG
 
 template <int RB, int BK>
 void launch_rb(dcs_ctx* ctx, const DcsGemm& g) {
+    ctx->note_gemm((BK == 128 ? DCS_GEMM_K_ROWS_1_128 : RB == 1 ? DCS_GEMM_K_ROWS_1_32 : RB == 2 ? DCS_GEMM_K_ROWS_2_32 : DCS_GEMM_K_ROWS_4_32) +
+                   (g.a_vec ? 1 : 0), 0, 0, RB);
     dim3 grid((unsigned)dcs_cdiv(g.M, 16 * RB), (unsigned)(g.n_cols / BN));
     if (g.a_vec)
         hipLaunchKernelGGL((gemm_rows_kernel<RB, BK, true>), grid, dim3(kThreads), 0, ctx->stream, g);
@@ -340,6 +342,17 @@ void launch_rb(dcs_ctx* ctx, const DcsGemm& g) {
 }
 
 }  // namespace
+
+void dcs_gemm_pack_bfrag(const float* B, int K, int ldb, int n_cols, float* out) {
+    const int kc = dcs_bfrag_chunks(K), nt = n_cols / 16;
+    for (int t = 0; t < nt; ++t)
+        for (int c = 0; c < kc; ++c)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e) {
+                    const int k = 16 * c + 4 * (lane >> 4) + e;
+                    out[(((size_t)t * kc + c) * 64 + lane) * 4 + e] = k < K ? B[(size_t)k * ldb + 16 * t + (lane & 15)] : 0.f;
+                }
+}
 
 int dcs_launch_gemm_rows(dcs_ctx* ctx, const DcsGemm& g, int tag) {
     if (g.M <= 0) return DCS_OK;
@@ -380,6 +393,7 @@ int dcs_launch_gemm_rows(dcs_ctx* ctx, const DcsGemm& g, int tag) {
             q.xcd_slices = xcd_env ? 1 : 0;
             // 64 x 64 LDS tiles reuse every operand 4x more often than the 16 x 16 register tiles (which stream A and B
             // from L2 with 4 flop/B): worth it from a few row groups on
+            ctx->note_gemm(tiled ? DCS_GEMM_K_KSPLIT_64 : DCS_GEMM_K_KSPLIT_16, ksplit, kchunk, tiled ? 4 : 1);
             if (tiled)
                 hipLaunchKernelGGL((gemm_rows_kernel<4, 32, true>), dim3((unsigned)dcs_cdiv(g.M, 64), (unsigned)(g.n_cols / BN),
                                                                           (unsigned)ksplit),
@@ -414,6 +428,7 @@ int dcs_launch_gemm_rows(dcs_ctx* ctx, const DcsGemm& g, int tag) {
     const int64_t sk_max = sk_env >= 0 ? sk_env : (int64_t)ctx->n_cu / 2;
     if (g.a_vec && groups16 * col_groups <= sk_max) {
         dim3 grid((unsigned)groups16, (unsigned)(g.n_cols / 16));
+        ctx->note_gemm(g.Bfrag ? DCS_GEMM_K_SPLITK_BFRAG : DCS_GEMM_K_SPLITK, 0, 0, 1);
         if (g.Bfrag) hipLaunchKernelGGL(gemm_rows_splitk_kernel<true>, grid, dim3(kThreads), 0, ctx->stream, g);
         else hipLaunchKernelGGL(gemm_rows_splitk_kernel<false>, grid, dim3(kThreads), 0, ctx->stream, g);
     } else if (groups16 * col_groups <= 2 * (int64_t)ctx->n_cu)

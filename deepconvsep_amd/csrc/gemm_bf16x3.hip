@@ -524,6 +524,7 @@ bool dcs_launch_gemm_bf16x3_longk(dcs_ctx* ctx, const DcsGemm& g) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
     DcsGemmBranches none{};
+    ctx->note_gemm((rbt == 8 ? DCS_GEMM_K_LONGK_8 : DCS_GEMM_K_LONGK_11) + (g.bq_f32 ? 1 : 0), ksplit, q.kchunk, rbt);
     hipLaunchKernelGGL(kern, dim3((unsigned)col_wgs, 1, (unsigned)ksplit), dim3(kThreads), lds, ctx->stream, q, none);
     hipLaunchKernelGGL(gemm_longk_reduce_kernel, dim3((unsigned)dcs_cdiv(g.M * g.n_cols, 64)), dim3(kThreads), 0, ctx->stream, q, ksplit);
     return true;
@@ -570,6 +571,8 @@ bool dcs_launch_gemm_bf16x3(dcs_ctx* ctx, const DcsGemm& g) {
     if (groups16 * col_groups <= 4 * (int64_t)ctx->n_cu || g.n_cols < 1024 || g.M < 128) return false;
     if (dcs_launch_gemm_bf16x3_skinny(ctx, g, nullptr)) return true;
     constexpr int xcd_map = 1;
+    ctx->note_gemm(groups16 * col_groups <= 16 * (int64_t)ctx->n_cu ? DCS_GEMM_K_BF16X3_2 : DCS_GEMM_K_BF16X3_4, 0, 0,
+                   groups16 * col_groups <= 16 * (int64_t)ctx->n_cu ? 2 : 4);
     if (groups16 * col_groups <= 16 * (int64_t)ctx->n_cu)
         hipLaunchKernelGGL((gemm_bf16x3_kernel<2>), dim3((unsigned)dcs_cdiv(g.M, 32), (unsigned)col_groups), dim3(kThreads), 0,
                            ctx->stream, g, xcd_map);
@@ -609,6 +612,7 @@ bool dcs_launch_gemm_bf16x3_skinny(dcs_ctx* ctx, const DcsGemm& g, const DcsGemm
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
+    ctx->note_gemm((rbt == 8 ? DCS_GEMM_K_SKINNY_8 : DCS_GEMM_K_SKINNY_11) + (aq ? 1 : 0) + (g.bq_f32 ? 2 : 0), 0, 0, rbt, aq ? 1 : 0);
     hipLaunchKernelGGL(kern, dim3((unsigned)dcs_cdiv(g.n_cols, 64 * cb), (unsigned)(b.n > 0 ? b.n : 1)), dim3(kThreads), lds,
                        ctx->stream, g, b);
     return true;

@@ -354,6 +354,7 @@ bool dcs_launch_gemm_f16_skinny(dcs_ctx* ctx, const float* Z, int64_t ldz, int M
         g.C[b] = reinterpret_cast<_Float16*>(C[b]);
     }
     const dim3 grid((unsigned)(n_cols / 128), (unsigned)n_br);
+    ctx->note_gemm(rows_pad == 128 ? DCS_GEMM_K_F16_SKINNY_8 : DCS_GEMM_K_F16_SKINNY_11, 0, 0, rows_pad / 16);
     if (rows_pad == 128) hipLaunchKernelGGL((gemm_f16_skinny_kernel<8>), grid, dim3(kThreads), 0, ctx->stream, g);
     else hipLaunchKernelGGL((gemm_f16_skinny_kernel<11>), grid, dim3(kThreads), 0, ctx->stream, g);
     return true;
@@ -387,6 +388,7 @@ bool dcs_launch_gemm_f16_longk(dcs_ctx* ctx, const void* A, int64_t lda, int M, 
     g.partial = partial;
     g.kts = (nkt + ksplit - 1) / ksplit;
     const dim3 grid((unsigned)(n_cols / 128), 1, (unsigned)ksplit);
+    ctx->note_gemm((M <= 128 ? DCS_GEMM_K_F16_LONGK_8 : DCS_GEMM_K_F16_LONGK_11) + (a_f16 ? 1 : 0), ksplit, (int64_t)g.kts * 32, M <= 128 ? 8 : 11);
     if (a_f16) {
         if (M <= 128) hipLaunchKernelGGL((gemm_f16_longk_kernel<8, true>), grid, dim3(kThreads), 0, ctx->stream, g);
         else hipLaunchKernelGGL((gemm_f16_longk_kernel<11, true>), grid, dim3(kThreads), 0, ctx->stream, g);

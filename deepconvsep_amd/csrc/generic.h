@@ -70,6 +70,7 @@ void dcs_decoder_fused_pack(const float* W1p, int nf1, int C, std::vector<uint16
 bool dcs_decoder_fused_ok(const DcsColConv& a, int F);
 // gemm_f16.hip: the per-source dense layers on f16 weights, f16 channels-last output (f16 switch + fused decoder)
 size_t dcs_gemm_bh_bytes(int K, int n_out);
+size_t dcs_gemm_ah_bytes(int K, int rows_pad);   // the two f16 planes of A that dcs_launch_gemm_f16_skinny leaves in Ah_scratch
 int dcs_gemm_pack_bh(dcs_ctx* ctx, const float* B_d, int K, int ldb, int n_out, int nch, int npos, int chpad, void* Bh_d);
 int dcs_gemm_pack_bias_cl(dcs_ctx* ctx, const float* bias_d, int n_out, int nch, int npos, int chpad, float* out_d);
 int dcs_gemm_pack_bh_plain(dcs_ctx* ctx, const float* B_d, int K, int ldb, int n_cols, void* Bh_d);   // B in its own column order

@@ -296,13 +296,7 @@ int pack_dsd(dcs_model* m, const std::vector<std::vector<float>>& P) {
             // 64-K steps per column block, the chunks past K zero
             const int K = m->tc * CI, kc = dcs_bfrag_chunks(K), nt = m->hid64 / 16;
             std::vector<float> fr((size_t)nt * kc * 64 * 4, 0.f);
-            for (int t = 0; t < nt; ++t)
-                for (int c = 0; c < kc; ++c)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e) {
-                            const int k = 16 * c + 4 * (lane >> 4) + e;
-                            if (k < K) fr[(((size_t)t * kc + c) * 64 + lane) * 4 + e] = B2fc[(size_t)k * m->hid64 + 16 * t + (lane & 15)];
-                        }
+            dcs_gemm_pack_bfrag(B2fc.data(), K, m->hid64, m->hid64, fr.data());
             DCS_CHECK(upload(&m->B2fc_frag, fr, "dsd.B2fc_frag"));
         }
     }

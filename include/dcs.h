@@ -758,6 +758,109 @@ DCS_API int dcs_debug_stft_inverse_unit_f32(dcs_stft* plan, const float* mag_d, 
 #define DCS_STFT_INV_CHAIN 5      /* eight waves walk consecutive runs of frames and meet at seams */
 DCS_API int dcs_debug_stft_last_kernel(const dcs_stft* plan, int* forward, int* inverse, int64_t* param);
 
+/* Test aids for the GEMM kernels and operand packers of csrc/gemm.hip, gemm_bf16x3.hip and gemm_f16.hip
+ * (tests/test_gpu_gemm_kernels.py); no reference counterpart.  The contract of every kernel:
+ *   C[crow(r)][0 .. n_store) = act(a_scale * A[arow(r)][0 .. K) . B[K][ldb] + bias),   r = 0 .. M - 1
+ *   arow(r) = a_rowmap ? a_rowmap[r] : (r / a_gdiv) * a_gmul + r % a_gdiv  (rows of lda floats), crow alike with ldc.
+ * B is padded with zero rows to round_up(K, 128) rows, ldb and n_cols are multiples of 64.  Every buffer comes with its
+ * element count (n_*: floats, ints for the row map; *_bytes: bytes) and the entry refuses with DCS_EINVAL, launching
+ * nothing, an argument set whose largest address lies outside those counts -- the row map is read back from the device
+ * and checked (one stream synchronisation per call: these are no production entry points) -- or whose pointers are not
+ * 16-byte aligned.  A launcher that does not take the shape yields DCS_EUNSUPPORTED.
+ *   which = DCS_GEMM_VIA_ROWS   dcs_launch_gemm_rows, the launcher of the graphs, with its own choice of kernel and its
+ *                               own refusals (n_cols % 64; a_vec with K % 4 or lda % 4)
+ *           DCS_GEMM_VIA_SKINNY the all-rows bf16 x 3 kernel; n_br = 0: Bq / bias / C, n_br = 1 .. 4: br_Bq / br_bias /
+ *                               br_C (each of Bq_bytes, n_bias, n_C; a branch's bias may be null)
+ *           DCS_GEMM_VIA_LONGK  the bf16 x 3 long-K launch (slices into the context's scratch, then the reduce pass)
+ * Bq (nullable): dcs_debug_gemm_pack's DCS_GEMM_PACK_BQ planes, or with bq_f32 its DCS_GEMM_PACK_B32 pieces; Aq
+ * (nullable): DCS_GEMM_PACK_SPLIT_A planes of aq_rows rows; Bfrag (nullable): DCS_GEMM_PACK_BFRAG order. */
+typedef struct dcs_debug_gemm_args {
+    const float* A; int64_t n_A; int64_t lda; int32_t a_gdiv; int64_t a_gmul; float a_scale;
+    const int32_t* a_rowmap; int64_t n_rowmap;
+    const float* B; int64_t n_B; int32_t ldb;
+    const float* bias; int64_t n_bias;
+    float* C; int64_t n_C; int64_t ldc; int32_t c_gdiv; int64_t c_gmul;
+    int64_t M; int32_t n_cols, n_store, K, relu, a_vec;
+    const void* Bq; int64_t Bq_bytes; int32_t bq_f32;
+    const void* Aq; int64_t Aq_bytes; int32_t aq_rows;
+    const float* Bfrag; int64_t n_Bfrag;
+    int32_t n_br;
+    const void* br_Bq[4]; const float* br_bias[4]; float* br_C[4];
+} dcs_debug_gemm_args;
+#define DCS_GEMM_VIA_ROWS 0
+#define DCS_GEMM_VIA_SKINNY 1
+#define DCS_GEMM_VIA_LONGK 2
+DCS_API int dcs_debug_gemm(dcs_ctx* ctx, int which, const dcs_debug_gemm_args* args);
+/* The f16 all-rows kernel: C_b[M][n_cols] halves (ldc apart) = f16(relu(Z . Bh_b + bias_b)), b < n_br; Z [M][K] floats ldz
+ * apart; Bh_b: DCS_GEMM_PACK_BH planes of Bh_bytes each; bias_b: n_bias >= n_cols floats; C_b: n_C halves; Ah_scratch:
+ * Ah_bytes >= dcs_debug_gemm_bytes(DCS_GEMM_PACK_SPLIT_A_F16, K, M <= 128 ? 128 : 176) -- the launcher leaves A's two f16
+ * planes there ([k tile][plane][rows][4 pieces of 8 k]; rows >= M zero). */
+DCS_API int dcs_debug_gemm_f16_skinny(dcs_ctx* ctx, const float* Z_d, int64_t n_Z, int64_t ldz, int M, int K, int n_cols,
+                                      int n_br, const void* const* Bh_d, int64_t Bh_bytes, const float* const* bias_d,
+                                      int64_t n_bias, void* const* C_d, int64_t n_C, int64_t ldc, void* Ah_scratch_d,
+                                      int64_t Ah_bytes);
+/* The f16 long-K kernel and the reduce pass behind it: C[M][n_store) floats = act(A . Bh + bias).  A: n_A elements, floats
+ * (a_f16 = 0) or halves (a_f16 != 0: K == lda, lda % 32 == 0); Bh: one f16 plane of n_cols columns. */
+DCS_API int dcs_debug_gemm_f16_longk(dcs_ctx* ctx, const void* A_d, int64_t n_A, int64_t lda, int M, int K, int n_cols,
+                                     const void* Bh_d, int64_t Bh_bytes, int a_f16, const float* bias_d, int64_t n_bias,
+                                     float* C_d, int64_t n_C, int64_t ldc, int n_store, int relu);
+/* The packing kernels.  p[0 .. 3] by kind:
+ *   DCS_GEMM_PACK_BQ / _B32     src B [K][ld] floats, n columns; p = {perm_c, perm_p}: output column j < perm_c * perm_p is
+ *                               source column (j % perm_c) * perm_p + j / perm_c
+ *   DCS_GEMM_PACK_BH            src B [K][ld], n output columns; p = {nch, npos, chpad}: output column pos * chpad + ch is
+ *                               source column ch * npos + pos, zero for ch >= nch or pos >= npos.  _BH_PLAIN: no p
+ *   DCS_GEMM_PACK_BIAS_CL       src bias [nch * npos], n outputs, p as for _BH; K and ld unused
+ *   DCS_GEMM_PACK_SPLIT_A       src A [p[0] = M rows][ld], n = rows_pad
+ *   DCS_GEMM_PACK_BFRAG         on the HOST: src and dst are host pointers (the packer of the DSD model's folded layer)
+ * dst holds dst_bytes >= dcs_debug_gemm_bytes(kind, K, n) bytes.  DCS_GEMM_PACK_SPLIT_A_F16 has a size only: its kernel
+ * runs inside dcs_debug_gemm_f16_skinny. */
+#define DCS_GEMM_PACK_BQ 0
+#define DCS_GEMM_PACK_B32 1
+#define DCS_GEMM_PACK_BH 2
+#define DCS_GEMM_PACK_BH_PLAIN 3
+#define DCS_GEMM_PACK_BIAS_CL 4
+#define DCS_GEMM_PACK_SPLIT_A 5
+#define DCS_GEMM_PACK_BFRAG 6
+#define DCS_GEMM_PACK_SPLIT_A_F16 7
+DCS_API int64_t dcs_debug_gemm_bytes(int kind, int K, int n);
+DCS_API int dcs_debug_gemm_pack(dcs_ctx* ctx, int kind, const float* src, int64_t n_src, int K, int64_t ld, int n,
+                                const int64_t* p, void* dst, int64_t dst_bytes);
+/* Which kernel the context's last GEMM launch ran (any entry point; 0 = none yet) and params = {K slices, K per slice, row
+ * blocks of 16 per workgroup, 1 if pre-split rows (Aq) were used}, 0 where there is none.  One host store per launch. */
+#define DCS_GEMM_K_ROWS_1_128 1          /* gemm_rows_kernel<1, 128, false>; + 1: the float4 (a_vec) instance */
+#define DCS_GEMM_K_ROWS_1_128_VEC 2
+#define DCS_GEMM_K_ROWS_1_32 3
+#define DCS_GEMM_K_ROWS_1_32_VEC 4
+#define DCS_GEMM_K_ROWS_2_32 5
+#define DCS_GEMM_K_ROWS_2_32_VEC 6
+#define DCS_GEMM_K_ROWS_4_32 7
+#define DCS_GEMM_K_ROWS_4_32_VEC 8
+#define DCS_GEMM_K_SPLITK 9              /* gemm_rows_splitk_kernel<false>, all of K */
+#define DCS_GEMM_K_SPLITK_BFRAG 10       /* gemm_rows_splitk_kernel<true> */
+#define DCS_GEMM_K_KSPLIT_16 11          /* gemm_rows_splitk_kernel<false> per K slice + gemm_ksplit_reduce_kernel */
+#define DCS_GEMM_K_KSPLIT_64 12          /* gemm_rows_kernel<4, 32, true> per K slice + gemm_ksplit_reduce_kernel */
+#define DCS_GEMM_K_BF16X3_2 13           /* gemm_bf16x3_kernel<2> */
+#define DCS_GEMM_K_BF16X3_4 14
+#define DCS_GEMM_K_SKINNY_8 15           /* gemm_bf16x3_skinny_kernel<8, 2>; + 1: AQ, + 2: B32 */
+#define DCS_GEMM_K_SKINNY_8_AQ 16
+#define DCS_GEMM_K_SKINNY_8_B32 17
+#define DCS_GEMM_K_SKINNY_8_AQ_B32 18
+#define DCS_GEMM_K_SKINNY_11 19
+#define DCS_GEMM_K_SKINNY_11_AQ 20
+#define DCS_GEMM_K_SKINNY_11_B32 21
+#define DCS_GEMM_K_SKINNY_11_AQ_B32 22
+#define DCS_GEMM_K_LONGK_8 23            /* the same kernel per K slice + gemm_longk_reduce_kernel; + 1: B32 */
+#define DCS_GEMM_K_LONGK_8_B32 24
+#define DCS_GEMM_K_LONGK_11 25
+#define DCS_GEMM_K_LONGK_11_B32 26
+#define DCS_GEMM_K_F16_SKINNY_8 27       /* gemm_split_a_f16_kernel + gemm_f16_skinny_kernel<8> */
+#define DCS_GEMM_K_F16_SKINNY_11 28
+#define DCS_GEMM_K_F16_LONGK_8 29        /* gemm_f16_longk_kernel<8, false>; + 1: f16 rows (A16) */
+#define DCS_GEMM_K_F16_LONGK_8_A16 30
+#define DCS_GEMM_K_F16_LONGK_11 31
+#define DCS_GEMM_K_F16_LONGK_11_A16 32
+DCS_API int dcs_debug_gemm_last_kernel(const dcs_ctx* ctx, int* code, int64_t* params);
+
 #ifdef __cplusplus
 }
 #endif
