@@ -124,6 +124,8 @@ def load():
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)
     proto("dcs_mwf_frames_per_block", i32)
+    proto("dcs_mask_fold_apply", i32, vp, vp, i64, i64, i32, i32, i32, i32, i32, POINTER(c_double), vp, i64, i32, i64, i64, vp,
+          i64, i64, vp, i64)
     proto("dcs_resample_length", i64, i64, i32, i32)
     proto("dcs_resample_plan", i32, vp, i32, i32, POINTER(c_double), i64, POINTER(vp))
     proto("dcs_resample_plan_destroy", i32, vp)

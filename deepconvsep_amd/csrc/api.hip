@@ -613,6 +613,12 @@ extern "C" int dcs_overlap_add(dcs_ctx* ctx, const float* out_d, int64_t n, int 
         DCS_FAIL(DCS_EINVAL, "dcs_overlap_add: bad shape");
     if (ov > 256) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_overlap_add: overlap > 256");
     DCS_ON_DEVICE(ctx->device);
+    DCS_CHECK(dcs_ctx_ola_rise(ctx, rise_h, ov));
+    return dcs_launch_overlap_add(ctx, out_d, n, S, tc, ov, F, ctx->ola_rise_d, sep_d, sep_stride, ld);
+}
+
+// the context's cross-fade ramp (ctx->ola_rise_d) holds rise_h[0 .. ov) as float32 on return: uploaded when the values change
+int dcs_ctx_ola_rise(dcs_ctx* ctx, const double* rise_h, int ov) {
     std::vector<float> rise(ov);
     for (int i = 0; i < ov; ++i) rise[i] = (float)rise_h[i];
     if (ov > 0 && (rise != ctx->ola_rise_h || !ctx->ola_rise_d)) {
@@ -625,5 +631,5 @@ extern "C" int dcs_overlap_add(dcs_ctx* ctx, const float* out_d, int64_t n, int 
         DCS_HIP(hipMemcpy(ctx->ola_rise_d, rise.data(), ov * sizeof(float), hipMemcpyHostToDevice));
         ctx->ola_rise_h = rise;
     }
-    return dcs_launch_overlap_add(ctx, out_d, n, S, tc, ov, F, ctx->ola_rise_d, sep_d, sep_stride, ld);
+    return DCS_OK;
 }

@@ -304,3 +304,5 @@ int dcs_launch_tile(dcs_ctx* ctx, const float* mag, int64_t ch_stride, int64_t l
 // out: source s of the n tiles at out + s * out_src_stride (0: dense [S][n][tc][F])
 int dcs_launch_overlap_add(dcs_ctx* ctx, const float* out, int64_t n, int S, int tc, int ov, int F,
                            const float* rise_d, float* sep, int64_t sep_stride, int64_t ld, int64_t out_src_stride = 0);
+// ctx->ola_rise_d = rise_h[0 .. ov) as float32 (api.hip): uploaded, after a stream synchronisation, when the values change
+int dcs_ctx_ola_rise(dcs_ctx* ctx, const double* rise_h, int ov);

@@ -360,15 +360,17 @@ class Network(object):
         return out
 
     @_on_ctx_stream
-    def forward_raw(self, tiles_t, tie_mode=TIE_ALL):
+    def forward_raw(self, tiles_t, tie_mode=TIE_ALL, channel_major=False):
         """Network output before masking, ``[n, out_channels, tc, F]`` (testing aid).  For the DSD
-        graph the kernel emits channel-major ``[out_channels, n, tc, F]``; it is permuted here."""
+        graph the kernel emits channel-major ``[out_channels, n, tc, F]``; it is permuted here.
+        ``channel_major=True``: the buffer as ``dcs_model_forward`` wrote it, ``[out_channels, n, tc, F]``, no copy
+        (what :func:`mask_fold_apply` reads)."""
         torch = _torch()
         n = int(tiles_t.shape[0])
         tiles_t = tiles_t.contiguous()
         out = torch.empty((self.out_channels, n, self.tc, self.F), dtype=torch.float32, device=tiles_t.device)
         _lib.check(self.ctx._lib.dcs_model_forward(self._h, _ptr(tiles_t), n, int(tie_mode), _ptr(out)))
-        return out.permute(1, 0, 2, 3).contiguous()
+        return out if channel_major else out.permute(1, 0, 2, 3).contiguous()
 
     @_on_ctx_stream
     def separate(self, plan, audio_t, overlap, tiler=TILER_SCRIPT, scale=0.3, eps_mode=None, tie_mode=TIE_ALL,
@@ -522,6 +524,38 @@ def tile(ctx, mag_t, time_context, overlap, tiler, scale=1.0):
 def mwf(ctx, mag_t, phase_t, src_t, niter, pre_div=1.0, eps=1e-10):
     """:meth:`Context.mwf`: the multichannel Wiener filter the reference left unfinished (util.py:633-719) on the device."""
     return ctx.mwf(mag_t, phase_t, src_t, niter, pre_div, eps)
+
+
+def mask_fold_apply(ctx, p, mag, time_context, overlap, eps_mode, n_frames=None, want_mask=False):
+    """``dcs_mask_fold_apply``: the soft masks of the rectified network output ``p`` ``[S, n, tc, F]`` (the first ``S``
+    channels of ``Network.forward_raw(..., channel_major=True)``; a view whose source stride is larger is fine), cross-faded
+    over the tiles like ``overlapadd_multi``, times the magnitudes ``mag`` ``[C, T, F]`` of every channel -> ``est``
+    ``[C, S, n_frames, F]`` (``n_frames`` defaults to ``T``; rows past the last tile are zero) and, with ``want_mask``, the
+    cross-faded masks ``[S, n_frames, F]`` as well.  float32 device tensors; ``eps_mode`` ``EPS_A`` or ``EPS_B``."""
+    torch = _torch()
+    if p.dim() != 4 or mag.dim() != 3 or int(p.shape[2]) != int(time_context) or int(p.shape[3]) != int(mag.shape[2]):
+        raise ValueError("mask_fold_apply expects p [S, n, %d, F] and mag [C, T, F], got %r and %r"
+                         % (int(time_context), tuple(p.shape), tuple(mag.shape)))
+    if any(t.dtype != torch.float32 or t.device != ctx.device for t in (p, mag)):
+        raise ValueError("mask_fold_apply expects float32 tensors on %s" % (ctx.device,))
+    S, n, tc, F = (int(x) for x in p.shape)
+    C, T = int(mag.shape[0]), int(mag.shape[1])
+    rows = T if n_frames is None else int(n_frames)
+    if rows < 0 or rows > T:
+        raise ValueError("mask_fold_apply: n_frames %d outside 0 .. %d, the rows of mag" % (rows, T))
+    rise = np.ascontiguousarray(np.linspace(0., 1.0, num=int(overlap)), dtype=np.float64)
+    with ctx.stream_scope():
+        if n == 0:
+            p = torch.empty((S, 1), dtype=torch.float32, device=mag.device)   # never read; an empty tensor has no address
+        elif (S > 1 and p.stride(0) < n * tc * F) or not p[0].is_contiguous():
+            p = p.contiguous()
+        mag = mag.contiguous()
+        est = torch.empty((C, S, rows, F), dtype=torch.float32, device=mag.device)
+        mask = torch.empty((S, rows, F), dtype=torch.float32, device=mag.device) if want_mask else None
+        _lib.check(ctx._lib.dcs_mask_fold_apply(ctx._h, _ptr(p), int(p.stride(0)), n, S, tc, int(overlap), F, int(eps_mode),
+                                                rise.ctypes.data_as(POINTER(c_double)), _ptr(mag), T * F, C, rows, F,
+                                                _ptr(est), S * rows * F, rows * F, _ptr(mask), rows * F))
+    return (est, mask) if want_mask else est
 
 
 def pcm_to_int16(ctx, pcm_t, out=None):

@@ -21,7 +21,8 @@ import scipy.io.wavfile
 from . import _lib
 from .arch import ARCHS, TIE_ALL, TILER_LIBRARY, TILER_SCRIPT
 from .resample import TARGET_RATE, out_length as resampled_length, ratio as rate_ratio
-from .runtime import Network, StftPlan, _on_ctx_stream, default_context, overlap_add, pcm16_to_float, pcm_to_int16, tile
+from .runtime import (Network, StftPlan, _on_ctx_stream, default_context, mask_fold_apply, overlap_add, pcm16_to_float,
+                      pcm_to_int16, tile)
 
 
 def blackmanharris(n):
@@ -508,6 +509,81 @@ class Separator(object):
                 self.plan.inverse(out_mag[c, j], out_ph[c, j], n_out=L, out=pcm[c, j:j + 1])
         return pcm
 
+    def _require_mono_graph(self, what):
+        if self.arch_name == 'dsd_ild' or self.net.arch.C != 1:
+            raise ValueError("%s applies the masks of a single-input-channel graph to each channel; '%s' takes %d input "
+                             "channels" % (what, self.arch_name, self.net.arch.C))
+
+    @_on_ctx_stream
+    def channel_spectra(self, a3, want_p=False):
+        """Per-channel estimates of a stereo signal from a mono model.  ``a3 [3, L]`` float32 on the device: rows L, R and
+        the down-mix the network sees.  One STFT launch for the three rows, the tiles of the down-mix x ``scale_factor``,
+        one pass of all tiles through the network (its rectified output ``p`` stays channel-major, as
+        ``dcs_model_forward`` writes it), then ``dcs_mask_fold_apply``: the soft masks, cross-faded over the tiles,
+        times the UNSCALED magnitudes of L and R.  Returns ``(est [2, S, T, F], mag [2, T, F], ph [2, T, F])`` and, with
+        ``want_p``, ``p [S, n, tc, F]`` as a fourth item.  Raises what :meth:`separate_stepwise` raises when the tiler
+        yields no tile.
+
+        ``p`` of the whole file lives on the device while this runs: ``n * channels_out * tc * F * 4`` bytes -- 41 MB per
+        10 s of DSD (167 tiles, 4 x 30 x 513), about 5 GB for five minutes of Bach10 (2049 bins).  Nothing is chunked
+        here: the generic graphs bound their own scratch by passing the tiles through in chunks inside
+        ``dcs_model_forward``, the DSD graph's scratch grows with the tile count, and a signal that does not fit raises
+        ``MemoryError``."""
+        self._require_mono_graph("channel_spectra")
+        if a3.dim() != 2 or int(a3.shape[0]) != 3:
+            raise ValueError("channel_spectra expects a [3, samples] tensor (L, R, down-mix), got %r" % (tuple(a3.shape),))
+        mag, ph = self.plan.forward_clips(a3, phase=True)                                       # [3, T, F]
+        tiles, n = tile(self.ctx, mag[2], self.tc, self.overlap, self.tiler, self.scale_factor)
+        if n == 0:
+            raise IndexError("tuple index out of range")  # what overlapadd_multi hits on an empty output array
+        p = self.net.forward_raw(tiles, self.tie_mode, channel_major=True)[:self.net.S]         # [S, n, tc, F]
+        est = mask_fold_apply(self.ctx, p, mag[:2], self.tc, self.overlap, self.net.arch.eps_mode)
+        return (est, mag[:2], ph[:2], p) if want_p else (est, mag[:2], ph[:2])
+
+    @_on_ctx_stream
+    def separate_channels_device(self, a3, mwf_iters=0):
+        """``a3 [3, L]`` (L, R, down-mix) float32 on the device -> float32 PCM ``[2, S, L]``: :meth:`channel_spectra`, then
+        one inverse transform per channel with that channel's phase, or -- ``mwf_iters > 0`` -- the multichannel Wiener
+        filter and one inverse transform per (channel, source), each with its own phase."""
+        import torch
+        L = int(a3.shape[1])
+        est, mag, ph = self.channel_spectra(a3)
+        S = int(est.shape[1])
+        pcm = torch.empty((2, S, L), dtype=torch.float32, device=a3.device)
+        if not mwf_iters:
+            for c in range(2):
+                self.plan.inverse(est[c], ph[c], n_out=L, pre_div=1.0, out=pcm[c])
+            return pcm
+        out_mag, out_ph = self.ctx.mwf(mag, ph, est, int(mwf_iters), pre_div=1.0)
+        for c in range(2):
+            for j in range(S):
+                self.plan.inverse(out_mag[c, j], out_ph[c, j], n_out=L, out=pcm[c, j:j + 1])
+        return pcm
+
+    @_on_ctx_stream
+    def separate_channels(self, audio, mwf_iters=0, sample_rate=TARGET_RATE):
+        """Stereo stems from a mono model: ``audio [L, 2]`` -> float64 ``[L, S, 2]`` (the layout of
+        :meth:`separate_stereo`).  The network sees the down-mix of the scripts (``to_mono``: the mean of L and R, or L + R
+        for iKala; formed on the host in float64, so its input is bit for bit that of ``separate(to_mono(audio))``); its
+        cross-faded masks are applied to each channel's own spectrum, which keeps its own phase.  ``mwf_iters > 0``: the
+        per-channel estimates go through that many iterations of the multichannel Wiener filter (``dcs_mwf_f32``) first.
+        ``sample_rate`` other than 44 100: the three signals are converted to 44 100 Hz on the device and the 2 S stems
+        back (:meth:`_at_model_rate`).  Single-input-channel graphs only (``ValueError`` otherwise)."""
+        self._require_mono_graph("separate_channels")
+        audio = np.asarray(audio)
+        if audio.ndim != 2 or audio.shape[1] != 2:
+            raise ValueError("separate_channels takes a stereo signal [L, 2], got shape %r" % (audio.shape,))
+        a3 = self.ctx.to_device(np.stack([audio[:, 0], audio[:, 1], to_mono(audio, self.arch_name)]), np.float32)
+
+        def run(a3):
+            return self.separate_channels_device(a3, int(mwf_iters))
+        if int(sample_rate) == TARGET_RATE:
+            pcm = self.ctx.to_host(run(a3))
+        else:
+            pcm = self.ctx.to_host(self._at_model_rate(a3, sample_rate, run))                  # [2 S, L]
+            pcm = pcm.reshape(2, -1, pcm.shape[-1])
+        return np.ascontiguousarray(pcm.astype(np.float64).transpose(2, 1, 0))                  # [L, S, 2]
+
     @_on_ctx_stream
     def separate_scoreinformed(self, audio, melody, timbre_model_path=None, sample_rate=TARGET_RATE):
         """Score-informed separation (examples/bach10_scoreinformed/separate_bach10.py:497-541), stage by stage on the
@@ -601,12 +677,17 @@ def output_paths(arch_name, filein, outdir):
 
 def train_auto(arch_name, filein, outdir, model, scale_factor=0.3, time_context=30, overlap=20, batch_size=32,
                input_size=513, frameSize=None, hopSize=None, window=None, fused=True, device=None, score_normalise='max',
-               score_mixture='ch0', resample=False):
+               score_mixture='ch0', resample=False, stereo=False, mwf_iters=0):
     """``train_auto`` of the separate scripts: wav in, one wav per source out.  ``score_normalise`` / ``score_mixture``
     (score-informed only): ``('sum', 'sum')`` = what the trainer's own separation block computes
     (bach10_scoreinformed/trainCNNrwc.py:360-416), for models that trainer wrote; the default is the separate script's.
     ``resample=True``: a file at another rate than 44 100 Hz, which the scripts refuse, is converted on the device,
-    separated and written at ITS OWN rate (``Separator.separate(..., sample_rate=)``)."""
+    separated and written at ITS OWN rate (``Separator.separate(..., sample_rate=)``).
+    ``stereo=True`` (single-channel graphs): a two-channel file gives two-channel stems under the same names
+    (``Separator.separate_channels``: the masks of the down-mix on each channel's own spectrum), after ``mwf_iters``
+    iterations of the multichannel Wiener filter when that is not 0; a mono file is separated as without it."""
+    if mwf_iters and not stereo:
+        raise ValueError("mwf_iters needs stereo=True: the Wiener filter works on two-channel estimates")
     d_frame, d_hop, d_win, _, _ = _SCRIPT_DEFAULTS[arch_name]
     frameSize = d_frame if frameSize is None else frameSize
     hopSize = d_hop if hopSize is None else hopSize
@@ -616,7 +697,13 @@ def train_auto(arch_name, filein, outdir, model, scale_factor=0.3, time_context=
                     hopSize, window, tiler='library' if arch_name == 'bach10_si' else 'script', device=device,
                     score_normalise=score_normalise, score_mixture=score_mixture)
     sampleRate, audioObj = read_wav(filein)
-    if sampleRate == 44100 or resample:
+    if stereo:
+        sep._require_mono_graph("stereo=True")
+    if (sampleRate == 44100 or resample) and stereo and audioObj.ndim == 2 and audioObj.shape[1] > 1:
+        pcm = sep.separate_channels(audioObj[:, :2], mwf_iters=mwf_iters, sample_rate=sampleRate)   # [L, S, 2]
+        for i, path in enumerate(output_paths(arch_name, filein, outdir)):
+            write_wav(path, pcm[:, i, :], sampleRate)
+    elif sampleRate == 44100 or resample:
         audio = to_mono(audioObj, arch_name)
         if arch_name == 'bach10_si':
             from .score import melody_table

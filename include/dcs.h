@@ -458,6 +458,31 @@ DCS_API int dcs_mwf_f32(dcs_ctx* ctx, const float* mag_d, const float* phase_d, 
  * pass adds up min(ceil(n_frames / this), 32) sets of sums */
 DCS_API int dcs_mwf_frames_per_block(void);
 
+/* ------------------------------------------------------------------ per-channel masks of the mono models (csrc/chanmask.hip) */
+/* Every published model but the ILD one sees a mono down-mix (separate_dsd.py:285-287, separate_ikala.py:229) and the scripts
+ * write mono stems.  This applies the network's soft masks (separate_dsd.py:258-271, separate_bach10.py:251-264), cross-faded
+ * over the tiles as overlapadd_multi stitches them (util.py:297-327), to the magnitudes of EACH input channel: the estimates a
+ * per-channel iSTFT -- or first dcs_mwf_f32, the filter of util.py:633-719 -- turns into stereo stems.  Per frame t, bin f:
+ *   per covering tile k (frame j = t - k st of it, st = time_context - overlap), float32, eps_r = 5e-19f:
+ *     DCS_EPS_A:  q_s = p_s + eps_r,  den = ((q_0 + q_1) + ...),  m_s = q_s / den
+ *     DCS_EPS_B:  den = ((p_0 + p_1) + ...) + eps_r,              m_s = p_s / den
+ *   the fold of dcs_overlap_add on the masks: owner tile k0 = t < overlap ? 0 : min((t - overlap) / st, n_tiles - 1), acc = m[k0],
+ *     then for increasing k > k0 with k st <= t:  acc = fma(rise[overlap - 1 - j], acc, rise[j] * m[k])  (the product rounded)
+ *   mask_d[s][t, f] = acc_s,   est_d[c][s][t, f] = acc_s * mag_d[c][t, f]
+ * p_d: the rectified network output as dcs_model_forward leaves it, element (s, k, j, f) at p_d + s p_src_stride + (k
+ * time_context + j) F + f (the stride lets S < channels_out through); rise_h = np.linspace(0, 1, overlap) as float64, as for
+ * dcs_overlap_add; mag_d [C][n_frames, ld] (channel stride mag_ch_stride), scaled however the caller likes; est_d
+ * [C][S][n_frames, ld] (strides est_ch_stride, est_src_stride) and mask_d [S][n_frames, ld] (stride mask_src_stride), either may be
+ * NULL.  Rows past the last tile (t - k0 st >= time_context; every row when n_tiles == 0) are written as zeros, columns
+ * F .. ld-1 are never written.  One launch, no atomics: the same bits every run.  DCS_EINVAL for S or C outside 1 .. 8, overlap
+ * outside 1 .. time_context - 1, F < 1, ld < F, a negative count, an eps_mode that is neither convention, a NULL p_d, mag_d or
+ * rise_h, or both outputs NULL; n_frames == 0 does nothing.  Enqueued on the ctx stream (a ramp whose values differ from the
+ * previous call's is uploaded first, after a stream synchronisation, as in dcs_overlap_add). */
+DCS_API int dcs_mask_fold_apply(dcs_ctx* ctx, const float* p_d, int64_t p_src_stride, int64_t n_tiles, int S, int time_context,
+                                int overlap, int F, int eps_mode, const double* rise_h, const float* mag_d, int64_t mag_ch_stride,
+                                int C, int64_t n_frames, int64_t ld, float* est_d, int64_t est_ch_stride, int64_t est_src_stride,
+                                float* mask_d, int64_t mask_src_stride);
+
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
 /* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is
  * the rate change in front of the STFT and behind the iSTFT that lets every other file through.  For up / down = fo / fi in
