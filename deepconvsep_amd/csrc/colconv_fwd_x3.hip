@@ -254,6 +254,7 @@ bool dcs_launch_colconv_fwd_x3(dcs_ctx* ctx, const DcsColConv& a0, int64_t n_ima
     // equal shares: the fewest rounds, then as many workgroups as give every one the same number of items (+- 1)
     const int64_t rounds = dcs_cdiv(d.n_items, n_pairs);
     const unsigned grid = (unsigned)dcs_cdiv(d.n_items, rounds);
+    ctx->note_conv(DCS_CONV_ROLE_CONV2, DCS_CONV_K_COLCONV_FWD_X3, 0, 0, grid);
     hipLaunchKernelGGL((colconv_fwd_x3_kernel<20, 30>), dim3(grid), dim3(kTh), 0, ctx->stream, a, d);
     return true;
 }

@@ -520,12 +520,14 @@ bool dcs_launch_colconv_wreg(dcs_ctx* ctx, const DcsColConv& a, int64_t n_images
     const unsigned grid = (unsigned)std::min<int64_t>(dcs_cdiv(n_units, 4), ctx->n_cu);
     const u32x4* wq = reinterpret_cast<const u32x4*>(Wq);
     if (a.ph == a.kh - 1 && a.H == 11 && a.Ho == 30) {
+        ctx->note_conv(DCS_CONV_ROLE_CONV2T, DCS_CONV_K_WREG_GATHER, 0, 0, grid);
         hipLaunchKernelGGL((colconv_wreg_gather_kernel<20, 11>), dim3(grid), dim3(kThreads), 0, ctx->stream, a, wq, n_units);
         return true;
     }
     if (a.ph == 0 && a.H == 30 && a.Ho == 11) {
         if (a.in_f16 && ((a.in_n_stride & 7) || (reinterpret_cast<uintptr_t>(a.in) & 15))) return false;
 #define DCS_SC(O16_, I16_) hipLaunchKernelGGL((colconv_wreg_scatter_kernel<20, 30, 8, O16_, I16_>), dim3(grid), dim3(kThreads), 0, ctx->stream, a, wq, n_units)
+        ctx->note_conv(DCS_CONV_ROLE_CONV2, DCS_CONV_K_WREG_SCATTER + (a.in_f16 ? 1 : 0) + (a.out_f16 ? 2 : 0), 0, 0, grid);
         if (a.out_f16) { if (a.in_f16) DCS_SC(true, true); else DCS_SC(true, false); }
         else { if (a.in_f16) DCS_SC(false, true); else DCS_SC(false, false); }
 #undef DCS_SC
@@ -600,6 +602,7 @@ bool dcs_launch_decoder_fused(dcs_ctx* ctx, const DcsColConv& a, int64_t n_image
     const u32x4* wq = reinterpret_cast<const u32x4*>(Wq);
 #define DCS_GO(CL_, IN16_) \
     hipLaunchKernelGGL((colconv_deconv1_fused_kernel<20, 11, CL_, IN16_>), dim3(grid), dim3(kThreads), 0, ctx->stream, a, wq, d)
+    ctx->note_conv(DCS_CONV_ROLE_DECODER, in_f16 ? DCS_CONV_K_FUSED_CL16 : in_channels_last ? DCS_CONV_K_FUSED_CL : DCS_CONV_K_FUSED, 0, best, grid);
     if (in_f16) DCS_GO(true, true);
     else if (in_channels_last) DCS_GO(true, false);
     else DCS_GO(false, false);

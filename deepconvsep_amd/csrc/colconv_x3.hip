@@ -571,6 +571,7 @@ bool dcs_launch_decoder_x3(dcs_ctx* ctx, const DcsColConv& a, int64_t n_images, 
     d.runs_per_image = best;
     d.n_runs = n_images * best;
     const unsigned grid = (unsigned)std::min<int64_t>(d.n_runs, n_pairs);
+    ctx->note_conv(DCS_CONV_ROLE_DECODER, n_out == 4 ? DCS_CONV_K_FUSED_X3_4 : DCS_CONV_K_FUSED_X3_1, 0, best, grid);
     if (n_out == 4)
         hipLaunchKernelGGL((colconv_deconv1_fused_x3_kernel<20, 11, 4>), dim3(grid), dim3(kTh), 0, ctx->stream, a, d);
     else

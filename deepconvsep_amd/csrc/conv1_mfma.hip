@@ -276,5 +276,7 @@ bool dcs_launch_conv1_mfma(dcs_ctx* ctx, const float* x, const void* Wq, const f
         hipLaunchKernelGGL((conv1_mfma_kernel<4, 1>), grid, dim3(kThreads), 0, ctx->stream, x, wq, bias, out, NF, tc, F, w1);
     else
         hipLaunchKernelGGL((conv1_mfma_kernel<4, 0>), grid, dim3(kThreads), 0, ctx->stream, x, wq, bias, out, NF, tc, F, w1);
+    ctx->note_conv(DCS_CONV_ROLE_CONV1, out_f16 ? DCS_CONV_K_CONV1_MFMA_1_CL16 : (C == 1 ? DCS_CONV_K_CONV1_MFMA_1 : DCS_CONV_K_CONV1_MFMA_4) + (channels_last ? 1 : 0),
+                   0, 0, (int64_t)grid.x * grid.y);
     return true;
 }

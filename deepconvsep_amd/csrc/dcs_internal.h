@@ -158,6 +158,14 @@ struct dcs_ctx {
         last_gemm = code;
         last_gemm_param[0] = ksplit; last_gemm_param[1] = kchunk; last_gemm_param[2] = rbt; last_gemm_param[3] = aq;
     }
+    // the same for the convolution kernels of the generic graphs, per role (DCS_CONV_ROLE_*, DCS_CONV_K_*, 0 = none):
+    // dcs_debug_conv_last_kernel; {band, column tile, pstage} for the slab kernels, else {xb_per_wg, runs_per_image, workgroups}
+    int last_conv[DCS_CONV_ROLES] = {0};
+    int64_t last_conv_param[DCS_CONV_ROLES][3] = {{0}};
+    void note_conv(int role, int code, int64_t p0 = 0, int64_t p1 = 0, int64_t p2 = 0) {
+        last_conv[role] = code;
+        last_conv_param[role][0] = p0; last_conv_param[role][1] = p1; last_conv_param[role][2] = p2;
+    }
 };
 
 // RAII-ish helper: records a start event on construction and a stop event in done().

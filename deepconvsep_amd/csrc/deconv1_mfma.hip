@@ -200,6 +200,7 @@ bool dcs_launch_deconv1_mfma(dcs_ctx* ctx, const float* g, const void* Wq, float
     const int64_t n_units = n_images * ((tc + 1) / 2);
     const unsigned grid = (unsigned)std::min<int64_t>(dcs_cdiv(n_units, 4), (int64_t)ctx->n_cu * 3);
     const u32x4* wq = reinterpret_cast<const u32x4*>(Wq);
+    ctx->note_conv(DCS_CONV_ROLE_CONV1T, C == 1 ? DCS_CONV_K_DECONV1_MFMA_1 : DCS_CONV_K_DECONV1_MFMA_4, 0, 0, grid);
     if (C == 1)
         hipLaunchKernelGGL((deconv1_mfma_kernel<1>), dim3(grid), dim3(kThreads), 0, ctx->stream, g, wq, out, NF, tc, F, w1, n_units);
     else

@@ -95,6 +95,8 @@ int dcs_generic_create(dcs_ctx* ctx, const DcsGenericDims& d, int C, int tc, int
                        const std::vector<std::vector<float>>& params, DcsGenericNet** out);
 void dcs_generic_destroy(DcsGenericNet* g);
 int dcs_generic_set_conv_f16(DcsGenericNet* g, int on);
+int dcs_generic_debug_conv_stage(DcsGenericNet* g, int stage, dcs_debug_conv_args* args);   // dcs_debug_conv_stage (include/dcs.h)
+int dcs_generic_debug_fold_weights(DcsGenericNet* g, float* out_h, int64_t n_out, int64_t* rows, int64_t* cols);        // dcs_debug_conv_fold_weights
 int dcs_generic_set_score_semantics(DcsGenericNet* g, int normalise, int mixture);
 // tiles [n, C, tc, F] -> mask_mode 0/1: out [S, n, tc, F] masked; mask_mode 2: p [n, n_branch*C, tc, F]
 int dcs_generic_forward(DcsGenericNet* g, const float* tiles, int64_t n, int mask_mode, int tie_mode, float* out);

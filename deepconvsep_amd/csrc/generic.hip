@@ -1593,6 +1593,7 @@ bool launch_slabconv(dcs_ctx* ctx, SlabConvArgs a, int64_t n_images, const uint1
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
+    ctx->note_conv(a.ph == 0 && a.pw == 0 ? DCS_CONV_ROLE_CONV2 : DCS_CONV_ROLE_CONV2T, DCS_CONV_K_SLAB_MX_0 + (mode ? 1 : 0), band, 0, a.tstage);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_images * a.n_bands)), dim3(64 * kSlabWaves), lds, ctx->stream, a,
                        reinterpret_cast<const u32x4*>(Wq));
     return true;
@@ -1623,6 +1624,7 @@ int launch_colconv(dcs_ctx* ctx, ColConvArgs a, int64_t n_images, const _Float16
         auto kern = colconv_f16_kernel;
         if (lds > 48 * 1024)
             DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ctx->note_conv(a.ph == 0 ? DCS_CONV_ROLE_CONV2 : DCS_CONV_ROLE_CONV2T, DCS_CONV_K_COLCONV_F16, per, 0, n_images * ((a.n_xb + per - 1) / per));
         hipLaunchKernelGGL(kern, dim3((unsigned)(n_images * ((a.n_xb + per - 1) / per))), dim3(kColThreads), lds, ctx->stream,
                            a, Wh);
         return DCS_OK;
@@ -1638,6 +1640,7 @@ int launch_colconv(dcs_ctx* ctx, ColConvArgs a, int64_t n_images, const _Float16
     if (lds > 48 * 1024)
         DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int64_t groups = (a.n_xb + per - 1) / per;
+    ctx->note_conv(a.ph == 0 ? DCS_CONV_ROLE_CONV2 : DCS_CONV_ROLE_CONV2T, a.ph == 0 ? DCS_CONV_K_COLCONV : DCS_CONV_K_COLCONV_T, per, 0, n_images * groups);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_images * groups)), dim3(kColThreads), lds, ctx->stream, a);
     return DCS_OK;
 }
@@ -1713,7 +1716,9 @@ DcsGemm dense_gemm(const DcsGenericNet* g, const float* Z, float* D, int64_t n, 
 void launch_conv2_general(const DcsGenericNet* g, const IgemmArgs& a, int64_t n_images, bool transpose) {
     dcs_ctx* ctx = g->ctx;
     const int f16 = g->conv_f16 ? 1 : 0;
+    const int role = transpose ? DCS_CONV_ROLE_CONV2T : DCS_CONV_ROLE_CONV2;
     if (f16 && !g->use_slabconv) {
+        ctx->note_conv(role, DCS_CONV_K_IGEMM_F16, 0, 0, dcs_cdiv(a.M, 128));
         hipLaunchKernelGGL(conv_igemm_f16_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a,
                            transpose ? g->W2t_h : g->W2m_h);
         return;
@@ -1727,6 +1732,7 @@ void launch_conv2_general(const DcsGenericNet* g, const IgemmArgs& a, int64_t n_
         const uint16_t* Wps = transpose ? (f16 ? g->Wps_t_h : g->Wps_t_q3) : (f16 ? g->Wps_h : g->Wps_q3);
         if (launch_slabconv(ctx, c, n_images, Wq, f16, Wps)) return;
     }
+    ctx->note_conv(role, transpose ? DCS_CONV_K_IGEMM_T : DCS_CONV_K_IGEMM, 0, 0, dcs_cdiv(a.M, 128));
     hipLaunchKernelGGL(conv_igemm_kernel, dim3((unsigned)dcs_cdiv(a.M, 128)), dim3(kThreads), 0, ctx->stream, a);
 }
 
@@ -1800,6 +1806,7 @@ int conv1_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
                                g->frames_rows == (n - 1) * g->frames_st + tc && g->frames_st < tc;
         const dim3 grid1((unsigned)dcs_cdiv(d.w1, kThreads), (unsigned)(n * tc));
         if (fused_pool) {   // conv1 + max-pool: pooled rows to p1, the un-pooling routing bits where the activations would go
+            ctx->note_conv(DCS_CONV_ROLE_CONV1, DCS_CONV_K_CONV1_REG3_POOL, 0, 0, (int64_t)grid1.x * grid1.y);
             hipLaunchKernelGGL((conv1_reg_kernel<30, 3, true>), grid1, dim3(kThreads), 0, ctx->stream, k.tiles, g->W1t, g->bias1, k.p1,
                                C, tc, F, d.kw1, d.w1, reinterpret_cast<unsigned*>(k.a1b), d.wp, pool_words(d),
                                k.tie_mode == DCS_TIE_FIRST ? 1 : 0);
@@ -1816,19 +1823,24 @@ int conv1_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
             h.a1_layout = kChannelsLastF16;
         } else if (g->W1m && dcs_launch_conv1_mfma(ctx, k.tiles, g->W1m, g->bias1, k.a1b, n, C, d.nf1, tc, F, d.kw1, d.sw1, d.w1, want_cl)) {
             if (want_cl) h.a1_layout = kChannelsLastF32;
-        } else if (env().conv1_reg && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 4)   // the register kernel is built for 30 filters
+        } else if (env().conv1_reg && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 4) {   // the register kernel is built for 30 filters
+            ctx->note_conv(DCS_CONV_ROLE_CONV1, DCS_CONV_K_CONV1_REG4, 0, 0, (int64_t)grid1.x * grid1.y);
             hipLaunchKernelGGL((conv1_reg_kernel<30, 4>), grid1, dim3(kThreads), 0, ctx->stream, k.tiles, g->W1t, g->bias1, k.a1b, C,
                                tc, F, d.kw1, d.w1);
-        else if (env().conv1_reg && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 3)
+        } else if (env().conv1_reg && d.nf1 == 30 && d.kw1 <= 32 && d.sw1 == 3) {
+            ctx->note_conv(DCS_CONV_ROLE_CONV1, DCS_CONV_K_CONV1_REG3, 0, 0, (int64_t)grid1.x * grid1.y);
             hipLaunchKernelGGL((conv1_reg_kernel<30, 3>), grid1, dim3(kThreads), 0, ctx->stream, k.tiles, g->W1t, g->bias1, k.a1b, C,
                                tc, F, d.kw1, d.w1);
-        else
+        } else {
+            ctx->note_conv(DCS_CONV_ROLE_CONV1, DCS_CONV_K_CONV1, 0, 0, (int64_t)grid1.x * grid1.y);
             hipLaunchKernelGGL(kern, grid1, dim3(kThreads), lds, ctx->stream, k.tiles, g->W1c, g->bias1, k.a1b, C, tc, F, d.kw1,
                                d.sw1, d.w1);
+        }
         tm.done();
     }
     if (d.pool_w && !fused_pool) {
         DcsTimer tm(ctx, DCS_TAG_POOL);
+        ctx->note_conv(DCS_CONV_ROLE_POOL, DCS_CONV_K_POOL, 0, 0, dcs_cdiv(n * d.nf1 * tc * d.wp, kThreads));
         hipLaunchKernelGGL(pool_kernel, dim3((unsigned)dcs_cdiv(n * d.nf1 * tc * d.wp, kThreads)), dim3(kThreads), 0,
                            ctx->stream, k.a1b, k.p1, n * d.nf1 * tc, d.w1, d.wp, d.pool_w);
         tm.done();
@@ -1864,12 +1876,16 @@ int conv2_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
     h.fold2 = g->B2fc && g->K2fc > 0 && !g->conv_f16 && h.a1_layout == kChannelFirst;
     if (h.fold2) return DCS_OK;
     if (h.a2_f16) {
-        if (pitch16 != d.flat)
+        if (pitch16 != d.flat) {
+            ctx->note_conv(DCS_CONV_ROLE_PAD, DCS_CONV_K_ZERO_PAD, 0, 0, dcs_cdiv(n * ((pitch16 - d.flat) / 2), kThreads));
             hipLaunchKernelGGL(zero_pad_cols_kernel, dim3((unsigned)dcs_cdiv(n * ((pitch16 - d.flat) / 2), kThreads)), dim3(kThreads), 0,
                                ctx->stream, k.a2b, n, d.flat / 2, pitch16 / 2);
-    } else if (g->flat_p != d.flat)
+        }
+    } else if (g->flat_p != d.flat) {
+        ctx->note_conv(DCS_CONV_ROLE_PAD, DCS_CONV_K_ZERO_PAD, 0, 0, dcs_cdiv(n * (g->flat_p - d.flat), kThreads));
         hipLaunchKernelGGL(zero_pad_cols_kernel, dim3((unsigned)dcs_cdiv(n * (g->flat_p - d.flat), kThreads)), dim3(kThreads), 0,
                            ctx->stream, k.a2b, n, d.flat, g->flat_p);
+    }
     IgemmArgs a{};
     a.in = h.a1; a.in_n_stride = (int64_t)d.nf1 * planep; a.Cin = d.nf1; a.H = tc; a.W = d.wp;
     a.Wm = g->W2m; a.koff = g->k2off; a.kuv = g->k2uv; a.bias = g->bias2;
@@ -2058,6 +2074,15 @@ int dense_stage(DcsGenericNet* g, const Chunk& k, Handoff& h) {
     return DCS_OK;
 }
 
+// do both InverseLayers run as one kernel on a D that arrives channels-last (d_cl) or channel-first?  c: the transposed conv2
+bool decoder_fuses(const DcsGenericNet* g, const ColConvArgs& c, bool d_cl) {
+    if (!g->use_colconv) return false;
+    bool fuse_x3 = false;
+    plans_channels_last(g, nullptr, &fuse_x3);
+    return g->conv_f16 ? (g->C == 1 && g->W1q && g->Wcol_t_r && dcs_decoder_fused_ok(c, g->F))
+                       : (fuse_x3 && d_cl);            // f32-class: only on the channels-last layout
+}
+
 // the decoder: both InverseLayers as one kernel, or InverseLayer(conv2), InverseLayer(pool) and InverseLayer(conv1)
 int decoder_stage(DcsGenericNet* g, const Chunk& k, const Handoff& h) {
     const DcsGenericDims& d = g->d;
@@ -2078,10 +2103,7 @@ int decoder_stage(DcsGenericNet* g, const Chunk& k, const Handoff& h) {
         c.in = a.in; c.in_n_stride = a.in_n_stride; c.Cin = a.Cin; c.H = a.H; c.W = a.W;
         c.Wk = g->Wcol_t; c.bias = a.bias; c.out = a.out; c.out_n_stride = a.out_n_stride; c.Cout = a.Cout; c.Ho = a.Ho;
         c.ph = d.kh2 - 1; c.kh = d.kh2; c.n_xb = (c.W + 15) / 16;
-        bool fuse_x3 = false;
-        plans_channels_last(g, nullptr, &fuse_x3);
-        fused = g->conv_f16 ? (C == 1 && g->W1q && g->Wcol_t_r && dcs_decoder_fused_ok(c, F))
-                            : (fuse_x3 && d_cl);       // f32-class: only on the channels-last layout
+        fused = decoder_fuses(g, c, d_cl);
         if (dense16) {
             if (!fused) DCS_FAIL(DCS_EHIP, "generic graph: f16 dense output planned without the fused decoder");
             c.in_n_stride = g->n_out16;                    // halves: D16[image = tile * NB + branch][position][32]
@@ -2116,6 +2138,7 @@ int decoder_stage(DcsGenericNet* g, const Chunk& k, const Handoff& h) {
         DcsTimer tm(ctx, DCS_TAG_UNPOOL);
         const int64_t rows_g = n * NB * d.nf1 * tc;
         if (d.pool_w != 4 || rows_g > 0x7fffffff) DCS_FAIL(DCS_EUNSUPPORTED, "un-pool: pool width %d, %lld rows", d.pool_w, (long long)rows_g);
+        ctx->note_conv(DCS_CONV_ROLE_UNPOOL, DCS_CONV_K_UNPOOL, 0, 0, dcs_cdiv(rows_g, 4));
         hipLaunchKernelGGL((unpool_kernel<4>), dim3((unsigned)dcs_cdiv(rows_g, 4)), dim3(kThreads), 0,
                            ctx->stream, k.g2, k.a1b, k.g1, (unsigned)rows_g, (unsigned)(d.nf1 * tc), (unsigned)NB, d.w1, d.wp,
                            k.tie_mode == DCS_TIE_FIRST ? 1 : 0);
@@ -2131,19 +2154,23 @@ int decoder_stage(DcsGenericNet* g, const Chunk& k, const Handoff& h) {
     DcsTimer tm(ctx, DCS_TAG_FINAL);
     if (fused_pool) {   // un-pool + conv1^T: reads the pooled gradient and the routing bits
         const int nqb = (F + 11) / 12;
+        ctx->note_conv(DCS_CONV_ROLE_CONV1T, DCS_CONV_K_DECONV1_REG3_POOL, 0, 0, dcs_cdiv((int64_t)tc * nqb, kThreads) * n * NB);
         hipLaunchKernelGGL((deconv1_reg_kernel<3, 10, true>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
                            dim3(kThreads), 0, ctx->stream, k.g2, g->W1p, k.o, d.nf1, C, tc, F, d.w1, nqb, pool_bits, d.wp,
                            pool_words(d), NB);
     } else if (g->W1dq && dcs_launch_deconv1_mfma(ctx, k.g1, g->W1dq, k.o, n * NB, d.nf1, C, tc, F, d.w1)) {
     } else if (g->W1p && env().deconv1_reg && d.sw1 == 3 && (d.kw1 + 2) / 3 == 10) {
         const int nqb = (F + 11) / 12;
+        ctx->note_conv(DCS_CONV_ROLE_CONV1T, DCS_CONV_K_DECONV1_REG3, 0, 0, dcs_cdiv((int64_t)tc * nqb, kThreads) * n * NB);
         hipLaunchKernelGGL((deconv1_reg_kernel<3, 10>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
                            dim3(kThreads), 0, ctx->stream, k.g1, g->W1p, k.o, d.nf1, C, tc, F, d.w1, nqb);
     } else if (g->W1p && env().deconv1_reg && d.sw1 == 4 && (d.kw1 + 3) / 4 == 8) {
         const int nqb = (F + 15) / 16;
+        ctx->note_conv(DCS_CONV_ROLE_CONV1T, DCS_CONV_K_DECONV1_REG4, 0, 0, dcs_cdiv((int64_t)tc * nqb, kThreads) * n * NB);
         hipLaunchKernelGGL((deconv1_reg_kernel<4, 8>), dim3((unsigned)dcs_cdiv((int64_t)tc * nqb, kThreads), (unsigned)(n * NB)),
                            dim3(kThreads), 0, ctx->stream, k.g1, g->W1p, k.o, d.nf1, C, tc, F, d.w1, nqb);
     } else {
+        ctx->note_conv(DCS_CONV_ROLE_CONV1T, DCS_CONV_K_DECONV1, 0, 0, dcs_cdiv(F, kThreads) * n * NB * tc);
         hipLaunchKernelGGL(kern, dim3((unsigned)dcs_cdiv(F, kThreads), (unsigned)(n * NB * tc)), dim3(kThreads), lds,
                            ctx->stream, k.g1, g->W1c, k.o, C, tc, F, d.kw1, d.sw1, d.w1);
     }
@@ -2408,5 +2435,172 @@ int dcs_generic_separate(DcsGenericNet* g, dcs_stft* plan, const float* audio, i
     if (phase_out)
         DCS_HIP(hipMemcpy2DAsync(phase_out, ld_out * 4, phase, ld * 4, (size_t)F * 4, (size_t)T,
                                  hipMemcpyDeviceToDevice, ctx->stream));
+    return DCS_OK;
+}
+
+// Test aid (include/dcs.h, "Test aids for the convolution kernels"): one of conv1_stage / conv2_stage / decoder_stage on the
+// caller's buffers.  Every buffer must hold what forward_chunk would have carved for it -- the stages and their kernels index
+// nothing else -- and nothing is launched unless all of them do.
+int dcs_generic_debug_conv_stage(DcsGenericNet* g, int stage, dcs_debug_conv_args* a) {
+    if (!g || !a) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: null argument");
+    const DcsGenericDims& d = g->d;
+    dcs_ctx* ctx = g->ctx;
+    const int C = g->C, tc = g->tc, F = g->F;
+    if (stage != DCS_CONV_STAGE_CONV1 && stage != DCS_CONV_STAGE_CONV2 && stage != DCS_CONV_STAGE_DECODER)
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: stage %d", stage);
+    if (a->n < 1 || a->n > (1 << 20)) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: %lld tiles", (long long)a->n);
+    if (a->n_branch < 1 || a->n_branch > d.n_branch) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: %d branches of %d", a->n_branch, d.n_branch);
+    if (a->tie_mode != DCS_TIE_ALL && a->tie_mode != DCS_TIE_FIRST) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: tie mode %d", a->tie_mode);
+    const int64_t n = a->n, NB = a->n_branch;
+    const int64_t plane1 = (int64_t)tc * d.w1, planep = (int64_t)tc * d.wp;
+    const bool pool = d.pool_w != 0;
+    // a buffer the stage can touch: there, 16-byte aligned (the strictest rule of the launchers), at least `need` bytes
+    auto have = [](const void* p, int64_t bytes, int64_t need, const char* name) -> bool {
+        if (!p || (reinterpret_cast<uintptr_t>(p) & 15) || bytes < need) {
+            dcs_set_error("dcs_debug_conv_stage: %s: %s, %lld bytes of the %lld the stage can touch", name,
+                          !p ? "null" : (reinterpret_cast<uintptr_t>(p) & 15) ? "not 16-byte aligned" : "short", (long long)bytes, (long long)need);
+            return false;
+        }
+        return true;
+    };
+    const int64_t a1b_need = n * d.nf1 * plane1 * 4, p1_need = n * d.nf1 * planep * 4, a2b_need = n * (int64_t)g->flat_p * 4;
+    const int n_out16 = (int)dcs_round_up((int64_t)d.h2 * d.w2 * 32, 128);
+    int64_t D_need = n * NB * (int64_t)g->flat_p * 4;
+    Chunk k{};
+    k.n = n; k.n_total = n; k.k_first = 0; k.NB = (int)NB; k.mask_mode = 2; k.tie_mode = a->tie_mode;
+    k.tiles = a->tiles;
+    k.a1b = static_cast<float*>(a->a1b);
+    k.p1 = pool ? static_cast<float*>(a->p1) : k.a1b;
+    k.a2b = static_cast<float*>(a->a2b);
+    k.D = static_cast<float*>(a->D);
+    k.g2 = static_cast<float*>(a->g2);
+    k.g1 = pool ? static_cast<float*>(a->g1) : k.g2;
+    k.o = static_cast<float*>(a->o);
+    Handoff h;
+    bool per_frame = false;
+    if (stage == DCS_CONV_STAGE_CONV1) {
+        if (!have(a->tiles, a->tiles_bytes, n * C * tc * F * 4, "tiles") || !have(a->a1b, a->a1b_bytes, a1b_need, "a1b")) return DCS_EINVAL;
+        if (pool && !have(a->p1, a->p1_bytes, p1_need, "p1")) return DCS_EINVAL;
+        if (a->frames_src) {
+            if (a->frames_stride < 1 || a->frames_stride >= tc || (int64_t)a->frames_rows != (n - 1) * a->frames_stride + tc)
+                DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: %d frame rows at a stride of %d for %lld tiles", a->frames_rows, a->frames_stride, (long long)n);
+            if (!have(a->frames_src, a->frames_bytes, (int64_t)C * a->frames_rows * F * 4, "frames_src")) return DCS_EINVAL;
+            per_frame = true;
+        }
+    } else if (stage == DCS_CONV_STAGE_CONV2) {
+        if (!have(a->a2b, a->a2b_bytes, a2b_need, "a2b")) return DCS_EINVAL;
+        if (a->a1_layout < DCS_CONV_LAYOUT_CHANNEL_FIRST || a->a1_layout > DCS_CONV_LAYOUT_CL_F16)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: a1 layout %d", a->a1_layout);
+        if (a->a1_rows < 1 || a->a1_rows > tc || (a->a1_layout == DCS_CONV_LAYOUT_CHANNEL_FIRST && a->a1_rows != tc))
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: a1 tiles %d rows apart", a->a1_rows);
+        const int64_t rows = (n - 1) * a->a1_rows + tc;
+        const int64_t in_need = a->a1_layout == DCS_CONV_LAYOUT_CHANNEL_FIRST ? (pool ? p1_need : a1b_need)
+                                : a->a1_layout == DCS_CONV_LAYOUT_CL_F32    ? rows * d.w1 * d.nf1 * 4
+                                                                            : rows * d.w1 * 32 * 2;
+        if (pool ? !have(a->p1, a->p1_bytes, in_need, "p1") : !have(a->a1b, a->a1b_bytes, in_need, "a1b")) return DCS_EINVAL;
+        if (a->a1_layout != DCS_CONV_LAYOUT_CHANNEL_FIRST) {   // only the kernels conv1_stage plans these layouts for read them
+            ColConvArgs c2{};
+            c2.Cin = d.nf1; c2.H = tc; c2.W = d.w1; c2.Cout = d.nf2; c2.Ho = d.h2; c2.ph = 0; c2.kh = d.kh2;
+            const bool cl32 = a->a1_layout == DCS_CONV_LAYOUT_CL_F32;
+            const bool ok = g->use_colconv && !pool && d.wp == d.w1 &&
+                            (cl32 ? (!g->conv_f16 && g->Wfx3 && dcs_colconv_fwd_x3_ok(c2) && ((a->a1_rows * (int64_t)d.w1 * d.nf1) & 1) == 0)
+                                  : (g->conv_f16 && C == 1 && g->Wcol_h && g->Wcol_r && d.nf1 <= 32 && dcs_colconv_wreg_scatter_ok(c2)));
+            if (!ok) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_conv_stage: no conv2 of this model reads a1 in layout %d", a->a1_layout);
+        }
+        h.a1 = k.p1;
+        h.a1_layout = (MapLayout)a->a1_layout;
+        h.a1_rows = a->a1_rows;
+    } else {
+        if (a->d_layout < DCS_CONV_LAYOUT_CHANNEL_FIRST || a->d_layout > DCS_CONV_LAYOUT_CL_F16)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: D layout %d", a->d_layout);
+        if (a->d_layout == DCS_CONV_LAYOUT_CL_F16 && n * NB * (int64_t)n_out16 * 2 > D_need) D_need = n * NB * (int64_t)n_out16 * 2;
+        if (!have(a->D, a->D_bytes, D_need, "D") || !have(a->g2, a->g2_bytes, n * NB * d.nf1 * planep * 4, "g2") ||
+            !have(a->o, a->o_bytes, n * NB * C * tc * F * 4, "o"))
+            return DCS_EINVAL;
+        if (pool && (!have(a->g1, a->g1_bytes, n * NB * d.nf1 * plane1 * 4, "g1") || !have(a->a1b, a->a1b_bytes, a1b_need, "a1b"))) return DCS_EINVAL;
+        const bool d_cl = a->d_layout != DCS_CONV_LAYOUT_CHANNEL_FIRST;
+        ColConvArgs c{};
+        c.Cin = d.nf2; c.H = d.h2; c.W = d.w2; c.Cout = d.nf1; c.Ho = tc; c.ph = d.kh2 - 1; c.kh = d.kh2;
+        // channels-last D without the one-kernel decoder: decoder_stage would redo the dense layers from Z, which is not here
+        if (d_cl && (!decoder_fuses(g, c, true) || (d.nf2 & 1) || (g->flat_p & 1) ||
+                     (a->d_layout == DCS_CONV_LAYOUT_CL_F16 && !(g->conv_f16 && (g->hid64 & 31) == 0))))
+            DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_conv_stage: the decoder of this model does not read D in layout %d", a->d_layout);
+        h.d_layout = (MapLayout)a->d_layout;
+    }
+    DCS_ON_DEVICE(ctx->device);
+    for (int r = 0; r < DCS_CONV_ROLES; ++r) ctx->note_conv(r, 0);
+    // the model's per-call state is put back as it was found (conv2_stage may still pack the f16 bottleneck plane on first
+    // need, as a forward pass of the same size would: a cache, not a setting)
+    const float* const frames_src0 = g->frames_src;
+    const int frames_rows0 = g->frames_rows, frames_st0 = g->frames_st, n_out16_0 = g->n_out16;
+    int rc;
+    if (stage == DCS_CONV_STAGE_CONV1) {
+        g->frames_src = per_frame ? a->frames_src : nullptr;
+        g->frames_rows = per_frame ? a->frames_rows : 0;
+        g->frames_st = per_frame ? a->frames_stride : 0;
+        rc = conv1_stage(g, k, h);
+        g->frames_src = frames_src0; g->frames_rows = frames_rows0; g->frames_st = frames_st0;
+    } else if (stage == DCS_CONV_STAGE_CONV2) {
+        rc = conv2_stage(g, k, h);
+    } else {
+        if (a->d_layout == DCS_CONV_LAYOUT_CL_F16) g->n_out16 = n_out16;   // what dense_stage sets when it writes this layout
+        rc = decoder_stage(g, k, h);
+        g->n_out16 = n_out16_0;
+    }
+    DCS_CHECK(rc);
+    DCS_HIP(hipGetLastError());
+    DCS_HIP(hipStreamSynchronize(ctx->stream));
+    a->a1_layout = (int)h.a1_layout; a->a1_rows = h.a1_rows; a->fold2 = h.fold2 ? 1 : 0; a->a2_f16 = h.a2_f16 ? 1 : 0;
+    return DCS_OK;
+}
+
+// Test aid: the folded conv2 + bottleneck weights copied to the host, [rows = nf1 tc wp][cols = hid64].  A model that folds
+// (dcs_generic_create decides by the two layers' cost) hands out its own B2fc; for one that does not, fold_conv2_fc_kernel is
+// run here as dcs_generic_create runs it -- same arguments, same grid -- into a block of its own: the filters in the kernel's
+// order come back from W2m ([(ci, u, v)][32 co], the same flipped filter)
+int dcs_generic_debug_fold_weights(DcsGenericNet* g, float* out_h, int64_t n_out, int64_t* rows, int64_t* cols) {
+    if (!g) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_fold_weights: null argument");
+    const DcsGenericDims& d = g->d;
+    const int64_t Kf = (int64_t)d.nf1 * g->tc * d.wp;
+    if (d.kw2 < 2 || Kf >= (1 << 30)) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_conv_fold_weights: conv2 of this graph is never folded into the bottleneck layer");
+    if (rows) *rows = Kf;
+    if (cols) *cols = g->hid64;
+    if (!out_h) return DCS_OK;                           // the shape alone
+    if (n_out < Kf * g->hid64)
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_fold_weights: room for %lld floats, the weights are %lld", (long long)n_out, (long long)(Kf * g->hid64));
+    dcs_ctx* ctx = g->ctx;
+    DCS_ON_DEVICE(ctx->device);
+    DCS_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t bytes = (size_t)Kf * g->hid64 * sizeof(float);
+    if (g->B2fc && g->K2fc == Kf) {
+        DCS_HIP(hipMemcpy(out_h, g->B2fc, bytes, hipMemcpyDeviceToHost));
+        return DCS_OK;
+    }
+    const int kh = d.kh2, kw = d.kw2, nf1 = d.nf1, nf2 = d.nf2;
+    std::vector<float> W2m((size_t)dcs_round_up(g->K2, 32) * 32), Wf2((size_t)kh * kw * nf2 * nf1);
+    DCS_HIP(hipMemcpy(W2m.data(), g->W2m, W2m.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int co = 0; co < nf2; ++co)
+        for (int ci = 0; ci < nf1; ++ci)
+            for (int u = 0; u < kh; ++u)
+                for (int v = 0; v < kw; ++v)
+                    Wf2[((size_t)(u * kw + v) * nf2 + co) * nf1 + ci] = W2m[((size_t)(ci * kh + u) * kw + v) * 32 + co];
+    float *Wf2_d = nullptr, *fold_d = nullptr;
+    int rc = upload(&Wf2_d, Wf2, "debug.Wf2");
+    const size_t fold_bytes = (size_t)dcs_round_up(Kf, 128) * g->hid64 * sizeof(float);
+    if (rc == DCS_OK && dcs_dev_alloc((void**)&fold_d, fold_bytes, "debug.B2fc") != hipSuccess) {
+        (void)hipGetLastError();
+        rc = DCS_ENOMEM;
+    }
+    if (rc == DCS_OK) {
+        if (hipMemsetAsync(fold_d, 0, fold_bytes, ctx->stream) != hipSuccess) rc = DCS_EHIP;
+        if (rc == DCS_OK)
+            hipLaunchKernelGGL(fold_conv2_fc_kernel, dim3((unsigned)Kf), dim3(kThreads), 0, ctx->stream, Wf2_d, g->Bfc, fold_d, nf1, nf2, kh,
+                               kw, g->tc, d.wp, d.h2, d.w2, g->hid64);
+        if (rc == DCS_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)) rc = DCS_EHIP;
+        if (rc == DCS_OK && hipMemcpy(out_h, fold_d, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = DCS_EHIP;
+    }
+    dcs_dev_free(Wf2_d);
+    dcs_dev_free(fold_d);
+    if (rc != DCS_OK) DCS_FAIL(rc, "dcs_debug_conv_fold_weights: folding on the device failed");
     return DCS_OK;
 }

@@ -663,6 +663,28 @@ extern "C" int dcs_model_set_latency_stages(dcs_model* m, int stages) {
 extern "C" int dcs_model_num_sources(const dcs_model* m) { return m ? m->d.S : DCS_EINVAL; }
 extern "C" int dcs_model_out_channels(const dcs_model* m) { return m ? m->d.n_branch * m->C : DCS_EINVAL; }
 
+// test aids for the convolution kernels of the generic graphs (include/dcs.h)
+extern "C" int dcs_debug_conv_stage(dcs_model* m, int stage, dcs_debug_conv_args* args) {
+    if (!m || !args) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_stage: null argument");
+    if (!m->gen) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_conv_stage: not a generic-graph model (ikala / bach10 / score-informed)");
+    return dcs_generic_debug_conv_stage(m->gen, stage, args);
+}
+
+extern "C" int dcs_debug_conv_fold_weights(const dcs_model* m, float* out_h, int64_t n_out, int64_t* rows, int64_t* cols) {
+    if (!m) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_fold_weights: null model");
+    if (!m->gen) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_conv_fold_weights: not a generic-graph model");
+    return dcs_generic_debug_fold_weights(m->gen, out_h, n_out, rows, cols);
+}
+
+extern "C" int dcs_debug_conv_last_kernel(const dcs_model* m, int* codes, int64_t* params) {
+    if (!m) DCS_FAIL(DCS_EINVAL, "dcs_debug_conv_last_kernel: null model");
+    for (int r = 0; r < DCS_CONV_ROLES; ++r) {
+        if (codes) codes[r] = m->ctx->last_conv[r];
+        for (int i = 0; i < 3 && params; ++i) params[3 * r + i] = m->ctx->last_conv_param[r][i];
+    }
+    return DCS_OK;
+}
+
 // ONE place decides which one-batch stages (dsd_lat.hip) a call takes: separate_impl (what runs), separate_graphed (whether
 // the call is replayed from a hipGraph) and dcs_model_final_kernel (what bench.py prices) all ask here.  plan == nullptr /
 // ov < 0: the caller does not know them (dcs_model_final_kernel) -- the frame-size and covering-tile conditions are then

@@ -408,6 +408,7 @@ bool dcs_launch_slabconv_ps(dcs_ctx* ctx, DcsSlabConv a, int64_t n_images, const
     const int nw = 16, nbw = 2;
     const int slots = nw * nbw;
     int band = 0, xt = 0, ps_best = 1;
+    bool strips = false;
     size_t lds = 0;
     double best = 0.0;
     for (int cxt = pu ? 1 : nxb_all; cxt <= nxb_all && cxt <= slots; ++cxt) {     // 16-column blocks per tile
@@ -452,7 +453,7 @@ bool dcs_launch_slabconv_ps(dcs_ctx* ctx, DcsSlabConv a, int64_t n_images, const
         for (int ps = 5; ps >= 1; --ps) {
             const size_t need = (size_t)2 * ps * np * 128 * 16 + (size_t)(rows * sw + 1) * rec;
             if (need <= 160 * 1024) {
-                band = a.Ho; xt = 16; lds = need; ps_best = ps;
+                band = a.Ho; xt = 16; lds = need; ps_best = ps; strips = true;
                 break;
             }
         }
@@ -475,6 +476,12 @@ bool dcs_launch_slabconv_ps(dcs_ctx* ctx, DcsSlabConv a, int64_t n_images, const
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
+    // (kw == 1 is only ever asked for with three bf16 planes, launch_colconv; without the tap-pair mask, kw > 64, no graph has:
+    // should either be reached one day, DCS_CONV_K_UNLISTED fails every comparison with an expected code)
+    ctx->note_conv(a.ph == 0 && a.pw == 0 ? DCS_CONV_ROLE_CONV2 : DCS_CONV_ROLE_CONV2T,
+                   pu ? (mode ? DCS_CONV_K_UNLISTED : DCS_CONV_K_SLAB_PS_COL_0)
+                      : !fast ? DCS_CONV_K_UNLISTED : (strips ? DCS_CONV_K_SLAB_PS_STRIP_0 : DCS_CONV_K_SLAB_PS_0) + (mode ? 1 : 0),
+                   band, xt, ps_best);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_images * a.n_bands * a.n_xt)), dim3(64 * nw), lds, ctx->stream, a,
                        reinterpret_cast<const u32x4*>(Wq));
     return true;

@@ -886,6 +886,115 @@ DCS_API int dcs_debug_gemm_pack(dcs_ctx* ctx, int kind, const float* src, int64_
 #define DCS_GEMM_K_F16_LONGK_11_A16 32
 DCS_API int dcs_debug_gemm_last_kernel(const dcs_ctx* ctx, int* code, int64_t* params);
 
+/* Test aids for the convolution kernels of the generic graphs (ikala / bach10 / score-informed: csrc/generic.hip,
+ * slabconv_ps.hip, colconv_fwd_x3.hip, colconv_wreg.hip, colconv_x3.hip, conv1_mfma.hip, deconv1_mfma.hip;
+ * tests/test_gpu_conv_kernels.py); no reference counterpart.  dcs_debug_conv_stage runs ONE stage of a model's forward
+ * pass -- the very function the graph calls, so the choice of kernel is the production one -- on the caller's buffers:
+ *   DCS_CONV_STAGE_CONV1    tiles [n][C][tc][F] -> a1b (and, in a graph with a pool layer, p1)
+ *   DCS_CONV_STAGE_CONV2    a1b (p1 in a graph with a pool layer), laid out as a1_layout / a1_rows say -> a2b
+ *   DCS_CONV_STAGE_DECODER  D, laid out as d_layout says -> o [n][n_branch * C][tc][F] (through g2, g1 where the two
+ *                           InverseLayers run as separate kernels; a graph with a pool layer reads a1b as conv1 left it)
+ * Every buffer a stage can touch comes with its byte count and must be 16-byte aligned and hold what the forward pass
+ * itself would have carved for n tiles and n_branch branches:
+ *   tiles n C tc F floats | a1b n nf1 tc w1 floats | p1 n nf1 tc wp | a2b n flat_p | D n n_branch flat_p (f16 layout: n
+ *   n_branch round_up(32 h2 w2, 128) halves if that is more) | g2 n n_branch nf1 tc wp | g1 n n_branch nf1 tc w1 | o n n_branch C tc F
+ * (flat_p = nf2 h2 w2 rounded up to 4).  DCS_EINVAL, and nothing launched, for a null or misaligned buffer the stage needs, a
+ * short byte count, n or n_branch out of range, an unknown layout or tie mode.  DCS_EUNSUPPORTED, and nothing launched, for a
+ * layout the model's plan cannot consume (a channels-last a1 without the kernel that reads it; a channels-last D where
+ * the decoder would not run as one kernel and would have to redo the dense layers, which needs their input).
+ * conv1 may be given the clip's frames (frames_src [C][frames_rows][F], tile k = rows k * frames_stride .. + tc, frames_rows =
+ * (n - 1) * frames_stride + tc, 0 < frames_stride < tc): it then runs per frame where the graph would.  On return a1_layout,
+ * a1_rows, fold2 and a2_f16 hold what the stage handed on (conv2 reads the first two as its input).  One stream
+ * synchronisation per call.  The model is left as it was found, except that conv2 may pack the f16 plane of the bottleneck
+ * weights on first need, as a forward pass of the same size would. */
+#define DCS_CONV_STAGE_CONV1 0
+#define DCS_CONV_STAGE_CONV2 1
+#define DCS_CONV_STAGE_DECODER 2
+#define DCS_CONV_LAYOUT_CHANNEL_FIRST 0   /* f32 [image][channel][row][x] */
+#define DCS_CONV_LAYOUT_CL_F32 1          /* f32 [image][row][x][channel] */
+#define DCS_CONV_LAYOUT_CL_F16 2          /* f16 [image][row][x][32], channels 30 and 31 zero */
+typedef struct dcs_debug_conv_args {
+    int64_t n; int32_t n_branch, tie_mode;
+    const float* tiles; int64_t tiles_bytes;
+    void* a1b; int64_t a1b_bytes;
+    void* p1; int64_t p1_bytes;
+    void* a2b; int64_t a2b_bytes;
+    void* D; int64_t D_bytes;
+    void* g2; int64_t g2_bytes;
+    void* g1; int64_t g1_bytes;
+    void* o; int64_t o_bytes;
+    const float* frames_src; int64_t frames_bytes; int32_t frames_rows, frames_stride;
+    int32_t a1_layout, a1_rows;           /* in: conv2; out: conv1 */
+    int32_t d_layout;                     /* in: decoder */
+    int32_t fold2, a2_f16;                /* out: conv2 */
+} dcs_debug_conv_args;
+DCS_API int dcs_debug_conv_stage(dcs_model* m, int stage, dcs_debug_conv_args* args);
+/* Which kernel each role of the model's context launched last (any entry point; 0 = none since the last
+ * dcs_debug_conv_stage began, which clears them) and three choices of its launcher: codes[DCS_CONV_ROLES],
+ * params[DCS_CONV_ROLES][3] = {band, column tile, tap pairs per weight stage} for the slab kernels, else {column blocks per
+ * workgroup, runs per image, workgroups} (0 where there is none).  Host-side bookkeeping, one store per launch. */
+#define DCS_CONV_ROLE_CONV1 0
+#define DCS_CONV_ROLE_POOL 1
+#define DCS_CONV_ROLE_CONV2 2
+#define DCS_CONV_ROLE_CONV2T 3
+#define DCS_CONV_ROLE_UNPOOL 4
+#define DCS_CONV_ROLE_CONV1T 5
+#define DCS_CONV_ROLE_DECODER 6           /* both InverseLayers as one kernel */
+#define DCS_CONV_ROLE_PAD 7               /* zero_pad_cols_kernel in front of conv2 */
+#define DCS_CONV_ROLES 8
+#define DCS_CONV_K_CONV1 1                /* conv1_kernel<30> */
+#define DCS_CONV_K_CONV1_REG4 2           /* conv1_reg_kernel<30, 4> */
+#define DCS_CONV_K_CONV1_REG3 3           /* conv1_reg_kernel<30, 3> */
+#define DCS_CONV_K_CONV1_REG3_POOL 4      /* conv1_reg_kernel<30, 3, true> */
+#define DCS_CONV_K_CONV1_MFMA_1 5         /* conv1_mfma_kernel<1, 0>; + 1: channels-last, + 2: f16 channels-last */
+#define DCS_CONV_K_CONV1_MFMA_1_CL 6
+#define DCS_CONV_K_CONV1_MFMA_1_CL16 7
+#define DCS_CONV_K_CONV1_MFMA_4 8         /* conv1_mfma_kernel<4, 0>; + 1: channels-last */
+#define DCS_CONV_K_CONV1_MFMA_4_CL 9
+#define DCS_CONV_K_POOL 10                /* pool_kernel */
+#define DCS_CONV_K_UNPOOL 11              /* unpool_kernel<4> */
+#define DCS_CONV_K_IGEMM 12               /* conv_igemm_kernel, forward */
+#define DCS_CONV_K_IGEMM_T 13             /* conv_igemm_kernel, transposed */
+#define DCS_CONV_K_IGEMM_F16 14           /* conv_igemm_f16_kernel (either direction: the role says which) */
+#define DCS_CONV_K_SLAB_MX_0 15           /* slabconv_mx_kernel<0>; + 1: <1> */
+#define DCS_CONV_K_SLAB_MX_1 16
+#define DCS_CONV_K_SLAB_PS_0 17           /* slabconv_ps_kernel<0, 16, false, true>, row bands; + 1: mode 1 */
+#define DCS_CONV_K_SLAB_PS_1 18
+#define DCS_CONV_K_SLAB_PS_STRIP_0 19     /* the same kernel on column strips; + 1: mode 1 */
+#define DCS_CONV_K_SLAB_PS_STRIP_1 20
+#define DCS_CONV_K_SLAB_PS_COL_0 21       /* slabconv_ps_kernel<0, 16, true, false>: kw == 1 */
+#define DCS_CONV_K_COLCONV 22             /* colconv_kernel, forward */
+#define DCS_CONV_K_COLCONV_T 23           /* colconv_kernel, transposed */
+#define DCS_CONV_K_COLCONV_F16 24         /* colconv_f16_kernel (either direction) */
+#define DCS_CONV_K_COLCONV_FWD_X3 25      /* colconv_fwd_x3_kernel<20, 30> */
+#define DCS_CONV_K_WREG_SCATTER 26        /* colconv_wreg_scatter_kernel<20, 30, 8, false, false>; + 1: f16 in, + 2: f16 out */
+#define DCS_CONV_K_WREG_SCATTER_I16 27
+#define DCS_CONV_K_WREG_SCATTER_O16 28
+#define DCS_CONV_K_WREG_SCATTER_I16_O16 29
+#define DCS_CONV_K_WREG_GATHER 30         /* colconv_wreg_gather_kernel<20, 11> */
+#define DCS_CONV_K_DECONV1 31             /* deconv1_kernel<30> */
+#define DCS_CONV_K_DECONV1_REG3 32        /* deconv1_reg_kernel<3, 10> */
+#define DCS_CONV_K_DECONV1_REG3_POOL 33   /* deconv1_reg_kernel<3, 10, true> */
+#define DCS_CONV_K_DECONV1_REG4 34        /* deconv1_reg_kernel<4, 8> */
+#define DCS_CONV_K_DECONV1_MFMA_1 35      /* deconv1_mfma_kernel<1> */
+#define DCS_CONV_K_DECONV1_MFMA_4 36      /* deconv1_mfma_kernel<4> */
+#define DCS_CONV_K_FUSED 37               /* colconv_deconv1_fused_kernel<20, 11, false, false>; + 1: channels-last, + 2: f16 */
+#define DCS_CONV_K_FUSED_CL 38
+#define DCS_CONV_K_FUSED_CL16 39
+#define DCS_CONV_K_FUSED_X3_1 40          /* colconv_deconv1_fused_x3_kernel<20, 11, 1> */
+#define DCS_CONV_K_FUSED_X3_4 41          /* colconv_deconv1_fused_x3_kernel<20, 11, 4> */
+#define DCS_CONV_K_ZERO_PAD 42            /* zero_pad_cols_kernel */
+#define DCS_CONV_K_UNLISTED 255           /* an instance no graph reaches today (slabconv_ps_kernel without its tap-pair mask, or kw == 1 on one f16 plane) */
+DCS_API int dcs_debug_conv_last_kernel(const dcs_model* m, int* codes, int64_t* params);
+/* The weights of conv2 + BiasLayer + bottleneck layer folded into one affine map of conv2's input (fold_conv2_fc_kernel),
+ * copied to out_h (HOST memory, n_out floats of room): [rows = nf1 * tc * wp, row (ci, r, x)][cols = the hidden width rounded
+ * up to 64]; *rows and *cols (nullable) are set, and with out_h null only they.  A model that runs folded (the iKala graphs
+ * where conv2 costs at least four times what the fold adds to the layer, e.g. 513 bins) hands out the weights it uses; for a
+ * smaller one the kernel is run for this call as model creation would run it, into a block that is freed again.
+ * DCS_EUNSUPPORTED for the column-filter graphs (kw == 1: never folded), DCS_EINVAL when n_out is short.  Synchronises the
+ * stream. */
+DCS_API int dcs_debug_conv_fold_weights(const dcs_model* m, float* out_h, int64_t n_out, int64_t* rows, int64_t* cols);
+
 #ifdef __cplusplus
 }
 #endif
