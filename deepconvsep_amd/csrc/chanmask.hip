@@ -9,6 +9,7 @@
 // One thread per (frame, bin), coalesced along the bins; the tiles that cover a frame are the same for the whole workgroup.
 // Each (tile, frame, bin) of p is read exactly once, nothing is accumulated across threads: the same bits every run.
 #include "dcs_internal.h"
+#include "chanmask.h"       // soft_masks: the masks of one tile position
 
 namespace {
 
@@ -30,23 +31,6 @@ struct ChanMaskArgs {
     float* mask;              // [S][T, ld] or null
     int64_t mask_src_stride;
 };
-
-// the masks of one tile position: p[s] -> m[s], the expressions and the order of mask_kernel
-template <int SA>
-__device__ __forceinline__ void soft_masks(float (&p)[SA], int S, int mode) {
-    const float eps_r = 5e-19f;
-    float den = 0.f;
-#pragma unroll
-    for (int s = 0; s < SA; ++s)
-        if (s < S) {
-            if (mode == DCS_EPS_A) p[s] += eps_r;
-            den = (s == 0) ? p[s] : den + p[s];
-        }
-    if (mode == DCS_EPS_B) den += eps_r;
-#pragma unroll
-    for (int s = 0; s < SA; ++s)
-        if (s < S) p[s] = p[s] / den;
-}
 
 // MM > 0: a frame is covered by at most MM tiles and S == SS; all MM x SS values of p and the C magnitudes are requested
 // before the first is used (see mask_ola_kernel).  MM == 0: any tile count, any S <= 8, one tile after the other.

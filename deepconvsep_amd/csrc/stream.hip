@@ -1,0 +1,468 @@
+// dcs_stream: separation of a signal that arrives in blocks (include/dcs.h has the contract, DESIGN.md section 4r the
+// formulas and the state sizes).
+//
+// The whole-file paths run STFT -> tiles -> network -> fold -> iSTFT once, on a signal that is complete and resident.  Here
+// the same values are produced as the samples come: every frame depends on N samples, every tile on tc frames, the fold of a
+// frame on the tiles that cover it and an output sample on the N / hop frames that cover it, so a sample of the whole-file
+// result is final tc hop + N samples after it went in.  A push appends samples to a ring, transforms the frames that became
+// complete into a ring of magnitude / phase rows and hands out the tiles that became ready; the caller runs them through the
+// network; a pull folds the masks of those tiles (and of the few before them, kept in a ring of p) over the frames no later
+// tile can reach, inverts each of these frames into a ring of windowed time-domain frames and gathers the samples no later
+// frame can reach.  All counts are host integers.  Every kernel is a pure function of ABSOLUTE sample, frame and tile indices
+// (a ring slot is index mod ring length), nothing is accumulated across threads and no ring slot is read before the push or
+// pull that needs it has written it: however the signal is cut into blocks, the same bits come out.
+#include "dcs_internal.h"
+#include "fft_frame.h"
+#include "chanmask.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int kMaxSources = 8;
+
+__device__ __forceinline__ int64_t ring_slot(int64_t i, int64_t len) { return i % len; }
+
+// ------------------------------------------------------------------------------------------ push: samples into the ring
+__global__ __launch_bounds__(kThreads) void stream_append_kernel(const float* __restrict__ audio, int64_t n, int64_t p0,
+                                                                 float* __restrict__ ring, int64_t cap) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) ring[ring_slot(p0 + i, cap)] = audio[i];
+}
+
+// ------------------------------------------------------------------------------------------ push: the frames that became complete
+// Frame n = n0 + blockIdx.x covers samples [n hop - N/2, n hop + N/2); samples < 0 or >= lim (the samples pushed so far, the
+// signal's length once it has ended) read as zero, as stft_norm pads.  The tail is stft_forward_kernel's, term for term.
+__global__ __launch_bounds__(kThreads) void stream_frames_kernel(
+    const float* __restrict__ ring, int64_t cap, int64_t lim, int64_t n0, int64_t rf, float* __restrict__ mag_ring,
+    float* __restrict__ phase_ring, float* __restrict__ mag_out, float* __restrict__ phase_out, int64_t ld,
+    const float* __restrict__ win, const float2* __restrict__ tw, int N, int hop, int log2m, float sqrt_n, int tw_lds) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int M = N >> 1;
+    const int tid = threadIdx.x;
+    const int64_t n = n0 + blockIdx.x;
+    const int64_t base = n * (int64_t)hop - M;
+    const float2* Z = render_frame<float, float2, false>(smem, win, tw, tw_lds, M, log2m, base, [&](int64_t q) -> float {
+        return (q < 0 || q >= lim) ? 0.f : ring[ring_slot(q, cap)];
+    });
+    float* mrow = mag_ring + ring_slot(n, rf) * (int64_t)(M + 1);
+    float* prow = phase_ring + ring_slot(n, rf) * (int64_t)(M + 1);
+    float* mo = mag_out ? mag_out + (int64_t)blockIdx.x * ld : nullptr;
+    float* po = phase_out ? phase_out + (int64_t)blockIdx.x * ld : nullptr;
+    for (int k = tid; k <= M; k += kThreads) {
+        const float2 zk = Z[k & (M - 1)];
+        const float2 zm = Z[(M - k) & (M - 1)];
+        // E = (zk + conj(zm))/2 ; O = -i (zk - conj(zm))/2 ; X = E + w^k O
+        const float er = 0.5f * (zk.x + zm.x), ei = 0.5f * (zk.y - zm.y);
+        const float orr = 0.5f * (zk.y + zm.y), oi = -0.5f * (zk.x - zm.x);
+        const float2 w = tw[k];
+        const float xr = er + (w.x * orr - w.y * oi);
+        const float xi = ei + (w.x * oi + w.y * orr);
+        const float ax = dcs_sqrt(xr * xr + xi * xi);
+        const float mg = ax / sqrt_n, ph = dcs_atan2(xi, xr);
+        mrow[k] = mg;
+        prow[k] = ph;
+        if (mo) mo[k] = mg;
+        if (po) po[k] = ph;
+    }
+    for (int k = M + 1 + tid; k < ld; k += kThreads) {   // row padding of the caller's copies
+        if (mo) mo[k] = 0.f;
+        if (po) po[k] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ push: the tiles that became ready
+// tiles[i][0][j][:] = scale * mag[(k0 + i) st + j][:], zero for rows >= T (the library tiler's last tiles, after the end)
+__global__ __launch_bounds__(kThreads) void stream_tiles_kernel(const float* __restrict__ mag_ring, int64_t rf, int F, int tc,
+                                                                int st, int64_t k0, int64_t T, float scale,
+                                                                float* __restrict__ tiles) {
+    const int64_t i = blockIdx.x / tc;
+    const int j = (int)(blockIdx.x - i * tc);
+    const int64_t t = (k0 + i) * st + j;
+    float* dst = tiles + (i * tc + j) * (int64_t)F;
+    if (t < T) {
+        const float* src = mag_ring + ring_slot(t, rf) * (int64_t)F;
+        for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = scale * src[f];
+    } else {
+        for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ pull: p of the new tiles into its ring
+__global__ __launch_bounds__(kThreads) void stream_keep_p_kernel(const float* __restrict__ p, int64_t p_src_stride, int64_t k0,
+                                                                 int64_t tile_elems, float* __restrict__ p_ring, int64_t rp) {
+    const int64_t i = blockIdx.x;                       // tile of this pull
+    const int s = blockIdx.z;
+    const float* src = p + s * p_src_stride + i * tile_elems;
+    float* dst = p_ring + ((int64_t)s * rp + ring_slot(k0 + i, rp)) * tile_elems;
+    for (int64_t e = (int64_t)blockIdx.y * kThreads + threadIdx.x; e < tile_elems; e += (int64_t)gridDim.y * kThreads)
+        dst[e] = src[e];
+}
+
+// ------------------------------------------------------------------------------------------ pull: fold + apply
+// The per-frame definition of dcs_mask_fold_apply (mask_fold_apply_kernel<0, 0>, expression for expression) with absolute
+// t = t0 + blockIdx.x and k, p and the magnitudes read from their rings.  n = the tiles that exist so far: mid-stream every
+// frame folded has its owner below n, so the clamp acts only after the end.  est[s][blockIdx.x][f] = acc_s * mag[t][f].
+__global__ __launch_bounds__(kThreads) void stream_fold_kernel(
+    const float* __restrict__ p_ring, int64_t rp, int64_t n, int S, int tc, int ov, int F, int mode,
+    const float* __restrict__ rise, const float* __restrict__ mag_ring, int64_t rf, int64_t t0, float* __restrict__ est,
+    int64_t est_src_stride, float* __restrict__ est_out, int64_t out_src_stride, int64_t ld) {
+    const int f = blockIdx.y * kThreads + threadIdx.x;
+    if (f >= F) return;
+    const int64_t t = t0 + blockIdx.x;
+    const int st = tc - ov;
+    const int64_t tile_elems = (int64_t)tc * F, src_stride = rp * tile_elems;
+    int64_t k0 = (t < ov) ? 0 : (t - ov) / st;
+    if (k0 > n - 1) k0 = n - 1;
+    const int64_t j0 = (n > 0) ? t - k0 * st : tc;
+    const float mg = mag_ring[ring_slot(t, rf) * (int64_t)F + f];
+
+    float acc[kMaxSources];
+#pragma unroll
+    for (int s = 0; s < kMaxSources; ++s) acc[s] = 0.f;
+    if (j0 < tc) {                                       // else: past the last tile, the zeros of util.py:313
+        for (int64_t k = k0; k < n && k * st <= t; ++k) {
+            const int j = (int)(t - k * st);
+            const int64_t r = ring_slot(k, rp) * tile_elems + (int64_t)j * F + f;
+            float p[kMaxSources];
+#pragma unroll
+            for (int s = 0; s < kMaxSources; ++s) p[s] = s < S ? p_ring[s * src_stride + r] : 0.f;
+            soft_masks<kMaxSources>(p, S, mode);
+            if (k == k0) {
+#pragma unroll
+                for (int s = 0; s < kMaxSources; ++s) acc[s] = p[s];
+            } else {
+                const float down = rise[ov - 1 - j], up = rise[j];
+#pragma unroll
+                for (int s = 0; s < kMaxSources; ++s) acc[s] = fmaf(down, acc[s], __fmul_rn(up, p[s]));   // one explicit form: see overlap_add_kernel
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < kMaxSources; ++s)
+        if (s < S) {
+            const float e = __fmul_rn(acc[s], mg);
+            est[s * est_src_stride + (int64_t)blockIdx.x * F + f] = e;
+            if (est_out) est_out[s * out_src_stride + (int64_t)blockIdx.x * ld + f] = e;
+        }
+}
+
+// ------------------------------------------------------------------------------------------ pull: one frame of one source back to time
+// y_n = w * irfft(est[s][n] sqrt(N) exp(j phase[n])) into slot n mod rt of the time-frame ring [rt][S][N]: the packed real-inverse
+// pre-processing, transform and window product of istft_fused_kernel (fft.hip), term for term, for ONE frame -- the sum over
+// the frames that cover a sample is stream_gather_kernel's.  Workgroup (blockIdx.x, blockIdx.y) = (frame t0 + x, source y).
+__global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
+    const float* __restrict__ est, int64_t est_src_stride, const float* __restrict__ phase_ring, int64_t rf, int64_t t0,
+    float* __restrict__ tf_ring, int64_t rt, int S, const float* __restrict__ win, const float2* __restrict__ tw, int N, int log2m,
+    float sqrt_n, int tw_lds) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int M = N >> 1;
+    const int tid = threadIdx.x;
+    const int s = blockIdx.y;
+    const int64_t n = t0 + blockIdx.x;
+    float2* buf0 = reinterpret_cast<float2*>(smem);
+    float2* buf1 = buf0 + M;  // M+1 entries: holds X first, then serves as the FFT ping-pong buffer
+    float2* X = buf1;
+    if (tw_lds) {
+        float2* twl = buf1 + (M + 1);
+        for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
+        tw = twl;
+    }
+    const float* mrow = est + s * est_src_stride + (int64_t)blockIdx.x * (M + 1);
+    const float* prow = phase_ring + ring_slot(n, rf) * (int64_t)(M + 1);
+    for (int k = tid; k <= M; k += kThreads) {
+        const float a = mrow[k] * sqrt_n;
+        float sn, cs;
+        dcs_sincos(prow[k], &sn, &cs);
+        float2 x = mk<float2, float>(a * cs, a * sn);
+        if (k == 0 || k == M) x.y = 0.f;
+        X[k] = x;
+    }
+    __syncthreads();
+    for (int k = tid; k < M; k += kThreads) {
+        const float2 xk = X[k];
+        const float2 xm = X[M - k];
+        // E = (xk + conj(xm))/2 ; D = (xk - conj(xm))/2 ; O = D * conj(w^k) ; Z = E + i O
+        const float er = 0.5f * (xk.x + xm.x), ei = 0.5f * (xk.y - xm.y);
+        const float dr = 0.5f * (xk.x - xm.x), di = 0.5f * (xk.y + xm.y);
+        const float2 w = tw[k];
+        const float orr = dr * w.x + di * w.y;
+        const float oi = di * w.x - dr * w.y;
+        buf0[k] = mk<float2, float>(er - oi, ei + orr);
+    }
+    __syncthreads();
+    const float2* z = fft_lds<float, float2, +1>(buf0, buf1, tw, M, log2m);
+    const float inv_m = 1.f / (float)M;
+    const float2* w2 = reinterpret_cast<const float2*>(win);
+    float2* dst = reinterpret_cast<float2*>(tf_ring + (ring_slot(n, rt) * S + s) * (int64_t)N);
+    for (int m = tid; m < M; m += kThreads) {
+        const float2 v = z[m];
+        const float2 w = w2[m];
+        dst[m] = mk<float2, float>((v.x * inv_m) * w.x, (v.y * inv_m) * w.y);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ pull: the samples that became final
+// out[s][q - q0] = (y_lo[..] + y_{lo+1}[..] + ... in increasing n) / norm over the frames n < T with n hop <= q + N/2 < n hop + N,
+// norm = the sum of w^2 over the same frames, 0 replaced by 1 (istft_norm).  T = the frames folded so far (every frame there is,
+// once the signal has ended): mid-stream a sample is emitted only when all its frames are below it.
+__global__ __launch_bounds__(kThreads) void stream_gather_kernel(const float* __restrict__ tf_ring, int64_t rt, int S, int N,
+                                                                 int hop, int64_t T, const float* __restrict__ wsq, int64_t q0,
+                                                                 int64_t n_out, float* __restrict__ pcm, int64_t pcm_stride) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n_out) return;
+    const int s = blockIdx.y;
+    const int64_t p = q0 + i + (N >> 1);                // position in the padded signal
+    int64_t n_hi = p / hop;
+    if (n_hi > T - 1) n_hi = T - 1;
+    const int64_t n_lo = (p < N) ? 0 : (p - N) / hop + 1;
+    float acc = 0.f, norm = 0.f;
+    for (int64_t n = n_lo; n <= n_hi; ++n) {
+        const int64_t off = p - n * hop;
+        acc += tf_ring[(ring_slot(n, rt) * S + s) * (int64_t)N + off];
+        norm += wsq[off];
+    }
+    if (norm == 0.f) norm = 1.f;
+    pcm[s * pcm_stride + i] = acc / norm;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ the handle
+struct dcs_stream {
+    dcs_stft* plan = nullptr;
+    dcs_ctx* ctx = nullptr;
+    int S = 0, tc = 0, ov = 0, st = 0, tiler = 0, eps_mode = 0, N = 0, hop = 0, F = 0;
+    float scale = 1.f;
+    int64_t max_push = 0;
+    // ring lengths: samples; frames a push can complete, the end included; tiles it can return; frame rows; tiles of p; frames
+    // a pull can fold; time-domain frames
+    int64_t cap = 0, fp = 0, max_tiles = 0, rf = 0, rp = 0, ff = 0, rt = 0;
+    float *samples = nullptr, *mag = nullptr, *phase = nullptr, *p = nullptr, *est = nullptr, *tf = nullptr, *rise = nullptr;
+    int64_t bytes = 0;
+    // host counts (the table of include/dcs.h): samples pushed, frames transformed, tiles handed out, frames folded, samples
+    // emitted; T and L are known once the signal has ended
+    int64_t P = 0, A = 0, K = 0, Tf = 0, E = 0, T = 0, L = 0;
+    int64_t pending = 0;       // tiles of the last push, which the next pull must bring p for
+    bool want_pull = false, ended = false;
+};
+
+extern "C" int dcs_stream_create(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
+                                 const double* rise_h, int64_t max_push, dcs_stream** out) {
+    if (!plan || !rise_h || !out) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: null argument");
+    if (S < 1 || S > kMaxSources) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: %d sources (1 .. %d)", S, kMaxSources);
+    if (overlap < 1 || overlap >= time_context)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_create: overlap %d not in [1, %d)", overlap, time_context);
+    if (tiler != DCS_TILER_SCRIPT && tiler != DCS_TILER_LIBRARY) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: bad tiler");
+    if (eps_mode != DCS_EPS_A && eps_mode != DCS_EPS_B) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: bad eps_mode");
+    if (max_push < 1 || max_push > (1LL << 30)) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: max_push %lld not in [1, 2^30]", (long long)max_push);
+    const int N = plan->frame, hop = plan->hop, H = N / 2;
+    if (hop > H) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: hopSize %d above frameSize / 2 = %d", hop, H);
+    if (N % hop) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_stream_create: hopSize %d does not divide frameSize %d", hop, N);
+    if (N < 64) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_stream_create: frameSize %d below 64", N);
+    DCS_ON_DEVICE(plan->ctx->device);
+
+    dcs_stream* s = new dcs_stream();
+    s->plan = plan;
+    s->ctx = plan->ctx;
+    s->S = S; s->tc = time_context; s->ov = overlap; s->st = time_context - overlap;
+    s->tiler = tiler; s->eps_mode = eps_mode; s->scale = scale;
+    s->N = N; s->hop = hop; s->F = H + 1; s->max_push = max_push;
+    s->cap = N + max_push;                                            // a new frame reaches back less than N samples before the push
+    s->fp = (max_push + H + hop - 1) / hop + 3;                       // T - A <= (L - P + N/2) / hop + 3 at the end; fewer mid-stream
+    s->max_tiles = (s->fp + s->st - 1) / s->st + 2;
+    s->rf = time_context + s->fp;                                     // A - Tf < tc after a pull, plus one push
+    s->rp = (time_context + s->st - 1) / s->st + s->max_tiles;        // the tiles that reach the oldest unfolded frame, plus one push
+    s->ff = time_context + s->fp;                                     // T - Tf of a pull
+    s->rt = N / hop + s->ff;                                          // the frames that reach the oldest sample not yet emitted, plus one pull
+
+    const int64_t F = s->F;
+    struct { float** ptr; int64_t elems; const char* name; } blocks[] = {
+        {&s->samples, s->cap, "stream.samples"},
+        {&s->mag, s->rf * F, "stream.mag"},
+        {&s->phase, s->rf * F, "stream.phase"},
+        {&s->p, (int64_t)S * s->rp * time_context * F, "stream.p"},
+        {&s->est, (int64_t)S * s->ff * F, "stream.est"},
+        {&s->tf, s->rt * S * N, "stream.tf"},
+        {&s->rise, overlap, "stream.rise"},
+    };
+    for (auto& b : blocks) {
+        const hipError_t e = dcs_dev_alloc((void**)b.ptr, (size_t)b.elems * sizeof(float), b.name);
+        if (e != hipSuccess) {
+            dcs_set_error("dcs_stream_create: %lld bytes for %s: %s", (long long)(b.elems * sizeof(float)), b.name,
+                          hipGetErrorString(e));
+            dcs_stream_destroy(s);
+            return e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP;
+        }
+        s->bytes += b.elems * (int64_t)sizeof(float);
+    }
+    std::vector<float> rise((size_t)overlap);
+    for (int i = 0; i < overlap; ++i) rise[i] = (float)rise_h[i];
+    if (hipMemcpy(s->rise, rise.data(), rise.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        dcs_stream_destroy(s);
+        DCS_FAIL(DCS_EHIP, "dcs_stream_create: uploading the cross-fade ramp failed");
+    }
+    *out = s;
+    return DCS_OK;
+}
+
+extern "C" int dcs_stream_destroy(dcs_stream* s) {
+    if (!s) return DCS_OK;
+    DCS_ON_DEVICE(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    dcs_dev_free(s->samples);
+    dcs_dev_free(s->mag);
+    dcs_dev_free(s->phase);
+    dcs_dev_free(s->p);
+    dcs_dev_free(s->est);
+    dcs_dev_free(s->tf);
+    dcs_dev_free(s->rise);
+    delete s;
+    return DCS_OK;
+}
+
+extern "C" int dcs_stream_reset(dcs_stream* s) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_reset: null stream");
+    // the rings keep their contents: no slot is read before the push or pull that needs it has written it
+    s->P = s->A = s->K = s->Tf = s->E = s->T = s->L = s->pending = 0;
+    s->want_pull = s->ended = false;
+    return DCS_OK;
+}
+
+extern "C" int64_t dcs_stream_max_tiles(const dcs_stream* s) { return s ? s->max_tiles : -1; }
+extern "C" int64_t dcs_stream_bytes(const dcs_stream* s) { return s ? s->bytes : -1; }
+
+extern "C" int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, int last, float* tiles_d, int64_t tiles_cap,
+                               int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ld, int64_t* n_frames_out) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: null stream");
+    if (s->want_pull) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: the tiles of the previous push have not been pulled");
+    if (s->ended) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: the signal has ended (dcs_stream_reset starts another)");
+    if (n < 0 || n > s->max_push)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_push: %lld samples (0 .. max_push = %lld)", (long long)n, (long long)s->max_push);
+    if (n > 0 && !audio_d) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: null audio");
+    if ((mag_d || phase_d) && ld < s->F) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: ld %lld below the %d bins", (long long)ld, s->F);
+    const int N = s->N, hop = s->hop, H = N / 2;
+    const int64_t P = s->P + n;
+    int64_t A, K, T = 0;
+    if (last) {
+        T = dcs_frame_count(P, hop);
+        A = T;
+        K = dcs_tile_count(T, s->tc, s->ov, s->tiler);
+    } else {
+        A = P < H ? 0 : (P - H) / hop + 1;
+        K = A < s->tc ? 0 : (A - s->tc) / s->st + 1;
+    }
+    const int64_t n_frames = A - s->A, n_tiles = K - s->K;
+    if (n_frames < 0 || n_frames > s->fp || n_tiles < 0 || n_tiles > s->max_tiles)
+        DCS_FAIL(DCS_EHIP, "dcs_stream_push: internal count out of range (%lld frames, %lld tiles)", (long long)n_frames,
+                 (long long)n_tiles);
+    if (n_tiles > tiles_cap || (n_tiles > 0 && !tiles_d))
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_push: %lld tiles become ready, room for %lld (dcs_stream_max_tiles: %lld)",
+                 (long long)n_tiles, (long long)(tiles_d ? tiles_cap : 0), (long long)s->max_tiles);
+    DCS_ON_DEVICE(s->ctx->device);
+    hipStream_t q = s->ctx->stream;
+    if (n > 0) {
+        hipLaunchKernelGGL(stream_append_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, q, audio_d, n, s->P,
+                           s->samples, s->cap);
+        DCS_HIP(hipGetLastError());
+    }
+    if (n_frames > 0)
+        DCS_CHECK((launch_frames<float, float2>(s->plan, stream_frames_kernel, n_frames, 0, s->plan->win_f, s->plan->tw_f,
+                                                (const float*)s->samples, s->cap, P, s->A, s->rf, s->mag, s->phase, mag_d,
+                                                phase_d, ld)));
+    if (n_tiles > 0) {
+        DcsTimer tm(s->ctx, DCS_TAG_TILE);
+        hipLaunchKernelGGL(stream_tiles_kernel, dim3((unsigned)(n_tiles * s->tc)), dim3(kThreads), 0, q, (const float*)s->mag,
+                           s->rf, s->F, s->tc, s->st, s->K, A, s->scale, tiles_d);
+        tm.done();
+        DCS_HIP(hipGetLastError());
+    }
+    s->P = P; s->A = A; s->K = K;
+    s->pending = n_tiles;
+    s->want_pull = true;
+    if (last) {
+        s->ended = true;
+        s->T = T;
+        s->L = P;
+    }
+    if (n_tiles_out) *n_tiles_out = n_tiles;
+    if (n_frames_out) *n_frames_out = n_frames;
+    return DCS_OK;
+}
+
+extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
+                               int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_src_stride,
+                               int64_t ld) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: null stream");
+    if (!s->want_pull) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: no push to pull for");
+    if (n_tiles != s->pending)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: p of %lld tiles, the preceding push returned %lld", (long long)n_tiles,
+                 (long long)s->pending);
+    if (n_tiles > 0 && !p_d) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: null p");
+    const int64_t tile_elems = (int64_t)s->tc * s->F;
+    if (n_tiles > 0 && s->S > 1 && p_src_stride < n_tiles * tile_elems)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: source stride %lld below %lld tiles", (long long)p_src_stride, (long long)n_tiles);
+    if (est_d && ld < s->F) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: ld %lld below the %d bins", (long long)ld, s->F);
+    if (s->ended && s->K == 0) {
+        s->want_pull = false;
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: %lld frames give no tile (the reference fails in overlapadd_multi)", (long long)s->T);
+    }
+    const int N = s->N, hop = s->hop, H = N / 2;
+    const int64_t Tf = s->ended ? s->T : s->K * s->st;
+    int64_t E = s->ended ? s->L : Tf * hop - H;
+    if (E < 0) E = 0;
+    const int64_t n_fold = Tf - s->Tf, n_pcm = E - s->E;
+    if (n_fold < 0 || n_fold > s->ff || n_pcm < 0)
+        DCS_FAIL(DCS_EHIP, "dcs_stream_pull: internal count out of range (%lld frames, %lld samples)", (long long)n_fold,
+                 (long long)n_pcm);
+    if (n_pcm > 0 && (!pcm_d || n_pcm > pcm_cap || (s->S > 1 && pcm_stride < n_pcm)))
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: %lld samples become final, room for %lld (source stride %lld)", (long long)n_pcm,
+                 (long long)(pcm_d ? pcm_cap : 0), (long long)pcm_stride);
+    if (est_d && s->S > 1 && est_src_stride < n_fold * ld)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: estimate stride %lld below %lld rows", (long long)est_src_stride, (long long)n_fold);
+    DCS_ON_DEVICE(s->ctx->device);
+    hipStream_t q = s->ctx->stream;
+    const int64_t k_first = s->K - n_tiles;
+    if (n_tiles > 0) {
+        const unsigned gy = (unsigned)(tile_elems < 64 * kThreads ? dcs_cdiv(tile_elems, kThreads) : 64);
+        hipLaunchKernelGGL(stream_keep_p_kernel, dim3((unsigned)n_tiles, gy, (unsigned)s->S), dim3(kThreads), 0, q, p_d,
+                           p_src_stride, k_first, tile_elems, s->p, s->rp);
+        DCS_HIP(hipGetLastError());
+    }
+    if (n_fold > 0) {
+        {
+            DcsTimer tm(s->ctx, DCS_TAG_MASK);
+            hipLaunchKernelGGL(stream_fold_kernel, dim3((unsigned)n_fold, (unsigned)dcs_cdiv(s->F, kThreads)), dim3(kThreads), 0, q,
+                               (const float*)s->p, s->rp, s->K, s->S, s->tc, s->ov, s->F, s->eps_mode, (const float*)s->rise,
+                               (const float*)s->mag, s->rf, s->Tf, s->est, s->ff * s->F, est_d, est_src_stride, ld);
+            tm.done();
+            DCS_HIP(hipGetLastError());
+        }
+        const int M = N / 2;
+        size_t lds = (3 * (size_t)M + 2) * sizeof(float2);
+        const int tw_lds = lds <= 64 * 1024;
+        if (!tw_lds) lds = (2 * (size_t)M + 1) * sizeof(float2);
+        if (lds > 48 * 1024)
+            DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stream_inverse_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DcsTimer tm(s->ctx, DCS_TAG_ISTFT);
+        hipLaunchKernelGGL(stream_inverse_kernel, dim3((unsigned)n_fold, (unsigned)s->S), dim3(kThreads), lds, q,
+                           (const float*)s->est, s->ff * s->F, (const float*)s->phase, s->rf, s->Tf, s->tf, s->rt, s->S,
+                           (const float*)s->plan->win_f, (const float2*)s->plan->tw_f, N, s->plan->log2m,
+                           (float)sqrt((double)N), tw_lds);
+        tm.done();
+        DCS_HIP(hipGetLastError());
+    }
+    if (n_pcm > 0) {
+        DcsTimer tm(s->ctx, DCS_TAG_ISTFT);
+        hipLaunchKernelGGL(stream_gather_kernel, dim3((unsigned)dcs_cdiv(n_pcm, kThreads), (unsigned)s->S), dim3(kThreads), 0, q,
+                           (const float*)s->tf, s->rt, s->S, N, hop, Tf, (const float*)s->plan->wsq_f, s->E, n_pcm, pcm_d,
+                           pcm_stride);
+        tm.done();
+        DCS_HIP(hipGetLastError());
+    }
+    s->Tf = Tf; s->E = E;
+    s->want_pull = false;
+    if (n_out) *n_out = n_pcm;
+    return DCS_OK;
+}

@@ -503,6 +503,106 @@ class Network(object):
             pass
 
 
+class Stream(object):
+    """``dcs_stream``: the device state of a streaming separation on one STFT plan -- sample, frame, ``p`` and time-frame rings
+    whose size depends on ``(frameSize, hop, time_context, overlap, S, max_push)`` alone.  ``push`` and ``pull`` alternate
+    strictly; the counts of every call are host integers (:class:`deepconvsep_amd.streaming.StreamCounts`), so the outputs are
+    allocated at their exact size before the call and nothing waits for the device."""
+
+    def __init__(self, plan, S, time_context, overlap, tiler=TILER_SCRIPT, eps_mode=EPS_A, scale=1.0, max_push=65536):
+        from .streaming import StreamCounts
+        self.ctx, self.plan = plan.ctx, plan
+        self.S, self.tc, self.F = int(S), int(time_context), plan.bins
+        self.max_push = int(max_push)
+        rise = np.ascontiguousarray(np.linspace(0., 1.0, num=max(int(overlap), 1)), dtype=np.float64)
+        h = c_void_p()
+        _lib.check(self.ctx._lib.dcs_stream_create(plan._h, self.S, self.tc, int(overlap), int(tiler), int(eps_mode),
+                                                   float(scale), rise.ctypes.data_as(POINTER(c_double)), self.max_push,
+                                                   byref(h)))
+        self._h = h
+        self.counts = StreamCounts(plan.frame, plan.hop, time_context, overlap, tiler)
+        self.max_tiles = int(self.ctx._lib.dcs_stream_max_tiles(h))
+        self.pushed, self.ended = 0, False
+        self._tiles = self._frames = self._folded = self._emitted = 0
+
+    @property
+    def bytes(self):
+        return int(self.ctx._lib.dcs_stream_bytes(self._h))
+
+    @_on_ctx_stream
+    def push(self, audio_t=None, last=False, want_frames=False):
+        """Appends ``audio_t`` (float32 device tensor ``[n]``, ``n <= max_push``; None: no samples), ``last=True`` ends the
+        signal.  Returns the tiles that became ready, ``[n_new, 1, tc, F]`` -- with ``want_frames`` also the magnitude and phase
+        rows of the frames that became complete, ``[n_frames, F]`` each."""
+        torch = _torch()
+        n = 0 if audio_t is None else int(audio_t.numel())
+        if audio_t is not None and (audio_t.dim() != 1 or audio_t.dtype != torch.float32 or not audio_t.is_contiguous()):
+            raise ValueError("Stream.push takes a contiguous float32 [n] tensor")
+        c, P = self.counts, self.pushed + n
+        want_t = max(0, min(c.tiles(P, bool(last)) - self._tiles, self.max_tiles))
+        want_f = max(0, c.frames(P, bool(last)) - self._frames) if want_frames else 0
+        tiles = torch.empty((want_t, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+        mag = torch.empty((want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
+        ph = torch.empty((want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
+        nt, nf = c_int64(), c_int64()
+        _lib.check(self.ctx._lib.dcs_stream_push(self._h, _ptr(audio_t) if n else None, n, 1 if last else 0,
+                                                 _ptr(tiles) if want_t else None, want_t, byref(nt),
+                                                 _ptr(mag) if want_f else None, _ptr(ph) if want_f else None, self.F, byref(nf)))
+        self.pushed, self.ended = P, bool(last)
+        self._tiles += nt.value
+        self._frames += nf.value
+        self.last_tiles, self.last_frames = nt.value, nf.value
+        if nt.value != want_t or (want_frames and nf.value != want_f):
+            raise _lib.DcsError("dcs_stream_push returned %d tiles and %d frames, the host counts say %d and %d"
+                                % (nt.value, nf.value, want_t, want_f))
+        return (tiles, mag, ph) if want_frames else tiles
+
+    @_on_ctx_stream
+    def pull(self, p=None, want_est=False):
+        """``p``: the first ``S`` channels of ``Network.forward_raw(tiles, ..., channel_major=True)`` for exactly the tiles of
+        the preceding push (``[S, n, tc, F]`` float32, a view with a larger source stride is fine; None when the push returned
+        none).  Returns the samples that became final, ``[S, n_out]`` float32 -- with ``want_est`` also the estimates of the
+        frames that were folded, ``[S, rows, F]``."""
+        torch = _torch()
+        n = 0 if p is None else int(p.shape[1])
+        if p is not None:
+            if p.dim() != 4 or tuple(p.shape[2:]) != (self.tc, self.F) or int(p.shape[0]) != self.S or p.dtype != torch.float32:
+                raise ValueError("Stream.pull expects p [%d, n, %d, %d] float32, got %r" % (self.S, self.tc, self.F, tuple(p.shape)))
+            if n and not p[0].is_contiguous():
+                p = p.contiguous()
+        c = self.counts
+        n_pcm = c.emitted(self.pushed, self.ended) - self._emitted
+        n_fold = c.folded(self.pushed, self.ended) - self._folded
+        pcm = torch.empty((self.S, n_pcm), dtype=torch.float32, device=self.ctx.device)
+        est = torch.empty((self.S, n_fold, self.F), dtype=torch.float32, device=self.ctx.device) if want_est else None
+        got = c_int64()
+        _lib.check(self.ctx._lib.dcs_stream_pull(self._h, _ptr(p) if n else None, int(p.stride(0)) if n else 0, n,
+                                                 _ptr(pcm) if n_pcm else None, n_pcm, n_pcm, byref(got),
+                                                 _ptr(est) if want_est and n_fold else None, n_fold * self.F, self.F))
+        self._emitted += got.value
+        self._folded += n_fold
+        self.last_samples = got.value
+        if got.value != n_pcm:
+            raise _lib.DcsError("dcs_stream_pull returned %d samples, the host counts say %d" % (got.value, n_pcm))
+        return (pcm, est) if want_est else pcm
+
+    def reset(self):
+        _lib.check(self.ctx._lib.dcs_stream_reset(self._h))
+        self.pushed, self.ended = 0, False
+        self._tiles = self._frames = self._folded = self._emitted = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.dcs_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def tile(ctx, mag_t, time_context, overlap, tiler, scale=1.0):
     """``generate_overlapadd`` on the device: mag_t ``[T,F]`` or ``[C,T,F]`` float32 -> (tiles
     ``[n,C,tc,F]``, n)."""

@@ -514,6 +514,15 @@ class Separator(object):
             raise ValueError("%s applies the masks of a single-input-channel graph to each channel; '%s' takes %d input "
                              "channels" % (what, self.arch_name, self.net.arch.C))
 
+    def stream(self, max_block=65536, sample_rate=TARGET_RATE):
+        """A :class:`deepconvsep_amd.streaming.StreamSeparator` on this separator's model and plan: ``push(block)`` the samples
+        of a mono 44 100 Hz signal as they come, get the finished stems back ``time_context * hopSize + frameSize`` samples
+        behind at the most, in device memory that depends on ``max_block`` and not on the signal's length.  The values are
+        those of :meth:`channel_spectra`'s composition on a mono signal (the cross-faded masks on the unscaled magnitudes).
+        Single-input-channel graphs only (``ValueError`` otherwise)."""
+        from .streaming import StreamSeparator
+        return StreamSeparator(self, max_block=max_block, sample_rate=sample_rate)
+
     @_on_ctx_stream
     def channel_spectra(self, a3, want_p=False):
         """Per-channel estimates of a stereo signal from a mono model.  ``a3 [3, L]`` float32 on the device: rows L, R and

@@ -483,6 +483,57 @@ DCS_API int dcs_mask_fold_apply(dcs_ctx* ctx, const float* p_d, int64_t p_src_st
                                 int C, int64_t n_frames, int64_t ld, float* est_d, int64_t est_ch_stride, int64_t est_src_stride,
                                 float* mask_d, int64_t mask_src_stride);
 
+/* ------------------------------------------------------------------ streaming separation (csrc/stream.hip) */
+/* Every path above separates a signal that is complete and resident.  A stream takes the signal in blocks and hands back the
+ * samples of the SAME whole-file computation (stft_norm -> tiler -> network -> the fold of dcs_mask_fold_apply -> istft_norm) as
+ * soon as no later input can change them, in memory that does not depend on the signal's length.  With N = frameSize, h = hop,
+ * H = N / 2, st = time_context - overlap, P samples pushed so far and, once the signal has ended, L samples in all -- host
+ * integers, no call waits for the device to know them:
+ *   complete frames  A = P < H ? 0 : (P - H) / h + 1          after the end  T = dcs_frame_count(L, h)
+ *   ready tiles      K = A < tc ? 0 : (A - tc) / st + 1                      dcs_tile_count(T, tc, overlap, tiler)
+ *   folded frames    Tf = K st                                               T
+ *   emitted samples  E = max(0, Tf h - H)                                    L
+ * Frame n covers samples [n h - H, n h - H + N); samples < 0 and >= L read as zero.  Mid-stream E > P - tc h - N once A >= tc.
+ *   frames  mag[n][f] = |rfft(w frame_n)| / sqrt(N), phase = angle(.), as dcs_stft_forward_f32
+ *   tiles   tiles[k][0][j][f] = scale * mag[k st + j][f], zero for rows >= T
+ *   fold    est[s][t][f] = acc_s[t][f] * mag[t][f]: the per-frame definition of dcs_mask_fold_apply on the UNSCALED
+ *           magnitudes (pre_div = 1), n_tiles = the tiles so far (mid-stream the owner of a folded frame is always below it)
+ *   inverse y_n = w * irfft(est[s][n] sqrt(N) exp(j phase[n])),  out[s][q] = (y_lo[..] + y_lo+1[..] + ... in increasing n) / norm(q)
+ *           over the frames n < Tf with n h <= q + H < n h + N, norm = the sum of w^2 over the same frames, 0 replaced by 1
+ * float32 on the device, no atomics, every kernel a pure function of absolute sample / frame / tile indices: the bits that come
+ * out do not depend on how the signal is cut into blocks.
+ * Supported: N % h == 0 (else DCS_EUNSUPPORTED), h <= N / 2, N >= 64, 1 <= overlap < time_context, S in 1 .. 8, a known tiler
+ * and eps_mode, 1 <= max_push <= 2^30 (else DCS_EINVAL); one signal channel.  rise_h as for dcs_overlap_add.  All state -- a
+ * ring of N + max_push samples, rings of magnitude / phase rows, of p for the last ceil(tc / st) tiles plus one push's, of
+ * windowed time-domain frames [N / h + frames per pull][S][N], the estimates of one pull -- is allocated by create; its size is a
+ * function of (N, h, tc, overlap, S, max_push) alone, push and pull allocate nothing.  No ring slot is read before the push or
+ * pull that needs it has written it, so create and reset initialise nothing.  The plan must outlive the stream. */
+typedef struct dcs_stream dcs_stream;
+DCS_API int dcs_stream_create(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
+                              const double* rise_h, int64_t max_push, dcs_stream** out);
+DCS_API int dcs_stream_destroy(dcs_stream* s);
+/* back to the empty state (P = 0, not ended); nothing is reallocated */
+DCS_API int dcs_stream_reset(dcs_stream* s);
+/* the most tiles one push can return, the end included; the device bytes the stream holds */
+DCS_API int64_t dcs_stream_max_tiles(const dcs_stream* s);
+DCS_API int64_t dcs_stream_bytes(const dcs_stream* s);
+/* Appends audio_d[0 .. n), 0 <= n <= max_push; last != 0 ends the signal (n == 0 is fine).  Transforms the frames that became
+ * complete -- mag_d / phase_d [n_frames, ld], either may be NULL, receive their rows, columns past the bins zero -- and writes the
+ * tiles that became ready, tiles_d [n_tiles, 1, time_context, N / 2 + 1] (tiles_cap: the tiles it has room for).  The counts
+ * returned are the formulas above.  Enqueued on the ctx stream of the plan. */
+DCS_API int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, int last, float* tiles_d, int64_t tiles_cap,
+                            int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ld, int64_t* n_frames_out);
+/* p_d: the first S channels of what dcs_model_forward wrote for EXACTLY the tiles of the preceding push, element (s, k, j, f)
+ * at p_d + s p_src_stride + (k time_context + j) (N / 2 + 1) + f.  Folds the frames no later tile can reach -- est_d
+ * [S][n rows, ld] (source stride est_src_stride), may be NULL, receives their estimates -- inverts them and writes the samples
+ * that became final, pcm_d [S][n_out] (source stride pcm_stride, room for pcm_cap samples per source).  Pushes and pulls
+ * alternate strictly: a pull with another tile count than the push returned, a pull without a push, two pushes in a row or a
+ * push after the end give DCS_EINVAL.  An ended signal that yields no tile at all makes the last pull fail with DCS_EINVAL, as
+ * dcs_separate fails. */
+DCS_API int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
+                            int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_src_stride,
+                            int64_t ld);
+
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
 /* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is
  * the rate change in front of the STFT and behind the iSTFT that lets every other file through.  For up / down = fo / fi in
