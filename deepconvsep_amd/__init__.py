@@ -9,10 +9,10 @@ from .arch import (ARCHS, EPS_A, EPS_B, TIE_ALL, TIE_FIRST, TILER_LIBRARY, TILER
 from .transform import TransformFFT, Transforms, compute_file, compute_inverse, sinebell, transformFFT
 from .evaluation import bss_eval, bss_eval_images, bss_eval_sources
 from .runtime import mwf
-from .resample import Resampler, resample
+from .resample import ResampleCounts, Resampler, StreamResampler, resample
 from .separation import (PredictFunction, Separator, blackmanharris, generate_overlapadd, load_model,
                          overlapadd, overlapadd_multi, save_model, train_auto)
-from .streaming import StreamCounts, StreamSeparator
+from .streaming import ChannelStreamSeparator, RateStream, StreamCounts, StreamSeparator
 from .training import FeatureWindows, Trainer, glorot_init
 from .stereo_training import StereoFeatureWindows, StereoTrainer
 from .score_training import ScoreFeatureWindows, ScoreTrainer
@@ -23,6 +23,7 @@ from .score_render import ScoreInformedRenderedWindows, render_score_informed_fe
 __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "TILER_SCRIPT", "TransformFFT",
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
            "Separator", "blackmanharris", "generate_overlapadd", "load_model", "save_model", "overlapadd",
-           "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "mwf", "Resampler", "resample", "StreamCounts", "StreamSeparator", "Trainer", "FeatureWindows", "glorot_init",
+           "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "mwf", "Resampler", "resample", "StreamCounts", "StreamSeparator",
+           "ChannelStreamSeparator", "RateStream", "ResampleCounts", "StreamResampler", "Trainer", "FeatureWindows", "glorot_init",
            "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features",
            "ScoreInformedRenderedWindows", "render_score_informed_features"]

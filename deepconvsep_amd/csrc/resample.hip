@@ -99,6 +99,43 @@ __global__ __launch_bounds__(THREADS) void resample_kernel(ResampleArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------ the stream (dcs_resample_stream)
+constexpr int kMaxStreamRows = 64;
+
+// samples [p0, p0 + n) of row blockIdx.y into slot (absolute index) mod cap of its ring
+__global__ __launch_bounds__(kThreadsL2) void resample_stream_append_kernel(const float* __restrict__ in, int64_t in_stride,
+                                                                           int64_t n, int64_t p0, float* __restrict__ ring,
+                                                                           int64_t cap) {
+    const int64_t i = (int64_t)blockIdx.x * kThreadsL2 + threadIdx.x;
+    if (i < n) ring[blockIdx.y * cap + (p0 + i) % cap] = in[blockIdx.y * in_stride + i];
+}
+
+// Output m = m0 + i of row blockIdx.y: resample_kernel's chain -- one fmaf per tap of the phase row in ascending n, starting
+// from 0, zero for n outside [0, lim) -- with the samples read from the ring by their ABSOLUTE index.  lim = the samples pushed
+// so far: mid-stream only outputs whose every tap lies below it are asked for, so lim acts only after the end, as n_in does.
+__global__ __launch_bounds__(kThreadsL2) void resample_stream_kernel(const float* __restrict__ ring, int64_t cap, int64_t lim,
+                                                                    const float* __restrict__ taps,
+                                                                    const int2* __restrict__ phase, int up, int down, int kpad,
+                                                                    int64_t m0, int64_t n_out, float* __restrict__ out,
+                                                                    int64_t out_stride) {
+    const int64_t i = (int64_t)blockIdx.x * kThreadsL2 + threadIdx.x;
+    if (i >= n_out) return;
+    const int64_t q = (m0 + i) * down;
+    const int64_t n0 = q / up;
+    const int p = (int)(q - n0 * up);
+    const int2 ph = phase[p];
+    const float* row = taps + (size_t)p * kpad;
+    const float* x = ring + blockIdx.y * cap;
+    const int64_t n_first = n0 + ph.x;
+    float acc = 0.f;
+    for (int j = 0; j < ph.y; ++j) {
+        const int64_t n = n_first + j;
+        const float v = (n >= 0 && n < lim) ? x[n % cap] : 0.f;
+        acc = fmaf(v, row[j], acc);
+    }
+    out[blockIdx.y * out_stride + i] = acc;
+}
+
 int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // floats of input the outputs of `threads` consecutive lanes reach: the largest n0 - n0_base plus the widest row
@@ -112,6 +149,7 @@ struct dcs_resampler {
     dcs_ctx* ctx = nullptr;
     int up = 1, down = 1, kpad = 0;
     int min_first = 0, max_end = 0;       // over the phases: min first[p], max first[p] + count[p]
+    int64_t half = 0;                     // the filter's half-width: what a stream sizes its history by
     bool table_lds = false;
     float* taps_d = nullptr;
     int2* phase_d = nullptr;
@@ -170,6 +208,7 @@ extern "C" int dcs_resample_plan(dcs_ctx* ctx, int up, int down, const double* t
     r->kpad = (int)kpad;
     r->min_first = min_first;
     r->max_end = max_end;
+    r->half = half;
     r->table_lds = table_lds;
     auto upload = [&](void** dst, const void* src, size_t bytes, const char* name) -> int {
         DCS_HIP(dcs_dev_alloc(dst, bytes, name));
@@ -245,5 +284,105 @@ extern "C" int dcs_resample_f32(dcs_resampler* r, const float* in_d, int64_t n_i
                            (size_t)a.span * sizeof(float), ctx->stream, a);
     }
     DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the stream
+// `rows` signals in lock-step on one plan.  A push appends its samples to a ring per row and computes the outputs that became
+// final: output m is final once every tap of it lies below the P samples pushed, m down + half < P up, and after the end the
+// outputs are the ceil(L up / down) of dcs_resample_f32.  An output not yet emitted reaches back less than 2 half / up + 2
+// samples behind P, so a ring of max_push + 2 half / up + 2 samples holds everything a push reads.
+struct dcs_resample_stream {
+    dcs_resampler* r = nullptr;
+    dcs_ctx* ctx = nullptr;
+    int rows = 0;
+    int64_t max_push = 0, cap = 0, bytes = 0;
+    float* ring = nullptr;
+    int64_t P = 0, M = 0;        // samples pushed, outputs emitted
+    bool ended = false;
+};
+
+extern "C" int dcs_resample_stream_create(dcs_resampler* r, int rows, int64_t max_push, dcs_resample_stream** out) {
+    if (!r || !out) DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_create: null argument");
+    if (rows < 1 || rows > kMaxStreamRows)
+        DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_create: %d rows (1 .. %d)", rows, kMaxStreamRows);
+    if (max_push < 1 || max_push > (1LL << 30))
+        DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_create: max_push %lld not in [1, 2^30]", (long long)max_push);
+    DCS_ON_DEVICE(r->ctx->device);
+    dcs_resample_stream* s = new dcs_resample_stream();
+    s->r = r;
+    s->ctx = r->ctx;
+    s->rows = rows;
+    s->max_push = max_push;
+    s->cap = max_push + (2 * r->half) / r->up + 2;
+    s->bytes = (int64_t)rows * s->cap * (int64_t)sizeof(float);
+    const hipError_t e = dcs_dev_alloc((void**)&s->ring, (size_t)s->bytes, "resample.stream");
+    if (e != hipSuccess) {
+        dcs_set_error("dcs_resample_stream_create: %lld bytes: %s", (long long)s->bytes, hipGetErrorString(e));
+        delete s;
+        return e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP;
+    }
+    *out = s;
+    return DCS_OK;
+}
+
+extern "C" int dcs_resample_stream_destroy(dcs_resample_stream* s) {
+    if (!s) return DCS_OK;
+    DCS_ON_DEVICE(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    dcs_dev_free(s->ring);
+    delete s;
+    return DCS_OK;
+}
+
+extern "C" int dcs_resample_stream_reset(dcs_resample_stream* s) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_reset: null stream");
+    // the ring keeps its contents: no slot is read before the push that needs it has written it
+    s->P = s->M = 0;
+    s->ended = false;
+    return DCS_OK;
+}
+
+extern "C" int64_t dcs_resample_stream_bytes(const dcs_resample_stream* s) { return s ? s->bytes : -1; }
+
+extern "C" int dcs_resample_stream_push(dcs_resample_stream* s, const float* in_d, int64_t in_stride, int64_t n, int last,
+                                        float* out_d, int64_t out_stride, int64_t out_cap, int64_t* n_out) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: null stream");
+    if (s->ended) DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: the signal has ended (dcs_resample_stream_reset starts another)");
+    if (n < 0 || n > s->max_push)
+        DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: %lld samples (0 .. max_push = %lld)", (long long)n, (long long)s->max_push);
+    if (n > 0 && !in_d) DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: null input");
+    const dcs_resampler* r = s->r;
+    const int64_t P = s->P + n;
+    if (P > (INT64_MAX - r->down - r->half) / r->up)
+        DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: %lld samples x %d overflow", (long long)P, r->up);
+    int64_t M;
+    if (last) M = (P * r->up + r->down - 1) / r->down;
+    else M = P * r->up - 1 - r->half < 0 ? 0 : (P * r->up - 1 - r->half) / r->down + 1;
+    const int64_t n_new = M - s->M;
+    if (n_new < 0) DCS_FAIL(DCS_EHIP, "dcs_resample_stream_push: internal count out of range (%lld outputs)", (long long)n_new);
+    if (n_new > 0 && (!out_d || n_new > out_cap))
+        DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: %lld samples become final, room for %lld", (long long)n_new,
+                 (long long)(out_d ? out_cap : 0));
+    if (s->rows > 1 && ((n > 0 && in_stride < n) || (n_new > 0 && out_stride < n_new)))
+        DCS_FAIL(DCS_EINVAL, "dcs_resample_stream_push: strides %lld / %lld below the counts %lld / %lld", (long long)in_stride,
+                 (long long)out_stride, (long long)n, (long long)n_new);
+    dcs_ctx* ctx = r->ctx;
+    DCS_ON_DEVICE(ctx->device);
+    if (n > 0) {
+        hipLaunchKernelGGL(resample_stream_append_kernel, dim3((unsigned)dcs_cdiv(n, kThreadsL2), (unsigned)s->rows),
+                           dim3(kThreadsL2), 0, ctx->stream, in_d, in_stride, n, s->P, s->ring, s->cap);
+        DCS_HIP(hipGetLastError());
+    }
+    if (n_new > 0) {
+        hipLaunchKernelGGL(resample_stream_kernel, dim3((unsigned)dcs_cdiv(n_new, kThreadsL2), (unsigned)s->rows),
+                           dim3(kThreadsL2), 0, ctx->stream, (const float*)s->ring, s->cap, P, (const float*)r->taps_d,
+                           (const int2*)r->phase_d, r->up, r->down, r->kpad, s->M, n_new, out_d, out_stride);
+        DCS_HIP(hipGetLastError());
+    }
+    s->P = P;
+    s->M = M;
+    if (last) s->ended = true;
+    if (n_out) *n_out = n_new;
     return DCS_OK;
 }

@@ -11,6 +11,12 @@
 // frame can reach.  All counts are host integers.  Every kernel is a pure function of ABSOLUTE sample, frame and tile indices
 // (a ring slot is index mod ring length), nothing is accumulated across threads and no ring slot is read before the push or
 // pull that needs it has written it: however the signal is cut into blocks, the same bits come out.
+//
+// A CHANNEL stream (dcs_stream_create_channels) carries C signal channels next to the down-mix the network sees: C + 1 rows of
+// samples and magnitudes (the down-mix last), phases of the C channels.  The tiles come from the down-mix row, the fold
+// computes acc_s once per (frame, bin) and multiplies it with every channel's magnitude, the inverse and the gather run per
+// (channel, source).  The kernels are the same ones: a row / channel index from the grid selects the ring, and the mono
+// stream is the case of one row that is its own down-mix.
 #include "dcs_internal.h"
 #include "fft_frame.h"
 #include "chanmask.h"
@@ -20,35 +26,42 @@
 namespace {
 
 constexpr int kMaxSources = 8;
+constexpr int kMaxChannels = 8;                         // the range of dcs_mask_fold_apply
 
 __device__ __forceinline__ int64_t ring_slot(int64_t i, int64_t len) { return i % len; }
 
 // ------------------------------------------------------------------------------------------ push: samples into the ring
-__global__ __launch_bounds__(kThreads) void stream_append_kernel(const float* __restrict__ audio, int64_t n, int64_t p0,
-                                                                 float* __restrict__ ring, int64_t cap) {
+// row blockIdx.y of the caller's block into row blockIdx.y of the ring [rows][cap]
+__global__ __launch_bounds__(kThreads) void stream_append_kernel(const float* __restrict__ audio, int64_t row_stride, int64_t n,
+                                                                 int64_t p0, float* __restrict__ ring, int64_t cap) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < n) ring[ring_slot(p0 + i, cap)] = audio[i];
+    if (i < n) ring[blockIdx.y * cap + ring_slot(p0 + i, cap)] = audio[blockIdx.y * row_stride + i];
 }
 
 // ------------------------------------------------------------------------------------------ push: the frames that became complete
 // Frame n = n0 + blockIdx.x covers samples [n hop - N/2, n hop + N/2); samples < 0 or >= lim (the samples pushed so far, the
 // signal's length once it has ended) read as zero, as stft_norm pads.  The tail is stft_forward_kernel's, term for term.
+// Row r = blockIdx.y of the sample ring goes to row r of the magnitude ring [rows][rf][F]; the first n_ph rows also keep their
+// phase (ring [n_ph][rf][F]) and copy both to the caller (row r at + r out_ch_stride).
 __global__ __launch_bounds__(kThreads) void stream_frames_kernel(
     const float* __restrict__ ring, int64_t cap, int64_t lim, int64_t n0, int64_t rf, float* __restrict__ mag_ring,
-    float* __restrict__ phase_ring, float* __restrict__ mag_out, float* __restrict__ phase_out, int64_t ld,
-    const float* __restrict__ win, const float2* __restrict__ tw, int N, int hop, int log2m, float sqrt_n, int tw_lds) {
+    float* __restrict__ phase_ring, int n_ph, float* __restrict__ mag_out, float* __restrict__ phase_out, int64_t out_ch_stride,
+    int64_t ld, const float* __restrict__ win, const float2* __restrict__ tw, int N, int hop, int log2m, float sqrt_n, int tw_lds) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int M = N >> 1;
     const int tid = threadIdx.x;
     const int64_t n = n0 + blockIdx.x;
     const int64_t base = n * (int64_t)hop - M;
+    const int r = blockIdx.y;
+    const bool keep = r < n_ph;
+    ring += r * cap;
     const float2* Z = render_frame<float, float2, false>(smem, win, tw, tw_lds, M, log2m, base, [&](int64_t q) -> float {
         return (q < 0 || q >= lim) ? 0.f : ring[ring_slot(q, cap)];
     });
-    float* mrow = mag_ring + ring_slot(n, rf) * (int64_t)(M + 1);
-    float* prow = phase_ring + ring_slot(n, rf) * (int64_t)(M + 1);
-    float* mo = mag_out ? mag_out + (int64_t)blockIdx.x * ld : nullptr;
-    float* po = phase_out ? phase_out + (int64_t)blockIdx.x * ld : nullptr;
+    float* mrow = mag_ring + (r * rf + ring_slot(n, rf)) * (int64_t)(M + 1);
+    float* prow = keep ? phase_ring + (r * rf + ring_slot(n, rf)) * (int64_t)(M + 1) : nullptr;
+    float* mo = (mag_out && keep) ? mag_out + r * out_ch_stride + (int64_t)blockIdx.x * ld : nullptr;
+    float* po = (phase_out && keep) ? phase_out + r * out_ch_stride + (int64_t)blockIdx.x * ld : nullptr;
     for (int k = tid; k <= M; k += kThreads) {
         const float2 zk = Z[k & (M - 1)];
         const float2 zm = Z[(M - k) & (M - 1)];
@@ -61,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void stream_frames_kernel(
         const float ax = dcs_sqrt(xr * xr + xi * xi);
         const float mg = ax / sqrt_n, ph = dcs_atan2(xi, xr);
         mrow[k] = mg;
-        prow[k] = ph;
+        if (prow) prow[k] = ph;
         if (mo) mo[k] = mg;
         if (po) po[k] = ph;
     }
@@ -102,11 +115,12 @@ __global__ __launch_bounds__(kThreads) void stream_keep_p_kernel(const float* __
 // ------------------------------------------------------------------------------------------ pull: fold + apply
 // The per-frame definition of dcs_mask_fold_apply (mask_fold_apply_kernel<0, 0>, expression for expression) with absolute
 // t = t0 + blockIdx.x and k, p and the magnitudes read from their rings.  n = the tiles that exist so far: mid-stream every
-// frame folded has its owner below n, so the clamp acts only after the end.  est[s][blockIdx.x][f] = acc_s * mag[t][f].
+// frame folded has its owner below n, so the clamp acts only after the end.  est[c][s][blockIdx.x][f] = acc_s * mag[c][t][f]
+// for the C channels of the magnitude ring: acc_s is computed once.
 __global__ __launch_bounds__(kThreads) void stream_fold_kernel(
     const float* __restrict__ p_ring, int64_t rp, int64_t n, int S, int tc, int ov, int F, int mode,
-    const float* __restrict__ rise, const float* __restrict__ mag_ring, int64_t rf, int64_t t0, float* __restrict__ est,
-    int64_t est_src_stride, float* __restrict__ est_out, int64_t out_src_stride, int64_t ld) {
+    const float* __restrict__ rise, const float* __restrict__ mag_ring, int64_t rf, int C, int64_t t0, float* __restrict__ est,
+    int64_t est_src_stride, float* __restrict__ est_out, int64_t out_ch_stride, int64_t out_src_stride, int64_t ld) {
     const int f = blockIdx.y * kThreads + threadIdx.x;
     if (f >= F) return;
     const int64_t t = t0 + blockIdx.x;
@@ -115,7 +129,6 @@ __global__ __launch_bounds__(kThreads) void stream_fold_kernel(
     int64_t k0 = (t < ov) ? 0 : (t - ov) / st;
     if (k0 > n - 1) k0 = n - 1;
     const int64_t j0 = (n > 0) ? t - k0 * st : tc;
-    const float mg = mag_ring[ring_slot(t, rf) * (int64_t)F + f];
 
     float acc[kMaxSources];
 #pragma unroll
@@ -138,19 +151,23 @@ __global__ __launch_bounds__(kThreads) void stream_fold_kernel(
             }
         }
     }
+    for (int c = 0; c < C; ++c) {
+        const float mg = mag_ring[(c * rf + ring_slot(t, rf)) * (int64_t)F + f];
 #pragma unroll
-    for (int s = 0; s < kMaxSources; ++s)
-        if (s < S) {
-            const float e = __fmul_rn(acc[s], mg);
-            est[s * est_src_stride + (int64_t)blockIdx.x * F + f] = e;
-            if (est_out) est_out[s * out_src_stride + (int64_t)blockIdx.x * ld + f] = e;
-        }
+        for (int s = 0; s < kMaxSources; ++s)
+            if (s < S) {
+                const float e = __fmul_rn(acc[s], mg);
+                est[(c * S + s) * est_src_stride + (int64_t)blockIdx.x * F + f] = e;
+                if (est_out) est_out[c * out_ch_stride + s * out_src_stride + (int64_t)blockIdx.x * ld + f] = e;
+            }
+    }
 }
 
 // ------------------------------------------------------------------------------------------ pull: one frame of one source back to time
-// y_n = w * irfft(est[s][n] sqrt(N) exp(j phase[n])) into slot n mod rt of the time-frame ring [rt][S][N]: the packed real-inverse
+// y_n = w * irfft(est[c][s][n] sqrt(N) exp(j phase[c][n])) into slot n mod rt of the time-frame ring [rt][C][S][N]: the packed real-inverse
 // pre-processing, transform and window product of istft_fused_kernel (fft.hip), term for term, for ONE frame -- the sum over
-// the frames that cover a sample is stream_gather_kernel's.  Workgroup (blockIdx.x, blockIdx.y) = (frame t0 + x, source y).
+// the frames that cover a sample is stream_gather_kernel's.  Workgroup (blockIdx.x, blockIdx.y, blockIdx.z) = (frame t0 + x,
+// source y, channel z of gridDim.z).
 __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
     const float* __restrict__ est, int64_t est_src_stride, const float* __restrict__ phase_ring, int64_t rf, int64_t t0,
     float* __restrict__ tf_ring, int64_t rt, int S, const float* __restrict__ win, const float2* __restrict__ tw, int N, int log2m,
@@ -158,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int M = N >> 1;
     const int tid = threadIdx.x;
-    const int s = blockIdx.y;
+    const int s = blockIdx.y, c = blockIdx.z, C = gridDim.z;
     const int64_t n = t0 + blockIdx.x;
     float2* buf0 = reinterpret_cast<float2*>(smem);
     float2* buf1 = buf0 + M;  // M+1 entries: holds X first, then serves as the FFT ping-pong buffer
@@ -168,8 +185,8 @@ __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
         for (int k = tid; k <= M; k += kThreads) twl[k] = tw[k];
         tw = twl;
     }
-    const float* mrow = est + s * est_src_stride + (int64_t)blockIdx.x * (M + 1);
-    const float* prow = phase_ring + ring_slot(n, rf) * (int64_t)(M + 1);
+    const float* mrow = est + (c * S + s) * est_src_stride + (int64_t)blockIdx.x * (M + 1);
+    const float* prow = phase_ring + (c * rf + ring_slot(n, rf)) * (int64_t)(M + 1);
     for (int k = tid; k <= M; k += kThreads) {
         const float a = mrow[k] * sqrt_n;
         float sn, cs;
@@ -194,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
     const float2* z = fft_lds<float, float2, +1>(buf0, buf1, tw, M, log2m);
     const float inv_m = 1.f / (float)M;
     const float2* w2 = reinterpret_cast<const float2*>(win);
-    float2* dst = reinterpret_cast<float2*>(tf_ring + (ring_slot(n, rt) * S + s) * (int64_t)N);
+    float2* dst = reinterpret_cast<float2*>(tf_ring + ((ring_slot(n, rt) * C + c) * S + s) * (int64_t)N);
     for (int m = tid; m < M; m += kThreads) {
         const float2 v = z[m];
         const float2 w = w2[m];
@@ -203,15 +220,16 @@ __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
 }
 
 // ------------------------------------------------------------------------------------------ pull: the samples that became final
-// out[s][q - q0] = (y_lo[..] + y_{lo+1}[..] + ... in increasing n) / norm over the frames n < T with n hop <= q + N/2 < n hop + N,
+// out[c][s][q - q0] (c = blockIdx.z of gridDim.z channels) = (y_lo[..] + y_{lo+1}[..] + ... in increasing n) / norm over the frames n < T with n hop <= q + N/2 < n hop + N,
 // norm = the sum of w^2 over the same frames, 0 replaced by 1 (istft_norm).  T = the frames folded so far (every frame there is,
 // once the signal has ended): mid-stream a sample is emitted only when all its frames are below it.
 __global__ __launch_bounds__(kThreads) void stream_gather_kernel(const float* __restrict__ tf_ring, int64_t rt, int S, int N,
                                                                  int hop, int64_t T, const float* __restrict__ wsq, int64_t q0,
-                                                                 int64_t n_out, float* __restrict__ pcm, int64_t pcm_stride) {
+                                                                 int64_t n_out, float* __restrict__ pcm, int64_t pcm_ch_stride,
+                                                                 int64_t pcm_stride) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n_out) return;
-    const int s = blockIdx.y;
+    const int s = blockIdx.y, c = blockIdx.z, C = gridDim.z;
     const int64_t p = q0 + i + (N >> 1);                // position in the padded signal
     int64_t n_hi = p / hop;
     if (n_hi > T - 1) n_hi = T - 1;
@@ -219,11 +237,11 @@ __global__ __launch_bounds__(kThreads) void stream_gather_kernel(const float* __
     float acc = 0.f, norm = 0.f;
     for (int64_t n = n_lo; n <= n_hi; ++n) {
         const int64_t off = p - n * hop;
-        acc += tf_ring[(ring_slot(n, rt) * S + s) * (int64_t)N + off];
+        acc += tf_ring[((ring_slot(n, rt) * C + c) * S + s) * (int64_t)N + off];
         norm += wsq[off];
     }
     if (norm == 0.f) norm = 1.f;
-    pcm[s * pcm_stride + i] = acc / norm;
+    pcm[c * pcm_ch_stride + s * pcm_stride + i] = acc / norm;
 }
 
 }  // namespace
@@ -233,6 +251,9 @@ struct dcs_stream {
     dcs_stft* plan = nullptr;
     dcs_ctx* ctx = nullptr;
     int S = 0, tc = 0, ov = 0, st = 0, tiler = 0, eps_mode = 0, N = 0, hop = 0, F = 0;
+    // C: the signal channels of a channel stream, 0 for the mono stream; rows of samples and magnitudes (the down-mix last);
+    // nch: the rows that keep their phase and come back as stems (the mono stream's one row is both)
+    int C = 0, rows = 1, nch = 1;
     float scale = 1.f;
     int64_t max_push = 0;
     // ring lengths: samples; frames a push can complete, the end included; tiles it can return; frame rows; tiles of p; frames
@@ -247,19 +268,21 @@ struct dcs_stream {
     bool want_pull = false, ended = false;
 };
 
-extern "C" int dcs_stream_create(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
-                                 const double* rise_h, int64_t max_push, dcs_stream** out) {
-    if (!plan || !rise_h || !out) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: null argument");
-    if (S < 1 || S > kMaxSources) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: %d sources (1 .. %d)", S, kMaxSources);
-    if (overlap < 1 || overlap >= time_context)
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_create: overlap %d not in [1, %d)", overlap, time_context);
-    if (tiler != DCS_TILER_SCRIPT && tiler != DCS_TILER_LIBRARY) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: bad tiler");
-    if (eps_mode != DCS_EPS_A && eps_mode != DCS_EPS_B) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: bad eps_mode");
-    if (max_push < 1 || max_push > (1LL << 30)) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: max_push %lld not in [1, 2^30]", (long long)max_push);
+namespace {
+
+// C = 0: the mono stream
+int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, int eps_mode,
+                  float scale, const double* rise_h, int64_t max_push, dcs_stream** out) {
+    if (!plan || !rise_h || !out) DCS_FAIL(DCS_EINVAL, "%s: null argument", who);
+    if (S < 1 || S > kMaxSources) DCS_FAIL(DCS_EINVAL, "%s: %d sources (1 .. %d)", who, S, kMaxSources);
+    if (overlap < 1 || overlap >= time_context) DCS_FAIL(DCS_EINVAL, "%s: overlap %d not in [1, %d)", who, overlap, time_context);
+    if (tiler != DCS_TILER_SCRIPT && tiler != DCS_TILER_LIBRARY) DCS_FAIL(DCS_EINVAL, "%s: bad tiler", who);
+    if (eps_mode != DCS_EPS_A && eps_mode != DCS_EPS_B) DCS_FAIL(DCS_EINVAL, "%s: bad eps_mode", who);
+    if (max_push < 1 || max_push > (1LL << 30)) DCS_FAIL(DCS_EINVAL, "%s: max_push %lld not in [1, 2^30]", who, (long long)max_push);
     const int N = plan->frame, hop = plan->hop, H = N / 2;
-    if (hop > H) DCS_FAIL(DCS_EINVAL, "dcs_stream_create: hopSize %d above frameSize / 2 = %d", hop, H);
-    if (N % hop) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_stream_create: hopSize %d does not divide frameSize %d", hop, N);
-    if (N < 64) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_stream_create: frameSize %d below 64", N);
+    if (hop > H) DCS_FAIL(DCS_EINVAL, "%s: hopSize %d above frameSize / 2 = %d", who, hop, H);
+    if (N % hop) DCS_FAIL(DCS_EUNSUPPORTED, "%s: hopSize %d does not divide frameSize %d", who, hop, N);
+    if (N < 64) DCS_FAIL(DCS_EUNSUPPORTED, "%s: frameSize %d below 64", who, N);
     DCS_ON_DEVICE(plan->ctx->device);
 
     dcs_stream* s = new dcs_stream();
@@ -267,6 +290,7 @@ extern "C" int dcs_stream_create(dcs_stft* plan, int S, int time_context, int ov
     s->ctx = plan->ctx;
     s->S = S; s->tc = time_context; s->ov = overlap; s->st = time_context - overlap;
     s->tiler = tiler; s->eps_mode = eps_mode; s->scale = scale;
+    s->C = C; s->rows = C ? C + 1 : 1; s->nch = C ? C : 1;
     s->N = N; s->hop = hop; s->F = H + 1; s->max_push = max_push;
     s->cap = N + max_push;                                            // a new frame reaches back less than N samples before the push
     s->fp = (max_push + H + hop - 1) / hop + 3;                       // T - A <= (L - P + N/2) / hop + 3 at the end; fewer mid-stream
@@ -278,19 +302,18 @@ extern "C" int dcs_stream_create(dcs_stft* plan, int S, int time_context, int ov
 
     const int64_t F = s->F;
     struct { float** ptr; int64_t elems; const char* name; } blocks[] = {
-        {&s->samples, s->cap, "stream.samples"},
-        {&s->mag, s->rf * F, "stream.mag"},
-        {&s->phase, s->rf * F, "stream.phase"},
+        {&s->samples, s->rows * s->cap, "stream.samples"},
+        {&s->mag, s->rows * s->rf * F, "stream.mag"},
+        {&s->phase, s->nch * s->rf * F, "stream.phase"},
         {&s->p, (int64_t)S * s->rp * time_context * F, "stream.p"},
-        {&s->est, (int64_t)S * s->ff * F, "stream.est"},
-        {&s->tf, s->rt * S * N, "stream.tf"},
+        {&s->est, (int64_t)s->nch * S * s->ff * F, "stream.est"},
+        {&s->tf, s->rt * s->nch * S * N, "stream.tf"},
         {&s->rise, overlap, "stream.rise"},
     };
     for (auto& b : blocks) {
         const hipError_t e = dcs_dev_alloc((void**)b.ptr, (size_t)b.elems * sizeof(float), b.name);
         if (e != hipSuccess) {
-            dcs_set_error("dcs_stream_create: %lld bytes for %s: %s", (long long)(b.elems * sizeof(float)), b.name,
-                          hipGetErrorString(e));
+            dcs_set_error("%s: %lld bytes for %s: %s", who, (long long)(b.elems * sizeof(float)), b.name, hipGetErrorString(e));
             dcs_stream_destroy(s);
             return e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP;
         }
@@ -300,10 +323,25 @@ extern "C" int dcs_stream_create(dcs_stft* plan, int S, int time_context, int ov
     for (int i = 0; i < overlap; ++i) rise[i] = (float)rise_h[i];
     if (hipMemcpy(s->rise, rise.data(), rise.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         dcs_stream_destroy(s);
-        DCS_FAIL(DCS_EHIP, "dcs_stream_create: uploading the cross-fade ramp failed");
+        DCS_FAIL(DCS_EHIP, "%s: uploading the cross-fade ramp failed", who);
     }
     *out = s;
     return DCS_OK;
+}
+
+}  // namespace
+
+extern "C" int dcs_stream_create(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
+                                 const double* rise_h, int64_t max_push, dcs_stream** out) {
+    return stream_create("dcs_stream_create", plan, S, 0, time_context, overlap, tiler, eps_mode, scale, rise_h, max_push, out);
+}
+
+extern "C" int dcs_stream_create_channels(dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, int eps_mode,
+                                          float scale, const double* rise_h, int64_t max_push, dcs_stream** out) {
+    if (C < 1 || C > kMaxChannels)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_create_channels: %d channels (1 .. %d)", C, kMaxChannels);
+    return stream_create("dcs_stream_create_channels", plan, S, C, time_context, overlap, tiler, eps_mode, scale, rise_h, max_push,
+                         out);
 }
 
 extern "C" int dcs_stream_destroy(dcs_stream* s) {
@@ -332,15 +370,20 @@ extern "C" int dcs_stream_reset(dcs_stream* s) {
 extern "C" int64_t dcs_stream_max_tiles(const dcs_stream* s) { return s ? s->max_tiles : -1; }
 extern "C" int64_t dcs_stream_bytes(const dcs_stream* s) { return s ? s->bytes : -1; }
 
-extern "C" int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, int last, float* tiles_d, int64_t tiles_cap,
-                               int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ld, int64_t* n_frames_out) {
-    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: null stream");
-    if (s->want_pull) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: the tiles of the previous push have not been pulled");
-    if (s->ended) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: the signal has ended (dcs_stream_reset starts another)");
+namespace {
+
+// both kinds of push: audio_d rows at row_stride, the callers' frame copies at ch_stride (neither is read for one row)
+int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t row_stride, int64_t n, int last, float* tiles_d,
+                int64_t tiles_cap, int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ch_stride, int64_t ld,
+                int64_t* n_frames_out) {
+    if (s->want_pull) DCS_FAIL(DCS_EINVAL, "%s: the tiles of the previous push have not been pulled", who);
+    if (s->ended) DCS_FAIL(DCS_EINVAL, "%s: the signal has ended (dcs_stream_reset starts another)", who);
     if (n < 0 || n > s->max_push)
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_push: %lld samples (0 .. max_push = %lld)", (long long)n, (long long)s->max_push);
-    if (n > 0 && !audio_d) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: null audio");
-    if ((mag_d || phase_d) && ld < s->F) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: ld %lld below the %d bins", (long long)ld, s->F);
+        DCS_FAIL(DCS_EINVAL, "%s: %lld samples (0 .. max_push = %lld)", who, (long long)n, (long long)s->max_push);
+    if (n > 0 && !audio_d) DCS_FAIL(DCS_EINVAL, "%s: null audio", who);
+    if (n > 0 && s->rows > 1 && row_stride < n)
+        DCS_FAIL(DCS_EINVAL, "%s: row stride %lld below %lld samples", who, (long long)row_stride, (long long)n);
+    if ((mag_d || phase_d) && ld < s->F) DCS_FAIL(DCS_EINVAL, "%s: ld %lld below the %d bins", who, (long long)ld, s->F);
     const int N = s->N, hop = s->hop, H = N / 2;
     const int64_t P = s->P + n;
     int64_t A, K, T = 0;
@@ -354,26 +397,29 @@ extern "C" int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, i
     }
     const int64_t n_frames = A - s->A, n_tiles = K - s->K;
     if (n_frames < 0 || n_frames > s->fp || n_tiles < 0 || n_tiles > s->max_tiles)
-        DCS_FAIL(DCS_EHIP, "dcs_stream_push: internal count out of range (%lld frames, %lld tiles)", (long long)n_frames,
+        DCS_FAIL(DCS_EHIP, "%s: internal count out of range (%lld frames, %lld tiles)", who, (long long)n_frames,
                  (long long)n_tiles);
     if (n_tiles > tiles_cap || (n_tiles > 0 && !tiles_d))
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_push: %lld tiles become ready, room for %lld (dcs_stream_max_tiles: %lld)",
+        DCS_FAIL(DCS_EINVAL, "%s: %lld tiles become ready, room for %lld (dcs_stream_max_tiles: %lld)", who,
                  (long long)n_tiles, (long long)(tiles_d ? tiles_cap : 0), (long long)s->max_tiles);
+    if ((mag_d || phase_d) && s->nch > 1 && ch_stride < n_frames * ld)
+        DCS_FAIL(DCS_EINVAL, "%s: channel stride %lld below %lld rows", who, (long long)ch_stride, (long long)n_frames);
     DCS_ON_DEVICE(s->ctx->device);
     hipStream_t q = s->ctx->stream;
     if (n > 0) {
-        hipLaunchKernelGGL(stream_append_kernel, dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, q, audio_d, n, s->P,
-                           s->samples, s->cap);
+        hipLaunchKernelGGL(stream_append_kernel, dim3((unsigned)dcs_cdiv(n, kThreads), (unsigned)s->rows), dim3(kThreads), 0, q,
+                           audio_d, row_stride, n, s->P, s->samples, s->cap);
         DCS_HIP(hipGetLastError());
     }
-    if (n_frames > 0)
-        DCS_CHECK((launch_frames<float, float2>(s->plan, stream_frames_kernel, n_frames, 0, s->plan->win_f, s->plan->tw_f,
-                                                (const float*)s->samples, s->cap, P, s->A, s->rf, s->mag, s->phase, mag_d,
-                                                phase_d, ld)));
+    if (n_frames > 0)   // grid (n_frames, rows)
+        DCS_CHECK((launch_frames<float, float2>(s->plan, stream_frames_kernel, n_frames, s->rows - 1, s->plan->win_f,
+                                                s->plan->tw_f, (const float*)s->samples, s->cap, P, s->A, s->rf, s->mag,
+                                                s->phase, s->nch, mag_d, phase_d, ch_stride, ld)));
     if (n_tiles > 0) {
         DcsTimer tm(s->ctx, DCS_TAG_TILE);
-        hipLaunchKernelGGL(stream_tiles_kernel, dim3((unsigned)(n_tiles * s->tc)), dim3(kThreads), 0, q, (const float*)s->mag,
-                           s->rf, s->F, s->tc, s->st, s->K, A, s->scale, tiles_d);
+        const float* mix = s->mag + (int64_t)(s->rows - 1) * s->rf * s->F;     // the down-mix: the last row
+        hipLaunchKernelGGL(stream_tiles_kernel, dim3((unsigned)(n_tiles * s->tc)), dim3(kThreads), 0, q, mix, s->rf, s->F, s->tc,
+                           s->st, s->K, A, s->scale, tiles_d);
         tm.done();
         DCS_HIP(hipGetLastError());
     }
@@ -390,22 +436,22 @@ extern "C" int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, i
     return DCS_OK;
 }
 
-extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
-                               int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_src_stride,
-                               int64_t ld) {
-    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: null stream");
-    if (!s->want_pull) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: no push to pull for");
+// both kinds of pull: channel c of the samples at + c pcm_ch_stride, of the estimates at + c est_ch_stride
+int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
+                int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_ch_stride,
+                int64_t est_src_stride, int64_t ld) {
+    if (!s->want_pull) DCS_FAIL(DCS_EINVAL, "%s: no push to pull for", who);
     if (n_tiles != s->pending)
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: p of %lld tiles, the preceding push returned %lld", (long long)n_tiles,
+        DCS_FAIL(DCS_EINVAL, "%s: p of %lld tiles, the preceding push returned %lld", who, (long long)n_tiles,
                  (long long)s->pending);
-    if (n_tiles > 0 && !p_d) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: null p");
+    if (n_tiles > 0 && !p_d) DCS_FAIL(DCS_EINVAL, "%s: null p", who);
     const int64_t tile_elems = (int64_t)s->tc * s->F;
     if (n_tiles > 0 && s->S > 1 && p_src_stride < n_tiles * tile_elems)
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: source stride %lld below %lld tiles", (long long)p_src_stride, (long long)n_tiles);
-    if (est_d && ld < s->F) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: ld %lld below the %d bins", (long long)ld, s->F);
+        DCS_FAIL(DCS_EINVAL, "%s: source stride %lld below %lld tiles", who, (long long)p_src_stride, (long long)n_tiles);
+    if (est_d && ld < s->F) DCS_FAIL(DCS_EINVAL, "%s: ld %lld below the %d bins", who, (long long)ld, s->F);
     if (s->ended && s->K == 0) {
         s->want_pull = false;
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: %lld frames give no tile (the reference fails in overlapadd_multi)", (long long)s->T);
+        DCS_FAIL(DCS_EINVAL, "%s: %lld frames give no tile (the reference fails in overlapadd_multi)", who, (long long)s->T);
     }
     const int N = s->N, hop = s->hop, H = N / 2;
     const int64_t Tf = s->ended ? s->T : s->K * s->st;
@@ -413,13 +459,16 @@ extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_st
     if (E < 0) E = 0;
     const int64_t n_fold = Tf - s->Tf, n_pcm = E - s->E;
     if (n_fold < 0 || n_fold > s->ff || n_pcm < 0)
-        DCS_FAIL(DCS_EHIP, "dcs_stream_pull: internal count out of range (%lld frames, %lld samples)", (long long)n_fold,
+        DCS_FAIL(DCS_EHIP, "%s: internal count out of range (%lld frames, %lld samples)", who, (long long)n_fold,
                  (long long)n_pcm);
-    if (n_pcm > 0 && (!pcm_d || n_pcm > pcm_cap || (s->S > 1 && pcm_stride < n_pcm)))
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: %lld samples become final, room for %lld (source stride %lld)", (long long)n_pcm,
-                 (long long)(pcm_d ? pcm_cap : 0), (long long)pcm_stride);
-    if (est_d && s->S > 1 && est_src_stride < n_fold * ld)
-        DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: estimate stride %lld below %lld rows", (long long)est_src_stride, (long long)n_fold);
+    if (n_pcm > 0 && (!pcm_d || n_pcm > pcm_cap || (s->S > 1 && pcm_stride < n_pcm) ||
+                      (s->nch > 1 && pcm_ch_stride < (s->S - 1) * pcm_stride + n_pcm)))
+        DCS_FAIL(DCS_EINVAL, "%s: %lld samples become final, room for %lld (source stride %lld, channel stride %lld)", who,
+                 (long long)n_pcm, (long long)(pcm_d ? pcm_cap : 0), (long long)pcm_stride, (long long)pcm_ch_stride);
+    if (est_d && ((s->S > 1 && est_src_stride < n_fold * ld) ||
+                  (s->nch > 1 && est_ch_stride < (s->S - 1) * est_src_stride + n_fold * ld)))
+        DCS_FAIL(DCS_EINVAL, "%s: estimate strides %lld / %lld below %lld rows", who, (long long)est_src_stride,
+                 (long long)est_ch_stride, (long long)n_fold);
     DCS_ON_DEVICE(s->ctx->device);
     hipStream_t q = s->ctx->stream;
     const int64_t k_first = s->K - n_tiles;
@@ -434,7 +483,8 @@ extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_st
             DcsTimer tm(s->ctx, DCS_TAG_MASK);
             hipLaunchKernelGGL(stream_fold_kernel, dim3((unsigned)n_fold, (unsigned)dcs_cdiv(s->F, kThreads)), dim3(kThreads), 0, q,
                                (const float*)s->p, s->rp, s->K, s->S, s->tc, s->ov, s->F, s->eps_mode, (const float*)s->rise,
-                               (const float*)s->mag, s->rf, s->Tf, s->est, s->ff * s->F, est_d, est_src_stride, ld);
+                               (const float*)s->mag, s->rf, s->nch, s->Tf, s->est, s->ff * s->F, est_d, est_ch_stride,
+                               est_src_stride, ld);
             tm.done();
             DCS_HIP(hipGetLastError());
         }
@@ -446,7 +496,7 @@ extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_st
             DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stream_inverse_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         DcsTimer tm(s->ctx, DCS_TAG_ISTFT);
-        hipLaunchKernelGGL(stream_inverse_kernel, dim3((unsigned)n_fold, (unsigned)s->S), dim3(kThreads), lds, q,
+        hipLaunchKernelGGL(stream_inverse_kernel, dim3((unsigned)n_fold, (unsigned)s->S, (unsigned)s->nch), dim3(kThreads), lds, q,
                            (const float*)s->est, s->ff * s->F, (const float*)s->phase, s->rf, s->Tf, s->tf, s->rt, s->S,
                            (const float*)s->plan->win_f, (const float2*)s->plan->tw_f, N, s->plan->log2m,
                            (float)sqrt((double)N), tw_lds);
@@ -455,9 +505,9 @@ extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_st
     }
     if (n_pcm > 0) {
         DcsTimer tm(s->ctx, DCS_TAG_ISTFT);
-        hipLaunchKernelGGL(stream_gather_kernel, dim3((unsigned)dcs_cdiv(n_pcm, kThreads), (unsigned)s->S), dim3(kThreads), 0, q,
-                           (const float*)s->tf, s->rt, s->S, N, hop, Tf, (const float*)s->plan->wsq_f, s->E, n_pcm, pcm_d,
-                           pcm_stride);
+        hipLaunchKernelGGL(stream_gather_kernel, dim3((unsigned)dcs_cdiv(n_pcm, kThreads), (unsigned)s->S, (unsigned)s->nch),
+                           dim3(kThreads), 0, q, (const float*)s->tf, s->rt, s->S, N, hop, Tf, (const float*)s->plan->wsq_f, s->E,
+                           n_pcm, pcm_d, pcm_ch_stride, pcm_stride);
         tm.done();
         DCS_HIP(hipGetLastError());
     }
@@ -465,4 +515,41 @@ extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_st
     s->want_pull = false;
     if (n_out) *n_out = n_pcm;
     return DCS_OK;
+}
+
+}  // namespace
+
+extern "C" int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, int last, float* tiles_d, int64_t tiles_cap,
+                               int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ld, int64_t* n_frames_out) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: null stream");
+    if (s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: a channel stream takes dcs_stream_push_channels");
+    return stream_push("dcs_stream_push", s, audio_d, 0, n, last, tiles_d, tiles_cap, n_tiles_out, mag_d, phase_d, 0, ld,
+                       n_frames_out);
+}
+
+extern "C" int dcs_stream_push_channels(dcs_stream* s, const float* audio_d, int64_t row_stride, int64_t n, int last,
+                                        float* tiles_d, int64_t tiles_cap, int64_t* n_tiles_out, float* mag_d, float* phase_d,
+                                        int64_t ch_stride, int64_t ld, int64_t* n_frames_out) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_channels: null stream");
+    if (!s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_channels: a mono stream takes dcs_stream_push");
+    return stream_push("dcs_stream_push_channels", s, audio_d, row_stride, n, last, tiles_d, tiles_cap, n_tiles_out, mag_d,
+                       phase_d, ch_stride, ld, n_frames_out);
+}
+
+extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
+                               int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_src_stride,
+                               int64_t ld) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: null stream");
+    if (s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: a channel stream takes dcs_stream_pull_channels");
+    return stream_pull("dcs_stream_pull", s, p_d, p_src_stride, n_tiles, pcm_d, 0, pcm_stride, pcm_cap, n_out, est_d, 0,
+                       est_src_stride, ld);
+}
+
+extern "C" int dcs_stream_pull_channels(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
+                                        int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d,
+                                        int64_t est_ch_stride, int64_t est_src_stride, int64_t ld) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_channels: null stream");
+    if (!s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_channels: a mono stream takes dcs_stream_pull");
+    return stream_pull("dcs_stream_pull_channels", s, p_d, p_src_stride, n_tiles, pcm_d, pcm_ch_stride, pcm_stride, pcm_cap,
+                       n_out, est_d, est_ch_stride, est_src_stride, ld);
 }

@@ -104,6 +104,89 @@ class Resampler(object):
             pass
 
 
+class ResampleCounts(object):
+    """How far a streaming conversion has come after ``P`` input samples -- integers only (the formulas of
+    ``dcs_resample_stream`` in include/dcs.h).  Output ``m`` touches inputs ``ceil((m down - half) / up) ..
+    floor((m down + half) / up)``; mid-stream it is final once all of them are below ``P``."""
+
+    def __init__(self, up, down, half):
+        self.up, self.down, self.half = int(up), int(down), int(half)
+        if self.up < 1 or self.down < 1 or self.half < 0:
+            raise ValueError("ResampleCounts needs up, down >= 1 and half >= 0")
+
+    def emitted(self, P, ended=False):
+        P = int(P)
+        if ended:
+            return out_length(P, self.up, self.down)
+        top = P * self.up - 1 - self.half
+        return 0 if top < 0 else top // self.down + 1
+
+    def history(self):
+        """samples before ``P`` an output not yet emitted can reach: strictly fewer than this"""
+        return 2 * self.half // self.up + 2
+
+    def delay_samples(self):
+        """input samples the outputs trail the input by (``half / up``)"""
+        return self.half / float(self.up)
+
+
+class StreamResampler(object):
+    """``dcs_resample_stream``: ``rows`` signals converted ``fi -> fo`` in lock-step as they arrive.  ``push(x)`` takes the
+    next samples (float32 device tensor ``[rows, n]`` with contiguous rows, ``n <= max_block``) and returns the outputs that
+    became final, ``[rows, n_i]`` on the device; ``push(x, last=True)`` ends the signal and returns the rest.  The outputs,
+    concatenated, are those of :class:`Resampler` on the whole signal bit for bit; the state is one ring of
+    ``max_block + counts.history()`` samples per row."""
+
+    def __init__(self, ctx, fi, fo, rows, max_block=65536, **design_kw):
+        self.ctx, self.rows, self.max_block = ctx, int(rows), int(max_block)
+        self.plan = ctx.resampler(fi, fo, **design_kw)
+        self.counts = ResampleCounts(self.plan.up, self.plan.down, self.plan.half)
+        h = c_void_p()
+        _lib.check(ctx._lib.dcs_resample_stream_create(self.plan._h, self.rows, self.max_block, byref(h)))
+        self._h = h
+        self.pushed, self.emitted, self.ended = 0, 0, False
+
+    def push(self, x=None, last=False):
+        import torch
+        n = 0 if x is None else int(x.shape[-1])
+        if x is not None and (x.dim() != 2 or int(x.shape[0]) != self.rows or x.dtype != torch.float32
+                              or x.device != self.ctx.device or (n and (x.stride(1) != 1 or x.stride(0) < n))):
+            raise ValueError("StreamResampler.push takes a float32 [%d, n] tensor with contiguous rows on %s"
+                             % (self.rows, self.ctx.device))
+        want = max(0, self.counts.emitted(self.pushed + n, bool(last)) - self.emitted)
+        got = ctypes.c_int64()
+        with self.ctx.stream_scope():
+            out = torch.empty((self.rows, want), dtype=torch.float32, device=self.ctx.device)
+            _lib.check(self.ctx._lib.dcs_resample_stream_push(self._h, c_void_p(x.data_ptr()) if n else None,
+                                                              int(x.stride(0)) if n else 0, n, 1 if last else 0,
+                                                              c_void_p(out.data_ptr()) if want else None, want, want, byref(got)))
+        self.pushed += n
+        self.emitted += got.value
+        self.ended = bool(last)
+        if got.value != want:
+            raise _lib.DcsError("dcs_resample_stream_push returned %d samples, the host counts say %d" % (got.value, want))
+        return out
+
+    def reset(self):
+        _lib.check(self.ctx._lib.dcs_resample_stream_reset(self._h))
+        self.pushed, self.emitted, self.ended = 0, 0, False
+
+    @property
+    def device_bytes(self):
+        return int(self.ctx._lib.dcs_resample_stream_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.dcs_resample_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def resample(audio, fi, fo, ctx=None, **kw):
     """Host array ``[L]`` or ``[n, L]`` at ``fi`` Hz -> float64 at ``fo`` Hz with the same leading shape (float32 on the
     device).  ``fi == fo`` returns an unchanged copy."""

@@ -516,14 +516,16 @@ class Stream(object):
         self.max_push = int(max_push)
         rise = np.ascontiguousarray(np.linspace(0., 1.0, num=max(int(overlap), 1)), dtype=np.float64)
         h = c_void_p()
-        _lib.check(self.ctx._lib.dcs_stream_create(plan._h, self.S, self.tc, int(overlap), int(tiler), int(eps_mode),
-                                                   float(scale), rise.ctypes.data_as(POINTER(c_double)), self.max_push,
-                                                   byref(h)))
+        _lib.check(self._create(int(overlap), int(tiler), int(eps_mode), float(scale), rise.ctypes.data_as(POINTER(c_double)), h))
         self._h = h
         self.counts = StreamCounts(plan.frame, plan.hop, time_context, overlap, tiler)
         self.max_tiles = int(self.ctx._lib.dcs_stream_max_tiles(h))
         self.pushed, self.ended = 0, False
         self._tiles = self._frames = self._folded = self._emitted = 0
+
+    def _create(self, overlap, tiler, eps_mode, scale, rise_p, h):
+        return self.ctx._lib.dcs_stream_create(self.plan._h, self.S, self.tc, overlap, tiler, eps_mode, scale, rise_p,
+                                               self.max_push, byref(h))
 
     @property
     def bytes(self):
@@ -601,6 +603,80 @@ class Stream(object):
             self.close()
         except Exception:
             pass
+
+
+class ChannelStream(Stream):
+    """``dcs_stream_create_channels``: a :class:`Stream` that carries ``channels`` signal channels next to the down-mix the
+    network sees -- one ring of ``p``, one fold per (frame, bin), an inverse per (channel, source).  The counts, the alternation
+    and ``reset`` / ``close`` / ``bytes`` / ``max_tiles`` are the mono stream's."""
+
+    def __init__(self, plan, S, channels, time_context, overlap, tiler=TILER_SCRIPT, eps_mode=EPS_A, scale=1.0, max_push=65536):
+        self.C = int(channels)
+        Stream.__init__(self, plan, S, time_context, overlap, tiler, eps_mode, scale, max_push)
+
+    def _create(self, overlap, tiler, eps_mode, scale, rise_p, h):
+        return self.ctx._lib.dcs_stream_create_channels(self.plan._h, self.S, self.C, self.tc, overlap, tiler, eps_mode, scale,
+                                                        rise_p, self.max_push, byref(h))
+
+    @_on_ctx_stream
+    def push(self, audio_t=None, last=False, want_frames=False):
+        """Appends ``audio_t`` (float32 device tensor ``[C + 1, n]``: the channels, then the down-mix; rows contiguous, a view
+        with a larger row stride is fine; ``n <= max_push``; None: no samples), ``last=True`` ends the signal.  Returns the
+        tiles of the down-mix that became ready, ``[n_new, 1, tc, F]`` -- with ``want_frames`` also the channels' magnitude and
+        phase rows of the frames that became complete, ``[C, n_frames, F]`` each."""
+        torch = _torch()
+        n = 0 if audio_t is None else int(audio_t.shape[-1])
+        if audio_t is not None and (audio_t.dim() != 2 or int(audio_t.shape[0]) != self.C + 1 or audio_t.dtype != torch.float32
+                                    or (n and (audio_t.stride(1) != 1 or audio_t.stride(0) < n))):
+            raise ValueError("ChannelStream.push takes a float32 [%d, n] tensor with contiguous rows" % (self.C + 1))
+        c, P = self.counts, self.pushed + n
+        want_t = max(0, min(c.tiles(P, bool(last)) - self._tiles, self.max_tiles))
+        want_f = max(0, c.frames(P, bool(last)) - self._frames) if want_frames else 0
+        tiles = torch.empty((want_t, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+        mag = torch.empty((self.C, want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
+        ph = torch.empty((self.C, want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
+        nt, nf = c_int64(), c_int64()
+        _lib.check(self.ctx._lib.dcs_stream_push_channels(self._h, _ptr(audio_t) if n else None, int(audio_t.stride(0)) if n else 0,
+                                                          n, 1 if last else 0, _ptr(tiles) if want_t else None, want_t, byref(nt),
+                                                          _ptr(mag) if want_f else None, _ptr(ph) if want_f else None,
+                                                          want_f * self.F, self.F, byref(nf)))
+        self.pushed, self.ended = P, bool(last)
+        self._tiles += nt.value
+        self._frames += nf.value
+        self.last_tiles, self.last_frames = nt.value, nf.value
+        if nt.value != want_t or (want_frames and nf.value != want_f):
+            raise _lib.DcsError("dcs_stream_push_channels returned %d tiles and %d frames, the host counts say %d and %d"
+                                % (nt.value, nf.value, want_t, want_f))
+        return (tiles, mag, ph) if want_frames else tiles
+
+    @_on_ctx_stream
+    def pull(self, p=None, want_est=False):
+        """``p`` as for :meth:`Stream.pull`.  Returns the samples that became final, ``[C, S, n_out]`` float32 -- with
+        ``want_est`` also the estimates of the frames that were folded, ``[C, S, rows, F]``."""
+        torch = _torch()
+        n = 0 if p is None else int(p.shape[1])
+        if p is not None:
+            if p.dim() != 4 or tuple(p.shape[2:]) != (self.tc, self.F) or int(p.shape[0]) != self.S or p.dtype != torch.float32:
+                raise ValueError("ChannelStream.pull expects p [%d, n, %d, %d] float32, got %r"
+                                 % (self.S, self.tc, self.F, tuple(p.shape)))
+            if n and not p[0].is_contiguous():
+                p = p.contiguous()
+        c = self.counts
+        n_pcm = c.emitted(self.pushed, self.ended) - self._emitted
+        n_fold = c.folded(self.pushed, self.ended) - self._folded
+        pcm = torch.empty((self.C, self.S, n_pcm), dtype=torch.float32, device=self.ctx.device)
+        est = torch.empty((self.C, self.S, n_fold, self.F), dtype=torch.float32, device=self.ctx.device) if want_est else None
+        got = c_int64()
+        _lib.check(self.ctx._lib.dcs_stream_pull_channels(self._h, _ptr(p) if n else None, int(p.stride(0)) if n else 0, n,
+                                                          _ptr(pcm) if n_pcm else None, self.S * n_pcm, n_pcm, n_pcm, byref(got),
+                                                          _ptr(est) if want_est and n_fold else None,
+                                                          self.S * n_fold * self.F, n_fold * self.F, self.F))
+        self._emitted += got.value
+        self._folded += n_fold
+        self.last_samples = got.value
+        if got.value != n_pcm:
+            raise _lib.DcsError("dcs_stream_pull_channels returned %d samples, the host counts say %d" % (got.value, n_pcm))
+        return (pcm, est) if want_est else pcm
 
 
 def tile(ctx, mag_t, time_context, overlap, tiler, scale=1.0):

@@ -523,6 +523,14 @@ class Separator(object):
         from .streaming import StreamSeparator
         return StreamSeparator(self, max_block=max_block, sample_rate=sample_rate)
 
+    def stream_channels(self, max_block=65536):
+        """A :class:`deepconvsep_amd.streaming.ChannelStreamSeparator` on this separator's model and plan: the stereo stems of
+        :meth:`separate_channels` (without the Wiener filter) on a stream -- ``push(block [n, 2])`` at 44 100 Hz, finished stems
+        ``[n_i, S, 2]`` back.  ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes any other rate.
+        Single-input-channel graphs only (``ValueError`` otherwise)."""
+        from .streaming import ChannelStreamSeparator
+        return ChannelStreamSeparator(self, max_block=max_block)
+
     @_on_ctx_stream
     def channel_spectra(self, a3, want_p=False):
         """Per-channel estimates of a stereo signal from a mono model.  ``a3 [3, L]`` float32 on the device: rows L, R and

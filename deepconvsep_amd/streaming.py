@@ -6,6 +6,10 @@ by block, the samples of the same computation (``stft_norm`` -> tiler -> network
 ``time_context * hop + frameSize`` samples behind the input at the most, in device memory that depends on the block size and
 not on the length of the signal.
 
+:class:`ChannelStreamSeparator` does the same for a stereo signal -- the stems of ``Separator.separate_channels`` on one engine
+-- and :class:`RateStream` puts either of them between two streaming sample-rate converters (``dcs_resample_stream``) for audio
+at another rate than 44 100 Hz.
+
 :class:`StreamCounts` is the host arithmetic of the schedule (the table in include/dcs.h); it needs neither the library nor a
 GPU.
 """
@@ -158,6 +162,254 @@ class StreamSeparator(object):
     def device_bytes(self):
         """device bytes the stream holds (``dcs_stream_bytes``): a function of the shapes and ``max_block`` alone"""
         return self._stream().bytes
+
+
+class ChannelStreamSeparator(object):
+    """``Separator.stream_channels()``: stereo stems from a mono model on a stream -- what ``Separator.separate_channels``
+    computes on a whole file (the cross-faded masks of the down-mix on each channel's own magnitudes, inverted with that
+    channel's phase), block by block on ONE engine (``dcs_stream_create_channels``): one ring of ``p``, one fold.
+
+    ``push(block)`` takes the next samples ``[n, 2]`` of a 44 100 Hz signal and returns the float64 samples ``[n_i, S, 2]`` that
+    became final, ``finish()`` ends the signal and returns the rest.  The down-mix the network sees is formed on the host in
+    float64 (``to_mono``), so its input is bit for bit that of ``StreamSeparator`` on ``to_mono(block)``.  ``push_device`` /
+    ``finish_device`` take float32 device tensors ``[3, n]`` (L, R, down-mix) and return ``[2, S, n_i]``.  Single-input-channel
+    graphs only."""
+
+    channels = 2
+
+    def __init__(self, separator, max_block=65536):
+        separator._require_mono_graph("stream_channels")
+        if int(max_block) < 1:
+            raise ValueError("max_block must be at least 1 sample")
+        self.sep, self.ctx = separator, separator.ctx
+        self.max_block = int(max_block)
+        self.counts = StreamCounts(separator.frameSize, separator.hopSize, separator.tc, separator.overlap, separator.tiler)
+        self._engine = None              # the device state: made by the first block
+        self._pushed, self._ended = 0, False
+
+    @property
+    def S(self):
+        return self.sep.net.S
+
+    def _stream(self):
+        if self._engine is None:
+            from .runtime import ChannelStream
+            s = self.sep
+            self._engine = ChannelStream(s.plan, s.net.S, self.channels, s.tc, s.overlap, s.tiler, s.net.arch.eps_mode,
+                                         s.scale_factor, self.max_block)
+        return self._engine
+
+    def _step(self, piece, last):
+        """one push -> network -> pull; ``piece`` float32 device tensor ``[3, n]`` or None"""
+        eng = self._stream()
+        tiles = eng.push(piece, last=last)
+        p = None
+        if int(tiles.shape[0]):
+            p = self.sep.net.forward_raw(tiles, self.sep.tie_mode, channel_major=True)[:self.S]
+        return eng.pull(p)
+
+    def push_device(self, a3):
+        """``a3`` float32 device tensor ``[3, n]`` (L, R, down-mix) -> float32 ``[2, S, n_i]`` on the device"""
+        torch = _runtime()._torch()
+        if self._ended:
+            raise ValueError("the stream has ended: reset() starts another signal")
+        if a3.dim() != 2 or int(a3.shape[0]) != self.channels + 1:
+            raise ValueError("a channel stream takes [3, n] tensors (L, R, down-mix), got shape %r" % (tuple(a3.shape),))
+        with self.ctx.stream_scope():
+            n = int(a3.shape[1])
+            outs = [self._step(a3[:, i:i + self.max_block], False) for i in range(0, n, self.max_block)]
+            self._pushed += n
+            if len(outs) == 1:
+                return outs[0]
+            if not outs:
+                return torch.empty((self.channels, self.S, 0), dtype=torch.float32, device=self.ctx.device)
+            return torch.cat(outs, dim=2)
+
+    def finish_device(self):
+        """ends the signal -> the remaining float32 samples ``[2, S, rest]`` on the device.  A signal too short for one tile
+        raises what ``Separator.separate_channels`` raises for it."""
+        if self._ended:
+            raise ValueError("the stream has ended: finish() was already called (reset() starts another signal)")
+        self._ended = True
+        if self.counts.tiles(self._pushed, True) == 0:
+            raise IndexError("tuple index out of range")  # what overlapadd_multi hits on an empty output array
+        with self.ctx.stream_scope():
+            return self._step(None, True)
+
+    def _to_host(self, pcm):
+        return np.ascontiguousarray(self.ctx.to_host(pcm).astype(np.float64).transpose(2, 1, 0))      # [n_i, S, 2]
+
+    def push(self, block):
+        from .separation import to_mono
+        block = np.asarray(block)
+        if block.ndim != 2 or block.shape[1] != self.channels:
+            raise ValueError("a channel stream takes stereo blocks ([n, 2] arrays), got shape %r" % (block.shape,))
+        if self._ended:
+            raise ValueError("the stream has ended: reset() starts another signal")
+        a3 = np.stack([block[:, 0], block[:, 1], to_mono(block, self.sep.arch_name)])
+        return self._to_host(self.push_device(self.ctx.to_device(a3, np.float32)))
+
+    def finish(self):
+        return self._to_host(self.finish_device())
+
+    def reset(self):
+        if self._engine is not None:
+            self._engine.reset()
+        self._pushed, self._ended = 0, False
+
+    @property
+    def device_bytes(self):
+        """device bytes the stream holds (``dcs_stream_bytes``): a function of the shapes and ``max_block`` alone"""
+        return self._stream().bytes
+
+
+class RateStream(object):
+    """A stream at any sample rate: ``inner`` (a :class:`StreamSeparator` or a :class:`ChannelStreamSeparator`) between two
+    streaming converters (``dcs_resample_stream``) -- ``sample_rate -> 44 100`` on the 1 or 3 signal rows in front, ``44 100 ->
+    sample_rate`` on the ``S`` or ``2 S`` stems behind.  ``push`` takes blocks at ``sample_rate`` in the layout ``inner`` takes
+    and returns the finished stems at ``sample_rate`` in the layout ``inner`` returns; ``finish()`` flushes the three stages and
+    crops, as the whole-file paths do (``Separator._at_model_rate``), so that the lengths add up to the samples pushed.  Each
+    stage's outputs are those of the whole-file conversion bit for bit, so the result is the whole-file ``Resampler`` in front,
+    ``inner`` on the 44 100 Hz signal cut where the converter's counts cut it, and the whole-file ``Resampler`` behind.  All
+    device state is sized by ``inner.max_block`` and the filter design; ``sample_rate == 44100`` passes straight through."""
+
+    def __init__(self, inner, sample_rate):
+        from .resample import TARGET_RATE
+        if not isinstance(inner, (StreamSeparator, ChannelStreamSeparator)):
+            raise TypeError("RateStream wraps a StreamSeparator or a ChannelStreamSeparator, got %r" % (type(inner).__name__,))
+        if int(sample_rate) != sample_rate or int(sample_rate) < 1:
+            raise ValueError("sample_rate must be a positive integer, got %r" % (sample_rate,))
+        self.inner, self.ctx = inner, inner.ctx
+        self.sample_rate, self.model_rate = int(sample_rate), TARGET_RATE
+        self.stereo = isinstance(inner, ChannelStreamSeparator)
+        self.max_block = inner.max_block
+        self.passthrough = self.sample_rate == self.model_rate
+        self._down = self._up = None     # the converters: made by the first block
+        self._pushed = self._emitted = 0
+        self._ended = False
+
+    @property
+    def S(self):
+        return self.inner.S
+
+    def _stages(self):
+        if self._down is None:
+            from .resample import StreamResampler
+            rows_in, rows_out = (3, 2 * self.S) if self.stereo else (1, self.S)
+            self._down = StreamResampler(self.ctx, self.sample_rate, self.model_rate, rows_in, self.max_block)
+            self._up = StreamResampler(self.ctx, self.model_rate, self.sample_rate, rows_out, self.max_block)
+        return self._down, self._up
+
+    def latency_samples(self):
+        """Mid-stream ``pushed - emitted < latency_samples()`` (input samples at ``sample_rate``) once output has started: with
+        ``r = sample_rate / 44100``, the front filter's ``(half + 1) / up`` input samples, plus ``r`` times the inner stream's
+        look-ahead (``StreamCounts.latency_samples``) and the back filter's ``(half + 1) / up`` samples at 44 100 Hz."""
+        if self.passthrough:
+            return self.inner.counts.latency_samples()
+        from .resample import design
+        up_d, _, _, half_d = design(self.sample_rate, self.model_rate)
+        up_u, down_u, _, half_u = design(self.model_rate, self.sample_rate)
+        bound = (half_d + 1) / float(up_d) + (self.inner.counts.latency_samples() * up_u + half_u + 1) / float(down_u)
+        return int(np.ceil(bound))
+
+    def _back(self, pcm, last):
+        """the stems at 44 100 Hz (``[S, n]`` or ``[2, S, n]``; None: none) through the back converter, in pieces of at most
+        ``max_block``"""
+        torch = _runtime()._torch()
+        _, up = self._stages()
+        rows = pcm.reshape(up.rows, int(pcm.shape[-1])) if pcm is not None else None
+        n = 0 if rows is None else int(rows.shape[1])
+        cuts = list(range(0, n, self.max_block)) or [0]
+        outs = []
+        for i in cuts:
+            piece = rows[:, i:i + self.max_block] if n else None
+            outs.append(up.push(piece, last=last and i == cuts[-1]))
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+        if last:                                                    # ceil(ceil(L u / d) d / u) >= L: crop, as _at_model_rate
+            out = out[:, :max(0, self._pushed - self._emitted)]
+        self._emitted += int(out.shape[1])
+        return out.reshape(2, self.S, int(out.shape[1])) if self.stereo else out
+
+    def push_device(self, x):
+        """``x`` float32 device tensor at ``sample_rate``: ``[n]`` (mono inner) or ``[3, n]`` (L, R, down-mix) -> the finished
+        stems at ``sample_rate``, ``[S, n_i]`` or ``[2, S, n_i]``"""
+        if self.passthrough:
+            return self.inner.push_device(x)
+        torch = _runtime()._torch()
+        if self._ended:
+            raise ValueError("the stream has ended: reset() starts another signal")
+        if x.dim() != (2 if self.stereo else 1) or (self.stereo and int(x.shape[0]) != 3):
+            raise ValueError("this stream takes %s tensors, got shape %r" % ("[3, n]" if self.stereo else "[n]", tuple(x.shape)))
+        down, _ = self._stages()
+        with self.ctx.stream_scope():
+            rows = x if self.stereo else x.reshape(1, int(x.shape[0]))
+            n = int(rows.shape[1])
+            outs = []
+            for i in range(0, n, self.max_block):
+                y = down.push(rows[:, i:i + self.max_block].contiguous())
+                self._pushed += int(min(self.max_block, n - i))
+                outs.append(self._back(self.inner.push_device(y if self.stereo else y[0]), False))
+            if len(outs) == 1:
+                return outs[0]
+            if not outs:
+                shape = (2, self.S, 0) if self.stereo else (self.S, 0)
+                return torch.empty(shape, dtype=torch.float32, device=self.ctx.device)
+            return torch.cat(outs, dim=-1)
+
+    def finish_device(self):
+        """ends the signal: flushes the front converter, the inner stream and the back converter -> the remaining stems,
+        cropped so that the lengths add up to the samples pushed"""
+        if self.passthrough:
+            return self.inner.finish_device()
+        torch = _runtime()._torch()
+        if self._ended:
+            raise ValueError("the stream has ended: finish() was already called (reset() starts another signal)")
+        self._ended = True
+        down, _ = self._stages()
+        with self.ctx.stream_scope():
+            y = down.push(None, last=True)
+            first = self.inner.push_device(y if self.stereo else y[0])
+            rest = self.inner.finish_device()
+            return torch.cat([self._back(first, False), self._back(rest, True)], dim=-1)
+
+    def push(self, block):
+        if self.passthrough:
+            return self.inner.push(block)
+        from .separation import to_mono
+        block = np.asarray(block)
+        if self._ended:
+            raise ValueError("the stream has ended: reset() starts another signal")
+        if self.stereo:
+            if block.ndim != 2 or block.shape[1] != 2:
+                raise ValueError("this stream takes stereo blocks ([n, 2] arrays), got shape %r" % (block.shape,))
+            block = np.stack([block[:, 0], block[:, 1], to_mono(block, self.inner.sep.arch_name)])
+        elif block.ndim != 1:
+            raise ValueError("this stream takes mono blocks ([n] arrays), got shape %r" % (block.shape,))
+        return self._to_host(self.push_device(self.ctx.to_device(block, np.float32)))
+
+    def finish(self):
+        if self.passthrough:
+            return self.inner.finish()
+        return self._to_host(self.finish_device())
+
+    def _to_host(self, pcm):
+        return self.inner._to_host(pcm) if self.stereo else self.ctx.to_host(pcm).astype(np.float64)
+
+    def reset(self):
+        self.inner.reset()
+        for st in (self._down, self._up):
+            if st is not None:
+                st.reset()
+        self._pushed = self._emitted = 0
+        self._ended = False
+
+    @property
+    def device_bytes(self):
+        """the inner stream's bytes plus the two converters' rings"""
+        if self.passthrough:
+            return self.inner.device_bytes
+        down, up = self._stages()
+        return self.inner.device_bytes + down.device_bytes + up.device_bytes
 
 
 def _runtime():

@@ -1,12 +1,17 @@
 """Separate a 16-bit PCM wav file block by block: neither the file nor its stems are ever whole in memory.
 
-    python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536]
+    python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536] [--stereo] [--resample]
 
 The file is read with the standard ``wave`` module ``--block`` frames at a time; each block is scaled and mixed down the way
 the architecture's separate script does it (element-wise, so block by block equals the whole file), pushed into
 ``Separator.stream()`` and the samples that come back are appended to the stems, under the script's own file names, as
 ``(x * 32767).astype(int16)``.  The stems trail the input by ``time_context * hopSize + frameSize`` samples at the most; host and
 device memory depend on ``--block``, not on the length of the file.
+
+``--stereo``: a two-channel file gives one two-channel stem per source (``Separator.stream_channels()``: the masks of the
+down-mix on each channel's own spectrum with its own phase) where it otherwise is mixed down.  ``--resample``: a file at any
+sample rate is converted to 44 100 Hz block by block on the device and the stems are converted back and written at the file's
+own rate (``RateStream``); without it such a file is refused, as the reference's scripts refuse it.
 """
 import argparse
 import os
@@ -38,35 +43,45 @@ def main(argv=None):
     ap.add_argument("-o", "--outdir", required=True)
     ap.add_argument("-m", "--model", required=True, help="path_to_model.pkl")
     ap.add_argument("--block", type=int, default=65536, help="frames read and pushed at a time")
+    ap.add_argument("--stereo", action="store_true", help="two-channel stems from a two-channel file")
+    ap.add_argument("--resample", action="store_true", help="take any sample rate; the stems keep the file's rate")
     args = ap.parse_args(argv)
 
     import deepconvsep_amd as dcs
     from deepconvsep_amd.separation import _SCRIPT_DEFAULTS, output_paths, to_mono
+    from deepconvsep_amd.streaming import RateStream
 
     frame, hop, window, overlap, bins = _SCRIPT_DEFAULTS[args.arch]
     src = wave.open(args.input, "rb")
     if src.getsampwidth() != 2 or src.getcomptype() != "NONE":
         raise SystemExit("%s is not a 16-bit PCM wav file" % args.input)
-    if src.getframerate() != 44100:
+    rate = src.getframerate()
+    if rate != 44100 and not args.resample:
         raise SystemExit("Sample rate is not 44100")
+    if args.stereo and src.getnchannels() != 2:
+        raise SystemExit("--stereo takes a two-channel file, %s has %d" % (args.input, src.getnchannels()))
     sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
-    stream = sep.stream(max_block=args.block)
+    stream = sep.stream_channels(max_block=args.block) if args.stereo else sep.stream(max_block=args.block)
+    if rate != 44100:
+        stream = RateStream(stream, rate)
     os.makedirs(args.outdir, exist_ok=True)
     outs = []
     for path in output_paths(args.arch, args.input, args.outdir):
         w = wave.open(path, "wb")
-        w.setnchannels(1)
+        w.setnchannels(2 if args.stereo else 1)
         w.setsampwidth(2)
-        w.setframerate(44100)
+        w.setframerate(rate)
         outs.append(w)
 
     def write(pcm):
+        if args.stereo:
+            pcm = pcm.transpose(1, 0, 2)                                  # [n, S, 2] -> per source [n, 2], interleaved
         for w, x in zip(outs, pcm):
-            w.writeframes((x * np.iinfo(np.int16).max).astype('<i2').tobytes())
+            w.writeframes(np.ascontiguousarray((x * np.iinfo(np.int16).max).astype('<i2')).tobytes())
 
     try:
         for blk in read_blocks(src, args.block):
-            write(stream.push(to_mono(blk, args.arch)))
+            write(stream.push(blk if args.stereo else to_mono(blk, args.arch)))
         write(stream.finish())
     finally:
         src.close()

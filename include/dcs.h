@@ -503,7 +503,7 @@ DCS_API int dcs_mask_fold_apply(dcs_ctx* ctx, const float* p_d, int64_t p_src_st
  * float32 on the device, no atomics, every kernel a pure function of absolute sample / frame / tile indices: the bits that come
  * out do not depend on how the signal is cut into blocks.
  * Supported: N % h == 0 (else DCS_EUNSUPPORTED), h <= N / 2, N >= 64, 1 <= overlap < time_context, S in 1 .. 8, a known tiler
- * and eps_mode, 1 <= max_push <= 2^30 (else DCS_EINVAL); one signal channel.  rise_h as for dcs_overlap_add.  All state -- a
+ * and eps_mode, 1 <= max_push <= 2^30 (else DCS_EINVAL); one signal channel (dcs_stream_create_channels below: several).  rise_h as for dcs_overlap_add.  All state -- a
  * ring of N + max_push samples, rings of magnitude / phase rows, of p for the last ceil(tc / st) tiles plus one push's, of
  * windowed time-domain frames [N / h + frames per pull][S][N], the estimates of one pull -- is allocated by create; its size is a
  * function of (N, h, tc, overlap, S, max_push) alone, push and pull allocate nothing.  No ring slot is read before the push or
@@ -533,6 +533,30 @@ DCS_API int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, int 
 DCS_API int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
                             int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_src_stride,
                             int64_t ld);
+/* A CHANNEL stream: C signal channels (1 <= C <= 8, the range of dcs_mask_fold_apply) next to the down-mix the network sees,
+ * for stems per channel from the mono models -- the masks of the down-mix on every channel's own magnitudes with its own phase,
+ * as Separator.separate_channels computes them on a whole file.  The schedule, the counts, the refusals and the invariants are
+ * the mono stream's; the kernels are the same ones with a row / channel index, every expression term for term.  State: sample
+ * rings (C + 1)(N + max_push), magnitude rows (C + 1) rf F, phase rows C rf F, estimates C S ff F, time frames rt C S N, the
+ * ring of p ONCE (rf = ff = tc + fp, fp = ceil((max_push + H) / h) + 3, rt = N / h + ff): a function of (N, h, tc, overlap,
+ * S, C, max_push) alone.  destroy, reset, max_tiles and bytes are dcs_stream's.  dcs_stream_push / _pull on a channel stream and
+ * the two calls below on a mono stream give DCS_EINVAL. */
+DCS_API int dcs_stream_create_channels(dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, int eps_mode,
+                                       float scale, const double* rise_h, int64_t max_push, dcs_stream** out);
+/* audio_d: C + 1 rows of n samples, row r at audio_d + r row_stride (>= n): rows 0 .. C - 1 the channels, row C the down-mix,
+ * which the caller forms (so the network's input is that of the mono stream on the same down-mix, bit for bit).  All rows go
+ * into their rings and are transformed; the tiles come from the down-mix row alone.  mag_d / phase_d [C][n_frames, ld] (channel
+ * stride ch_stride >= n_frames ld, either may be NULL) receive the CHANNELS' rows. */
+DCS_API int dcs_stream_push_channels(dcs_stream* s, const float* audio_d, int64_t row_stride, int64_t n, int last,
+                                     float* tiles_d, int64_t tiles_cap, int64_t* n_tiles_out, float* mag_d, float* phase_d,
+                                     int64_t ch_stride, int64_t ld, int64_t* n_frames_out);
+/* p_d as for dcs_stream_pull; it goes into its ring once and one fold per (frame, bin) computes acc_s, then
+ * est[c][s][t][f] = acc_s[t][f] * mag[c][t][f] for every channel.  One inverse per (frame, channel, source) with that channel's
+ * phase; pcm_d [C][S][n_out] (element (c, s, i) at pcm_d + c pcm_ch_stride + s pcm_stride + i), est_d [C][S][rows, ld] (channel
+ * stride est_ch_stride, source stride est_src_stride; may be NULL).  Strides below the counts give DCS_EINVAL. */
+DCS_API int dcs_stream_pull_channels(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
+                                     int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d,
+                                     int64_t est_ch_stride, int64_t est_src_stride, int64_t ld);
 
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
 /* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is
@@ -560,6 +584,25 @@ DCS_API int dcs_resample_plan_destroy(dcs_resampler* r);
  * stream of the plan. */
 DCS_API int dcs_resample_f32(dcs_resampler* r, const float* in_d, int64_t n_in, int64_t n_clips, int64_t in_stride,
                              float* out_d, int64_t out_stride);
+/* The same conversion of a signal that arrives in blocks: `rows` signals (1 .. 64) in lock-step on a plan, which must outlive the
+ * stream.  Output m touches inputs ceil((m down - half) / up) .. floor((m down + half) / up), so after P samples mid-stream
+ *   M(P) = P up - 1 - half < 0 ? 0 : (P up - 1 - half) / down + 1
+ * outputs are final (every tap below P), after the end ceil(L up / down); an output not yet emitted reaches back less than
+ * 2 half / up + 2 samples behind P.  Every output is the fmaf chain of dcs_resample_f32 -- its phase row in ascending n from 0,
+ * zero for inputs outside [0, L) -- so the concatenated outputs equal dcs_resample_f32 on the complete signal bit for bit,
+ * however it is cut; they trail the input by half / up input samples.  State: one ring of max_push + 2 half / up + 2 samples
+ * per row, allocated by create (1 <= max_push <= 2^30, else DCS_EINVAL); a push allocates nothing, reset reallocates nothing. */
+typedef struct dcs_resample_stream dcs_resample_stream;
+DCS_API int dcs_resample_stream_create(dcs_resampler* r, int rows, int64_t max_push, dcs_resample_stream** out);
+DCS_API int dcs_resample_stream_destroy(dcs_resample_stream* s);
+DCS_API int dcs_resample_stream_reset(dcs_resample_stream* s);
+DCS_API int64_t dcs_resample_stream_bytes(const dcs_resample_stream* s);
+/* Appends n samples per row (row k at in_d + k in_stride, 0 <= n <= max_push), last != 0 ends the signal, and writes the
+ * outputs that became final (row k at out_d + k out_stride, *n_out of them per row, the formulas above).  DCS_EINVAL, before
+ * anything is launched or written: n out of range, a push after the end, out_cap below what becomes final, strides below the
+ * counts when rows > 1, a P up past int64.  Enqueued on the ctx stream of the plan. */
+DCS_API int dcs_resample_stream_push(dcs_resample_stream* s, const float* in_d, int64_t in_stride, int64_t n, int last,
+                                     float* out_d, int64_t out_stride, int64_t out_cap, int64_t* n_out);
 
 /* ------------------------------------------------------------------ timing aid for bench.py */
 /* Average duration (ms) of the kernels tagged `which` since the last reset, measured with HIP events

@@ -2,7 +2,13 @@
 tile), run the tile through the network, pull the finished samples -- and of the push + pull machinery alone, with the network
 left out (a fixed ``p``).  Each step ends with a stream synchronisation, as a live caller that plays the samples would.
 
-    python scripts/bench_stream.py [--steps 200] [--warmup 20]
+    python scripts/bench_stream.py [--steps 200] [--warmup 20] [--channels 2] [--rate 48000]
+
+``--channels 2`` adds, in the same run, the stereo step on one channel engine (``Separator.stream_channels()``) and the stereo
+step composed of three mono ``runtime.Stream`` engines -- L, R and the down-mix -- that share one ``p``, which is what the mono
+API allows.  ``--rate R`` adds the step of a ``RateStream`` at ``R`` Hz around the mono stream (and, with ``--channels 2``, around
+the stereo one); its block is one stride of audio at that rate.  The launch counts per step are those of the code: append,
+frames, tiles, the network call, keep-p, fold, inverse, gather per engine; append and convert per converter.
 
 Prints one JSON line: the median and mean wall time per step in milliseconds, next to the block's duration in audio time."""
 import argparse
@@ -20,10 +26,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--channels", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--rate", type=int, default=44100)
     args = ap.parse_args(argv)
     import torch
     import deepconvsep_amd as dcs
     from deepconvsep_amd import runtime
+    from deepconvsep_amd.streaming import RateStream
     from deepconvsep_amd.synth import synth_audio, synth_params
 
     N, hop, F, tc, ov = 1024, 512, 513, 30, 25
@@ -55,13 +64,49 @@ def main(argv=None):
         eng.pull(p if int(tiles.shape[0]) else None)
 
     mach = timed(machinery)
+    extra = {}
+
+    def med(t):
+        return round(float(np.median(t)), 4)
+    if args.channels == 2:
+        a3 = torch.stack([audio, torch.roll(audio, 977), 0.5 * (audio + torch.roll(audio, 977))])
+        cs = sep.stream_channels(max_block=block)
+        stereo = timed(lambda i: cs.push_device(a3[:, i * block:(i + 1) * block]))
+        engines = [runtime.Stream(sep.plan, sep.net.S, tc, ov, sep.tiler, sep.net.arch.eps_mode, 0.3, max_push=block)
+                   for _ in range(3)]
+
+        def three(i):
+            tiles = [e.push(a3[r, i * block:(i + 1) * block]) for r, e in enumerate(engines)][2]
+            q = None
+            if int(tiles.shape[0]):
+                q = sep.net.forward_raw(tiles, sep.tie_mode, channel_major=True)[:sep.net.S]
+            return [e.pull(q) for e in engines]
+
+        composed = timed(three)
+        extra.update({"stereo_step_ms_median": med(stereo), "stereo_launches_per_step": 7 + 1,
+                      "stereo_three_engines_step_ms_median": med(composed), "stereo_three_engines_launches_per_step": 3 * 7 + 1,
+                      "stereo_device_bytes": cs.device_bytes,
+                      "stereo_three_engines_device_bytes": sum(e.bytes for e in engines)})
+    if args.rate != 44100:
+        rblock = block * args.rate // 44100
+        raudio = ctx.to_device(0.5 * synth_audio(rblock * (total + tc + 2), seed=1), np.float32)
+        rs = RateStream(sep.stream(max_block=rblock), args.rate)
+        rated = timed(lambda i: rs.push_device(raudio[i * rblock:(i + 1) * rblock]))
+        extra.update({"rate": args.rate, "rate_block_samples": rblock, "rate_step_ms_median": med(rated),
+                      "rate_launches_per_step": 7 + 1 + 4, "rate_device_bytes": rs.device_bytes})
+        if args.channels == 2:
+            r3 = torch.stack([raudio, torch.roll(raudio, 977), 0.5 * (raudio + torch.roll(raudio, 977))])
+            rs2 = RateStream(sep.stream_channels(max_block=rblock), args.rate)
+            rated2 = timed(lambda i: rs2.push_device(r3[:, i * rblock:(i + 1) * rblock]))
+            extra.update({"rate_stereo_step_ms_median": med(rated2), "rate_stereo_device_bytes": rs2.device_bytes})
     print(json.dumps({"bench": "stream", "graph": "dsd", "bins": F, "block_samples": block,
                       "block_audio_ms": round(1e3 * block / 44100.0, 3), "steps": args.steps,
                       "step_ms_median": round(float(np.median(full)), 4), "step_ms_mean": round(float(full.mean()), 4),
                       "step_ms_max": round(float(full.max()), 4),
                       "push_pull_only_ms_median": round(float(np.median(mach)), 4),
                       "push_pull_only_ms_mean": round(float(mach.mean()), 4),
-                      "stream_device_bytes": ss.device_bytes, "device": torch.cuda.get_device_name(0)}))
+                      "stream_device_bytes": ss.device_bytes, "launches_per_step": 7 + 1, **extra,
+                      "device": torch.cuda.get_device_name(0)}))
 
 
 if __name__ == "__main__":
