@@ -166,6 +166,16 @@ struct dcs_ctx {
         last_conv[role] = code;
         last_conv_param[role][0] = p0; last_conv_param[role][1] = p1; last_conv_param[role][2] = p2;
     }
+    // the same for the decoder kernels of the DSD graphs (DCS_DSD_ROLE_*, DCS_DSD_K_*): dcs_debug_dsd_last_kernel;
+    // {X, Xt, waves per workgroup, deconv2 workgroups, cbw, n_colg, final workgroups per clip, mmax}
+    int last_dsd[DCS_DSD_ROLES] = {0};
+    int64_t last_dsd_param[DCS_DSD_PARAMS] = {0};
+    void note_dsd(int role, int code, int64_t p0 = 0, int64_t p1 = 0, int64_t p2 = 0, int64_t p3 = 0) {
+        last_dsd[role] = code;
+        if (role == DCS_DSD_ROLE_GSPLIT) return;
+        int64_t* p = last_dsd_param + (role == DCS_DSD_ROLE_FINAL ? 4 : 0);
+        p[0] = p0; p[1] = p1; p[2] = p2; p[3] = p3;
+    }
 };
 
 // RAII-ish helper: records a start event on construction and a stop event in done().

@@ -56,7 +56,8 @@ int dsd_final_cbw(const dcs_ctx* ctx, int64_t rows, int F, int64_t n_clips);
 // split planes (DsdFinalArgs::Gs) instead of f32 G
 bool dsd_final_bf16x3(const dcs_ctx* ctx, int64_t rows, int F, int64_t n_clips, int CI, int mask_mode);
 
-// ---- bf16x3 variant of the fused final kernel (dsd_bf16x3.hip; DCS_FINAL_BF16X3=0 switches it off)
+// ---- bf16x3 variant of the fused final kernel (dsd_bf16x3.hip): taken when the caller passes the planes (DsdFinalArgs::Gs, Bpk);
+// no environment switch selects it any more
 inline int dsd_gs_pitch(int CI, int tc) { return ((CI + kDsdGch - 1) / kDsdGch) * tc * 3; }  // 16-byte pieces per (tile, branch)
 int dcs_launch_dsd_gsplit(dcs_ctx* ctx, const float* G, void* Gs, int64_t n_items, int tc, int ngg);
 // streaming transposed conv2 on the bf16 matrix pipe (many items): D f32 in, the bf16 planes of G out.  Bq: the conv2

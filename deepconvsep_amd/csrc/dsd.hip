@@ -99,6 +99,14 @@ __global__ __launch_bounds__(kThreads) void deconv2_kernel(const float* __restri
         for (int dt = lo; dt <= hi; ++dt) sum += P[(t - dt) * gcols + c * kh + dt];
         Gp[((ci / kDsdGch) * tc + t) * kDsdGch + (ci % kDsdGch)] = sum;
     }
+    // the channels that pad the last group of 8 (CI .. 8 ngg - 1) are zero, as the streaming kernels leave them: g_split_kernel
+    // splits them and the bf16 x 3 final kernels multiply them by zero weights, which needs them finite
+    const int npad = ngg * kDsdGch - CI;
+    if (grp == (int)gridDim.y - 1)
+        for (int o = tid; o < tc * npad; o += kThreads) {
+            const int t = o / npad, ci = CI + (o - t * npad);
+            Gp[((ci / kDsdGch) * tc + t) * kDsdGch + (ci % kDsdGch)] = 0.f;
+        }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -676,10 +684,12 @@ int dcs_launch_dsd_deconv2(dcs_ctx* ctx, const float* D, const float* Bw, const 
         // Gs: the consumer is the bf16x3 final kernel -- the three bf16 planes are written directly, f32 G is not
         hipLaunchKernelGGL(kern, dim3((unsigned)(n_full * X + Xt)), dim3(kThreads), lds2, ctx->stream, D, Bws,
                            Gs ? reinterpret_cast<float*>(Gs) : G, n_ks, H2, kh, tc, ngg, n_full, X, tail_ch, Xt);
+        ctx->note_dsd(DCS_DSD_ROLE_DECONV2, Gs ? DCS_DSD_K_DECONV2_STREAM_SPLIT : DCS_DSD_K_DECONV2_STREAM, X, Xt, 4, n_full * X + Xt);
         tm.done();
     } else {
         hipLaunchKernelGGL(deconv2_kernel<13>, dim3((unsigned)n_ks, (unsigned)NG), dim3(kThreads), lds, ctx->stream, D,
                            Bw, G, H2, CP, CI, kh, tc, GS, gcols);
+        ctx->note_dsd(DCS_DSD_ROLE_DECONV2, DCS_DSD_K_DECONV2, 0, 0, 4, n_ks * NG);
         tm.done();
         if (Gs) DCS_CHECK(dcs_launch_dsd_gsplit(ctx, G, Gs, n_ks, tc, ngg));   // few tiles: one-shot kernel, then one pass that splits G
     }
@@ -715,6 +725,7 @@ int dcs_launch_dsd_final(dcs_ctx* ctx, const DsdFinalArgs& a, bool fold) {
     DcsTimer tm(ctx, DCS_TAG_FINAL);
     if (a.Gs && a.Bpk && fold && a.nbr != 4 && cbw == 2 && a.mask_mode < 2 && a.bias_half == 0) {   // bf16x3 path (the caller asked dsd_final_bf16x3)
         const int rc = dcs_launch_dsd_final_bf16x3(ctx, a, n_colg, n_wg, n_clips);
+        if (rc == DCS_OK) ctx->note_dsd(DCS_DSD_ROLE_FINAL, DCS_DSD_K_FINAL_BF16X3 + a.mask_mode, cbw, n_colg, n_wg, a.mmax);
         tm.done();
         return rc;
     }
@@ -740,6 +751,7 @@ int dcs_launch_dsd_final(dcs_ctx* ctx, const DsdFinalArgs& a, bool fold) {
             else hipLaunchKernelGGL((final_kernel<false, 2, 1, 4>), dim3((unsigned)(n_rg * ((a.F + 63) / 64)), n_clips),
                                     dim3(kThreads), 0, ctx->stream, a, (a.F + 63) / 64);
         }
+        ctx->note_dsd(DCS_DSD_ROLE_FINAL, DCS_DSD_K_FINAL4 + (fold ? 2 : 0) + a.mask_mode - 2, 1, (a.F + 63) / 64, n_rg * ((a.F + 63) / 64), a.mmax);
         tm.done();
         DCS_HIP(hipGetLastError());
         return DCS_OK;
@@ -754,6 +766,7 @@ int dcs_launch_dsd_final(dcs_ctx* ctx, const DsdFinalArgs& a, bool fold) {
         else DCS_FINAL(false, 2);
     }
 #undef DCS_FINAL
+    ctx->note_dsd(DCS_DSD_ROLE_FINAL, DCS_DSD_K_FINAL + ((fold ? 3 : 0) + (a.mask_mode < 2 ? a.mask_mode : 2)) * 2 + cbw - 1, cbw, n_colg, n_wg, a.mmax);
     tm.done();
     DCS_HIP(hipGetLastError());
     return DCS_OK;

@@ -1,5 +1,5 @@
 // The fused final kernel of dsd.hip on the 16-bit-input matrix pipe with fp32-class results (the default for launches
-// large enough for 128-bin workgroups; DCS_FINAL_BF16X3=0 selects the f32 kernel).
+// large enough for 128-bin workgroups; a caller that passes no planes gets the f32 kernel).
 //
 // Why: scripts/ubench/mfma16_valu.hip (profiles/r01_d_ubench_mfma16_valu.txt) -- v_mfma_f32_16x16x32_bf16 takes 6.9 ns
 // per SIMD for 16 384 flop and runs BESIDE the VALU, while the f32 MFMA (13.9 ns for 2 048 flop) executes on the
@@ -603,6 +603,7 @@ int dcs_launch_dsd_deconv2_bf16(dcs_ctx* ctx, const float* D, const void* Bq, vo
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_full * X + Xt)), dim3(64 * nw), lds, ctx->stream, D,
                        reinterpret_cast<const u32x4*>(Bq), reinterpret_cast<u32x4*>(Gs), n_ks, H2, kh, tc, ngg, n_full, X,
                        tail_ch, Xt);
+    ctx->note_dsd(DCS_DSD_ROLE_DECONV2, nw == 16 ? DCS_DSD_K_DECONV2_BF16_16 : DCS_DSD_K_DECONV2_BF16_4, X, Xt, nw, n_full * X + Xt);
     DCS_HIP(hipGetLastError());
     return DCS_OK;
 }
@@ -613,6 +614,7 @@ int dcs_launch_dsd_gsplit(dcs_ctx* ctx, const float* G, void* Gs, int64_t n_item
     const int64_t n_rows = n_items * ngg * tc;
     hipLaunchKernelGGL(g_split_kernel, dim3((unsigned)dcs_cdiv(n_rows, kThreads)), dim3(kThreads), 0, ctx->stream, G,
                        reinterpret_cast<u32x4*>(Gs), n_rows);
+    ctx->note_dsd(DCS_DSD_ROLE_GSPLIT, DCS_DSD_K_GSPLIT);
     DCS_HIP(hipGetLastError());
     return DCS_OK;
 }

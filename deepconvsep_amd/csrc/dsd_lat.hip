@@ -533,14 +533,22 @@ __global__ __launch_bounds__(512) void lat_final_kernel(const DsdFinalArgs a) {
             const int idx = tid + u * 512;
             const int q4 = idx & 15, ri = (idx >> 4) & 15, c = idx >> 8;
             const int col4 = (int)blockIdx.x * 64 + q4 * 4;
-            if (ri < rows_here && col4 + 3 < ld4) {
+            if (ri < rows_here && col4 < a.F) {
                 const f32x4 first = *reinterpret_cast<const f32x4*>(xch + ((0 * 4 + c) * 16 + ri) * 64 + q4 * 4);
                 const f32x4 second = *reinterpret_cast<const f32x4*>(xch + ((1 * 4 + c) * 16 + ri) * 64 + q4 * 4);
                 const float dp = dp_t[ri];
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fmaf(dp, first[e], second[e]);
-                *reinterpret_cast<f32x4*>(a.out + c * a.out_src_stride + (int64_t)(row0 + ri) * ld4 + col4) = v;
+                // the row's pad columns [F, out_ld) are not the kernel's: the piece that holds the last bins is stored bin by bin
+                float* op = a.out + c * a.out_src_stride + (int64_t)(row0 + ri) * ld4 + col4;
+                if (col4 + 3 < a.F) {
+                    *reinterpret_cast<f32x4*>(op) = v;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (col4 + e < a.F) op[e] = v[e];
+                }
             }
         }
     }
@@ -933,6 +941,7 @@ int dcs_launch_lat_deconv2(dcs_ctx* ctx, const float* D, const float* Wp, float*
     DcsTimer tm(ctx, DCS_TAG_DECONV2);
     hipLaunchKernelGGL(lat_deconv2_kernel, dim3((unsigned)n_items, 7), dim3(256), 0, ctx->stream, D, Wp, G,
                        reinterpret_cast<u32x4*>(Gs));
+    ctx->note_dsd(DCS_DSD_ROLE_DECONV2, DCS_DSD_K_LAT_DECONV2, 0, 0, 4, n_items * 7);
     tm.done();
     DCS_HIP(hipGetLastError());
     return DCS_OK;
@@ -970,6 +979,7 @@ int dcs_launch_lat_final(dcs_ctx* ctx, const DsdFinalArgs& a) {
         hipLaunchKernelGGL(k0, grid, dim3(512), lds, ctx->stream, a);
     else
         hipLaunchKernelGGL(k1, grid, dim3(512), lds, ctx->stream, a);
+    ctx->note_dsd(DCS_DSD_ROLE_FINAL, DCS_DSD_K_LAT_FINAL + a.mask_mode, 1, grid.x, (int64_t)grid.x * grid.y, a.mmax);
     tm.done();
     DCS_HIP(hipGetLastError());
     return DCS_OK;

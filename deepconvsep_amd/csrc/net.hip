@@ -512,6 +512,26 @@ char* dsd_carve(const dcs_model* m, char* p, int64_t n, int64_t rows1, int64_t r
     return p;
 }
 
+// What every caller of the final launchers fills the same way (dsd_forward_tiles, separate_impl, dcs_separate_stereo and the test
+// aid dcs_debug_dsd_stage): weights, the ramp of the last ensure_rise, tile geometry, the bin axis over (channel, bin) and the four
+// branches of the stereo model.  ov < 1: unfolded, rows = n * tc rows of the tiles themselves.  Clips, planes and the clip table
+// are the caller's.
+DsdFinalArgs dsd_final_args(const dcs_model* m, const float* G, const float* mix, int64_t mix_ld, float scale, float* out,
+                            int64_t out_src_stride, int64_t out_ld, int64_t n, int64_t rows, int ov, int mask_mode) {
+    const int tc = m->tc, st = ov > 0 ? tc - ov : tc;
+    const int64_t ld = dcs_round_up(m->F, 4);
+    DsdFinalArgs a{};
+    a.G = G; a.Bw = m->Bfin; a.ldb = m->Fpad; a.bias = m->bout;
+    a.mix = mix; a.mix_ld = mix_ld; a.mix_scale = scale;
+    a.out = out; a.out_src_stride = out_src_stride; a.out_ld = out_ld;
+    a.rise = m->rise_d; a.n = n; a.rows = rows; a.tc = tc; a.ov = ov > 0 ? ov : 0; a.st = st;
+    a.F = (int)((m->C - 1) * ld + m->F); a.CI = m->CI; a.mmax = ov > 0 ? (ov + st - 1) / st + 1 : 1; a.mask_mode = mask_mode;
+    a.g_tile_stride = m->d.n_fc * (int64_t)dsd_g_pitch(m->CI, tc);       // compact ragged layout: G of clip c at its tile offset
+    a.gs_tile_stride = m->d.n_fc * (int64_t)dsd_gs_pitch(m->CI, tc);
+    if (m->arch == DCS_ARCH_DSD_ILD) { a.nbr = 4; a.bias_half = (int)ld; }
+    return a;
+}
+
 int dsd_forward_tiles(dcs_model* m, const float* tiles, int64_t n, int mask_mode, float* out) {
     const int tc = m->tc, F = m->F;
     const int64_t rows1 = n * tc, rows2 = n * m->d.h2;
@@ -521,12 +541,7 @@ int dsd_forward_tiles(dcs_model* m, const float* tiles, int64_t n, int mask_mode
     const bool vec = (F % 4 == 0) && (((uintptr_t)tiles & 15) == 0);
     DCS_CHECK(dsd_encode(m, tiles, F, vec, 1.f, n, tc, false, w));
     DCS_CHECK(ensure_rise(m, 1));
-    DsdFinalArgs a{};
-    a.G = w.G; a.Bw = m->Bfin; a.ldb = m->Fpad; a.bias = m->bout;
-    a.mix = tiles; a.mix_ld = F; a.mix_scale = 1.f;
-    a.out = out; a.out_src_stride = n * tc * (int64_t)F; a.out_ld = F;
-    a.rise = m->rise_d; a.n = n; a.rows = n * tc; a.tc = tc; a.ov = 0; a.st = tc;
-    a.F = F; a.CI = m->CI; a.mmax = 1; a.mask_mode = mask_mode;
+    const DsdFinalArgs a = dsd_final_args(m, w.G, tiles, F, 1.f, out, n * tc * (int64_t)F, F, n, n * tc, 0, mask_mode);
     return dcs_launch_dsd_final(m->ctx, a, false);
 }
 
@@ -683,6 +698,117 @@ extern "C" int dcs_debug_conv_last_kernel(const dcs_model* m, int* codes, int64_
         for (int i = 0; i < 3 && params; ++i) params[3 * r + i] = m->ctx->last_conv_param[r][i];
     }
     return DCS_OK;
+}
+
+// test aids for the decoder kernels of the DSD graphs (include/dcs.h)
+extern "C" int dcs_debug_dsd_last_kernel(const dcs_model* m, int* codes, int64_t* params) {
+    if (!m) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_last_kernel: null model");
+    for (int r = 0; r < DCS_DSD_ROLES && codes; ++r) codes[r] = m->ctx->last_dsd[r];
+    for (int i = 0; i < DCS_DSD_PARAMS && params; ++i) params[i] = m->ctx->last_dsd_param[i];
+    return DCS_OK;
+}
+
+extern "C" int dcs_debug_dsd_stage(dcs_model* m, int stage, dcs_debug_dsd_args* q) {
+    if (!m || !q) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: null argument");
+    if (m->arch != DCS_ARCH_DSD && m->arch != DCS_ARCH_DSD_ILD)
+        DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_dsd_stage: not a DSD or stereo (ILD) model");
+    if (q->family != DCS_DSD_FAMILY_THROUGHPUT && q->family != DCS_DSD_FAMILY_ONE_BATCH)
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: family %d", q->family);
+    DCS_ON_DEVICE(m->ctx->device);
+    dcs_ctx* ctx = m->ctx;
+    for (int r = 0; r < DCS_DSD_ROLES; ++r) ctx->note_dsd(r, 0);
+    const bool lat = q->family == DCS_DSD_FAMILY_ONE_BATCH;
+    const int tc = m->tc, CI = m->CI, CP = m->CP, nbr = m->d.n_fc;
+    const int64_t gp = dsd_g_pitch(CI, tc), gsp = dsd_gs_pitch(CI, tc), lim = (int64_t)1 << 40;
+    // a buffer the stage uses: non-null, 16-byte aligned, at least `need` bytes
+    auto bad = [](const void* p, int64_t bytes, int64_t need) { return !p || ((uintptr_t)p & 15) || bytes < need; };
+    if (stage == DCS_DSD_STAGE_DECONV2) {
+        const int64_t n = q->n_items;
+        if (n < 1 || n > 0x7fffffff / 8) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: %lld items", (long long)n);
+        if (lat && !m->lat_ok) DCS_FAIL(DCS_EUNSUPPORTED, "dcs_debug_dsd_stage: the model has no one-batch kernels");
+        if (bad(q->D, q->D_bytes, n * m->d.h2 * CP * 4)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: D");
+        if (lat ? (!q->G && !q->Gs) : !q->G) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: no output buffer");
+        if (q->G && bad(q->G, q->G_bytes, n * gp * 4)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: G");
+        if (q->Gs && bad(q->Gs, q->Gs_bytes, n * gsp * 16)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: Gs");
+        const int rc = lat ? dcs_launch_lat_deconv2(ctx, q->D, m->Lw2p, q->G, q->Gs, n)
+                           : dcs_launch_dsd_deconv2(ctx, q->D, m->Bw2, m->Bw2s, q->G, n, m->d.h2, CP, CI, m->d.kh2, tc, m->d2_ng,
+                                                    m->d2_gs, m->d2_gcols, q->Gs, q->no_bq ? nullptr : m->Bw2q);
+        DCS_HIP(hipStreamSynchronize(ctx->stream));
+        return rc;
+    }
+    if (stage != DCS_DSD_STAGE_FINAL) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: stage %d", stage);
+    const bool ild = m->arch == DCS_ARCH_DSD_ILD, fold = q->fold != 0;
+    const int64_t ld = dcs_round_up(m->F, 4);
+    const int Fe = (int)((m->C - 1) * ld + m->F);     // bins of a row: the channels of the stereo model sit side by side
+    const int64_t n = q->n, rows = q->rows, n_clips = q->n_clips > 0 ? q->n_clips : 1;
+    if (fold && (q->ov < 1 || q->ov >= tc)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: overlap %d not in [1, %d)", q->ov, tc);
+    if (q->mask_mode < 0 || q->mask_mode > 3 || (q->mask_mode == 3 && !ild))
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: mask mode %d", q->mask_mode);
+    if (n < 1 || rows < 1 || n > 0x7fffffff / tc || rows > 0x7fffffff - 16 || n_clips > 65535 || (!fold && rows != n * tc))
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: %lld tiles, %lld rows, %lld clips", (long long)n, (long long)rows, (long long)n_clips);
+    if (q->mix_ld < Fe || q->out_ld < Fe || q->mix_ld >= (1 << 24) || q->out_ld >= (1 << 24) || q->out_src_stride < rows * q->out_ld ||
+        q->out_src_stride > lim)
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: row pitches %lld / %lld, source stride %lld", (long long)q->mix_ld,
+                 (long long)q->out_ld, (long long)q->out_src_stride);
+    if (n_clips > 1 && (q->g_clip_tiles < 0 || q->g_clip_tiles > lim || q->mix_clip_stride < 0 || q->mix_clip_stride > lim ||
+                        q->out_clip_stride < 4 * q->out_src_stride || q->out_clip_stride > lim))
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: clip strides");
+    if (lat && !fold) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: the one-batch final kernel folds");
+    if (q->clip_tab_h && !fold) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: a clip table belongs to the folded form");
+    // the last tile and the last mixture float any clip reaches
+    int64_t tiles_end = 0, mix_end = 0;
+    bool compact = false;
+    for (int64_t c = 0; c < n_clips; ++c) {
+        int64_t rows_c = rows, n_c = n, mix_off = n_clips > 1 ? c * q->mix_clip_stride : 0, tile_off = n_clips > 1 ? c * q->g_clip_tiles : 0;
+        if (q->clip_tab_h) {
+            const int64_t* t = q->clip_tab_h + kDcsClipTab * c;
+            rows_c = t[1]; n_c = t[2];
+            if (rows_c < 1 || rows_c > rows || n_c < 1 || n_c > n) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: clip %lld of the table", (long long)c);
+            if (c == 0) compact = t[3] >= 0;
+            if ((t[3] >= 0) != compact) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: row offsets of both kinds in the clip table");
+            if (compact) {
+                if (t[3] > lim || t[4] < 0 || t[4] > lim) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: offsets of clip %lld", (long long)c);
+                mix_off = t[3] * q->mix_ld;
+                tile_off = t[4];
+            }
+        }
+        if (tile_off + n_c > tiles_end) tiles_end = tile_off + n_c;
+        if (mix_off + (rows_c - 1) * q->mix_ld + Fe > mix_end) mix_end = mix_off + (rows_c - 1) * q->mix_ld + Fe;
+    }
+    const int cbw = dsd_final_cbw(ctx, rows, Fe, n_clips);
+    const bool planes = lat || (q->Gs && m->Bpk && fold && !ild && cbw == 2 && q->mask_mode < 2);   // which operand the launcher reads
+    if (!planes && bad(q->G, q->G_bytes, tiles_end * nbr * gp * 4)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: G");
+    if (q->Gs && bad(q->Gs, q->Gs_bytes, tiles_end * nbr * gsp * 16)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: Gs");
+    if (bad(q->mix, q->mix_bytes, mix_end * 4)) DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: mixture");
+    if (bad(q->out, q->out_bytes, ((n_clips - 1) * q->out_clip_stride + 3 * q->out_src_stride + rows * q->out_ld) * 4))
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_dsd_stage: out");
+    DCS_CHECK(ensure_rise(m, fold ? q->ov : 1));
+    DsdFinalArgs a = dsd_final_args(m, q->G, q->mix, q->mix_ld, q->scale, q->out, q->out_src_stride, q->out_ld, n, rows,
+                                    fold ? q->ov : 0, q->mask_mode);
+    a.n_clips = (int)n_clips;
+    a.g_clip_stride = q->g_clip_tiles * nbr * gp;
+    a.mix_clip_stride = q->mix_clip_stride;
+    a.out_clip_stride = q->out_clip_stride;
+    if (q->Gs) {
+        a.Gs = q->Gs;
+        a.Bpk = m->Bpk;
+        a.gs_clip_stride = q->g_clip_tiles * nbr * gsp;
+    }
+    int64_t* tab_d = nullptr;
+    if (q->clip_tab_h) {
+        const size_t bytes = (size_t)n_clips * kDcsClipTab * sizeof(int64_t);
+        DCS_HIP(dcs_dev_alloc((void**)&tab_d, bytes, "debug.dsd.clip_tab"));
+        if (hipMemcpy(tab_d, q->clip_tab_h, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            dcs_dev_free(tab_d);
+            DCS_FAIL(DCS_EHIP, "dcs_debug_dsd_stage: clip table upload");
+        }
+        a.clip_tab = tab_d;
+    }
+    const int rc = lat ? dcs_launch_lat_final(ctx, a) : dcs_launch_dsd_final(ctx, a, fold);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    dcs_dev_free(tab_d);
+    if (se != hipSuccess) DCS_FAIL(DCS_EHIP, "dcs_debug_dsd_stage: %s", hipGetErrorString(se));
+    return rc;
 }
 
 // ONE place decides which one-batch stages (dsd_lat.hip) a call takes: separate_impl (what runs), separate_graphed (whether
@@ -863,19 +989,12 @@ static int separate_impl(dcs_model* m, dcs_stft* plan, const float* audio_d, int
         DCS_CHECK(dsd_encode(m, mag, ld, true, scale, n, st, true, w, n_clips, Trows, lat, ragged_compact ? rows_sum : 0,
                              ragged_compact ? tiles_sum : 0, ragged_compact ? rowmap_d : nullptr));
         DCS_CHECK(ensure_rise(m, ov));
-        DsdFinalArgs a{};
-        a.G = w.G; a.Bw = m->Bfin; a.ldb = m->Fpad; a.bias = m->bout;
-        a.mix = mag; a.mix_ld = ld; a.mix_scale = scale;
-        a.out = sep; a.out_src_stride = T * ld; a.out_ld = ld;
-        a.rise = m->rise_d; a.n = n; a.rows = T; a.tc = tc; a.ov = ov; a.st = st;
-        a.F = F; a.CI = m->CI; a.mmax = (ov + st - 1) / st + 1; a.mask_mode = eps_mode;
+        DsdFinalArgs a = dsd_final_args(m, w.G, mag, ld, scale, sep, T * ld, ld, n, T, ov, eps_mode);
         a.n_clips = (int)n_clips;
         a.g_clip_stride = n * m->d.n_fc * (int64_t)dsd_g_pitch(m->CI, tc);
         a.mix_clip_stride = Trows * ld;
         a.out_clip_stride = (int64_t)S * T * ld;
         a.clip_tab = clip_tab_d;
-        a.g_tile_stride = m->d.n_fc * (int64_t)dsd_g_pitch(m->CI, tc);       // compact ragged layout: G of clip c at its tile offset
-        a.gs_tile_stride = m->d.n_fc * (int64_t)dsd_gs_pitch(m->CI, tc);
         if (split) {
             a.Gs = w.Gs;
             a.Bpk = m->Bpk;
@@ -1096,13 +1215,7 @@ extern "C" int dcs_separate_stereo(dcs_model* m, dcs_stft* plan, const float* au
     DCS_CHECK(dcs_launch_stft_forward_f32_clips(plan, audio_d, L, channel_stride, C, mag, nullptr, unit, ld, Trows, T, true));
     DCS_CHECK(dsd_encode(m, mag, row, true, scale, n, st, true, w));
     DCS_CHECK(ensure_rise(m, ov));
-    DsdFinalArgs a{};
-    a.G = w.G; a.Bw = m->Bfin; a.ldb = m->Fpad; a.bias = m->bout;
-    a.mix = mag; a.mix_ld = row; a.mix_scale = scale;
-    a.out = sep; a.out_src_stride = T * row; a.out_ld = row;
-    a.rise = m->rise_d; a.n = n; a.rows = T; a.tc = tc; a.ov = ov; a.st = st;
-    a.F = (int)((C - 1) * ld + F); a.CI = m->CI; a.mmax = (ov + st - 1) / st + 1;
-    a.mask_mode = 3; a.nbr = 4; a.bias_half = (int)ld;
+    const DsdFinalArgs a = dsd_final_args(m, w.G, mag, row, scale, sep, T * row, row, n, T, ov, 3);
     DCS_CHECK(dcs_launch_dsd_final(m->ctx, a, true));
     for (int c = 0; c < C; ++c) {
         // per channel the S sources are inverted with that channel's phase (:313-316)

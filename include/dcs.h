@@ -1089,6 +1089,63 @@ DCS_API int dcs_debug_conv_last_kernel(const dcs_model* m, int* codes, int64_t* 
  * stream. */
 DCS_API int dcs_debug_conv_fold_weights(const dcs_model* m, float* out_h, int64_t n_out, int64_t* rows, int64_t* cols);
 
+/* Test aids for the decoder kernels of the DSD graphs (csrc/dsd.hip, dsd_bf16x3.hip, dsd_lat.hip; tests/test_gpu_dsd_kernels.py);
+ * no reference counterpart.  dcs_debug_dsd_stage runs ONE decoder stage of a DSD or stereo (ILD) model on the caller's buffers
+ * with the model's own packed weights (Bw2, Bw2s, Bw2q, Lw2p, Bfin, Bpk, bout, the cross-fade ramp):
+ *   DCS_DSD_STAGE_DECONV2  D [n_items][h2][52] floats -> G [n_items][7][tc][8] floats and / or Gs [n_items][7][tc][3][8] bf16
+ *   DCS_DSD_STAGE_FINAL    G or Gs of n tiles per clip, three (four: stereo model) branches per tile, and the mixture rows ->
+ *                          out: source s of clip c at out + c * out_clip_stride + s * out_src_stride, rows of out_ld floats
+ * family = DCS_DSD_FAMILY_THROUGHPUT: dcs_launch_dsd_deconv2 / dcs_launch_dsd_final as the separation paths call them, so the
+ * choice of kernel is the production one (G is required as they always carve it; Gs is optional; no_bq != 0 withholds the bf16
+ * planes of the conv2 weights, as a model without them would).  DCS_DSD_FAMILY_ONE_BATCH: dcs_launch_lat_deconv2 (G, Gs or both) /
+ * dcs_launch_lat_final (Gs).  The final stage fills the launcher's arguments as dcs_separate* / dcs_model_forward_masked /
+ * dcs_separate_stereo do: fold != 0: rows frames are folded from n tiles that start tc - ov frames apart, mixture x scale;
+ * fold == 0: rows = n * tc rows of the tiles themselves (ov ignored).  n_clips > 1: clip c reads its G at tile c * g_clip_tiles and
+ * its mixture at mix + c * mix_clip_stride; clip_tab_h (nullable, HOST, six int64 per clip {samples, frames, tiles, row offset,
+ * tile offset, rows}) is checked against the buffers and uploaded for the call (row offsets all < 0: the pitches above apply;
+ * all >= 0: the compact layout).  DCS_EINVAL, and nothing launched, for a null, misaligned (16 bytes) or short buffer -- every
+ * byte count must cover what the separation paths would carve for the same dimensions -- and for dimensions out of range;
+ * what the launchers refuse comes back as they return it, nothing launched either.  One stream synchronisation per call. */
+#define DCS_DSD_STAGE_DECONV2 0
+#define DCS_DSD_STAGE_FINAL 1
+#define DCS_DSD_FAMILY_THROUGHPUT 0
+#define DCS_DSD_FAMILY_ONE_BATCH 1
+typedef struct dcs_debug_dsd_args {
+    int32_t family, no_bq;
+    const float* D; int64_t D_bytes;
+    float* G; int64_t G_bytes;
+    void* Gs; int64_t Gs_bytes;
+    const float* mix; int64_t mix_bytes; int64_t mix_ld;
+    float* out; int64_t out_bytes; int64_t out_ld, out_src_stride;
+    int64_t n_items;                      /* deconv2: (tile, branch) items */
+    int64_t n, rows;                      /* final: tiles and output rows per clip (the maxima with a clip table) */
+    int32_t ov, fold, mask_mode; float scale;
+    int32_t n_clips; int64_t g_clip_tiles, mix_clip_stride, out_clip_stride;
+    const int64_t* clip_tab_h;
+} dcs_debug_dsd_args;
+DCS_API int dcs_debug_dsd_stage(dcs_model* m, int stage, dcs_debug_dsd_args* args);
+/* Which kernel each role of the model's context launched last (any entry point; 0 = none since the last dcs_debug_dsd_stage
+ * began, which clears them): codes[DCS_DSD_ROLES], and the launchers' choices params[DCS_DSD_PARAMS] = {X, Xt (workgroup
+ * columns per full / for the partial channel group of a streaming deconv2), waves per workgroup, deconv2 workgroups, cbw,
+ * n_colg, final workgroups per clip, mmax}.  Host-side bookkeeping, one store per launch.  Every pointer but m is nullable. */
+#define DCS_DSD_ROLE_DECONV2 0
+#define DCS_DSD_ROLE_GSPLIT 1
+#define DCS_DSD_ROLE_FINAL 2
+#define DCS_DSD_ROLES 3
+#define DCS_DSD_PARAMS 8
+#define DCS_DSD_K_DECONV2 1               /* deconv2_kernel<13> */
+#define DCS_DSD_K_DECONV2_STREAM 2        /* deconv2_stream_kernel<false> */
+#define DCS_DSD_K_DECONV2_STREAM_SPLIT 3  /* deconv2_stream_kernel<true> */
+#define DCS_DSD_K_DECONV2_BF16_4 4        /* deconv2_stream_bf16_kernel<4> */
+#define DCS_DSD_K_DECONV2_BF16_16 5       /* deconv2_stream_bf16_kernel<16> */
+#define DCS_DSD_K_GSPLIT 6                /* g_split_kernel */
+#define DCS_DSD_K_LAT_DECONV2 7           /* lat_deconv2_kernel */
+#define DCS_DSD_K_FINAL 8                 /* final_kernel<FOLD, MODE, CBW, 3>: 8 + (FOLD * 3 + MODE) * 2 + CBW - 1 = 8 .. 19 */
+#define DCS_DSD_K_FINAL4 20               /* final_kernel<FOLD, MODE, 1, 4>: 20 + FOLD * 2 + MODE - 2 = 20 .. 23 */
+#define DCS_DSD_K_FINAL_BF16X3 24         /* final_bf16x3_kernel<MODE>: 24 + MODE */
+#define DCS_DSD_K_LAT_FINAL 26            /* lat_final_kernel<MODE>: 26 + MODE */
+DCS_API int dcs_debug_dsd_last_kernel(const dcs_model* m, int* codes, int64_t* params);
+
 #ifdef __cplusplus
 }
 #endif
