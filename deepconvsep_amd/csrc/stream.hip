@@ -17,11 +17,20 @@
 // computes acc_s once per (frame, bin) and multiplies it with every channel's magnitude, the inverse and the gather run per
 // (channel, source).  The kernels are the same ones: a row / channel index from the grid selects the ring, and the mono
 // stream is the case of one row that is its own down-mix.
+//
+// A SCORE stream (dcs_stream_create_score) feeds the score-informed graphs: the note table is converted and uploaded once, a push
+// also writes the harmonic masks M_j of the frames it completed into a ring [ninst][rf][F] next to the magnitudes (one workgroup
+// per frame, from the few note rows that can meet the push's frames), the tiles carry one channel M_j * (scale * mag) per
+// instrument and the fold multiplies acc_s with the score-informed mixture formed from the two rings.  Everything else is the
+// mono stream.
 #include "dcs_internal.h"
 #include "fft_frame.h"
 #include "chanmask.h"
 
 #include <math.h>
+
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -101,6 +110,88 @@ __global__ __launch_bounds__(kThreads) void stream_tiles_kernel(const float* __r
     }
 }
 
+// ------------------------------------------------------------------------------------------ push (score): the masks of the new frames
+// The converted note table: one row of kRowHead + 2 npairs int32 per counting note row -- instrument, first frame, end frame, a
+// pad, then the bin pairs (f0, f1), an empty pair where the slot does not count -- sorted by first frame.
+constexpr int kRowHead = 4;
+constexpr int kMaskChunk = 4096;                        // bins per pass: 16 KB of LDS whatever the frame size
+
+struct ScoreVals {                                       // DCS_SCORE_NORM_MAX: the two values an instrument's mask takes
+    float lo[kMaxChannels], hi[kMaxChannels];
+};
+
+// Frame t = n0 + blockIdx.x: M_j[t][:] for every instrument into slot t mod rf of the ring [ninst][rf][F].  One LDS word per bin,
+// bit j = on_j: the lanes walk the (row, pair) items of the candidate rows [r_lo, r_hi) -- every row that covers a frame of this
+// push is among them -- and paint the bands of those that cover t with atomicOr (order-independent, so the bits are
+// deterministic); after the barrier each lane turns its bins into the ninst values.  normalise = DCS_SCORE_NORM_SUM:
+// score_sumnorm_kernel's expressions.
+__global__ __launch_bounds__(kThreads) void stream_masks_kernel(const int* __restrict__ table, int npairs, int r_lo, int r_hi,
+                                                                int64_t n0, int64_t rf, int F, int ninst, int normalise,
+                                                                ScoreVals vals, float* __restrict__ mask_ring) {
+    __shared__ unsigned bits[kMaskChunk];
+    const int tid = threadIdx.x;
+    const int64_t t = n0 + blockIdx.x;
+    const int64_t slot = ring_slot(t, rf);
+    const int W = kRowHead + 2 * npairs;
+    const int items = (r_hi - r_lo) * npairs;
+    for (int c0 = 0; c0 < F; c0 += kMaskChunk) {
+        const int c1 = c0 + kMaskChunk < F ? c0 + kMaskChunk : F;
+        for (int i = tid; i < c1 - c0; i += kThreads) bits[i] = 0u;
+        __syncthreads();
+        for (int it = tid; it < items; it += kThreads) {
+            const int* row = table + (int64_t)(r_lo + it / npairs) * W;
+            if (row[1] <= t && t < row[2]) {
+                const int k = it % npairs;
+                const int f0 = row[kRowHead + 2 * k] > c0 ? row[kRowHead + 2 * k] : c0;
+                const int f1 = row[kRowHead + 2 * k + 1] < c1 ? row[kRowHead + 2 * k + 1] : c1;
+                const unsigned bit = 1u << row[0];
+                for (int f = f0; f < f1; ++f) atomicOr(&bits[f - c0], bit);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < c1 - c0; i += kThreads) {
+            const unsigned on = bits[i];
+            float* dst = mask_ring + slot * (int64_t)F + c0 + i;
+            if (normalise == DCS_SCORE_NORM_SUM) {
+                float total = 0.f;
+                for (int j = 0; j < ninst; ++j) {
+                    const float v = ((on >> j) & 1u) ? 1.0f : 1e-18f;
+                    total = j == 0 ? v : __fadd_rn(total, v);
+                }
+                for (int j = 0; j < ninst; ++j)
+                    dst[j * rf * (int64_t)F] = __fdiv_rn(((on >> j) & 1u) ? 1.0f : 1e-18f, total);
+            } else {
+#pragma unroll
+                for (int j = 0; j < kMaxChannels; ++j)
+                    if (j < ninst) dst[j * rf * (int64_t)F] = ((on >> j) & 1u) ? vals.hi[j] : vals.lo[j];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------ push (score): the tiles that became ready
+// tiles[i][j][r][:] = M_j[t][:] * (scale * mag[t][:]), t = (k0 + i) st + r, zero for rows >= T: score_floor_kernel's product on
+// the tiler's rows.  Workgroup blockIdx.x = (i ninst + j) tc + r.
+__global__ __launch_bounds__(kThreads) void stream_score_tiles_kernel(const float* __restrict__ mag_ring,
+                                                                      const float* __restrict__ mask_ring, int64_t rf, int F, int tc,
+                                                                      int st, int ninst, int64_t k0, int64_t T, float scale,
+                                                                      float* __restrict__ tiles) {
+    const int64_t b = blockIdx.x / tc;
+    const int r = (int)(blockIdx.x - b * tc);
+    const int64_t i = b / ninst;
+    const int j = (int)(b - i * ninst);
+    const int64_t t = (k0 + i) * st + r;
+    float* dst = tiles + (int64_t)blockIdx.x * F;
+    if (t < T) {
+        const float* src = mag_ring + ring_slot(t, rf) * (int64_t)F;
+        const float* msk = mask_ring + (j * rf + ring_slot(t, rf)) * (int64_t)F;
+        for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = __fmul_rn(msk[f], __fmul_rn(scale, src[f]));
+    } else {
+        for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = 0.f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------ pull: p of the new tiles into its ring
 __global__ __launch_bounds__(kThreads) void stream_keep_p_kernel(const float* __restrict__ p, int64_t p_src_stride, int64_t k0,
                                                                  int64_t tile_elems, float* __restrict__ p_ring, int64_t rp) {
@@ -117,10 +208,15 @@ __global__ __launch_bounds__(kThreads) void stream_keep_p_kernel(const float* __
 // t = t0 + blockIdx.x and k, p and the magnitudes read from their rings.  n = the tiles that exist so far: mid-stream every
 // frame folded has its owner below n, so the clamp acts only after the end.  est[c][s][blockIdx.x][f] = acc_s * mag[c][t][f]
 // for the C channels of the magnitude ring: acc_s is computed once.
+// MIX: kMixMag the magnitude itself (the mono and channel streams); a score stream (C = 1) multiplies with the score-informed
+// mixture instead, formed from the mask ring [ninst][rf][F]: kMixCh0 M_0 * mag, kMixSum ((x_0 + x_1) + ...) with x_j = M_j * mag.
+enum { kMixMag = 0, kMixCh0 = 1, kMixSum = 2 };
+template <int MIX>
 __global__ __launch_bounds__(kThreads) void stream_fold_kernel(
     const float* __restrict__ p_ring, int64_t rp, int64_t n, int S, int tc, int ov, int F, int mode,
     const float* __restrict__ rise, const float* __restrict__ mag_ring, int64_t rf, int C, int64_t t0, float* __restrict__ est,
-    int64_t est_src_stride, float* __restrict__ est_out, int64_t out_ch_stride, int64_t out_src_stride, int64_t ld) {
+    int64_t est_src_stride, float* __restrict__ est_out, int64_t out_ch_stride, int64_t out_src_stride, int64_t ld,
+    const float* __restrict__ mask_ring, int ninst) {
     const int f = blockIdx.y * kThreads + threadIdx.x;
     if (f >= F) return;
     const int64_t t = t0 + blockIdx.x;
@@ -152,7 +248,14 @@ __global__ __launch_bounds__(kThreads) void stream_fold_kernel(
         }
     }
     for (int c = 0; c < C; ++c) {
-        const float mg = mag_ring[(c * rf + ring_slot(t, rf)) * (int64_t)F + f];
+        float mg = mag_ring[(c * rf + ring_slot(t, rf)) * (int64_t)F + f];
+        if (MIX != kMixMag) {
+            const float m = mg;
+            const float* mk_row = mask_ring + ring_slot(t, rf) * (int64_t)F + f;
+            mg = __fmul_rn(mk_row[0], m);
+            if (MIX == kMixSum)
+                for (int j = 1; j < ninst; ++j) mg = __fadd_rn(mg, __fmul_rn(mk_row[j * rf * (int64_t)F], m));
+        }
 #pragma unroll
         for (int s = 0; s < kMaxSources; ++s)
             if (s < S) {
@@ -266,13 +369,76 @@ struct dcs_stream {
     int64_t P = 0, A = 0, K = 0, Tf = 0, E = 0, T = 0, L = 0;
     int64_t pending = 0;       // tiles of the last push, which the next pull must bring p for
     bool want_pull = false, ended = false;
+    // a score stream (ninst > 0): the converted table on the device, the ring of mask rows, and on the host the first frames of
+    // the sorted rows with the running maximum of their end frames (the candidate range of a push)
+    int ninst = 0, npairs = 0, normalise = 0, mixture = 0;
+    int* table = nullptr;
+    float* masks = nullptr;
+    ScoreVals vals = {};
+    std::vector<int> row_t0, row_end_max;
 };
 
 namespace {
 
-// C = 0: the mono stream
+// the score of dcs_stream_create_score as the caller gave it
+struct ScoreSpec {
+    const double* notes;
+    int ninst, n_notes, width, normalise, mixture;
+};
+
+struct ScoreRow {
+    int inst, t0, t1;
+    std::vector<int> pairs;                              // npairs x (f0, f1)
+};
+
+// dcs_score_masks_scaled's reading of the table with start = 0 and stop = +inf: the counting rows sorted by first frame, and
+// the two values of DCS_SCORE_NORM_MAX per instrument
+int score_convert(const char* who, const ScoreSpec& sc, int F, std::vector<ScoreRow>* rows, ScoreVals* vals) {
+    const int npairs = (sc.width - 3) / 2;
+    const double t_max = 2147483647.0;
+    for (int j = 0; j < sc.ninst; ++j) {
+        bool any = false;
+        for (int p = 0; p < sc.n_notes; ++p) {
+            const double* n = sc.notes + ((size_t)j * sc.n_notes + p) * sc.width;
+            const double n0 = n[0], n1 = n[1], midi = n[2];
+            const double a = n0 > 0.0 ? n0 : 0.0, b = n1;
+            if (!(midi > 0) || !((b - a > 0 ? b - a : 0) > 0)) continue;
+            ScoreRow r;
+            r.inst = j;
+            r.t0 = (int)(a < t_max ? a : t_max);
+            r.t1 = (int)(b < t_max ? b : t_max);
+            r.pairs.assign((size_t)2 * npairs, 0);
+            bool painted = false;
+            for (int k = 0; k < npairs; ++k) {
+                const double fs = n[3 + 2 * k], fe = n[4 + 2 * k];
+                if (!(fe > 0)) continue;
+                if (!(fs > -1.0) || !(fe < (double)F + 1.0))             // the casts below truncate, as the whole-file call's
+                    DCS_FAIL(DCS_ESHAPE, "%s: bin range [%g, %g) outside 0..%d", who, fs, fe, F);
+                const int f0 = (int)fs, f1 = (int)fe;
+                if (f0 < 0 || f1 > F) DCS_FAIL(DCS_ESHAPE, "%s: bin range [%d, %d) outside 0..%d", who, f0, f1, F);
+                if (r.t1 > r.t0 && f1 > f0) {
+                    r.pairs[2 * k] = f0;
+                    r.pairs[2 * k + 1] = f1;
+                    painted = true;
+                }
+            }
+            if (painted) {
+                rows->push_back(r);
+                any = true;
+            }
+        }
+        // filtered[j] / np.max(filtered[j]) in float32, as dcs_score_masks_scaled forms the two values
+        const float floor_v = 1e-18f, maxv = any ? 1.0f : floor_v;
+        vals->lo[j] = floor_v / maxv;
+        vals->hi[j] = 1.0f / maxv;
+    }
+    std::stable_sort(rows->begin(), rows->end(), [](const ScoreRow& x, const ScoreRow& y) { return x.t0 < y.t0; });
+    return DCS_OK;
+}
+
+// C = 0: the mono stream; sc != nullptr: a score stream
 int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, int eps_mode,
-                  float scale, const double* rise_h, int64_t max_push, dcs_stream** out) {
+                  float scale, const double* rise_h, int64_t max_push, dcs_stream** out, const ScoreSpec* sc = nullptr) {
     if (!plan || !rise_h || !out) DCS_FAIL(DCS_EINVAL, "%s: null argument", who);
     if (S < 1 || S > kMaxSources) DCS_FAIL(DCS_EINVAL, "%s: %d sources (1 .. %d)", who, S, kMaxSources);
     if (overlap < 1 || overlap >= time_context) DCS_FAIL(DCS_EINVAL, "%s: overlap %d not in [1, %d)", who, overlap, time_context);
@@ -283,6 +449,24 @@ int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_contex
     if (hop > H) DCS_FAIL(DCS_EINVAL, "%s: hopSize %d above frameSize / 2 = %d", who, hop, H);
     if (N % hop) DCS_FAIL(DCS_EUNSUPPORTED, "%s: hopSize %d does not divide frameSize %d", who, hop, N);
     if (N < 64) DCS_FAIL(DCS_EUNSUPPORTED, "%s: frameSize %d below 64", who, N);
+    std::vector<ScoreRow> score_rows;
+    ScoreVals vals = {};
+    int64_t table_rows = 0;
+    if (sc) {
+        if (!sc->notes) DCS_FAIL(DCS_EINVAL, "%s: null argument", who);
+        if (sc->ninst < 1 || sc->ninst > kMaxChannels)
+            DCS_FAIL(DCS_EINVAL, "%s: %d instruments (1 .. %d)", who, sc->ninst, kMaxChannels);
+        if (sc->n_notes < 0 || sc->width < 5 || ((sc->width - 3) & 1))
+            DCS_FAIL(DCS_EINVAL, "%s: bad table shape (notes %d, width %d)", who, sc->n_notes, sc->width);
+        if (sc->normalise != DCS_SCORE_NORM_MAX && sc->normalise != DCS_SCORE_NORM_SUM)
+            DCS_FAIL(DCS_EINVAL, "%s: normalise %d", who, sc->normalise);
+        if (sc->mixture != DCS_MIX_CH0 && sc->mixture != DCS_MIX_SUM) DCS_FAIL(DCS_EINVAL, "%s: mixture %d", who, sc->mixture);
+        table_rows = (int64_t)sc->ninst * sc->n_notes;
+        if (table_rows * ((sc->width - 3) / 2) > (1LL << 30))
+            DCS_FAIL(DCS_EUNSUPPORTED, "%s: a table of %lld rows x %d pairs", who, (long long)table_rows, (sc->width - 3) / 2);
+        DCS_CHECK(score_convert(who, *sc, H + 1, &score_rows, &vals));
+        if (table_rows < 1) table_rows = 1;              // the block exists whatever the table holds
+    }
     DCS_ON_DEVICE(plan->ctx->device);
 
     dcs_stream* s = new dcs_stream();
@@ -319,6 +503,40 @@ int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_contex
         }
         s->bytes += b.elems * (int64_t)sizeof(float);
     }
+    if (sc) {
+        s->ninst = sc->ninst; s->npairs = (sc->width - 3) / 2; s->normalise = sc->normalise; s->mixture = sc->mixture;
+        s->vals = vals;
+        const int W = kRowHead + 2 * s->npairs;
+        // the table at its capacity (every row of the caller's table), so that the size does not depend on the notes
+        struct { void** ptr; int64_t bytes; const char* name; } extra[] = {
+            {(void**)&s->masks, (int64_t)s->ninst * s->rf * F * (int64_t)sizeof(float), "stream.masks"},
+            {(void**)&s->table, table_rows * W * (int64_t)sizeof(int), "stream.score"},
+        };
+        for (auto& b : extra) {
+            const hipError_t e = dcs_dev_alloc(b.ptr, (size_t)b.bytes, b.name);
+            if (e != hipSuccess) {
+                dcs_set_error("%s: %lld bytes for %s: %s", who, (long long)b.bytes, b.name, hipGetErrorString(e));
+                dcs_stream_destroy(s);
+                return e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP;
+            }
+            s->bytes += b.bytes;
+        }
+        std::vector<int> flat(score_rows.size() * (size_t)W, 0);
+        int end_max = 0;
+        for (size_t r = 0; r < score_rows.size(); ++r) {
+            const ScoreRow& row = score_rows[r];
+            int* dst = flat.data() + r * (size_t)W;
+            dst[0] = row.inst; dst[1] = row.t0; dst[2] = row.t1;
+            std::copy(row.pairs.begin(), row.pairs.end(), dst + kRowHead);
+            end_max = row.t1 > end_max ? row.t1 : end_max;
+            s->row_t0.push_back(row.t0);
+            s->row_end_max.push_back(end_max);
+        }
+        if (!flat.empty() && hipMemcpy(s->table, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+            dcs_stream_destroy(s);
+            DCS_FAIL(DCS_EHIP, "%s: uploading the note table failed", who);
+        }
+    }
     std::vector<float> rise((size_t)overlap);
     for (int i = 0; i < overlap; ++i) rise[i] = (float)rise_h[i];
     if (hipMemcpy(s->rise, rise.data(), rise.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
@@ -344,6 +562,14 @@ extern "C" int dcs_stream_create_channels(dcs_stft* plan, int S, int C, int time
                          out);
 }
 
+extern "C" int dcs_stream_create_score(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
+                                       const double* rise_h, int64_t max_push, const double* notes_h, int ninst, int n_notes,
+                                       int width, int normalise, int mixture, dcs_stream** out) {
+    const ScoreSpec sc = {notes_h, ninst, n_notes, width, normalise, mixture};
+    return stream_create("dcs_stream_create_score", plan, S, 0, time_context, overlap, tiler, eps_mode, scale, rise_h, max_push,
+                         out, &sc);
+}
+
 extern "C" int dcs_stream_destroy(dcs_stream* s) {
     if (!s) return DCS_OK;
     DCS_ON_DEVICE(s->ctx->device);
@@ -355,13 +581,15 @@ extern "C" int dcs_stream_destroy(dcs_stream* s) {
     dcs_dev_free(s->est);
     dcs_dev_free(s->tf);
     dcs_dev_free(s->rise);
+    dcs_dev_free(s->masks);
+    dcs_dev_free(s->table);
     delete s;
     return DCS_OK;
 }
 
 extern "C" int dcs_stream_reset(dcs_stream* s) {
     if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_reset: null stream");
-    // the rings keep their contents: no slot is read before the push or pull that needs it has written it
+    // the rings keep their contents: no slot is read before the push or pull that needs it has written it (the score stays too)
     s->P = s->A = s->K = s->Tf = s->E = s->T = s->L = s->pending = 0;
     s->want_pull = s->ended = false;
     return DCS_OK;
@@ -415,7 +643,27 @@ int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t ro
         DCS_CHECK((launch_frames<float, float2>(s->plan, stream_frames_kernel, n_frames, s->rows - 1, s->plan->win_f,
                                                 s->plan->tw_f, (const float*)s->samples, s->cap, P, s->A, s->rf, s->mag,
                                                 s->phase, s->nch, mag_d, phase_d, ch_stride, ld)));
-    if (n_tiles > 0) {
+    if (s->ninst && n_frames > 0) {
+        // the candidate rows of frames [s->A, A): first frame below A (the rows are sorted by it) and, by the running maximum of
+        // the end frames, no row before r_lo reaching s->A -- two binary searches, whatever the length of the score
+        const int64_t a_hi = A < 2147483647LL ? A : 2147483647LL, a_lo = s->A < 2147483647LL ? s->A : 2147483647LL;
+        const int r_hi = (int)(std::lower_bound(s->row_t0.begin(), s->row_t0.end(), (int)a_hi) - s->row_t0.begin());
+        int r_lo = (int)(std::upper_bound(s->row_end_max.begin(), s->row_end_max.end(), (int)a_lo) - s->row_end_max.begin());
+        if (r_lo > r_hi) r_lo = r_hi;
+        DcsTimer tm(s->ctx, DCS_TAG_SCORE);
+        hipLaunchKernelGGL(stream_masks_kernel, dim3((unsigned)n_frames), dim3(kThreads), 0, q, (const int*)s->table, s->npairs,
+                           r_lo, r_hi, s->A, s->rf, s->F, s->ninst, s->normalise, s->vals, s->masks);
+        tm.done();
+        DCS_HIP(hipGetLastError());
+    }
+    if (n_tiles > 0 && s->ninst) {
+        DcsTimer tm(s->ctx, DCS_TAG_TILE);
+        hipLaunchKernelGGL(stream_score_tiles_kernel, dim3((unsigned)(n_tiles * s->ninst * s->tc)), dim3(kThreads), 0, q,
+                           (const float*)s->mag, (const float*)s->masks, s->rf, s->F, s->tc, s->st, s->ninst, s->K, A, s->scale,
+                           tiles_d);
+        tm.done();
+        DCS_HIP(hipGetLastError());
+    } else if (n_tiles > 0) {
         DcsTimer tm(s->ctx, DCS_TAG_TILE);
         const float* mix = s->mag + (int64_t)(s->rows - 1) * s->rf * s->F;     // the down-mix: the last row
         hipLaunchKernelGGL(stream_tiles_kernel, dim3((unsigned)(n_tiles * s->tc)), dim3(kThreads), 0, q, mix, s->rf, s->F, s->tc,
@@ -481,10 +729,12 @@ int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_
     if (n_fold > 0) {
         {
             DcsTimer tm(s->ctx, DCS_TAG_MASK);
-            hipLaunchKernelGGL(stream_fold_kernel, dim3((unsigned)n_fold, (unsigned)dcs_cdiv(s->F, kThreads)), dim3(kThreads), 0, q,
+            auto fold = stream_fold_kernel<kMixMag>;
+            if (s->ninst) fold = s->mixture == DCS_MIX_SUM ? stream_fold_kernel<kMixSum> : stream_fold_kernel<kMixCh0>;
+            hipLaunchKernelGGL(fold, dim3((unsigned)n_fold, (unsigned)dcs_cdiv(s->F, kThreads)), dim3(kThreads), 0, q,
                                (const float*)s->p, s->rp, s->K, s->S, s->tc, s->ov, s->F, s->eps_mode, (const float*)s->rise,
                                (const float*)s->mag, s->rf, s->nch, s->Tf, s->est, s->ff * s->F, est_d, est_ch_stride,
-                               est_src_stride, ld);
+                               est_src_stride, ld, (const float*)s->masks, s->ninst);
             tm.done();
             DCS_HIP(hipGetLastError());
         }

@@ -509,6 +509,8 @@ class Stream(object):
     strictly; the counts of every call are host integers (:class:`deepconvsep_amd.streaming.StreamCounts`), so the outputs are
     allocated at their exact size before the call and nothing waits for the device."""
 
+    tile_channels = 1                # input channels of the tiles a push returns
+
     def __init__(self, plan, S, time_context, overlap, tiler=TILER_SCRIPT, eps_mode=EPS_A, scale=1.0, max_push=65536):
         from .streaming import StreamCounts
         self.ctx, self.plan = plan.ctx, plan
@@ -543,7 +545,7 @@ class Stream(object):
         c, P = self.counts, self.pushed + n
         want_t = max(0, min(c.tiles(P, bool(last)) - self._tiles, self.max_tiles))
         want_f = max(0, c.frames(P, bool(last)) - self._frames) if want_frames else 0
-        tiles = torch.empty((want_t, 1, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
+        tiles = torch.empty((want_t, self.tile_channels, self.tc, self.F), dtype=torch.float32, device=self.ctx.device)
         mag = torch.empty((want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
         ph = torch.empty((want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
         nt, nf = c_int64(), c_int64()
@@ -677,6 +679,35 @@ class ChannelStream(Stream):
         if got.value != n_pcm:
             raise _lib.DcsError("dcs_stream_pull_channels returned %d samples, the host counts say %d" % (got.value, n_pcm))
         return (pcm, est) if want_est else pcm
+
+
+class ScoreStream(Stream):
+    """``dcs_stream_create_score``: a :class:`Stream` for the score-informed graphs.  ``melody`` is the note table
+    ``[instruments, notes, 2*nharmonics+3]`` of ``score.melody_table``, read once, here; ``normalise`` ``'max'`` | ``'sum'`` and
+    ``mixture`` ``'ch0'`` | ``'sum'`` as in :meth:`Network.set_score_semantics`.  ``push`` returns tiles ``[n_new, instruments,
+    tc, F]`` -- channel ``j`` is the harmonic mask of instrument ``j`` times the scaled magnitudes -- and the fold of ``pull``
+    multiplies with the score-informed mixture; everything else (``pull``, ``reset``, which keeps the score, ``close``,
+    ``bytes``, ``max_tiles``, the counts) is the mono stream's."""
+
+    def __init__(self, plan, S, melody, time_context, overlap, tiler=TILER_LIBRARY, eps_mode=EPS_A, scale=1.0, max_push=65536,
+                 normalise='max', mixture='ch0'):
+        melody = np.ascontiguousarray(melody, dtype=np.float64)
+        if melody.ndim != 3:
+            raise ValueError("melody must be [instruments, notes, 2*nharmonics+3]")
+        try:
+            self._codes = ({'max': 0, 'sum': 1}[normalise], {'ch0': 0, 'sum': 1}[mixture])
+        except KeyError:
+            raise ValueError("normalise must be 'max' or 'sum', mixture 'ch0' or 'sum'")
+        self._melody = melody
+        self.ninst = self.tile_channels = int(melody.shape[0])
+        Stream.__init__(self, plan, S, time_context, overlap, tiler, eps_mode, scale, max_push)
+        del self._melody                 # the library keeps its own converted copy
+
+    def _create(self, overlap, tiler, eps_mode, scale, rise_p, h):
+        m = self._melody
+        return self.ctx._lib.dcs_stream_create_score(self.plan._h, self.S, self.tc, overlap, tiler, eps_mode, scale, rise_p,
+                                                     self.max_push, m.ctypes.data_as(POINTER(c_double)), int(m.shape[0]),
+                                                     int(m.shape[1]), int(m.shape[2]), self._codes[0], self._codes[1], byref(h))
 
 
 def tile(ctx, mag_t, time_context, overlap, tiler, scale=1.0):

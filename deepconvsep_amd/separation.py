@@ -519,9 +519,19 @@ class Separator(object):
         of a mono 44 100 Hz signal as they come, get the finished stems back ``time_context * hopSize + frameSize`` samples
         behind at the most, in device memory that depends on ``max_block`` and not on the signal's length.  The values are
         those of :meth:`channel_spectra`'s composition on a mono signal (the cross-faded masks on the unscaled magnitudes).
-        Single-input-channel graphs only (``ValueError`` otherwise)."""
+        Single-input-channel graphs only (``ValueError`` otherwise; the score-informed graphs: :meth:`stream_scoreinformed`)."""
         from .streaming import StreamSeparator
         return StreamSeparator(self, max_block=max_block, sample_rate=sample_rate)
+
+    def stream_scoreinformed(self, melody, max_block=65536):
+        """A :class:`deepconvsep_amd.streaming.ScoreStreamSeparator` on this separator's model and plan: score-informed
+        separation on a stream.  ``melody``: the note table of the whole signal (``score.melody_table`` with ``nframes`` the
+        signal's frame count), read once; the harmonic masks follow ``score_normalise``, the mixture ``score_mixture``, the
+        tiles this separator's ``tiler``.  ``push(block)`` takes mono 44 100 Hz samples and returns the finished stems
+        ``[S, n_i]``, as :meth:`stream` does; ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes any other
+        rate.  ``ValueError`` for a graph with one input channel, and when ``melody.shape[0]`` is not the graph's."""
+        from .streaming import ScoreStreamSeparator
+        return ScoreStreamSeparator(self, melody, max_block=max_block)
 
     def stream_channels(self, max_block=65536):
         """A :class:`deepconvsep_amd.streaming.ChannelStreamSeparator` on this separator's model and plan: the stereo stems of

@@ -6,6 +6,9 @@ by block, the samples of the same computation (``stft_norm`` -> tiler -> network
 ``time_context * hop + frameSize`` samples behind the input at the most, in device memory that depends on the block size and
 not on the length of the signal.
 
+:class:`ScoreStreamSeparator` does it for the score-informed graphs: the score is known before the audio, so the harmonic masks
+of every frame are formed as the frame arrives (``dcs_stream_create_score``).
+
 :class:`ChannelStreamSeparator` does the same for a stereo signal -- the stems of ``Separator.separate_channels`` on one engine
 -- and :class:`RateStream` puts either of them between two streaming sample-rate converters (``dcs_resample_stream``) for audio
 at another rate than 44 100 Hz.
@@ -81,7 +84,7 @@ class StreamSeparator(object):
     ``reset()`` starts another signal.  Single-input-channel graphs only."""
 
     def __init__(self, separator, max_block=65536, sample_rate=44100):
-        separator._require_mono_graph("stream")
+        self._check_graph(separator)
         if int(sample_rate) != 44100:
             raise ValueError("a stream takes 44 100 Hz audio, not %d Hz (convert the blocks first)" % int(sample_rate))
         if int(max_block) < 1:
@@ -91,6 +94,13 @@ class StreamSeparator(object):
         self.counts = StreamCounts(separator.frameSize, separator.hopSize, separator.tc, separator.overlap, separator.tiler)
         self._engine = None              # the device state: made by the first block
         self._pushed, self._ended = 0, False
+
+    @staticmethod
+    def _check_graph(separator):
+        if separator.net.arch.C != 1 and separator.arch_name != 'dsd_ild':
+            raise ValueError("stream feeds a single-input-channel graph; '%s' takes %d input channels, one per instrument of a "
+                             "score: use stream_scoreinformed(melody)" % (separator.arch_name, separator.net.arch.C))
+        separator._require_mono_graph("stream")
 
     @property
     def S(self):
@@ -162,6 +172,46 @@ class StreamSeparator(object):
     def device_bytes(self):
         """device bytes the stream holds (``dcs_stream_bytes``): a function of the shapes and ``max_block`` alone"""
         return self._stream().bytes
+
+
+class ScoreStreamSeparator(StreamSeparator):
+    """``Separator.stream_scoreinformed(melody)``: score-informed separation on a stream, with :class:`StreamSeparator`'s
+    interface (so :class:`RateStream` wraps it as it wraps that one).
+
+    ``melody`` is the note table ``[instruments, notes, 2*nharmonics+3]`` of ``score.melody_table`` for the WHOLE signal at
+    44 100 Hz -- it is known before the audio arrives and read once.  A push forms the harmonic masks of the frames it
+    completed (``filterSpec`` per absolute frame, the separator's ``score_normalise``), the tiles carry one channel per
+    instrument, mask times scaled magnitudes, and the fold multiplies the cross-faded soft masks with the score-informed
+    mixture on the unscaled magnitudes (the separator's ``score_mixture``).  The masks agree with the whole-file
+    ``dcs_score_masks`` whenever no note row ends past the signal's frame count, which a table built with ``nframes`` = that
+    count guarantees."""
+
+    def __init__(self, separator, melody, max_block=65536):
+        if separator.net.arch.C == 1:
+            raise ValueError("stream_scoreinformed feeds one input channel per instrument of the score; '%s' takes one input "
+                             "channel: use stream()" % separator.arch_name)
+        if separator.arch_name == 'dsd_ild':
+            raise ValueError("stream_scoreinformed: '%s' is no score-informed graph" % separator.arch_name)
+        melody = np.ascontiguousarray(melody, dtype=np.float64)
+        if melody.ndim != 3 or separator.net.arch.C != melody.shape[0]:
+            raise ValueError("the network takes %d score channels, the note table has %d"
+                             % (separator.net.arch.C, melody.shape[0] if melody.ndim else 0))
+        if int(max_block) < 1:
+            raise ValueError("max_block must be at least 1 sample")
+        self.sep, self.ctx = separator, separator.ctx
+        self.melody = melody
+        self.max_block = int(max_block)
+        self.counts = StreamCounts(separator.frameSize, separator.hopSize, separator.tc, separator.overlap, separator.tiler)
+        self._engine = None              # the device state: made by the first block
+        self._pushed, self._ended = 0, False
+
+    def _stream(self):
+        if self._engine is None:
+            from .runtime import ScoreStream
+            s = self.sep
+            self._engine = ScoreStream(s.plan, s.net.S, self.melody, s.tc, s.overlap, s.tiler, s.net.arch.eps_mode,
+                                       s.scale_factor, self.max_block, s.score_normalise, s.score_mixture)
+        return self._engine
 
 
 class ChannelStreamSeparator(object):

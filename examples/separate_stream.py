@@ -1,6 +1,7 @@
 """Separate a 16-bit PCM wav file block by block: neither the file nor its stems are ever whole in memory.
 
     python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536] [--stereo] [--resample]
+    python examples/separate_stream.py -a bach10_si -i mix.wav -o outdir -m model.pkl [--trainer-semantics] [--resample]
 
 The file is read with the standard ``wave`` module ``--block`` frames at a time; each block is scaled and mixed down the way
 the architecture's separate script does it (element-wise, so block by block equals the whole file), pushed into
@@ -12,6 +13,13 @@ device memory depend on ``--block``, not on the length of the file.
 down-mix on each channel's own spectrum with its own phase) where it otherwise is mixed down.  ``--resample``: a file at any
 sample rate is converted to 44 100 Hz block by block on the device and the stems are converted back and written at the file's
 own rate (``RateStream``); without it such a file is refused, as the reference's scripts refuse it.
+
+``-a bach10_si``: score-informed separation (``Separator.stream_scoreinformed``).  The four score files ``bassoon_b.txt,
+clarinet_b.txt, saxophone_b.txt, violin_b.txt`` are read next to the wav, as the separate script reads them, and the note table
+is built before the first block from the frame count the wav HEADER gives (``ceil(frames / hop) + 2`` at 44 100 Hz; with
+``--resample`` from the length the file has at 44 100 Hz).  ``--trainer-semantics``: masks divided by their sum over the
+instruments and soft masks on the channel sum, what the trainer's own models saw (``separate_bach10.py`` has the same
+option).  ``--stereo`` does not apply.
 """
 import argparse
 import os
@@ -22,7 +30,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-ARCHS = ("dsd", "hiphop", "ikala", "bach10")
+ARCHS = ("dsd", "hiphop", "ikala", "bach10", "bach10_si")
 
 
 def read_blocks(wav, block):
@@ -45,10 +53,18 @@ def main(argv=None):
     ap.add_argument("--block", type=int, default=65536, help="frames read and pushed at a time")
     ap.add_argument("--stereo", action="store_true", help="two-channel stems from a two-channel file")
     ap.add_argument("--resample", action="store_true", help="take any sample rate; the stems keep the file's rate")
+    ap.add_argument("--trainer-semantics", action="store_true",
+                    help="bach10_si: masks / their sum over the instruments, soft masks x the channel sum")
     args = ap.parse_args(argv)
+    score = args.arch == "bach10_si"
+    if score and args.stereo:
+        raise SystemExit("--stereo does not apply to bach10_si: the score-informed graphs take one channel per instrument")
+    if args.trainer_semantics and not score:
+        raise SystemExit("--trainer-semantics applies to bach10_si only")
 
     import deepconvsep_amd as dcs
-    from deepconvsep_amd.separation import _SCRIPT_DEFAULTS, output_paths, to_mono
+    from deepconvsep_amd.separation import (SI_SCORE_FILES, SI_SCORE_PARAMS, TARGET_RATE, _SCRIPT_DEFAULTS, output_paths,
+                                            rate_ratio, resampled_length, to_mono)
     from deepconvsep_amd.streaming import RateStream
 
     frame, hop, window, overlap, bins = _SCRIPT_DEFAULTS[args.arch]
@@ -60,8 +76,19 @@ def main(argv=None):
         raise SystemExit("Sample rate is not 44100")
     if args.stereo and src.getnchannels() != 2:
         raise SystemExit("--stereo takes a two-channel file, %s has %d" % (args.input, src.getnchannels()))
-    sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
-    stream = sep.stream_channels(max_block=args.block) if args.stereo else sep.stream(max_block=args.block)
+    if score:
+        from deepconvsep_amd.score import melody_table
+        sem = ('sum', 'sum') if args.trainer_semantics else ('max', 'ch0')
+        sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window,
+                            tiler='library', score_normalise=sem[0], score_mixture=sem[1])
+        # the frames of the signal the network sees, known from the header before any audio is read
+        n44 = src.getnframes() if rate == 44100 else resampled_length(src.getnframes(), *rate_ratio(rate, TARGET_RATE))
+        nframes = int(np.ceil(n44 / np.double(hop))) + 2
+        melody = melody_table(SI_SCORE_FILES, os.path.dirname(args.input), nframes, TARGET_RATE, hop, frame, **SI_SCORE_PARAMS)
+        stream = sep.stream_scoreinformed(melody, max_block=args.block)
+    else:
+        sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
+        stream = sep.stream_channels(max_block=args.block) if args.stereo else sep.stream(max_block=args.block)
     if rate != 44100:
         stream = RateStream(stream, rate)
     os.makedirs(args.outdir, exist_ok=True)

@@ -557,6 +557,36 @@ DCS_API int dcs_stream_push_channels(dcs_stream* s, const float* audio_d, int64_
 DCS_API int dcs_stream_pull_channels(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
                                      int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d,
                                      int64_t est_ch_stride, int64_t est_src_stride, int64_t ld);
+/* A SCORE stream: the score-informed graphs (dcs_model_forward's [n, ninst, tc, F] tiles) on a stream.  The score is known
+ * before the audio: notes_h [ninst][n_notes][width] is the table dcs_score_masks takes, read by the rules of that call -- a row
+ * counts if midi > 0 and its duration n1 - max(n0, 0) is positive, it covers the frames (int64)max(n0, 0) <= t < (int64)n1; a
+ * pair (fs, fe) counts if fe > 0 and covers the bins (int64)fs <= f < (int64)fe; width >= 5 and odd (else DCS_EINVAL); a bin
+ * range outside [0, F) gives DCS_ESHAPE.  1 <= ninst <= 8, normalise DCS_SCORE_NORM_MAX | _SUM, mixture DCS_MIX_CH0 | _SUM in
+ * any combination (else DCS_EINVAL); everything else as dcs_stream_create refuses it.  The table is converted (rows sorted by
+ * first frame, with the running maximum of their end frames, so that a push looks only at the rows that can meet its frames) and
+ * uploaded once, here; push and pull still allocate nothing and never wait for the device.  All arithmetic float32, every
+ * product, sum and quotient below rounded once, in the order written:
+ *   mask    for absolute frame t, instrument j, bin f:  on_j[t][f] = some counting row of j covers t and one of its counting
+ *           pairs covers f -- filterSpec with the window (0, +inf); rows t >= T never reach a tile (the tiler's zeros)
+ *     DCS_SCORE_NORM_MAX  M_j = on_j ? hi_j : lo_j,  hi_j = 1 / max_j,  lo_j = 1e-18f / max_j,  max_j = 1 if instrument j has any
+ *                         non-empty rectangle (frames and bins) in the table AS GIVEN, else 1e-18f (such an instrument: all ones)
+ *     DCS_SCORE_NORM_SUM  v_i = on_i ? 1 : 1e-18f,  total = ((v_0 + v_1) + ...),  M_j = v_j / total  (score_sumnorm_kernel's)
+ *           The one difference from dcs_score_masks_norm(.., start = 0, stop = n_frames, ..): there "any rectangle" and the
+ *           clip of a row are taken against stop = n_frames, here against +inf.  The two agree whenever no note row ends past
+ *           the signal's frame count (a row that only BEGINS there is the case that differs: it makes max_j = 1 here), which
+ *           holds for a table built by melody_table(..., nframes = T).
+ *   tiles   tiles[k][j][r][f] = M_j[t][f] * (scale * mag[t][f]),  t = k st + r,  zero for t >= T  (score_floor_kernel's product)
+ *   fold    est[s][t][f] = acc_s[t][f] * mix[t][f], acc_s exactly as in the mono stream, on the UNSCALED magnitudes (pre_div = 1):
+ *     DCS_MIX_CH0  mix = M_0 * mag        DCS_MIX_SUM  mix = ((x_0 + x_1) + ...),  x_j = M_j * mag
+ *   inverse, gather, schedule, counts, refusals: the mono stream's.
+ * dcs_stream_push / _pull / _reset / _destroy / _max_tiles / _bytes work on such a stream; tiles_d is [n_tiles, ninst,
+ * time_context, F]; reset keeps the score; dcs_stream_push_channels / _pull_channels give DCS_EINVAL.  State: the mono stream's
+ * plus a ring of mask rows [ninst][rf][F] (written by the push that completes a frame, next to its magnitudes) and the converted
+ * table (ninst n_notes rows of 4 + (width - 3) int32): dcs_stream_bytes is a function of (N, h, tc, overlap, S, ninst, n_notes,
+ * width, max_push) alone. */
+DCS_API int dcs_stream_create_score(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
+                                    const double* rise_h, int64_t max_push, const double* notes_h, int ninst, int n_notes,
+                                    int width, int normalise, int mixture, dcs_stream** out);
 
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
 /* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is

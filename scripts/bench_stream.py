@@ -2,13 +2,16 @@
 tile), run the tile through the network, pull the finished samples -- and of the push + pull machinery alone, with the network
 left out (a fixed ``p``).  Each step ends with a stream synchronisation, as a live caller that plays the samples would.
 
-    python scripts/bench_stream.py [--steps 200] [--warmup 20] [--channels 2] [--rate 48000]
+    python scripts/bench_stream.py [--steps 200] [--warmup 20] [--channels 2] [--rate 48000] [--score]
 
 ``--channels 2`` adds, in the same run, the stereo step on one channel engine (``Separator.stream_channels()``) and the stereo
 step composed of three mono ``runtime.Stream`` engines -- L, R and the down-mix -- that share one ``p``, which is what the mono
 API allows.  ``--rate R`` adds the step of a ``RateStream`` at ``R`` Hz around the mono stream (and, with ``--channels 2``, around
 the stereo one); its block is one stride of audio at that rate.  The launch counts per step are those of the code: append,
-frames, tiles, the network call, keep-p, fold, inverse, gather per engine; append and convert per converter.
+frames, tiles, the network call, keep-p, fold, inverse, gather per engine; append and convert per converter.  ``--score`` adds
+the score-informed step at the Bach10 shape (frameSize 4096, 2049 bins, four instruments, synthetic weights and a synthetic
+score as long as the run: ``Separator.stream_scoreinformed``, one launch more for the masks of the new frames) next to the mono
+``bach10`` stream's step at the same shape, and the device bytes of both.
 
 Prints one JSON line: the median and mean wall time per step in milliseconds, next to the block's duration in audio time."""
 import argparse
@@ -28,6 +31,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--channels", type=int, default=1, choices=(1, 2))
     ap.add_argument("--rate", type=int, default=44100)
+    ap.add_argument("--score", action="store_true")
     args = ap.parse_args(argv)
     import torch
     import deepconvsep_amd as dcs
@@ -99,6 +103,31 @@ def main(argv=None):
             rs2 = RateStream(sep.stream_channels(max_block=rblock), args.rate)
             rated2 = timed(lambda i: rs2.push_device(r3[:, i * rblock:(i + 1) * rblock]))
             extra.update({"rate_stereo_step_ms_median": med(rated2), "rate_stereo_device_bytes": rs2.device_bytes})
+    if args.score:
+        N4, F4 = 4096, 2049
+        n_frames = block * (total + tc) // hop + 3
+        rs_ = np.random.RandomState(3)
+        nharm, per_note = 20, 35                                      # back-to-back notes of 35 frames, 20 harmonic bands each
+        n_notes = n_frames // per_note + 1
+        melody = np.zeros((4, n_notes, 2 * nharm + 3))
+        for j in range(4):
+            for m in range(n_notes):
+                b0 = int(rs_.randint(8, 60))                          # the fundamental's bin
+                melody[j, m, :3] = (m * per_note, min(n_frames, (m + 1) * per_note), 40 + j)
+                for k in range(1, nharm + 1):
+                    if k * b0 + 3 <= F4:
+                        melody[j, m, 1 + 2 * k:3 + 2 * k] = (k * b0 - 2, k * b0 + 3)
+        sep_si = dcs.Separator("bach10_si", synth_params("bach10_si", tc, F4, seed=2), 0.3, tc, ov, 32, F4, N4, hop,
+                               dcs.blackmanharris, tiler='library', ctx=ctx)
+        sep_b = dcs.Separator("bach10", synth_params("bach10", tc, F4, seed=2), 0.3, tc, ov, 32, F4, N4, hop, dcs.blackmanharris,
+                              ctx=ctx)
+        sc, sb = sep_si.stream_scoreinformed(melody, max_block=block), sep_b.stream(max_block=block)
+        scored = timed(lambda i: sc.push_device(audio[i * block:(i + 1) * block]))
+        plain = timed(lambda i: sb.push_device(audio[i * block:(i + 1) * block]))
+        extra.update({"score_bins": F4, "score_instruments": 4, "score_note_rows": 4 * n_notes,
+                      "score_step_ms_median": med(scored), "score_launches_per_step": 8 + 1,
+                      "bach10_step_ms_median": med(plain), "score_device_bytes": sc.device_bytes,
+                      "bach10_device_bytes": sb.device_bytes})
     print(json.dumps({"bench": "stream", "graph": "dsd", "bins": F, "block_samples": block,
                       "block_audio_ms": round(1e3 * block / 44100.0, 3), "steps": args.steps,
                       "step_ms_median": round(float(np.median(full)), 4), "step_ms_mean": round(float(full.mean()), 4),
