@@ -125,6 +125,8 @@ def load():
     proto("dcs_debug_conv_fold_weights", i32, vp, vp, i64, POINTER(i64), POINTER(i64))
     proto("dcs_debug_dsd_stage", i32, vp, i32, vp)
     proto("dcs_debug_dsd_last_kernel", i32, vp, POINTER(i32), POINTER(i64))
+    proto("dcs_debug_d1_conv", i32, vp, i32, vp)
+    proto("dcs_debug_d1_aux", i32, vp, i32, vp)
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)

@@ -25,7 +25,7 @@
 
 #include "deep1x1.h"
 
-#include "deep1x1_igemm.h"
+#include "deep1x1_debug.h"
 
 using namespace d1;
 
@@ -56,11 +56,36 @@ __global__ __launch_bounds__(kThreads) void d1_mask_kernel(const float* __restri
 struct D1Layer {
     int Cin, Cinp, Cout, Coutp, kh;
     int Hi, Wi, Ho, Wo;
-    int K, Kpad;                // forward
-    int Kt[2], Ktpad[2];        // transposed, per output-column parity
     float *B = nullptr, *b0 = nullptr, *b1 = nullptr, *Bt[2] = {nullptr, nullptr};
 };
 
+
+// The operands of one convolution from its Lasagne weights W [Cout][Cin][kh][kw] (flip_filters=True: a true convolution);
+// kw = 5 (stride 2: the taps of an output-column parity p are j = p + 2 jt, ntap = 3 / 2 of them) or 1 (the 1x1 layer).
+//   forward                B[co][(i * kw + j) * Cinp + ci] = W[co][ci][kh-1-i][kw-1-j]                    [npad(Cout)][Kpad]
+//   transposed, parity p   Bt[p][ci][(i * ntap + jt) * Coutp + co] = W[co][ci][kh-1-i][kw-1-(p+2jt)]     [npad(Cin)][Ktpad[p]]
+// zero past K and past the live rows (the layouts D1Args documents).  With bt == nullptr only B is made.
+void pack_host(const float* Wk, int Cin, int Cout, int kh, int kw, std::vector<float>& B, std::vector<float>* bt) {
+    const int Cinp = (int)dcs_round_up(Cin, 4), Coutp = (int)dcs_round_up(Cout, 4);
+    auto w = [&](int co, int ci, int i, int j) { return Wk[(((size_t)co * Cin + ci) * kh + i) * kw + j]; };
+    const int Kpad = (int)dcs_round_up(kh * kw * Cinp, 16);
+    B.assign((size_t)npad_for(Cout) * Kpad, 0.f);
+    for (int co = 0; co < Cout; ++co)
+        for (int i = 0; i < kh; ++i)
+            for (int j = 0; j < kw; ++j)
+                for (int ci = 0; ci < Cin; ++ci)
+                    B[(size_t)co * Kpad + (i * kw + j) * Cinp + ci] = w(co, ci, kh - 1 - i, kw - 1 - j);
+    for (int p = 0; bt && p < 2; ++p) {
+        const int nt = (kw - p + 1) / 2;
+        const int Ktpad = (int)dcs_round_up(kh * nt * Coutp, 16);
+        bt[p].assign((size_t)npad_for(Cin) * Ktpad, 0.f);
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int i = 0; i < kh; ++i)
+                for (int jt = 0; jt < nt; ++jt)
+                    for (int co = 0; co < Cout; ++co)
+                        bt[p][(size_t)ci * Ktpad + (i * nt + jt) * Coutp + co] = w(co, ci, kh - 1 - i, kw - 1 - (p + 2 * jt));
+    }
+}
 
 int upload_f32(float** dst, const std::vector<float>& src, const char* name) {
     DCS_HIP(dcs_dev_alloc((void**)dst, src.size() * sizeof(float), name));
@@ -75,7 +100,6 @@ struct DcsDeep1x1Net {
     int C = 4, tc = 0, F = 0, nb = 1;
     D1Layer L[kLayers];
     float *B11 = nullptr, *b11_0 = nullptr, *b11_1 = nullptr, *fbias = nullptr;
-    int K11pad = 0;
     int score_norm = DCS_SCORE_NORM_MAX, mix_sum = 0;
     DcsBuffer ws;
     float* rise_d = nullptr;
@@ -140,31 +164,8 @@ int dcs_deep1x1_create(dcs_ctx* ctx, int C, int tc, int F, const float* const* p
         l.Cin = cin; l.Cinp = (int)dcs_round_up(cin, 4); l.Cout = kFilters[k]; l.Coutp = (int)dcs_round_up(l.Cout, 4);
         l.kh = kKh[k];
         l.Hi = H; l.Wi = W; l.Ho = H - l.kh + 1; l.Wo = (W - kKw) / 2 + 1;
-        const std::vector<float>& Wk = P[3 * k];   // [Cout][Cin][kh][5]; Lasagne flips the filter (flip_filters=True)
-        auto w = [&](int co, int ci, int i, int j) { return Wk[(((size_t)co * l.Cin + ci) * l.kh + i) * kKw + j]; };
-        // forward: B[co][(i * 5 + j) * Cinp + ci] = W[co][ci][kh-1-i][4-j]
-        l.K = l.kh * kKw * l.Cinp; l.Kpad = (int)dcs_round_up(l.K, 16);
-        const int npad = dcs_cdiv(l.Cout, 16 * nt_for(l.Cout)) * 16 * nt_for(l.Cout);
-        std::vector<float> B((size_t)npad * l.Kpad, 0.f);
-        for (int co = 0; co < l.Cout; ++co)
-            for (int i = 0; i < l.kh; ++i)
-                for (int j = 0; j < kKw; ++j)
-                    for (int ci = 0; ci < l.Cin; ++ci)
-                        B[(size_t)co * l.Kpad + (i * kKw + j) * l.Cinp + ci] = w(co, ci, l.kh - 1 - i, kKw - 1 - j);
-        // transposed, parity p: Bt[ci][(i * ntap + jt) * Coutp + co] = W[co][ci][kh-1-i][4-(p+2jt)]
-        const int npad_t = dcs_cdiv(l.Cin, 16 * nt_for(l.Cin)) * 16 * nt_for(l.Cin);
-        std::vector<float> Bt[2];
-        for (int p = 0; p < 2; ++p) {
-            const int nt = ntap_of(p);
-            l.Kt[p] = l.kh * nt * l.Coutp; l.Ktpad[p] = (int)dcs_round_up(l.Kt[p], 16);
-            Bt[p].assign((size_t)npad_t * l.Ktpad[p], 0.f);
-            for (int ci = 0; ci < l.Cin; ++ci)
-                for (int i = 0; i < l.kh; ++i)
-                    for (int jt = 0; jt < nt; ++jt)
-                        for (int co = 0; co < l.Cout; ++co)
-                            Bt[p][(size_t)ci * l.Ktpad[p] + (i * nt + jt) * l.Coutp + co] =
-                                w(co, ci, l.kh - 1 - i, kKw - 1 - (p + 2 * jt));
-        }
+        std::vector<float> B, Bt[2];
+        pack_host(P[3 * k].data(), l.Cin, l.Cout, l.kh, kKw, B, Bt);
         char name[32];
         snprintf(name, sizeof name, "deep1x1.conv%d_B", k + 1);
         rc = upload_f32(&l.B, B, name);
@@ -181,10 +182,8 @@ int dcs_deep1x1_create(dcs_ctx* ctx, int C, int tc, int F, const float* const* p
     if (rc == DCS_OK) {
         // 1x1: B[co][ci] = W[co][ci][0][0]
         const int n11 = kNf * nb_ok;
-        g->K11pad = (int)dcs_round_up(kNf, 16);
-        std::vector<float> B((size_t)dcs_cdiv(n11, 64) * 64 * g->K11pad, 0.f);
-        for (int co = 0; co < n11; ++co)
-            for (int ci = 0; ci < kNf; ++ci) B[(size_t)co * g->K11pad + ci] = P[18][(size_t)co * kNf + ci];
+        std::vector<float> B;
+        pack_host(P[18].data(), kNf, n11, 1, 1, B, nullptr);
         rc = upload_f32(&g->B11, B, "deep1x1.conv1x1_B");
         if (rc == DCS_OK) rc = upload_f32(&g->b11_0, P[19], "deep1x1.conv1x1_b");
         if (rc == DCS_OK) rc = upload_f32(&g->b11_1, P[20], "deep1x1.conv1x1_bias");
@@ -249,12 +248,9 @@ int forward_chunk(DcsDeep1x1Net* g, const float* x, int64_t nc, int64_t k_first,
     float* bufs[2] = {s.a, s.b};
     for (int k = 0; k < kLayers; ++k) {
         const D1Layer& l = g->L[k];
-        D1Args a{};
-        a.in = cur; a.Hi = l.Hi; a.Wi = l.Wi; a.Ci = l.Cinp;
-        a.Ho = l.Ho; a.Wo = l.Wo; a.Wq = l.Wo; a.kh = l.kh; a.ntap = kKw; a.stride = 2;
-        a.B = l.B; a.K = l.K; a.Kpad = l.Kpad; a.N = l.Cout; a.b0 = l.b0; a.b1 = l.b1;
+        D1Args a = forward_args(nc, l.Hi, l.Wi, l.Cinp, l.kh, kKw, 2, l.Cout);
+        a.in = cur; a.B = l.B; a.b0 = l.b0; a.b1 = l.b1;
         a.out = bufs[k & 1]; a.code_out = s.code[k]; a.Co = l.Coutp;
-        a.M = nc * l.Ho * l.Wo;
         launch<MODE_FWD>(ctx, a);
         cur = bufs[k & 1];
     }
@@ -263,11 +259,9 @@ int forward_chunk(DcsDeep1x1Net* g, const float* x, int64_t nc, int64_t k_first,
     // the masks read branch 0 alone; the raw output wants every branch the model holds
     const int nb_run = mask_mode == 2 ? g->nb : 1;
     {
-        D1Args a{};
-        a.in = cur; a.Hi = l6.Ho; a.Wi = l6.Wo; a.Ci = kNf;
-        a.Ho = l6.Ho; a.Wo = l6.Wo; a.Wq = l6.Wo; a.kh = 1; a.ntap = 1; a.stride = 1;
-        a.B = g->B11; a.K = kNf; a.Kpad = g->K11pad; a.N = kNf * nb_run; a.b0 = g->b11_0; a.b1 = g->b11_1;
-        a.out = s.g; a.M = m11;
+        D1Args a = forward_args(nc, l6.Ho, l6.Wo, kNf, 1, 1, 1, kNf * nb_run);
+        a.in = cur; a.B = g->B11; a.b0 = g->b11_0; a.b1 = g->b11_1;
+        a.out = s.g;
         launch<MODE_1X1>(ctx, a);
     }
     for (int br = 0; br < nb_run; ++br) {
@@ -276,12 +270,8 @@ int forward_chunk(DcsDeep1x1Net* g, const float* x, int64_t nc, int64_t k_first,
             const D1Layer& l = g->L[k];
             float* dst = bufs[k & 1];   // conv_k's input size; k = 0 writes p instead
             for (int par = 0; par < 2; ++par) {
-                D1Args a{};
-                a.in = cur; a.code = s.code[k]; a.Hi = l.Ho; a.Wi = l.Wo; a.Ci = l.Coutp;
-                a.Ho = l.Hi; a.Wo = l.Wi; a.Wq = (l.Wi - par + 1) / 2; a.par = par;
-                a.kh = l.kh; a.ntap = ntap_of(par);
-                a.B = l.Bt[par]; a.K = l.Kt[par]; a.Kpad = l.Ktpad[par]; a.N = l.Cin;
-                a.M = nc * l.Hi * a.Wq;
+                D1Args a = transposed_args(nc, l.Ho, l.Wo, l.Coutp, l.Hi, l.Wi, l.kh, kKw, par, l.Cin);
+                a.in = cur; a.code = s.code[k]; a.B = l.Bt[par];
                 if (a.M == 0) continue;
                 if (k > 0) {
                     a.out = dst; a.Co = l.Cinp;
@@ -380,5 +370,72 @@ int dcs_deep1x1_separate(DcsDeep1x1Net* g, dcs_stft* plan, const float* audio, i
     DCS_CHECK(dcs_launch_stft_inverse_f32_clips(plan, sep, rows * ld, unit, T * ld, ld, T, S, 1, scale, pcm, L));
     if (n_tiles_out) *n_tiles_out = n;
     if (n_frames_out) *n_frames_out = T;
+    return DCS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ test aids (include/dcs.h)
+extern "C" int dcs_debug_d1_conv(dcs_ctx* ctx, int mode, dcs_debug_d1_args* q) {
+    if (!ctx || !q) DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_conv: null argument");
+    if (mode == MODE_FWDC || mode == MODE_Q || mode == MODE_B11 || q->trainer_unit) return deep1x1_trainer_debug_conv(ctx, mode, q);
+    D1Args a;
+    DCS_CHECK(debug_conv_args(mode, q, &a));
+    DCS_ON_DEVICE(ctx->device);
+    switch (mode) {
+        case MODE_FWD: return debug_conv_run<MODE_FWD>(ctx, a);
+        case MODE_1X1: return debug_conv_run<MODE_1X1>(ctx, a);
+        case MODE_TR: return debug_conv_run<MODE_TR>(ctx, a);
+        default: return debug_conv_run<MODE_LAST>(ctx, a);
+    }
+}
+
+extern "C" int dcs_debug_d1_aux(dcs_ctx* ctx, int which, dcs_debug_d1_aux_args* q) {
+    if (!ctx || !q) DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: null argument");
+    if (which == DCS_D1_AUX_CODE_APPLY || which == DCS_D1_AUX_CODES_OUT || which == DCS_D1_AUX_PACK_DEVICE)
+        return deep1x1_trainer_debug_aux(ctx, which, q);
+    const int64_t big = (int64_t)1 << 30;
+    if (which == DCS_D1_AUX_TO_CL) {
+        if (q->n < 1 || q->plane < 1 || q->n > big || q->plane > big || q->n * q->plane > big)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: %lld tiles of %lld pixels", (long long)q->n, (long long)q->plane);
+        const int64_t px = q->n * q->plane;
+        if (dbg_bad(q->in, q->in_bytes, px * 16) || dbg_bad(q->out, q->out_bytes, px * 16)) DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: to_cl buffers");
+        DCS_ON_DEVICE(ctx->device);
+        hipLaunchKernelGGL(d1_to_cl_kernel, dim3((unsigned)dcs_cdiv(px, kThreads)), dim3(kThreads), 0, ctx->stream, (const float*)q->in,
+                           (float*)q->out, px, q->plane);
+    } else if (which == DCS_D1_AUX_MASK) {
+        if (q->n < 1 || q->plane < 1 || q->n > big || q->plane > big || q->n * q->plane > big || q->n_total < q->n || q->n_total > big ||
+            q->k_first < 0 || q->k_first + q->n > q->n_total || q->n_total * q->plane > big)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: tiles %lld + %lld of %lld, %lld pixels each", (long long)q->k_first, (long long)q->n,
+                     (long long)q->n_total, (long long)q->plane);
+        if (q->C < 1 || q->C > 64 || q->mix_n < 1 || q->mix_n > q->C || (q->mode != DCS_EPS_A && q->mode != DCS_EPS_B))
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: %d channels, mixture of %d, eps mode %d", q->C, q->mix_n, q->mode);
+        const int64_t px = q->n * q->plane;
+        if (dbg_bad(q->in, q->in_bytes, 4 * px * 4) || dbg_bad(q->in2, q->in2_bytes, q->C * px * 4) ||
+            dbg_bad(q->out, q->out_bytes, 4 * q->n_total * q->plane * 4))
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: mask buffers");
+        DCS_ON_DEVICE(ctx->device);
+        hipLaunchKernelGGL(d1_mask_kernel, dim3((unsigned)dcs_cdiv(px, kThreads)), dim3(kThreads), 0, ctx->stream, (const float*)q->in,
+                           (const float*)q->in2, (float*)q->out, q->n, q->n_total, q->k_first, q->C, q->plane, q->mode, q->mix_n);
+    } else if (which == DCS_D1_AUX_PACK_HOST) {
+        if ((q->kw != 1 && q->kw != kKw) || q->kh < 1 || q->kh > kDbgMaxKh || q->Cin < 1 || q->Cin > kDbgMaxCh || q->Cout < 1 ||
+            q->Cout > kDbgMaxCh)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: weights [%d][%d][%d][%d]", q->Cout, q->Cin, q->kh, q->kw);
+        const int64_t nw = (int64_t)q->Cout * q->Cin * q->kh * q->kw;
+        if (dbg_bad(q->in, q->in_bytes, nw * 4)) DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: W");
+        DCS_ON_DEVICE(ctx->device);
+        std::vector<float> W((size_t)nw), B, Bt[2];
+        DCS_HIP(hipMemcpy(W.data(), q->in, (size_t)nw * 4, hipMemcpyDeviceToHost));
+        pack_host(W.data(), q->Cin, q->Cout, q->kh, q->kw, B, Bt);
+        void* dst[3] = {q->out, q->out2, q->out3};
+        const int64_t have[3] = {q->out_bytes, q->out2_bytes, q->out3_bytes};
+        const std::vector<float>* src[3] = {&B, &Bt[0], &Bt[1]};
+        for (int i = 0; i < 3; ++i)
+            if (!src[i]->empty() && dbg_bad(dst[i], have[i], (int64_t)src[i]->size() * 4)) DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: operand %d", i);
+        for (int i = 0; i < 3; ++i)
+            if (!src[i]->empty()) DCS_HIP(hipMemcpy(dst[i], src[i]->data(), src[i]->size() * 4, hipMemcpyHostToDevice));
+    } else {
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: which = %d", which);
+    }
+    DCS_HIP(hipGetLastError());
+    DCS_HIP(hipStreamSynchronize(ctx->stream));
     return DCS_OK;
 }

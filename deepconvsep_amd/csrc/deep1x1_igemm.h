@@ -28,8 +28,10 @@ enum { MODE_FWD = 0, MODE_1X1 = 1, MODE_TR = 2, MODE_LAST = 3, MODE_FWDC = 4, MO
 struct D1Args {
     const float* in;            // channels-last [img][Hi][Wi][Ci]
     const uint8_t* code;        // MODE_TR / MODE_LAST / MODE_Q / MODE_B11: r'(pre) codes of `in`, same layout; MODE_FWDC: of `out`
-    int Hi, Wi, Ci;
-    int Ho, Wo, Wq, par;        // output rows / columns; this launch's columns q -> f = stride q (FWD) or 2 q + par (TR)
+    int Hi, Wi, Ci;             // Ci a multiple of 4; the contiguous run of K the kernel steps through -- ntap Ci floats (FWD: one
+                                // filter row of a pixel) or Ci floats (TR: one tap) -- holds at least 16: the walk (ki, kr) /
+                                // (ki, jt, c) starts at 4 (lane >> 4) without wrapping.  The graph's smallest are 20 and 32.
+    int Ho, Wo, Wq, par;       // output rows / columns; this launch's columns q -> f = stride q (FWD) or 2 q + par (TR)
     int kh, ntap, stride;
     const float* B;             // [Npad][Kpad] weights, one output channel's K contiguous, zero past K and past N
     int K, Kpad, N;
@@ -184,8 +186,36 @@ __global__ __launch_bounds__(kThreads) void d1_to_cl_kernel(const float* __restr
     *(f32x4*)(y + 4 * i) = f32x4{s[0], s[plane], s[2 * plane], s[3 * plane]};
 }
 
-int ntap_of(int par) { return par == 0 ? 3 : 2; }
 int nt_for(int N) { return N <= 16 ? 1 : (N <= 32 ? 2 : 4); }
+
+int npad_for(int N) { return dcs_cdiv(N, 16 * nt_for(N)) * 16 * nt_for(N); }   // rows of a B operand with N live ones
+
+// The geometry of a forward-type launch (MODE_FWD, MODE_1X1, MODE_FWDC): `images` images of [Hi][Wi][Cip] channels-last, a
+// valid kh x ntap convolution with column stride `stride` to N channels.  Operands, biases and outputs are the caller's.
+D1Args forward_args(int64_t images, int Hi, int Wi, int Cip, int kh, int ntap, int stride, int N) {
+    D1Args a{};
+    a.Hi = Hi; a.Wi = Wi; a.Ci = Cip;
+    a.Ho = Hi - kh + 1; a.Wo = (Wi - ntap) / stride + 1; a.Wq = a.Wo;
+    a.kh = kh; a.ntap = ntap; a.stride = stride;
+    a.K = kh * ntap * Cip; a.Kpad = (int)dcs_round_up(a.K, 16); a.N = N;
+    a.M = images * a.Ho * a.Wo;
+    return a;
+}
+
+// The geometry of one parity of a transposed-type launch (MODE_TR, MODE_LAST, MODE_Q, MODE_B11): the transpose of a valid
+// kh x kw convolution (kw == 5: column stride 2; kw == 1: the 1x1 layer, stride 1, parity 0 alone) that took [Ho][Wo] to
+// [Hi][Wi]; `in` is [images][Hi][Wi][Cip], the launch writes the output columns f = stride q + par, q < Wq.  M may be 0 (a
+// parity with no column): the caller skips that launch.
+D1Args transposed_args(int64_t images, int Hi, int Wi, int Cip, int Ho, int Wo, int kh, int kw, int par, int N) {
+    const int stride = kw == 1 ? 1 : 2;
+    D1Args a{};
+    a.Hi = Hi; a.Wi = Wi; a.Ci = Cip;
+    a.Ho = Ho; a.Wo = Wo; a.Wq = (Wo - par + stride - 1) / stride; a.par = par;
+    a.kh = kh; a.ntap = (kw - par + stride - 1) / stride;
+    a.K = kh * a.ntap * Cip; a.Kpad = (int)dcs_round_up(a.K, 16); a.N = N;
+    a.M = images * Ho * a.Wq;
+    return a;
+}
 
 template <int MODE>
 void launch(dcs_ctx* ctx, const D1Args& a) {

@@ -26,7 +26,7 @@
 // Internal parameter layout: W_l [kh i][5 j][Cin][Cout] = W[co][ci][kh-1-i][4-j] (b_l follows it: the ones row), W_7 [ci][co].
 #include <memory>
 
-#include "deep1x1_igemm.h"
+#include "deep1x1_debug.h"
 #include "train_ca.h"
 
 using namespace train;
@@ -126,7 +126,7 @@ struct Lay {
     uint8_t* code() const { return (uint8_t*)codef; }
 };
 
-int npad_of(int N) { return dcs_cdiv(N, 16 * d1::nt_for(N)) * 16 * d1::nt_for(N); }
+int npad_of(int N) { return d1::npad_for(N); }
 
 struct Deep1x1Trainer : dcs_trainer {
     Lay L[kL + 1];                // L[kL]: the 1x1 layer as a 1 x 1 convolution of its 200 live filters
@@ -190,11 +190,9 @@ struct Deep1x1Trainer : dcs_trainer {
 
     d1::D1Args fwd_args(int k, const float* in, float* out) {
         const Lay& l = L[k];
-        d1::D1Args a{};
-        a.in = in; a.Hi = l.Hi; a.Wi = l.Wi; a.Ci = l.Cinp;
-        a.Ho = l.Ho; a.Wo = l.Wo; a.Wq = l.Wo; a.kh = l.kh; a.ntap = k == kL ? 1 : kKw; a.stride = k == kL ? 1 : 2;
-        a.B = l.Bf; a.K = l.K; a.Kpad = l.Kpad; a.N = l.Cout;
-        a.out = out; a.Co = l.Coutp; a.M = l.px;
+        d1::D1Args a = d1::forward_args(B, l.Hi, l.Wi, l.Cinp, l.kh, k == kL ? 1 : kKw, k == kL ? 1 : 2, l.Cout);
+        a.in = in; a.B = l.Bf;
+        a.out = out; a.Co = l.Coutp;
         return a;
     }
 
@@ -202,12 +200,8 @@ struct Deep1x1Trainer : dcs_trainer {
     void transposed(int k, const float* in, float* out, bool q) {
         const Lay& l = L[k];
         for (int par = 0; par < 2; ++par) {
-            d1::D1Args a{};
-            a.in = in; a.code = l.code(); a.Hi = l.Ho; a.Wi = l.Wo; a.Ci = l.Coutp;
-            a.Ho = l.Hi; a.Wo = l.Wi; a.Wq = (l.Wi - par + 1) / 2; a.par = par;
-            a.kh = l.kh; a.ntap = d1::ntap_of(par);
-            a.B = l.Bt[par]; a.K = l.Kt[par]; a.Kpad = l.Ktpad[par]; a.N = l.Cin;
-            a.M = (int64_t)B * l.Hi * a.Wq;
+            d1::D1Args a = d1::transposed_args(B, l.Ho, l.Wo, l.Coutp, l.Hi, l.Wi, l.kh, kKw, par, l.Cin);
+            a.in = in; a.code = l.code(); a.B = l.Bt[par];
             if (a.M == 0) continue;
             a.out = out; a.Co = l.Cinp;
             if (q) {
@@ -284,11 +278,9 @@ struct Deep1x1Trainer : dcs_trainer {
         Lay& l7 = L[kL];
         float* ds = l6.X + l6.slot;
         {
-            d1::D1Args a{};
-            a.in = ds; a.code = l7.code(); a.Hi = l7.Ho; a.Wi = l7.Wo; a.Ci = l7.Coutp;
-            a.Ho = l7.Hi; a.Wo = l7.Wi; a.Wq = l7.Wi; a.kh = 1; a.ntap = 1;
-            a.B = l7.Bt[0]; a.K = l7.Kt[0]; a.Kpad = l7.Ktpad[0]; a.N = l7.Cin;
-            a.out = l6.D; a.Co = l7.Cinp; a.M = l7.px;
+            d1::D1Args a = d1::transposed_args(B, l7.Ho, l7.Wo, l7.Coutp, l7.Hi, l7.Wi, 1, 1, 0, l7.Cin);
+            a.in = ds; a.code = l7.code(); a.B = l7.Bt[0];
+            a.out = l6.D; a.Co = l7.Cinp;
             d1::launch<d1::MODE_B11>(ctx, a);
         }
         apply_code(l7, ds, true);
@@ -380,5 +372,71 @@ int deep1x1_trainer_new(int time_context, int F, int batch, const int64_t* shape
     std::unique_ptr<Deep1x1Trainer> t(new Deep1x1Trainer());
     t->shape(time_context, F, batch, nb);
     *out = t.release();
+    return DCS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ test aids (include/dcs.h)
+int deep1x1_trainer_debug_conv(dcs_ctx* ctx, int mode, dcs_debug_d1_args* q) {
+    d1::D1Args a;
+    DCS_CHECK(d1::debug_conv_args(mode, q, &a));
+    DCS_ON_DEVICE(ctx->device);
+    switch (mode) {
+        case d1::MODE_FWD: return d1::debug_conv_run<d1::MODE_FWD>(ctx, a);
+        case d1::MODE_TR: return d1::debug_conv_run<d1::MODE_TR>(ctx, a);
+        case d1::MODE_FWDC: return d1::debug_conv_run<d1::MODE_FWDC>(ctx, a);
+        case d1::MODE_Q: return d1::debug_conv_run<d1::MODE_Q>(ctx, a);
+        case d1::MODE_B11: return d1::debug_conv_run<d1::MODE_B11>(ctx, a);
+        default: DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_conv: the trainer launches no mode %d", mode);
+    }
+}
+
+int deep1x1_trainer_debug_aux(dcs_ctx* ctx, int which, dcs_debug_d1_aux_args* q) {
+    using d1::dbg_bad;
+    const int64_t big = (int64_t)1 << 30;
+    if (which == DCS_D1_AUX_CODE_APPLY) {
+        if (q->rows < 1 || q->rows > big || q->Cp < 1 || q->Cp > kThreads || q->C < 1 || q->C > q->Cp || q->per < 1 || q->per > big ||
+            q->nsum < 1 || q->nsum > 65536 || q->rows * q->Cp > big)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: %lld rows of %d (%d live) channels, %d workgroups of %lld rows", (long long)q->rows,
+                     q->Cp, q->C, q->nsum, (long long)q->per);
+        if (dbg_bad(q->out, q->out_bytes, q->rows * q->Cp * 4) || dbg_bad(q->in2, q->in2_bytes, q->rows * q->Cp) ||
+            (q->out2 && dbg_bad(q->out2, q->out2_bytes, (int64_t)q->nsum * q->C * 4)))
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: code_apply buffers");
+        DCS_ON_DEVICE(ctx->device);
+        hipLaunchKernelGGL(code_apply_kernel, dim3((unsigned)q->nsum), dim3(kThreads), 0, ctx->stream, (float*)q->out,
+                           (const uint8_t*)q->in2, q->rows, q->Cp, q->C, q->per, (float*)q->out2);
+    } else if (which == DCS_D1_AUX_CODES_OUT) {
+        if (q->n < 1 || q->n > big || q->hw < 1 || q->hw > big || q->Cp < 1 || q->Cp > d1::kDbgMaxCh || q->C < 1 || q->C > q->Cp ||
+            q->n * q->hw > big / q->Cp)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: %lld images of %lld pixels, %d of %d channels", (long long)q->n, (long long)q->hw, q->C,
+                     q->Cp);
+        const int64_t cnt = q->n * q->C * q->hw;
+        if (dbg_bad(q->in, q->in_bytes, q->n * q->hw * q->Cp) || dbg_bad(q->out, q->out_bytes, cnt * 4))
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: codes_out buffers");
+        DCS_ON_DEVICE(ctx->device);
+        hipLaunchKernelGGL(codes_out_kernel, dim3((unsigned)dcs_cdiv(cnt, kThreads)), dim3(kThreads), 0, ctx->stream,
+                           (const uint8_t*)q->in, (float*)q->out, cnt, q->hw, q->C, q->Cp);
+    } else if (which == DCS_D1_AUX_PACK_DEVICE) {
+        if ((q->kw != 1 && q->kw != kKw) || q->kh < 1 || q->kh > d1::kDbgMaxKh || q->Cin < 1 || q->Cin > d1::kDbgMaxCh || q->Cout < 1 ||
+            q->Cout > d1::kDbgMaxCh)
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: weights [%d][%d][%d][%d]", q->kh, q->kw, q->Cin, q->Cout);
+        PackArgs a{};
+        a.kw = q->kw; a.Cin = q->Cin; a.Cinp = (int)dcs_round_up(q->Cin, 4); a.Cout = q->Cout; a.Coutp = (int)dcs_round_up(q->Cout, 4);
+        a.Kpad = (int)dcs_round_up(q->kh * q->kw * a.Cinp, 16);
+        const int nt0 = (q->kw + 1) / 2, nt1 = q->kw / 2;
+        a.Ktpad0 = (int)dcs_round_up(q->kh * nt0 * a.Coutp, 16);
+        a.Ktpad1 = (int)dcs_round_up(q->kh * nt1 * a.Coutp, 16);
+        a.n = (int64_t)q->kh * q->kw * q->Cin * q->Cout;
+        if (dbg_bad(q->in, q->in_bytes, a.n * 4) || dbg_bad(q->out, q->out_bytes, (int64_t)npad_of(q->Cout) * a.Kpad * 4) ||
+            dbg_bad(q->out2, q->out2_bytes, (int64_t)npad_of(q->Cin) * a.Ktpad0 * 4) ||
+            (nt1 > 0 && dbg_bad(q->out3, q->out3_bytes, (int64_t)npad_of(q->Cin) * a.Ktpad1 * 4)))
+            DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: pack buffers");
+        a.W = (const float*)q->in; a.Bf = (float*)q->out; a.Bt0 = (float*)q->out2; a.Bt1 = (float*)q->out3;
+        DCS_ON_DEVICE(ctx->device);
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)dcs_cdiv(a.n, kThreads)), dim3(kThreads), 0, ctx->stream, a);
+    } else {
+        DCS_FAIL(DCS_EINVAL, "dcs_debug_d1_aux: which = %d", which);
+    }
+    DCS_HIP(hipGetLastError());
+    DCS_HIP(hipStreamSynchronize(ctx->stream));
     return DCS_OK;
 }

@@ -1176,6 +1176,79 @@ DCS_API int dcs_debug_dsd_stage(dcs_model* m, int stage, dcs_debug_dsd_args* arg
 #define DCS_DSD_K_LAT_FINAL 26            /* lat_final_kernel<MODE>: 26 + MODE */
 DCS_API int dcs_debug_dsd_last_kernel(const dcs_model* m, int* codes, int64_t* params);
 
+/* Test aids for the kernels of the deep score-informed graph build_ca_1x1 (csrc/deep1x1_igemm.h, deep1x1.hip, train_deep1x1.hip;
+ * tests/test_gpu_d1_kernels.py); no reference counterpart.  dcs_debug_d1_conv runs ONE d1::launch<MODE> -- one instance of
+ * d1_igemm_kernel<MODE, NT> -- on the caller's buffers for a geometry the caller gives; no model is needed.  The launch
+ * arguments are filled by the helpers the separator and the trainer fill theirs with (d1::forward_args / transposed_args), and
+ * the launch comes from the translation unit that launches that mode in production: DCS_D1_FWD, _1X1, _TR, _LAST from
+ * deep1x1.hip (with trainer_unit != 0, FWD and TR from the trainer's copy), DCS_D1_FWDC, _Q, _B11 from train_deep1x1.hip.
+ *   forward type (FWD, 1X1, FWDC)  in [images][Hi][Wi][Ci] channels-last; a valid kh x kw convolution with column stride
+ *                                  `stride`; Ho = Hi - kh + 1 and Wo = (Wi - kw) / stride + 1 are returned
+ *   transposed type (TR, LAST, Q, B11)  the transpose of the valid kh x kw convolution (kw == 5: stride 2; kw == 1: stride 1,
+ *                                  par 0) that took [Ho][Wo] to [Hi][Wi]; in and code [images][Hi][Wi][Ci]; one launch writes the
+ *                                  output columns of parity par.  Ho, Wo are the caller's: Hi == Ho - kh + 1, Wi == (Wo - kw) / stride + 1
+ * B is [Npad][Kpad] floats, Npad = N rounded up to 16 NT (NT = 1, 2, 4 for N <= 16, <= 32, above), Kpad = K rounded up to 16,
+ * K = kh ntap Ci, zero past K and past row N.  Outputs as D1Args documents them: FWD / FWDC / B11 [M][Co]; TR
+ * [images][Ho][Wo][Co]; 1X1 [N / 200 branches][M][200]; Q [images][N][Ho][Wo]; LAST [ch_off + N][n_total][Ho][Wo], this call's
+ * images from tile k_first.  code: r'(pre) bytes 0 / 1 / 2 of `in` (transposed type) or of `out` (FWDC, [M][Co]).
+ * DCS_EINVAL, and nothing launched, for a null pointer the mode uses, a pointer not aligned to 16 bytes, a byte count below what
+ * the geometry reads or writes, M == 0 (a parity without a column), a channel pitch (Ci, Co) that is not a multiple of 4,
+ * Co below N or above Npad, a contiguous K run (kw Ci floats of a forward type, Ci floats of a transposed type) below the 16
+ * that D1Args requires, and geometry out of range.  One stream synchronisation per call. */
+#define DCS_D1_FWD 0
+#define DCS_D1_1X1 1
+#define DCS_D1_TR 2
+#define DCS_D1_LAST 3
+#define DCS_D1_FWDC 4
+#define DCS_D1_Q 5
+#define DCS_D1_B11 6
+typedef struct dcs_debug_d1_args {
+    int32_t images, Hi, Wi, Ci;
+    int32_t Ho, Wo;                       /* transposed type: given; forward type: returned */
+    int32_t kh, kw, stride, par;
+    int32_t N, Co;
+    int64_t n_total, k_first; int32_t ch_off;     /* LAST */
+    int32_t trainer_unit;
+    const float* in; int64_t in_bytes;
+    const uint8_t* code; int64_t code_bytes;
+    const float* B; int64_t B_bytes;
+    const float* b0; int64_t b0_bytes;    /* FWD, 1X1, LAST, Q: N floats */
+    const float* b1; int64_t b1_bytes;    /* FWD, 1X1: N floats */
+    float* out; int64_t out_bytes;
+    uint8_t* code_out; int64_t code_out_bytes;    /* FWD: [M][Co] bytes */
+    int32_t nt, grid_x, grid_y, K, Kpad, Wq;      /* returned: the instance, its grid and the launch's K, Kpad, Wq */
+    int64_t M;                            /* returned */
+} dcs_debug_d1_args;
+DCS_API int dcs_debug_d1_conv(dcs_ctx* ctx, int mode, dcs_debug_d1_args* args);
+/* The small kernels around it and the two weight packers, with the same checks (every pointer a device pointer):
+ *   DCS_D1_AUX_TO_CL       d1_to_cl_kernel: in [n][4][plane] -> out [n][plane][4]
+ *   DCS_D1_AUX_MASK        d1_mask_kernel: in p [4][n][plane], in2 x [n][C][plane] -> out [4][n_total][plane] from tile k_first;
+ *                          mode DCS_EPS_A / DCS_EPS_B, the mixture the sum of the first mix_n channels of x
+ *   DCS_D1_AUX_CODE_APPLY  code_apply_kernel on nsum workgroups of `per` rows: out [rows][Cp] *= 0.5 in2 (code bytes [rows][Cp])
+ *                          in place; out2 (nullable) [nsum][C] the column sums of out as it was
+ *   DCS_D1_AUX_CODES_OUT   codes_out_kernel: in code bytes [n][hw][Cp] -> out [n][C][hw] floats
+ *   DCS_D1_AUX_PACK_HOST   the separator's host packer: in W [Cout][Cin][kh][kw] (Lasagne) -> out B, out2 Bt[0], out3 Bt[1],
+ *                          written whole (pads zero); kw 5 or 1 (kw == 1: out3 unused)
+ *   DCS_D1_AUX_PACK_DEVICE the trainer's pack_kernel: in W [kh][kw][Cin][Cout] (internal) -> the live elements of out, out2, out3;
+ *                          everything else is left as it was */
+#define DCS_D1_AUX_TO_CL 0
+#define DCS_D1_AUX_MASK 1
+#define DCS_D1_AUX_CODE_APPLY 2
+#define DCS_D1_AUX_CODES_OUT 3
+#define DCS_D1_AUX_PACK_HOST 4
+#define DCS_D1_AUX_PACK_DEVICE 5
+typedef struct dcs_debug_d1_aux_args {
+    int64_t n, plane, n_total, k_first, rows, per, hw;
+    int32_t C, Cp, mode, mix_n, nsum;
+    int32_t Cin, Cout, kh, kw;
+    const void* in; int64_t in_bytes;
+    const void* in2; int64_t in2_bytes;
+    void* out; int64_t out_bytes;
+    void* out2; int64_t out2_bytes;
+    void* out3; int64_t out3_bytes;
+} dcs_debug_d1_aux_args;
+DCS_API int dcs_debug_d1_aux(dcs_ctx* ctx, int which, dcs_debug_d1_aux_args* args);
+
 #ifdef __cplusplus
 }
 #endif
