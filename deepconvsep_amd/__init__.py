@@ -12,7 +12,8 @@ from .runtime import mwf
 from .resample import ResampleCounts, Resampler, StreamResampler, resample
 from .separation import (PredictFunction, Separator, blackmanharris, generate_overlapadd, load_model,
                          overlapadd, overlapadd_multi, save_model, train_auto)
-from .streaming import ChannelStreamSeparator, RateStream, ScoreStreamSeparator, StreamCounts, StreamSeparator
+from .streaming import (ChannelStreamSeparator, RateStream, ScoreStreamSeparator, StereoStreamSeparator, StreamCounts,
+                        StreamSeparator)
 from .training import FeatureWindows, Trainer, glorot_init
 from .stereo_training import StereoFeatureWindows, StereoTrainer
 from .score_training import ScoreFeatureWindows, ScoreTrainer
@@ -24,6 +25,6 @@ __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
            "Separator", "blackmanharris", "generate_overlapadd", "load_model", "save_model", "overlapadd",
            "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "mwf", "Resampler", "resample", "StreamCounts", "StreamSeparator",
-           "ChannelStreamSeparator", "ScoreStreamSeparator", "RateStream", "ResampleCounts", "StreamResampler", "Trainer", "FeatureWindows", "glorot_init",
+           "ChannelStreamSeparator", "ScoreStreamSeparator", "StereoStreamSeparator", "RateStream", "ResampleCounts", "StreamResampler", "Trainer", "FeatureWindows", "glorot_init",
            "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features",
            "ScoreInformedRenderedWindows", "render_score_informed_features"]

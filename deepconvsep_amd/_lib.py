@@ -143,6 +143,10 @@ def load():
     proto("dcs_stream_create_channels", i32, vp, i32, i32, i32, i32, i32, i32, f32, POINTER(c_double), i64, POINTER(vp))
     proto("dcs_stream_push_channels", i32, vp, vp, i64, i64, i32, vp, i64, POINTER(i64), vp, vp, i64, i64, POINTER(i64))
     proto("dcs_stream_pull_channels", i32, vp, vp, i64, i64, vp, i64, i64, i64, POINTER(i64), vp, i64, i64, i64)
+    proto("dcs_model_forward_stereo", i32, vp, vp, i64, vp)
+    proto("dcs_stream_create_stereo", i32, vp, i32, i32, i32, i32, i32, f32, POINTER(c_double), i64, POINTER(vp))
+    proto("dcs_stream_push_stereo", i32, vp, vp, i64, i64, i32, vp, i64, POINTER(i64), vp, vp, i64, i64, POINTER(i64))
+    proto("dcs_stream_pull_stereo", i32, vp, vp, i64, i64, i64, i64, vp, i64, i64, i64, POINTER(i64), vp, i64, i64, i64)
     proto("dcs_stream_create_score", i32, vp, i32, i32, i32, i32, i32, f32, POINTER(c_double), i64, POINTER(c_double), i32, i32,
           i32, i32, i32, POINTER(vp))
     proto("dcs_resample_stream_create", i32, vp, i32, i64, POINTER(vp))

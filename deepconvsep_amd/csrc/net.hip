@@ -545,6 +545,22 @@ int dsd_forward_tiles(dcs_model* m, const float* tiles, int64_t n, int mask_mode
     return dcs_launch_dsd_final(m->ctx, a, false);
 }
 
+// The two-channel sibling: tiles [n][tc][C][ld] in the row layout of dcs_separate_stereo (row = C * ld floats, the K axis pack_dsd
+// packed conv1 for: K1 = C * ld, zero weight rows under the pad columns), every tile encoded from its own tc rows; the final
+// kernel unfolded and raw, four branches, the bias per (source, channel): out [S][n tc][C ld].
+int dsd_forward_tiles_stereo(dcs_model* m, const float* tiles, int64_t n, float* out) {
+    const int tc = m->tc;
+    const int64_t ld = dcs_round_up(m->F, 4), row = m->C * ld;
+    const int64_t rows1 = n * tc, rows2 = n * m->d.h2;
+    DCS_CHECK(m->ws.ensure(dsd_scratch_bytes(m, n, rows1, rows2)));
+    DsdScratch w;
+    dsd_carve(m, (char*)m->ws.ptr, n, rows1, rows2, &w);
+    DCS_CHECK(dsd_encode(m, tiles, row, true, 1.f, n, tc, false, w));
+    DCS_CHECK(ensure_rise(m, 1));
+    const DsdFinalArgs a = dsd_final_args(m, w.G, tiles, row, 1.f, out, n * tc * row, row, n, n * tc, 0, 2);
+    return dcs_launch_dsd_final(m->ctx, a, false);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -859,6 +875,17 @@ extern "C" int dcs_model_forward_masked(dcs_model* m, const float* tiles_d, int6
 
 extern "C" int dcs_model_forward(dcs_model* m, const float* tiles_d, int64_t n, int tie_mode, float* p_d) {
     return forward_any(m, tiles_d, n, 2, tie_mode, p_d);
+}
+
+extern "C" int dcs_model_forward_stereo(dcs_model* m, const float* tiles_d, int64_t n, float* p_d) {
+    if (!m || !tiles_d || !p_d) DCS_FAIL(DCS_EINVAL, "dcs_model_forward_stereo: null argument");
+    if (m->arch != DCS_ARCH_DSD_ILD) DCS_FAIL(DCS_EINVAL, "dcs_model_forward_stereo: not a stereo (ILD) model");
+    if (n < 0 || n > 0x7fffffff / m->tc) DCS_FAIL(DCS_EINVAL, "dcs_model_forward_stereo: %lld tiles", (long long)n);
+    if (((uintptr_t)tiles_d & 15) || ((uintptr_t)p_d & 15))
+        DCS_FAIL(DCS_EINVAL, "dcs_model_forward_stereo: tiles and p must be 16-byte aligned");
+    if (n == 0) return DCS_OK;
+    DCS_ON_DEVICE(m->ctx->device);
+    return dsd_forward_tiles_stereo(m, tiles_d, n, p_d);
 }
 
 // ------------------------------------------------------------------------------------------------ fused path

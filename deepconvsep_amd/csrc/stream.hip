@@ -23,6 +23,12 @@
 // per frame, from the few note rows that can meet the push's frames), the tiles carry one channel M_j * (scale * mag) per
 // instrument and the fold multiplies acc_s with the score-informed mixture formed from the two rings.  Everything else is the
 // mono stream.
+//
+// A STEREO stream (dcs_stream_create_stereo) feeds the stereo (ILD) graph, which sees the C channels themselves and answers per
+// (source, channel): C rows of samples, magnitudes and phases and no down-mix, the tiles carry the channels of a frame side by
+// side (the row layout dcs_model_forward_stereo reads), the ring of p holds every (source, channel) once and the fold forms the
+// stereo trainer's mask per channel -- den over the sources of THAT channel plus 1e-13 -- and adds the trainer's constant to
+// the estimate.  Append, frames, inverse and gather are the kernels above with C rows.
 #include "dcs_internal.h"
 #include "fft_frame.h"
 #include "chanmask.h"
@@ -107,6 +113,25 @@ __global__ __launch_bounds__(kThreads) void stream_tiles_kernel(const float* __r
         for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = scale * src[f];
     } else {
         for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ push (stereo): the tiles that became ready
+// tiles[i][j][c][:] = scale * mag[c][(k0 + i) st + j][:] for channel c = blockIdx.y of the magnitude ring [C][rf][F], rows of
+// ldt = round_up(F, 4) floats: zero for rows >= T and for the columns F .. ldt - 1 (conv1's K axis runs over them)
+__global__ __launch_bounds__(kThreads) void stream_stereo_tiles_kernel(const float* __restrict__ mag_ring, int64_t rf, int F,
+                                                                       int ldt, int tc, int st, int64_t k0, int64_t T, float scale,
+                                                                       float* __restrict__ tiles) {
+    const int64_t i = blockIdx.x / tc;
+    const int j = (int)(blockIdx.x - i * tc);
+    const int c = blockIdx.y, C = gridDim.y;
+    const int64_t t = (k0 + i) * st + j;
+    float* dst = tiles + ((i * tc + j) * C + c) * (int64_t)ldt;
+    if (t < T) {
+        const float* src = mag_ring + (c * rf + ring_slot(t, rf)) * (int64_t)F;
+        for (int f = threadIdx.x; f < ldt; f += kThreads) dst[f] = f < F ? scale * src[f] : 0.f;
+    } else {
+        for (int f = threadIdx.x; f < ldt; f += kThreads) dst[f] = 0.f;
     }
 }
 
@@ -266,6 +291,79 @@ __global__ __launch_bounds__(kThreads) void stream_fold_kernel(
     }
 }
 
+// ------------------------------------------------------------------------------------------ pull (stereo): p of the new tiles into its ring
+// Row blockIdx.x = i tc + j of (source blockIdx.z, channel blockIdx.y): F floats from the caller's strides into the compact
+// ring [S][C][rp][tc][F].
+__global__ __launch_bounds__(kThreads) void stream_keep_p_stereo_kernel(const float* __restrict__ p, int64_t p_src_stride,
+                                                                        int64_t p_ch_stride, int64_t p_ld, int64_t k0, int tc, int F,
+                                                                        float* __restrict__ p_ring, int64_t rp) {
+    const int64_t i = blockIdx.x / tc;
+    const int j = (int)(blockIdx.x - i * tc);
+    const int c = blockIdx.y, C = gridDim.y, s = blockIdx.z;
+    const float* src = p + s * p_src_stride + c * p_ch_stride + (int64_t)blockIdx.x * p_ld;
+    float* dst = p_ring + ((((int64_t)s * C + c) * rp + ring_slot(k0 + i, rp)) * tc + j) * (int64_t)F;
+    for (int f = threadIdx.x; f < F; f += kThreads) dst[f] = src[f];
+}
+
+// ------------------------------------------------------------------------------------------ pull (stereo): fold + apply
+// stream_fold_kernel's walk over the covering tiles for channel c = blockIdx.z of gridDim.z, with the stereo trainer's mask
+// (dsd.hip MODE 3: den = ((p_0c + p_1c) + ...) + 1e-13f, m_s = p_sc / den) from the ring [S][C][rp][tc][F], and
+// est[c][s][blockIdx.x][f] = acc_sc * mag[c][t][f] + c0: product and sum each rounded once.  Rows past the last tile are zeros
+// without c0.
+__global__ __launch_bounds__(kThreads) void stream_fold_stereo_kernel(
+    const float* __restrict__ p_ring, int64_t rp, int64_t n, int S, int tc, int ov, int F, const float* __restrict__ rise,
+    const float* __restrict__ mag_ring, int64_t rf, int64_t t0, float c0, float* __restrict__ est, int64_t est_src_stride,
+    float* __restrict__ est_out, int64_t out_ch_stride, int64_t out_src_stride, int64_t ld) {
+    const int f = blockIdx.y * kThreads + threadIdx.x;
+    if (f >= F) return;
+    const int c = blockIdx.z, C = gridDim.z;
+    const int64_t t = t0 + blockIdx.x;
+    const int st = tc - ov;
+    const int64_t tile_elems = (int64_t)tc * F, src_stride = C * rp * tile_elems;
+    const float* pc = p_ring + c * rp * tile_elems;
+    const float eps_r = 1e-13f;
+    int64_t k0 = (t < ov) ? 0 : (t - ov) / st;
+    if (k0 > n - 1) k0 = n - 1;
+    const int64_t j0 = (n > 0) ? t - k0 * st : tc;
+    const bool covered = j0 < tc;
+
+    float acc[kMaxSources];
+#pragma unroll
+    for (int s = 0; s < kMaxSources; ++s) acc[s] = 0.f;
+    if (covered) {
+        for (int64_t k = k0; k < n && k * st <= t; ++k) {
+            const int j = (int)(t - k * st);
+            const int64_t r = ring_slot(k, rp) * tile_elems + (int64_t)j * F + f;
+            float p[kMaxSources];
+            float den = 0.f;
+#pragma unroll
+            for (int s = 0; s < kMaxSources; ++s) {
+                p[s] = s < S ? pc[s * src_stride + r] : 0.f;
+                if (s < S) den = s == 0 ? p[s] : __fadd_rn(den, p[s]);
+            }
+            den = __fadd_rn(den, eps_r);
+#pragma unroll
+            for (int s = 0; s < kMaxSources; ++s) p[s] = __fdiv_rn(p[s], den);
+            if (k == k0) {
+#pragma unroll
+                for (int s = 0; s < kMaxSources; ++s) acc[s] = p[s];
+            } else {
+                const float down = rise[ov - 1 - j], up = rise[j];
+#pragma unroll
+                for (int s = 0; s < kMaxSources; ++s) acc[s] = fmaf(down, acc[s], __fmul_rn(up, p[s]));   // as stream_fold_kernel
+            }
+        }
+    }
+    const float mg = mag_ring[(c * rf + ring_slot(t, rf)) * (int64_t)F + f];
+#pragma unroll
+    for (int s = 0; s < kMaxSources; ++s)
+        if (s < S) {
+            const float e = covered ? __fadd_rn(__fmul_rn(acc[s], mg), c0) : 0.f;
+            est[(c * S + s) * est_src_stride + (int64_t)blockIdx.x * F + f] = e;
+            if (est_out) est_out[c * out_ch_stride + s * out_src_stride + (int64_t)blockIdx.x * ld + f] = e;
+        }
+}
+
 // ------------------------------------------------------------------------------------------ pull: one frame of one source back to time
 // y_n = w * irfft(est[c][s][n] sqrt(N) exp(j phase[c][n])) into slot n mod rt of the time-frame ring [rt][C][S][N]: the packed real-inverse
 // pre-processing, transform and window product of istft_fused_kernel (fft.hip), term for term, for ONE frame -- the sum over
@@ -357,7 +455,8 @@ struct dcs_stream {
     // C: the signal channels of a channel stream, 0 for the mono stream; rows of samples and magnitudes (the down-mix last);
     // nch: the rows that keep their phase and come back as stems (the mono stream's one row is both)
     int C = 0, rows = 1, nch = 1;
-    float scale = 1.f;
+    bool stereo = false;       // a stereo stream: C rows, no down-mix, p per (source, channel)
+    float scale = 1.f, c0 = 0.f;   // c0: the stereo trainer's constant on the unscaled magnitudes, 1e-13f / scale
     int64_t max_push = 0;
     // ring lengths: samples; frames a push can complete, the end included; tiles it can return; frame rows; tiles of p; frames
     // a pull can fold; time-domain frames
@@ -436,9 +535,10 @@ int score_convert(const char* who, const ScoreSpec& sc, int F, std::vector<Score
     return DCS_OK;
 }
 
-// C = 0: the mono stream; sc != nullptr: a score stream
+// C = 0: the mono stream; sc != nullptr: a score stream; stereo: C rows and no down-mix
 int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, int eps_mode,
-                  float scale, const double* rise_h, int64_t max_push, dcs_stream** out, const ScoreSpec* sc = nullptr) {
+                  float scale, const double* rise_h, int64_t max_push, dcs_stream** out, const ScoreSpec* sc = nullptr,
+                  bool stereo = false) {
     if (!plan || !rise_h || !out) DCS_FAIL(DCS_EINVAL, "%s: null argument", who);
     if (S < 1 || S > kMaxSources) DCS_FAIL(DCS_EINVAL, "%s: %d sources (1 .. %d)", who, S, kMaxSources);
     if (overlap < 1 || overlap >= time_context) DCS_FAIL(DCS_EINVAL, "%s: overlap %d not in [1, %d)", who, overlap, time_context);
@@ -474,7 +574,9 @@ int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_contex
     s->ctx = plan->ctx;
     s->S = S; s->tc = time_context; s->ov = overlap; s->st = time_context - overlap;
     s->tiler = tiler; s->eps_mode = eps_mode; s->scale = scale;
-    s->C = C; s->rows = C ? C + 1 : 1; s->nch = C ? C : 1;
+    s->C = C; s->rows = stereo ? C : (C ? C + 1 : 1); s->nch = C ? C : 1;
+    s->stereo = stereo;
+    if (stereo) s->c0 = 1e-13f / scale;
     s->N = N; s->hop = hop; s->F = H + 1; s->max_push = max_push;
     s->cap = N + max_push;                                            // a new frame reaches back less than N samples before the push
     s->fp = (max_push + H + hop - 1) / hop + 3;                       // T - A <= (L - P + N/2) / hop + 3 at the end; fewer mid-stream
@@ -489,7 +591,7 @@ int stream_create(const char* who, dcs_stft* plan, int S, int C, int time_contex
         {&s->samples, s->rows * s->cap, "stream.samples"},
         {&s->mag, s->rows * s->rf * F, "stream.mag"},
         {&s->phase, s->nch * s->rf * F, "stream.phase"},
-        {&s->p, (int64_t)S * s->rp * time_context * F, "stream.p"},
+        {&s->p, (int64_t)S * (stereo ? C : 1) * s->rp * time_context * F, "stream.p"},
         {&s->est, (int64_t)s->nch * S * s->ff * F, "stream.est"},
         {&s->tf, s->rt * s->nch * S * N, "stream.tf"},
         {&s->rise, overlap, "stream.rise"},
@@ -560,6 +662,14 @@ extern "C" int dcs_stream_create_channels(dcs_stft* plan, int S, int C, int time
         DCS_FAIL(DCS_EINVAL, "dcs_stream_create_channels: %d channels (1 .. %d)", C, kMaxChannels);
     return stream_create("dcs_stream_create_channels", plan, S, C, time_context, overlap, tiler, eps_mode, scale, rise_h, max_push,
                          out);
+}
+
+extern "C" int dcs_stream_create_stereo(dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, float scale,
+                                        const double* rise_h, int64_t max_push, dcs_stream** out) {
+    if (C < 1 || C > kMaxChannels) DCS_FAIL(DCS_EINVAL, "dcs_stream_create_stereo: %d channels (1 .. %d)", C, kMaxChannels);
+    if (scale == 0.f) DCS_FAIL(DCS_EINVAL, "dcs_stream_create_stereo: scale 0");
+    return stream_create("dcs_stream_create_stereo", plan, S, C, time_context, overlap, tiler, DCS_EPS_B, scale, rise_h, max_push,
+                         out, nullptr, true);
 }
 
 extern "C" int dcs_stream_create_score(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
@@ -663,6 +773,12 @@ int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t ro
                            tiles_d);
         tm.done();
         DCS_HIP(hipGetLastError());
+    } else if (n_tiles > 0 && s->stereo) {
+        DcsTimer tm(s->ctx, DCS_TAG_TILE);
+        hipLaunchKernelGGL(stream_stereo_tiles_kernel, dim3((unsigned)(n_tiles * s->tc), (unsigned)s->C), dim3(kThreads), 0, q,
+                           (const float*)s->mag, s->rf, s->F, (int)dcs_round_up(s->F, 4), s->tc, s->st, s->K, A, s->scale, tiles_d);
+        tm.done();
+        DCS_HIP(hipGetLastError());
     } else if (n_tiles > 0) {
         DcsTimer tm(s->ctx, DCS_TAG_TILE);
         const float* mix = s->mag + (int64_t)(s->rows - 1) * s->rf * s->F;     // the down-mix: the last row
@@ -684,18 +800,34 @@ int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t ro
     return DCS_OK;
 }
 
-// both kinds of pull: channel c of the samples at + c pcm_ch_stride, of the estimates at + c est_ch_stride
+// every kind of pull: channel c of the samples at + c pcm_ch_stride, of the estimates at + c est_ch_stride; p_ch_stride and
+// p_ld are read for a stereo stream alone
 int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
                 int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_ch_stride,
-                int64_t est_src_stride, int64_t ld) {
+                int64_t est_src_stride, int64_t ld, int64_t p_ch_stride = 0, int64_t p_ld = 0) {
     if (!s->want_pull) DCS_FAIL(DCS_EINVAL, "%s: no push to pull for", who);
     if (n_tiles != s->pending)
         DCS_FAIL(DCS_EINVAL, "%s: p of %lld tiles, the preceding push returned %lld", who, (long long)n_tiles,
                  (long long)s->pending);
     if (n_tiles > 0 && !p_d) DCS_FAIL(DCS_EINVAL, "%s: null p", who);
     const int64_t tile_elems = (int64_t)s->tc * s->F;
-    if (n_tiles > 0 && s->S > 1 && p_src_stride < n_tiles * tile_elems)
+    if (n_tiles > 0 && !s->stereo && s->S > 1 && p_src_stride < n_tiles * tile_elems)
         DCS_FAIL(DCS_EINVAL, "%s: source stride %lld below %lld tiles", who, (long long)p_src_stride, (long long)n_tiles);
+    if (n_tiles > 0 && s->stereo) {
+        // the extent of one channel's rows, and of one source: the channels are whole planes or sit side by side in a row
+        if (p_ld < s->F || p_ch_stride < 0 || p_ld > (1LL << 40) || p_ch_stride > (1LL << 40))
+            DCS_FAIL(DCS_EINVAL, "%s: row pitch %lld below the %d bins (channel stride %lld)", who, (long long)p_ld, s->F,
+                     (long long)p_ch_stride);
+        const int64_t ch_extent = (n_tiles * s->tc - 1) * p_ld + s->F;
+        if (s->C > 1 && p_ch_stride < ch_extent && (p_ch_stride < s->F || p_ld < (s->C - 1) * p_ch_stride + s->F))
+            DCS_FAIL(DCS_EINVAL, "%s: channel stride %lld: neither whole planes of %lld floats nor side by side in rows of %lld",
+                     who, (long long)p_ch_stride, (long long)ch_extent, (long long)p_ld);
+        const int64_t src_extent = p_ch_stride >= ch_extent ? (s->C - 1) * p_ch_stride + ch_extent
+                                                             : (n_tiles * s->tc - 1) * p_ld + (s->C - 1) * p_ch_stride + s->F;
+        if (s->S > 1 && p_src_stride < src_extent)
+            DCS_FAIL(DCS_EINVAL, "%s: source stride %lld below the %lld floats of one source", who, (long long)p_src_stride,
+                     (long long)src_extent);
+    }
     if (est_d && ld < s->F) DCS_FAIL(DCS_EINVAL, "%s: ld %lld below the %d bins", who, (long long)ld, s->F);
     if (s->ended && s->K == 0) {
         s->want_pull = false;
@@ -720,14 +852,26 @@ int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_
     DCS_ON_DEVICE(s->ctx->device);
     hipStream_t q = s->ctx->stream;
     const int64_t k_first = s->K - n_tiles;
-    if (n_tiles > 0) {
+    if (n_tiles > 0 && s->stereo) {
+        hipLaunchKernelGGL(stream_keep_p_stereo_kernel, dim3((unsigned)(n_tiles * s->tc), (unsigned)s->C, (unsigned)s->S),
+                           dim3(kThreads), 0, q, p_d, p_src_stride, p_ch_stride, p_ld, k_first, s->tc, s->F, s->p, s->rp);
+        DCS_HIP(hipGetLastError());
+    } else if (n_tiles > 0) {
         const unsigned gy = (unsigned)(tile_elems < 64 * kThreads ? dcs_cdiv(tile_elems, kThreads) : 64);
         hipLaunchKernelGGL(stream_keep_p_kernel, dim3((unsigned)n_tiles, gy, (unsigned)s->S), dim3(kThreads), 0, q, p_d,
                            p_src_stride, k_first, tile_elems, s->p, s->rp);
         DCS_HIP(hipGetLastError());
     }
     if (n_fold > 0) {
-        {
+        if (s->stereo) {
+            DcsTimer tm(s->ctx, DCS_TAG_MASK);
+            hipLaunchKernelGGL(stream_fold_stereo_kernel, dim3((unsigned)n_fold, (unsigned)dcs_cdiv(s->F, kThreads), (unsigned)s->C),
+                               dim3(kThreads), 0, q, (const float*)s->p, s->rp, s->K, s->S, s->tc, s->ov, s->F, (const float*)s->rise,
+                               (const float*)s->mag, s->rf, s->Tf, s->c0, s->est, s->ff * s->F, est_d, est_ch_stride, est_src_stride,
+                               ld);
+            tm.done();
+            DCS_HIP(hipGetLastError());
+        } else {
             DcsTimer tm(s->ctx, DCS_TAG_MASK);
             auto fold = stream_fold_kernel<kMixMag>;
             if (s->ninst) fold = s->mixture == DCS_MIX_SUM ? stream_fold_kernel<kMixSum> : stream_fold_kernel<kMixCh0>;
@@ -772,6 +916,7 @@ int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_
 extern "C" int dcs_stream_push(dcs_stream* s, const float* audio_d, int64_t n, int last, float* tiles_d, int64_t tiles_cap,
                                int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ld, int64_t* n_frames_out) {
     if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: null stream");
+    if (s->stereo) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: a stereo stream takes dcs_stream_push_stereo");
     if (s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_push: a channel stream takes dcs_stream_push_channels");
     return stream_push("dcs_stream_push", s, audio_d, 0, n, last, tiles_d, tiles_cap, n_tiles_out, mag_d, phase_d, 0, ld,
                        n_frames_out);
@@ -781,6 +926,7 @@ extern "C" int dcs_stream_push_channels(dcs_stream* s, const float* audio_d, int
                                         float* tiles_d, int64_t tiles_cap, int64_t* n_tiles_out, float* mag_d, float* phase_d,
                                         int64_t ch_stride, int64_t ld, int64_t* n_frames_out) {
     if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_channels: null stream");
+    if (s->stereo) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_channels: a stereo stream takes dcs_stream_push_stereo");
     if (!s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_channels: a mono stream takes dcs_stream_push");
     return stream_push("dcs_stream_push_channels", s, audio_d, row_stride, n, last, tiles_d, tiles_cap, n_tiles_out, mag_d,
                        phase_d, ch_stride, ld, n_frames_out);
@@ -790,6 +936,7 @@ extern "C" int dcs_stream_pull(dcs_stream* s, const float* p_d, int64_t p_src_st
                                int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d, int64_t est_src_stride,
                                int64_t ld) {
     if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: null stream");
+    if (s->stereo) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: a stereo stream takes dcs_stream_pull_stereo");
     if (s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull: a channel stream takes dcs_stream_pull_channels");
     return stream_pull("dcs_stream_pull", s, p_d, p_src_stride, n_tiles, pcm_d, 0, pcm_stride, pcm_cap, n_out, est_d, 0,
                        est_src_stride, ld);
@@ -799,7 +946,26 @@ extern "C" int dcs_stream_pull_channels(dcs_stream* s, const float* p_d, int64_t
                                         int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d,
                                         int64_t est_ch_stride, int64_t est_src_stride, int64_t ld) {
     if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_channels: null stream");
+    if (s->stereo) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_channels: a stereo stream takes dcs_stream_pull_stereo");
     if (!s->C) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_channels: a mono stream takes dcs_stream_pull");
     return stream_pull("dcs_stream_pull_channels", s, p_d, p_src_stride, n_tiles, pcm_d, pcm_ch_stride, pcm_stride, pcm_cap,
                        n_out, est_d, est_ch_stride, est_src_stride, ld);
+}
+
+extern "C" int dcs_stream_push_stereo(dcs_stream* s, const float* audio_d, int64_t row_stride, int64_t n, int last, float* tiles_d,
+                                      int64_t tiles_cap, int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ch_stride,
+                                      int64_t ld, int64_t* n_frames_out) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_stereo: null stream");
+    if (!s->stereo) DCS_FAIL(DCS_EINVAL, "dcs_stream_push_stereo: not a stereo stream (dcs_stream_create_stereo)");
+    return stream_push("dcs_stream_push_stereo", s, audio_d, row_stride, n, last, tiles_d, tiles_cap, n_tiles_out, mag_d, phase_d,
+                       ch_stride, ld, n_frames_out);
+}
+
+extern "C" int dcs_stream_pull_stereo(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t p_ch_stride, int64_t p_ld,
+                                      int64_t n_tiles, float* pcm_d, int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap,
+                                      int64_t* n_out, float* est_d, int64_t est_ch_stride, int64_t est_src_stride, int64_t ld) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_stereo: null stream");
+    if (!s->stereo) DCS_FAIL(DCS_EINVAL, "dcs_stream_pull_stereo: not a stereo stream (dcs_stream_create_stereo)");
+    return stream_pull("dcs_stream_pull_stereo", s, p_d, p_src_stride, n_tiles, pcm_d, pcm_ch_stride, pcm_stride, pcm_cap, n_out,
+                       est_d, est_ch_stride, est_src_stride, ld, p_ch_stride, p_ld);
 }

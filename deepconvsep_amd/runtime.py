@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from .arch import (ARCHS, EPS_A, EPS_B, TIE_ALL, TIE_FIRST, TILER_LIBRARY, TILER_SCRIPT, check_params, live_params,
                    resolve as resolve_arch)
+from .streaming import stereo_ld
 
 
 def _torch():
@@ -373,6 +374,26 @@ class Network(object):
         return out if channel_major else out.permute(1, 0, 2, 3).contiguous()
 
     @_on_ctx_stream
+    def forward_stereo_tiles(self, tiles_t):
+        """The stereo (ILD) graph on tiles (``dcs_model_forward_stereo``): ``tiles_t`` ``[n, tc, C, ld]`` float32 in the row layout
+        -- the ``C = 2`` channels of a frame side by side, ``ld`` = F rounded up to 4, columns ``F .. ld-1`` zero
+        (``streaming.stereo_rows_from_tiles`` makes it from ``[n, C, tc, F]``) -> the rectified network output ``[S, n, tc, C, ld]``, the
+        buffer as the kernel wrote it (columns ``F .. ld-1`` unspecified).  ``ValueError`` for another graph or shape."""
+        torch = _torch()
+        ld = stereo_ld(self.F)
+        if self.arch.name != 'dsd_ild':
+            raise ValueError("forward_stereo_tiles runs the stereo (ILD) graph, not '%s'" % self.arch.name)
+        if tiles_t.dim() != 4 or tuple(tiles_t.shape[1:]) != (self.tc, self.arch.C, ld) or tiles_t.dtype != torch.float32:
+            raise ValueError("input tiles %r do not match the row layout (n, %d, %d, %d) float32"
+                             % (tuple(tiles_t.shape), self.tc, self.arch.C, ld))
+        n = int(tiles_t.shape[0])
+        tiles_t = tiles_t.contiguous()
+        out = torch.empty((self.S, n, self.tc, self.arch.C, ld), dtype=torch.float32, device=tiles_t.device)
+        if n:
+            _lib.check(self.ctx._lib.dcs_model_forward_stereo(self._h, _ptr(tiles_t), n, _ptr(out)))
+        return out
+
+    @_on_ctx_stream
     def separate(self, plan, audio_t, overlap, tiler=TILER_SCRIPT, scale=0.3, eps_mode=None, tie_mode=TIE_ALL,
                  out=None):
         """Fused file-level path: 1-D float32 device tensor -> ``[S, L]`` float32 PCM."""
@@ -678,6 +699,88 @@ class ChannelStream(Stream):
         self.last_samples = got.value
         if got.value != n_pcm:
             raise _lib.DcsError("dcs_stream_pull_channels returned %d samples, the host counts say %d" % (got.value, n_pcm))
+        return (pcm, est) if want_est else pcm
+
+
+class StereoStream(Stream):
+    """``dcs_stream_create_stereo``: a :class:`Stream` for the stereo (ILD) graph -- ``channels`` rows of samples, magnitudes and
+    phases and no down-mix; ``push`` returns tiles in the row layout ``[n_new, tc, C, ld]`` that
+    :meth:`Network.forward_stereo_tiles` takes, ``pull`` takes ``p`` per (source, channel) and folds the stereo trainer's
+    per-channel mask.  The counts, the alternation and ``reset`` / ``close`` / ``bytes`` / ``max_tiles`` are the mono stream's."""
+
+    def __init__(self, plan, S, channels, time_context, overlap, tiler=TILER_LIBRARY, scale=1.0, max_push=65536):
+        self.C = int(channels)
+        self.ld = stereo_ld(plan.bins)
+        Stream.__init__(self, plan, S, time_context, overlap, tiler, EPS_B, scale, max_push)
+
+    def _create(self, overlap, tiler, eps_mode, scale, rise_p, h):
+        return self.ctx._lib.dcs_stream_create_stereo(self.plan._h, self.S, self.C, self.tc, overlap, tiler, scale, rise_p,
+                                                      self.max_push, byref(h))
+
+    @_on_ctx_stream
+    def push(self, audio_t=None, last=False, want_frames=False):
+        """Appends ``audio_t`` (float32 device tensor ``[C, n]``, rows contiguous, a view with a larger row stride is fine;
+        ``n <= max_push``; None: no samples), ``last=True`` ends the signal.  Returns the tiles that became ready, ``[n_new, tc,
+        C, ld]`` -- with ``want_frames`` also the channels' magnitude and phase rows of the frames that became complete, ``[C,
+        n_frames, F]`` each."""
+        torch = _torch()
+        n = 0 if audio_t is None else int(audio_t.shape[-1])
+        if audio_t is not None and (audio_t.dim() != 2 or int(audio_t.shape[0]) != self.C or audio_t.dtype != torch.float32
+                                    or (n and (audio_t.stride(1) != 1 or audio_t.stride(0) < n))):
+            raise ValueError("StereoStream.push takes a float32 [%d, n] tensor with contiguous rows" % self.C)
+        c, P = self.counts, self.pushed + n
+        want_t = max(0, min(c.tiles(P, bool(last)) - self._tiles, self.max_tiles))
+        want_f = max(0, c.frames(P, bool(last)) - self._frames) if want_frames else 0
+        tiles = torch.empty((want_t, self.tc, self.C, self.ld), dtype=torch.float32, device=self.ctx.device)
+        mag = torch.empty((self.C, want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
+        ph = torch.empty((self.C, want_f, self.F), dtype=torch.float32, device=self.ctx.device) if want_frames else None
+        nt, nf = c_int64(), c_int64()
+        _lib.check(self.ctx._lib.dcs_stream_push_stereo(self._h, _ptr(audio_t) if n else None, int(audio_t.stride(0)) if n else 0,
+                                                        n, 1 if last else 0, _ptr(tiles) if want_t else None, want_t, byref(nt),
+                                                        _ptr(mag) if want_f else None, _ptr(ph) if want_f else None,
+                                                        want_f * self.F, self.F, byref(nf)))
+        self.pushed, self.ended = P, bool(last)
+        self._tiles += nt.value
+        self._frames += nf.value
+        self.last_tiles, self.last_frames = nt.value, nf.value
+        if nt.value != want_t or (want_frames and nf.value != want_f):
+            raise _lib.DcsError("dcs_stream_push_stereo returned %d tiles and %d frames, the host counts say %d and %d"
+                                % (nt.value, nf.value, want_t, want_f))
+        return (tiles, mag, ph) if want_frames else tiles
+
+    @_on_ctx_stream
+    def pull(self, p=None, want_est=False):
+        """``p`` for exactly the tiles of the preceding push (None when it returned none), float32: what
+        :meth:`Network.forward_stereo_tiles` returned, ``[S, n, tc, C, ld]``, or the Lasagne layout ``[S * C, n, tc, F]`` (output
+        channel ``s C + c``).  Returns the samples that became final, ``[C, S, n_out]`` float32 -- with ``want_est`` also the
+        estimates of the frames that were folded, ``[C, S, rows, F]``."""
+        torch = _torch()
+        n = 0 if p is None else int(p.shape[1])
+        if p is not None:
+            rows = p.dim() == 5 and tuple(p.shape) == (self.S, n, self.tc, self.C, self.ld)
+            planes = p.dim() == 4 and tuple(p.shape) == (self.S * self.C, n, self.tc, self.F)
+            if not (rows or planes) or p.dtype != torch.float32:
+                raise ValueError("StereoStream.pull expects p [%d, n, %d, %d, %d] or [%d, n, %d, %d] float32, got %r"
+                                 % (self.S, self.tc, self.C, self.ld, self.S * self.C, self.tc, self.F, tuple(p.shape)))
+            p = p.contiguous()
+            strides = ((n * self.tc * self.C * self.ld, self.ld, self.C * self.ld) if rows else
+                       (self.C * n * self.tc * self.F, n * self.tc * self.F, self.F))
+        c = self.counts
+        n_pcm = c.emitted(self.pushed, self.ended) - self._emitted
+        n_fold = c.folded(self.pushed, self.ended) - self._folded
+        pcm = torch.empty((self.C, self.S, n_pcm), dtype=torch.float32, device=self.ctx.device)
+        est = torch.empty((self.C, self.S, n_fold, self.F), dtype=torch.float32, device=self.ctx.device) if want_est else None
+        got = c_int64()
+        ss, cs, pl = strides if n else (0, 0, 0)
+        _lib.check(self.ctx._lib.dcs_stream_pull_stereo(self._h, _ptr(p) if n else None, ss, cs, pl, n,
+                                                        _ptr(pcm) if n_pcm else None, self.S * n_pcm, n_pcm, n_pcm, byref(got),
+                                                        _ptr(est) if want_est and n_fold else None,
+                                                        self.S * n_fold * self.F, n_fold * self.F, self.F))
+        self._emitted += got.value
+        self._folded += n_fold
+        self.last_samples = got.value
+        if got.value != n_pcm:
+            raise _lib.DcsError("dcs_stream_pull_stereo returned %d samples, the host counts say %d" % (got.value, n_pcm))
         return (pcm, est) if want_est else pcm
 
 

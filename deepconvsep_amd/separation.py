@@ -541,6 +541,15 @@ class Separator(object):
         from .streaming import ChannelStreamSeparator
         return ChannelStreamSeparator(self, max_block=max_block)
 
+    def stream_stereo(self, max_block=65536):
+        """A :class:`deepconvsep_amd.streaming.StereoStreamSeparator` on this separator's model and plan: the stereo stems of
+        :meth:`separate_stereo` (without the Wiener filter, which needs the whole signal) on a stream -- ``push(block [n, 2])``
+        at 44 100 Hz, finished stems ``[n_i, S, 2]`` back.  ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes
+        any other rate.  The ``dsd_ild`` graph only (``ValueError`` otherwise); :meth:`stream` and :meth:`stream_channels` keep
+        refusing that graph."""
+        from .streaming import StereoStreamSeparator
+        return StereoStreamSeparator(self, max_block=max_block)
+
     @_on_ctx_stream
     def channel_spectra(self, a3, want_p=False):
         """Per-channel estimates of a stereo signal from a mono model.  ``a3 [3, L]`` float32 on the device: rows L, R and

@@ -10,8 +10,9 @@ not on the length of the signal.
 of every frame are formed as the frame arrives (``dcs_stream_create_score``).
 
 :class:`ChannelStreamSeparator` does the same for a stereo signal -- the stems of ``Separator.separate_channels`` on one engine
--- and :class:`RateStream` puts either of them between two streaming sample-rate converters (``dcs_resample_stream``) for audio
-at another rate than 44 100 Hz.
+-- :class:`StereoStreamSeparator` streams the one graph that is stereo by construction (``dsd_ild``: the network sees both
+channels and answers per source and channel, ``dcs_stream_create_stereo``), and :class:`RateStream` puts any of them between two
+streaming sample-rate converters (``dcs_resample_stream``) for audio at another rate than 44 100 Hz.
 
 :class:`StreamCounts` is the host arithmetic of the schedule (the table in include/dcs.h); it needs neither the library nor a
 GPU.
@@ -71,6 +72,30 @@ class StreamCounts(object):
 
     def max_tiles(self, max_push):
         return (self.max_frames(max_push) + self.st - 1) // self.st + 2
+
+
+def stereo_ld(F):
+    """floats per channel in a row of the stereo (ILD) graph's row layout: the bins rounded up to a multiple of 4"""
+    return (int(F) + 3) // 4 * 4
+
+
+def stereo_rows_from_tiles(tiles):
+    """Lasagne tiles ``[n, C, tc, F]`` (NumPy) -> the row layout ``[n, tc, C, ld]`` ``dcs_model_forward_stereo`` reads: the
+    channels of a frame side by side, columns ``F .. ld-1`` zero"""
+    tiles = np.asarray(tiles)
+    n, C, tc, F = tiles.shape
+    rows = np.zeros((n, tc, C, stereo_ld(F)), dtype=tiles.dtype)
+    rows[..., :F] = tiles.transpose(0, 2, 1, 3)
+    return rows
+
+
+def stereo_tiles_from_rows(rows, F):
+    """the inverse, on any number of leading axes: ``[..., n, tc, C, ld]`` (NumPy, e.g. the ``[S, n, tc, C, ld]`` of
+    ``Network.forward_stereo_tiles``) -> ``[..., n, C, tc, F]``"""
+    rows = np.asarray(rows)
+    if rows.ndim < 4 or rows.shape[-1] != stereo_ld(F):
+        raise ValueError("rows %r are not [..., n, tc, C, %d]" % (rows.shape, stereo_ld(F)))
+    return np.ascontiguousarray(np.swapaxes(rows[..., :int(F)], -2, -3))
 
 
 class StreamSeparator(object):
@@ -226,6 +251,7 @@ class ChannelStreamSeparator(object):
     graphs only."""
 
     channels = 2
+    rows_in = 3                      # signal rows a device block carries: L, R, down-mix
 
     def __init__(self, separator, max_block=65536):
         separator._require_mono_graph("stream_channels")
@@ -259,12 +285,14 @@ class ChannelStreamSeparator(object):
         return eng.pull(p)
 
     def push_device(self, a3):
-        """``a3`` float32 device tensor ``[3, n]`` (L, R, down-mix) -> float32 ``[2, S, n_i]`` on the device"""
+        """``a3`` float32 device tensor ``[3, n]`` (L, R, down-mix; ``[2, n]``, L and R, for a :class:`StereoStreamSeparator`) ->
+        float32 ``[2, S, n_i]`` on the device"""
         torch = _runtime()._torch()
         if self._ended:
             raise ValueError("the stream has ended: reset() starts another signal")
-        if a3.dim() != 2 or int(a3.shape[0]) != self.channels + 1:
-            raise ValueError("a channel stream takes [3, n] tensors (L, R, down-mix), got shape %r" % (tuple(a3.shape),))
+        if a3.dim() != 2 or int(a3.shape[0]) != self.rows_in:
+            raise ValueError("this stream takes [%d, n] tensors (L, R%s), got shape %r"
+                             % (self.rows_in, ", down-mix" if self.rows_in == 3 else "", tuple(a3.shape)))
         with self.ctx.stream_scope():
             n = int(a3.shape[1])
             outs = [self._step(a3[:, i:i + self.max_block], False) for i in range(0, n, self.max_block)]
@@ -313,10 +341,61 @@ class ChannelStreamSeparator(object):
         return self._stream().bytes
 
 
+class StereoStreamSeparator(ChannelStreamSeparator):
+    """``Separator.stream_stereo()``: the stereo (ILD) DSD100 graph on a stream -- what ``Separator.separate_stereo`` computes
+    on a whole file (two-channel tiles from the library tiler, one network pass per tile, the stereo trainer's mask per channel,
+    cross-faded, on that channel's own magnitudes and phase), block by block (``dcs_stream_create_stereo``).
+
+    ``push(block)`` takes the next samples ``[n, 2]`` of a 44 100 Hz signal and returns the float64 samples ``[n_i, S, 2]`` that
+    became final, ``finish()`` ends the signal and returns the rest; ``push_device`` / ``finish_device`` take float32 device
+    tensors ``[2, n]`` and return ``[2, S, n_i]``.  Between the two halves of the stream the tiles that became ready go through
+    ``net.forward_stereo_tiles``.  ``reset``, ``device_bytes`` and ``counts`` as in the other classes.  The ``dsd_ild`` graph
+    only (``ValueError`` otherwise).  There is no Wiener filter on a stream (``separate_stereo(mwf_iters=...)``): its statistics
+    run over the whole signal."""
+
+    rows_in = 2                      # signal rows a device block carries: no down-mix
+
+    def __init__(self, separator, max_block=65536):
+        if separator.arch_name != 'dsd_ild':
+            raise ValueError("stream_stereo runs the stereo (ILD) graph; '%s' takes %d input channel(s): use stream() or "
+                             "stream_channels()" % (separator.arch_name, separator.net.arch.C))
+        if int(max_block) < 1:
+            raise ValueError("max_block must be at least 1 sample")
+        self.sep, self.ctx = separator, separator.ctx
+        self.max_block = int(max_block)
+        # the library tiler whatever the separator's: the stereo trainer calls util.generate_overlapadd (separate_stereo)
+        self.counts = StreamCounts(separator.frameSize, separator.hopSize, separator.tc, separator.overlap, TILER_LIBRARY)
+        self._engine = None              # the device state: made by the first block
+        self._pushed, self._ended = 0, False
+
+    def _stream(self):
+        if self._engine is None:
+            from .runtime import StereoStream
+            s = self.sep
+            self._engine = StereoStream(s.plan, s.net.S, self.channels, s.tc, s.overlap, TILER_LIBRARY, s.scale_factor,
+                                        self.max_block)
+        return self._engine
+
+    def _step(self, piece, last):
+        """one push -> network -> pull; ``piece`` float32 device tensor ``[2, n]`` or None"""
+        eng = self._stream()
+        tiles = eng.push(piece, last=last)
+        p = self.sep.net.forward_stereo_tiles(tiles) if int(tiles.shape[0]) else None
+        return eng.pull(p)
+
+    def push(self, block):
+        block = np.asarray(block)
+        if block.ndim != 2 or block.shape[1] != self.channels:
+            raise ValueError("a stereo stream takes stereo blocks ([n, 2] arrays), got shape %r" % (block.shape,))
+        if self._ended:
+            raise ValueError("the stream has ended: reset() starts another signal")
+        return self._to_host(self.push_device(self.ctx.to_device(np.ascontiguousarray(block.T), np.float32)))
+
+
 class RateStream(object):
-    """A stream at any sample rate: ``inner`` (a :class:`StreamSeparator` or a :class:`ChannelStreamSeparator`) between two
-    streaming converters (``dcs_resample_stream``) -- ``sample_rate -> 44 100`` on the 1 or 3 signal rows in front, ``44 100 ->
-    sample_rate`` on the ``S`` or ``2 S`` stems behind.  ``push`` takes blocks at ``sample_rate`` in the layout ``inner`` takes
+    """A stream at any sample rate: ``inner`` (a :class:`StreamSeparator`, a :class:`ChannelStreamSeparator` or a
+    :class:`StereoStreamSeparator`) between two streaming converters (``dcs_resample_stream``) -- ``sample_rate -> 44 100`` on
+    the 1, 3 or 2 signal rows in front, ``44 100 -> sample_rate`` on the ``S`` or ``2 S`` stems behind.  ``push`` takes blocks at ``sample_rate`` in the layout ``inner`` takes
     and returns the finished stems at ``sample_rate`` in the layout ``inner`` returns; ``finish()`` flushes the three stages and
     crops, as the whole-file paths do (``Separator._at_model_rate``), so that the lengths add up to the samples pushed.  Each
     stage's outputs are those of the whole-file conversion bit for bit, so the result is the whole-file ``Resampler`` in front,
@@ -326,7 +405,8 @@ class RateStream(object):
     def __init__(self, inner, sample_rate):
         from .resample import TARGET_RATE
         if not isinstance(inner, (StreamSeparator, ChannelStreamSeparator)):
-            raise TypeError("RateStream wraps a StreamSeparator or a ChannelStreamSeparator, got %r" % (type(inner).__name__,))
+            raise TypeError("RateStream wraps a StreamSeparator, a ChannelStreamSeparator or a StereoStreamSeparator, got %r"
+                            % (type(inner).__name__,))
         if int(sample_rate) != sample_rate or int(sample_rate) < 1:
             raise ValueError("sample_rate must be a positive integer, got %r" % (sample_rate,))
         self.inner, self.ctx = inner, inner.ctx
@@ -345,7 +425,7 @@ class RateStream(object):
     def _stages(self):
         if self._down is None:
             from .resample import StreamResampler
-            rows_in, rows_out = (3, 2 * self.S) if self.stereo else (1, self.S)
+            rows_in, rows_out = (self.inner.rows_in, 2 * self.S) if self.stereo else (1, self.S)
             self._down = StreamResampler(self.ctx, self.sample_rate, self.model_rate, rows_in, self.max_block)
             self._up = StreamResampler(self.ctx, self.model_rate, self.sample_rate, rows_out, self.max_block)
         return self._down, self._up
@@ -381,15 +461,17 @@ class RateStream(object):
         return out.reshape(2, self.S, int(out.shape[1])) if self.stereo else out
 
     def push_device(self, x):
-        """``x`` float32 device tensor at ``sample_rate``: ``[n]`` (mono inner) or ``[3, n]`` (L, R, down-mix) -> the finished
+        """``x`` float32 device tensor at ``sample_rate``: ``[n]`` (mono inner), ``[3, n]`` (L, R, down-mix) or ``[2, n]`` (a
+        :class:`StereoStreamSeparator`) -> the finished
         stems at ``sample_rate``, ``[S, n_i]`` or ``[2, S, n_i]``"""
         if self.passthrough:
             return self.inner.push_device(x)
         torch = _runtime()._torch()
         if self._ended:
             raise ValueError("the stream has ended: reset() starts another signal")
-        if x.dim() != (2 if self.stereo else 1) or (self.stereo and int(x.shape[0]) != 3):
-            raise ValueError("this stream takes %s tensors, got shape %r" % ("[3, n]" if self.stereo else "[n]", tuple(x.shape)))
+        if x.dim() != (2 if self.stereo else 1) or (self.stereo and int(x.shape[0]) != self.inner.rows_in):
+            raise ValueError("this stream takes %s tensors, got shape %r"
+                             % ("[%d, n]" % self.inner.rows_in if self.stereo else "[n]", tuple(x.shape)))
         down, _ = self._stages()
         with self.ctx.stream_scope():
             rows = x if self.stereo else x.reshape(1, int(x.shape[0]))
@@ -432,7 +514,10 @@ class RateStream(object):
         if self.stereo:
             if block.ndim != 2 or block.shape[1] != 2:
                 raise ValueError("this stream takes stereo blocks ([n, 2] arrays), got shape %r" % (block.shape,))
-            block = np.stack([block[:, 0], block[:, 1], to_mono(block, self.inner.sep.arch_name)])
+            rows = [block[:, 0], block[:, 1]]
+            if self.inner.rows_in == 3:
+                rows.append(to_mono(block, self.inner.sep.arch_name))
+            block = np.stack(rows)
         elif block.ndim != 1:
             raise ValueError("this stream takes mono blocks ([n] arrays), got shape %r" % (block.shape,))
         return self._to_host(self.push_device(self.ctx.to_device(block, np.float32)))

@@ -2,6 +2,7 @@
 
     python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536] [--stereo] [--resample]
     python examples/separate_stream.py -a bach10_si -i mix.wav -o outdir -m model.pkl [--trainer-semantics] [--resample]
+    python examples/separate_stream.py -a dsd_ild -i stereo_mix.wav -o outdir -m model.pkl [--block 65536] [--resample]
 
 The file is read with the standard ``wave`` module ``--block`` frames at a time; each block is scaled and mixed down the way
 the architecture's separate script does it (element-wise, so block by block equals the whole file), pushed into
@@ -20,6 +21,11 @@ is built before the first block from the frame count the wav HEADER gives (``cei
 ``--resample`` from the length the file has at 44 100 Hz).  ``--trainer-semantics``: masks divided by their sum over the
 instruments and soft masks on the channel sum, what the trainer's own models saw (``separate_bach10.py`` has the same
 option).  ``--stereo`` does not apply.
+
+``-a dsd_ild``: the stereo (ILD) DSD100 graph (``Separator.stream_stereo``), which sees both channels: a two-channel file gives
+one two-channel stem per source under the names ``examples/dsd100_2ch_ILD/separate_dsd_ild.py`` uses (``<outdir>/<source>.wav``),
+with that script's hyper-parameters.  ``--stereo`` is implied (and accepted); a mono file is refused.  No Wiener filter
+(``--mwf`` of that script): it needs the whole signal.
 """
 import argparse
 import os
@@ -30,7 +36,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-ARCHS = ("dsd", "hiphop", "ikala", "bach10", "bach10_si")
+ARCHS = ("dsd", "hiphop", "ikala", "bach10", "bach10_si", "dsd_ild")
+# separate_dsd_ild.py: (frameSize, hopSize, window, overlap, input_size)
+ILD_DEFAULTS = (1024, 512, np.hanning, 25, 513)
 
 
 def read_blocks(wav, block):
@@ -61,19 +69,25 @@ def main(argv=None):
         raise SystemExit("--stereo does not apply to bach10_si: the score-informed graphs take one channel per instrument")
     if args.trainer_semantics and not score:
         raise SystemExit("--trainer-semantics applies to bach10_si only")
+    ild = args.arch == "dsd_ild"
+    if ild:
+        args.stereo = True               # the graph is stereo by construction
 
     import deepconvsep_amd as dcs
     from deepconvsep_amd.separation import (SI_SCORE_FILES, SI_SCORE_PARAMS, TARGET_RATE, _SCRIPT_DEFAULTS, output_paths,
                                             rate_ratio, resampled_length, to_mono)
     from deepconvsep_amd.streaming import RateStream
 
-    frame, hop, window, overlap, bins = _SCRIPT_DEFAULTS[args.arch]
+    frame, hop, window, overlap, bins = ILD_DEFAULTS if ild else _SCRIPT_DEFAULTS[args.arch]
     src = wave.open(args.input, "rb")
     if src.getsampwidth() != 2 or src.getcomptype() != "NONE":
         raise SystemExit("%s is not a 16-bit PCM wav file" % args.input)
     rate = src.getframerate()
     if rate != 44100 and not args.resample:
         raise SystemExit("Sample rate is not 44100")
+    if ild and src.getnchannels() != 2:
+        raise SystemExit("-a dsd_ild takes a two-channel file (the network sees both channels), %s has %d"
+                         % (args.input, src.getnchannels()))
     if args.stereo and src.getnchannels() != 2:
         raise SystemExit("--stereo takes a two-channel file, %s has %d" % (args.input, src.getnchannels()))
     if score:
@@ -86,6 +100,9 @@ def main(argv=None):
         nframes = int(np.ceil(n44 / np.double(hop))) + 2
         melody = melody_table(SI_SCORE_FILES, os.path.dirname(args.input), nframes, TARGET_RATE, hop, frame, **SI_SCORE_PARAMS)
         stream = sep.stream_scoreinformed(melody, max_block=args.block)
+    elif ild:
+        sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
+        stream = sep.stream_stereo(max_block=args.block)
     else:
         sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
         stream = sep.stream_channels(max_block=args.block) if args.stereo else sep.stream(max_block=args.block)
@@ -93,7 +110,12 @@ def main(argv=None):
         stream = RateStream(stream, rate)
     os.makedirs(args.outdir, exist_ok=True)
     outs = []
-    for path in output_paths(args.arch, args.input, args.outdir):
+    if ild:
+        from deepconvsep_amd.stereo_training import SOURCES
+        paths = [os.path.join(args.outdir, s + ".wav") for s in SOURCES]
+    else:
+        paths = output_paths(args.arch, args.input, args.outdir)
+    for path in paths:
         w = wave.open(path, "wb")
         w.setnchannels(2 if args.stereo else 1)
         w.setsampwidth(2)

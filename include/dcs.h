@@ -256,6 +256,14 @@ DCS_API int dcs_model_forward_masked(dcs_model* m, const float* tiles_d, int64_t
                              float* out_d);
 /* lasagne.layers.get_output(network2): p_d [n, channels_out, tc, F] before masking (testing aid) */
 DCS_API int dcs_model_forward(dcs_model* m, const float* tiles_d, int64_t n_tiles, int tie_mode, float* p_d);
+/* The same for the stereo (ILD) graph (DCS_ARCH_DSD_ILD, else DCS_EINVAL), which dcs_model_forward refuses: tiles in the ROW
+ * layout of dcs_separate_stereo, the C = 2 channels of a frame side by side.  tiles_d [n_tiles][tc][C][ld], ld = F rounded up
+ * to 4, 16-byte aligned, columns F .. ld-1 ZERO on entry; every tile is encoded from its own tc rows.  p_d [S = 4][n_tiles tc]
+ * [C ld]: the rectified network output (output BiasLayer and rectifier applied, no mask) -- source s, input channel c is the
+ * reference's output channel s C + c (trainCNN_ILD_DSD100.py:106-111); columns F .. ld-1 of each channel are unspecified.
+ * DCS_EINVAL for a NULL pointer or a negative count; n_tiles == 0 does nothing.  What a stereo stream (below) runs between
+ * its push and its pull. */
+DCS_API int dcs_model_forward_stereo(dcs_model* m, const float* tiles_d, int64_t n_tiles, float* p_d);
 DCS_API int dcs_model_out_channels(const dcs_model* m);
 /* Which kernel the fused path (dcs_separate*) runs for the decoder's last stage (transposed conv1 + bias + rectify + mask
  * + cross-fade) on n_clips clips of n_frames frames each: 0 = f32 MFMA, 64-bin workgroups (small launches); 1 = f32
@@ -557,6 +565,40 @@ DCS_API int dcs_stream_push_channels(dcs_stream* s, const float* audio_d, int64_
 DCS_API int dcs_stream_pull_channels(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t n_tiles, float* pcm_d,
                                      int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap, int64_t* n_out, float* est_d,
                                      int64_t est_ch_stride, int64_t est_src_stride, int64_t ld);
+/* A STEREO stream: the stereo (ILD) graph, whose network sees the C channels themselves (1 <= C <= 8; the published graph has
+ * C = 2) and returns one output per (source, channel).  There is no down-mix row.  The schedule, the counts, the refusals and
+ * the invariants are the mono stream's; frames, inverse and gather are the same kernels with a channel index.
+ *   tiles   the row layout dcs_model_forward_stereo takes: tiles[k][j][c][f] = scale * mag[c][k st + j][f], zero for rows >= T
+ *           and for the columns F .. ld_t - 1, ld_t = F rounded up to 4
+ *   fold    per frame t, bin f, channel c, float32, eps_r = 1e-13f (1e-12 x 0.1, trainCNN_ILD_DSD100.py:152,164,187), every
+ *           sum, quotient and product rounded once, in the order written:
+ *             per covering tile k (row j = t - k st):  den = (((p_0c + p_1c) + ...) + eps_r,  m_s = p_sc / den
+ *             acc_sc: the fold of dcs_mask_fold_apply on m (owner tile k0, then fma(rise[ov-1-j], acc, rise[j] * m[k]))
+ *             est[c][s][t][f] = acc_sc * mag[c][t][f] + c0,   c0 = eps_r / scale formed once, by create, in float32
+ *           on the UNSCALED magnitudes: the cross-fade of mask * (scale * mag) + eps_r (:188) divided by scale, as the weights
+ *           of a frame sum to one -- dcs_separate_stereo's result in exact arithmetic.  Rows past the last tile are exact
+ *           zeros, without c0 (util.py:313).
+ * State: sample rings C (N + max_push), magnitude rows C rf F, phase rows C rf F, the ring of p S C rp tc F (every (source,
+ * channel) once), estimates C S ff F, time frames rt C S N, the ramp (rf = ff = tc + fp, fp = ceil((max_push + H) / h) + 3,
+ * rp = ceil(tc / st) + max_tiles, rt = N / h + ff): a function of (N, h, tc, overlap, S, C, max_push) alone.  destroy, reset,
+ * max_tiles and bytes are dcs_stream's.  The mono, channel and score calls on a stereo stream and the three calls below on any
+ * other stream give DCS_EINVAL; scale == 0 gives DCS_EINVAL. */
+DCS_API int dcs_stream_create_stereo(dcs_stft* plan, int S, int C, int time_context, int overlap, int tiler, float scale,
+                                     const double* rise_h, int64_t max_push, dcs_stream** out);
+/* audio_d: C rows of n samples, row c at audio_d + c row_stride (>= n).  mag_d / phase_d [C][n_frames, ld] (channel stride
+ * ch_stride >= n_frames ld, either may be NULL); tiles_d [n_tiles][time_context][C][ld_t]. */
+DCS_API int dcs_stream_push_stereo(dcs_stream* s, const float* audio_d, int64_t row_stride, int64_t n, int last, float* tiles_d,
+                                   int64_t tiles_cap, int64_t* n_tiles_out, float* mag_d, float* phase_d, int64_t ch_stride,
+                                   int64_t ld, int64_t* n_frames_out);
+/* p_d for EXACTLY the tiles of the preceding push, element (s, c, k, j, f) at p_d + s p_src_stride + c p_ch_stride + (k
+ * time_context + j) p_ld + f: dcs_model_forward_stereo's output has p_src_stride = n tc C ld_t, p_ch_stride = ld_t, p_ld = C
+ * ld_t; the Lasagne layout [S C][n][tc][F] has p_src_stride = C n tc F, p_ch_stride = n tc F, p_ld = F.  p_ld < F, a source
+ * stride below one source's extent, or channels that are neither whole planes (p_ch_stride >= the rows' extent) nor side by
+ * side in a row (p_ld >= (C - 1) p_ch_stride + F) give DCS_EINVAL.  p goes into its ring once.  One inverse per (frame,
+ * channel, source) with that channel's phase; pcm_d [C][S][n_out], est_d [C][S][rows, ld] as for dcs_stream_pull_channels. */
+DCS_API int dcs_stream_pull_stereo(dcs_stream* s, const float* p_d, int64_t p_src_stride, int64_t p_ch_stride, int64_t p_ld,
+                                   int64_t n_tiles, float* pcm_d, int64_t pcm_ch_stride, int64_t pcm_stride, int64_t pcm_cap,
+                                   int64_t* n_out, float* est_d, int64_t est_ch_stride, int64_t est_src_stride, int64_t ld);
 /* A SCORE stream: the score-informed graphs (dcs_model_forward's [n, ninst, tc, F] tiles) on a stream.  The score is known
  * before the audio: notes_h [ninst][n_notes][width] is the table dcs_score_masks takes, read by the rules of that call -- a row
  * counts if midi > 0 and its duration n1 - max(n0, 0) is positive, it covers the frames (int64)max(n0, 0) <= t < (int64)n1; a

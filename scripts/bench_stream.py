@@ -2,7 +2,7 @@
 tile), run the tile through the network, pull the finished samples -- and of the push + pull machinery alone, with the network
 left out (a fixed ``p``).  Each step ends with a stream synchronisation, as a live caller that plays the samples would.
 
-    python scripts/bench_stream.py [--steps 200] [--warmup 20] [--channels 2] [--rate 48000] [--score]
+    python scripts/bench_stream.py [--steps 200] [--warmup 20] [--channels 2] [--rate 48000] [--score] [--ild [--block 65536]]
 
 ``--channels 2`` adds, in the same run, the stereo step on one channel engine (``Separator.stream_channels()``) and the stereo
 step composed of three mono ``runtime.Stream`` engines -- L, R and the down-mix -- that share one ``p``, which is what the mono
@@ -11,7 +11,9 @@ the stereo one); its block is one stride of audio at that rate.  The launch coun
 frames, tiles, the network call, keep-p, fold, inverse, gather per engine; append and convert per converter.  ``--score`` adds
 the score-informed step at the Bach10 shape (frameSize 4096, 2049 bins, four instruments, synthetic weights and a synthetic
 score as long as the run: ``Separator.stream_scoreinformed``, one launch more for the masks of the new frames) next to the mono
-``bach10`` stream's step at the same shape, and the device bytes of both.
+``bach10`` stream's step at the same shape, and the device bytes of both.  ``--ild`` adds the step of the stereo (ILD) graph's own
+stream (``Separator.stream_stereo``: two-channel tiles, ``forward_stereo_tiles``, the per-channel fold; 7 launches + the network
+call) next to the mono DSD stream's step, both with blocks of ``--block`` samples (default: one stride), and the bytes of both.
 
 Prints one JSON line: the median and mean wall time per step in milliseconds, next to the block's duration in audio time."""
 import argparse
@@ -32,6 +34,8 @@ def main(argv=None):
     ap.add_argument("--channels", type=int, default=1, choices=(1, 2))
     ap.add_argument("--rate", type=int, default=44100)
     ap.add_argument("--score", action="store_true")
+    ap.add_argument("--ild", action="store_true")
+    ap.add_argument("--block", type=int, default=0, help="--ild: samples per push (default one stride)")
     args = ap.parse_args(argv)
     import torch
     import deepconvsep_amd as dcs
@@ -47,11 +51,11 @@ def main(argv=None):
     audio = ctx.to_device(0.5 * synth_audio(block * (total + tc), seed=0), np.float32)
     ss = sep.stream(max_block=block)
 
-    def timed(step):
-        for i in range(tc):                             # fill: the first tile needs tc frames
+    def timed(step, fill=tc):
+        for i in range(fill):                           # fill: the first tile needs tc frames
             step(i)
         times = []
-        for i in range(tc, tc + total):
+        for i in range(fill, fill + total):
             ctx.synchronize()
             t0 = time.perf_counter()
             step(i)
@@ -128,6 +132,19 @@ def main(argv=None):
                       "score_step_ms_median": med(scored), "score_launches_per_step": 8 + 1,
                       "bach10_step_ms_median": med(plain), "score_device_bytes": sc.device_bytes,
                       "bach10_device_bytes": sb.device_bytes})
+    if args.ild:
+        B = args.block or block
+        fill = -(-tc * hop // B) + 1
+        base = 0.5 * synth_audio(8 * B, seed=4, channels=2)                                   # repeated: the values do not matter
+        a2 = ctx.to_device(np.ascontiguousarray(base.T), np.float32).repeat(1, (total + fill) // 8 + 1)
+        sep_i = dcs.Separator("dsd_ild", synth_params("dsd_ild", tc, F, seed=7), 0.3, tc, ov, 32, F, N, hop, np.hanning,
+                              tiler='library', ctx=ctx)
+        si, sm = sep_i.stream_stereo(max_block=B), sep.stream(max_block=B)
+        ild = timed(lambda i: si.push_device(a2[:, i * B:(i + 1) * B]), fill)
+        mono = timed(lambda i: sm.push_device(a2[0, i * B:(i + 1) * B]), fill)
+        extra.update({"ild_block_samples": B, "ild_step_ms_median": med(ild), "ild_step_ms_max": round(float(ild.max()), 4),
+                      "ild_mono_dsd_step_ms_median": med(mono), "ild_launches_per_step": 7 + 1,
+                      "ild_device_bytes": si.device_bytes, "ild_mono_dsd_device_bytes": sm.device_bytes})
     print(json.dumps({"bench": "stream", "graph": "dsd", "bins": F, "block_samples": block,
                       "block_audio_ms": round(1e3 * block / 44100.0, 3), "steps": args.steps,
                       "step_ms_median": round(float(np.median(full)), 4), "step_ms_mean": round(float(full.mean()), 4),
