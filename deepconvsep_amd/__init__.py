@@ -8,7 +8,7 @@ from . import _lib
 from .arch import (ARCHS, EPS_A, EPS_B, TIE_ALL, TIE_FIRST, TILER_LIBRARY, TILER_SCRIPT)
 from .transform import TransformFFT, Transforms, compute_file, compute_inverse, sinebell, transformFFT
 from .evaluation import bss_eval, bss_eval_images, bss_eval_sources
-from .runtime import mwf
+from .runtime import MwfOnline, mwf
 from .resample import ResampleCounts, Resampler, StreamResampler, resample
 from .separation import (PredictFunction, Separator, blackmanharris, generate_overlapadd, load_model,
                          overlapadd, overlapadd_multi, save_model, train_auto)
@@ -24,7 +24,7 @@ from .score_render import ScoreInformedRenderedWindows, render_score_informed_fe
 __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "TILER_SCRIPT", "TransformFFT",
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
            "Separator", "blackmanharris", "generate_overlapadd", "load_model", "save_model", "overlapadd",
-           "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "mwf", "Resampler", "resample", "StreamCounts", "StreamSeparator",
+           "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "mwf", "MwfOnline", "Resampler", "resample", "StreamCounts", "StreamSeparator",
            "ChannelStreamSeparator", "ScoreStreamSeparator", "StereoStreamSeparator", "RateStream", "ResampleCounts", "StreamResampler", "Trainer", "FeatureWindows", "glorot_init",
            "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features",
            "ScoreInformedRenderedWindows", "render_score_informed_features"]

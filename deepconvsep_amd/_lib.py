@@ -131,6 +131,12 @@ def load():
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)
     proto("dcs_mwf_frames_per_block", i32)
+    proto("dcs_mwf_online_create", i32, vp, i32, i32, i32, f64, f64, f64, POINTER(vp))
+    proto("dcs_mwf_online_destroy", i32, vp)
+    proto("dcs_mwf_online_reset", i32, vp)
+    proto("dcs_mwf_online_bytes", i64, vp)
+    proto("dcs_mwf_online_frames", i64, vp)
+    proto("dcs_mwf_online_push_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, f32, vp, vp)
     proto("dcs_mask_fold_apply", i32, vp, vp, i64, i64, i32, i32, i32, i32, i32, POINTER(c_double), vp, i64, i32, i64, i64, vp,
           i64, i64, vp, i64)
     proto("dcs_stream_create", i32, vp, i32, i32, i32, i32, i32, f32, POINTER(c_double), i64, POINTER(vp))
@@ -149,7 +155,9 @@ def load():
     proto("dcs_stream_pull_stereo", i32, vp, vp, i64, i64, i64, i64, vp, i64, i64, i64, POINTER(i64), vp, i64, i64, i64)
     proto("dcs_stream_create_score", i32, vp, i32, i32, i32, i32, i32, f32, POINTER(c_double), i64, POINTER(c_double), i32, i32,
           i32, i32, i32, POINTER(vp))
-    proto("dcs_resample_stream_create", i32, vp, i32, i64, POINTER(vp))
+    proto("dcs_stream_set_mwf", i32, vp, i32, f64, f64, f64)
+    proto("dcs_stream_mwf_last", i32, vp, vp, vp, i64, i64, i64)
+    proto("dcs_resample_stream_create",i32, vp, i32, i64, POINTER(vp))
     proto("dcs_resample_stream_destroy", i32, vp)
     proto("dcs_resample_stream_reset", i32, vp)
     proto("dcs_resample_stream_bytes", i64, vp)

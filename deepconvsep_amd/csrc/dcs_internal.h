@@ -316,6 +316,9 @@ int dcs_score_masks_scaled(dcs_ctx* ctx, const float* mag_d, int64_t ld, int64_t
                            int ninst, int n_notes, int width, int64_t start, int64_t stop, float mag_scale, float* out_d,
                            float* mask_d, int normalise = DCS_SCORE_NORM_MAX);
 
+// the argument checks of dcs_mwf_online_create (mwf_online.hip), for dcs_stream_set_mwf to refuse the same values under its own name
+int dcs_mwf_online_check(const char* who, int F, int J, int niter, double forget, double loading, double eps);
+
 // ---------------------------------------------------------------------------------- tiling kernels
 int dcs_launch_tile(dcs_ctx* ctx, const float* mag, int64_t ch_stride, int64_t ld, int C, int64_t T, int F,
                     int tc, int ov, int tiler, float scale, float* tiles, int64_t n);

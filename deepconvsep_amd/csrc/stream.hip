@@ -29,6 +29,11 @@
 // side (the row layout dcs_model_forward_stereo reads), the ring of p holds every (source, channel) once and the fold forms the
 // stereo trainer's mask per channel -- den over the sources of THAT channel plus 1e-13 -- and adds the trainer's constant to
 // the estimate.  Append, frames, inverse and gather are the kernels above with C rows.
+//
+// The WIENER FILTER (dcs_stream_set_mwf, channel and stereo streams of two channels): a pull sends the rows it folded through the
+// online filter of mwf_online.hip -- causal, its state one 2x2 matrix per (source, bin), its bits independent of how the frames
+// reach it, so the rows may go in two pieces where they wrap in the rings -- into two buffers [C][S][ff][F], and the inverse
+// reads magnitudes AND phases from there (its second instantiation).  A stream that never arms it runs what it ran before.
 #include "dcs_internal.h"
 #include "fft_frame.h"
 #include "chanmask.h"
@@ -368,7 +373,9 @@ __global__ __launch_bounds__(kThreads) void stream_fold_stereo_kernel(
 // y_n = w * irfft(est[c][s][n] sqrt(N) exp(j phase[c][n])) into slot n mod rt of the time-frame ring [rt][C][S][N]: the packed real-inverse
 // pre-processing, transform and window product of istft_fused_kernel (fft.hip), term for term, for ONE frame -- the sum over
 // the frames that cover a sample is stream_gather_kernel's.  Workgroup (blockIdx.x, blockIdx.y, blockIdx.z) = (frame t0 + x,
-// source y, channel z of gridDim.z).
+// source y, channel z of gridDim.z).  OWN_PHASE (a stream with the Wiener filter armed): `phase_ring` is the filter's phase buffer, a
+// row per (channel, source, frame of the pull) laid out as est, instead of the ring's row per (channel, frame).
+template <bool OWN_PHASE>
 __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
     const float* __restrict__ est, int64_t est_src_stride, const float* __restrict__ phase_ring, int64_t rf, int64_t t0,
     float* __restrict__ tf_ring, int64_t rt, int S, const float* __restrict__ win, const float2* __restrict__ tw, int N, int log2m,
@@ -387,7 +394,8 @@ __global__ __launch_bounds__(kThreads) void stream_inverse_kernel(
         tw = twl;
     }
     const float* mrow = est + (c * S + s) * est_src_stride + (int64_t)blockIdx.x * (M + 1);
-    const float* prow = phase_ring + (c * rf + ring_slot(n, rf)) * (int64_t)(M + 1);
+    const float* prow = OWN_PHASE ? phase_ring + (c * S + s) * est_src_stride + (int64_t)blockIdx.x * (M + 1)
+                                  : phase_ring + (c * rf + ring_slot(n, rf)) * (int64_t)(M + 1);
     for (int k = tid; k <= M; k += kThreads) {
         const float a = mrow[k] * sqrt_n;
         float sn, cs;
@@ -445,6 +453,21 @@ __global__ __launch_bounds__(kThreads) void stream_gather_kernel(const float* __
     pcm[c * pcm_ch_stride + s * pcm_stride + i] = acc / norm;
 }
 
+// ------------------------------------------------------------------------------------------ the filtered rows of the last pull
+// row blockIdx.x of (channel c, source s) = blockIdx.z of the filter's two buffers [C][S][ff][F] to the caller
+__global__ __launch_bounds__(kThreads) void stream_mwf_copy_kernel(const float* __restrict__ fmag, const float* __restrict__ fphase,
+                                                                   int64_t buf_src_stride, int S, int F, float* __restrict__ mag,
+                                                                   float* __restrict__ phase, int64_t ch_stride, int64_t src_stride,
+                                                                   int64_t ld) {
+    const int f = blockIdx.y * kThreads + threadIdx.x;
+    if (f >= F) return;
+    const int c = blockIdx.z / S, s = blockIdx.z % S;
+    const int64_t i = (int64_t)blockIdx.z * buf_src_stride + (int64_t)blockIdx.x * F + f;
+    const int64_t o = c * ch_stride + s * src_stride + (int64_t)blockIdx.x * ld + f;
+    mag[o] = fmag[i];
+    phase[o] = fphase[i];
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ the handle
@@ -475,6 +498,10 @@ struct dcs_stream {
     float* masks = nullptr;
     ScoreVals vals = {};
     std::vector<int> row_t0, row_end_max;
+    // the online Wiener filter (dcs_stream_set_mwf; null: off), its outputs [C][S][ff][F] and the rows the last pull filtered
+    dcs_mwf_online* mwf = nullptr;
+    float *fmag = nullptr, *fphase = nullptr;
+    int64_t mwf_bytes = 0, mwf_rows = 0;
 };
 
 namespace {
@@ -693,6 +720,9 @@ extern "C" int dcs_stream_destroy(dcs_stream* s) {
     dcs_dev_free(s->rise);
     dcs_dev_free(s->masks);
     dcs_dev_free(s->table);
+    dcs_dev_free(s->fmag);
+    dcs_dev_free(s->fphase);
+    dcs_mwf_online_destroy(s->mwf);
     delete s;
     return DCS_OK;
 }
@@ -702,6 +732,63 @@ extern "C" int dcs_stream_reset(dcs_stream* s) {
     // the rings keep their contents: no slot is read before the push or pull that needs it has written it (the score stays too)
     s->P = s->A = s->K = s->Tf = s->E = s->T = s->L = s->pending = 0;
     s->want_pull = s->ended = false;
+    s->mwf_rows = 0;
+    if (s->mwf) DCS_CHECK(dcs_mwf_online_reset(s->mwf));      // frame 0 reads no state: nothing is cleared on the device
+    return DCS_OK;
+}
+
+extern "C" int dcs_stream_set_mwf(dcs_stream* s, int niter, double forget, double loading, double eps) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_mwf: null stream");
+    if (s->C != 2) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_mwf: a channel or stereo stream of 2 channels (this one has %d)", s->C);
+    if (s->P > 0 || s->want_pull || s->ended) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_mwf: the stream has samples (reset it first)");
+    DCS_CHECK(dcs_mwf_online_check("dcs_stream_set_mwf", s->F, s->S, niter, forget, loading, eps));
+    DCS_ON_DEVICE(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    dcs_mwf_online_destroy(s->mwf);
+    dcs_dev_free(s->fmag);
+    dcs_dev_free(s->fphase);
+    s->mwf = nullptr;
+    s->fmag = s->fphase = nullptr;
+    s->bytes -= s->mwf_bytes;
+    s->mwf_bytes = s->mwf_rows = 0;
+    if (niter == 0) return DCS_OK;
+    const int64_t buf = (int64_t)s->nch * s->S * s->ff * s->F * (int64_t)sizeof(float);
+    int rc = dcs_mwf_online_create(s->ctx, s->F, s->S, niter, forget, loading, eps, &s->mwf);
+    if (rc == DCS_OK) {
+        hipError_t e = dcs_dev_alloc((void**)&s->fmag, (size_t)buf, "stream.mwf_mag");
+        if (e == hipSuccess) e = dcs_dev_alloc((void**)&s->fphase, (size_t)buf, "stream.mwf_phase");
+        if (e != hipSuccess) {
+            dcs_set_error("dcs_stream_set_mwf: 2 x %lld bytes: %s", (long long)buf, hipGetErrorString(e));
+            rc = e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP;
+        }
+    }
+    if (rc != DCS_OK) {                                       // the stream is left with the filter off
+        dcs_mwf_online_destroy(s->mwf);
+        dcs_dev_free(s->fmag);
+        dcs_dev_free(s->fphase);
+        s->mwf = nullptr;
+        s->fmag = s->fphase = nullptr;
+        return rc;
+    }
+    s->mwf_bytes = 2 * buf + dcs_mwf_online_bytes(s->mwf);
+    s->bytes += s->mwf_bytes;
+    return DCS_OK;
+}
+
+extern "C" int dcs_stream_mwf_last(dcs_stream* s, float* mag_d, float* phase_d, int64_t ch_stride, int64_t src_stride, int64_t ld) {
+    if (!s) DCS_FAIL(DCS_EINVAL, "dcs_stream_mwf_last: null stream");
+    if (!s->mwf) DCS_FAIL(DCS_EINVAL, "dcs_stream_mwf_last: the filter is off (dcs_stream_set_mwf)");
+    const int64_t rows = s->mwf_rows;
+    if (rows == 0) return DCS_OK;
+    if (!mag_d || !phase_d) DCS_FAIL(DCS_EINVAL, "dcs_stream_mwf_last: null buffer");
+    if (ld < s->F || src_stride < rows * ld || ch_stride < (s->S - 1) * src_stride + rows * ld)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_mwf_last: ld %lld, strides %lld / %lld below %lld rows of %d bins", (long long)ld,
+                 (long long)src_stride, (long long)ch_stride, (long long)rows, s->F);
+    DCS_ON_DEVICE(s->ctx->device);
+    hipLaunchKernelGGL(stream_mwf_copy_kernel, dim3((unsigned)rows, (unsigned)dcs_cdiv(s->F, kThreads), (unsigned)(s->nch * s->S)),
+                       dim3(kThreads), 0, s->ctx->stream, (const float*)s->fmag, (const float*)s->fphase, s->ff * s->F, s->S, s->F,
+                       mag_d, phase_d, ch_stride, src_stride, ld);
+    DCS_HIP(hipGetLastError());
     return DCS_OK;
 }
 
@@ -882,17 +969,28 @@ int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_
             tm.done();
             DCS_HIP(hipGetLastError());
         }
+        if (s->mwf) {
+            // the online filter over exactly the rows this pull folded: the frames are contiguous in est, in the rings up to the
+            // wrap (the filter's bits do not depend on the cut)
+            for (int64_t t = s->Tf; t < Tf;) {
+                const int64_t slot = t % s->rf, n = std::min(Tf - t, s->rf - slot), row = t - s->Tf;
+                DCS_CHECK(dcs_mwf_online_push_f32(s->mwf, s->mag + slot * s->F, s->phase + slot * s->F, s->rf * s->F,
+                                                  s->est + row * s->F, (int64_t)s->S * s->ff * s->F, s->ff * s->F, s->F, n, 1.f,
+                                                  s->fmag + row * s->F, s->fphase + row * s->F));
+                t += n;
+            }
+        }
         const int M = N / 2;
         size_t lds = (3 * (size_t)M + 2) * sizeof(float2);
         const int tw_lds = lds <= 64 * 1024;
         if (!tw_lds) lds = (2 * (size_t)M + 1) * sizeof(float2);
+        auto inverse = s->mwf ? stream_inverse_kernel<true> : stream_inverse_kernel<false>;
         if (lds > 48 * 1024)
-            DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stream_inverse_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            DCS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(inverse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         DcsTimer tm(s->ctx, DCS_TAG_ISTFT);
-        hipLaunchKernelGGL(stream_inverse_kernel, dim3((unsigned)n_fold, (unsigned)s->S, (unsigned)s->nch), dim3(kThreads), lds, q,
-                           (const float*)s->est, s->ff * s->F, (const float*)s->phase, s->rf, s->Tf, s->tf, s->rt, s->S,
-                           (const float*)s->plan->win_f, (const float2*)s->plan->tw_f, N, s->plan->log2m,
+        hipLaunchKernelGGL(inverse, dim3((unsigned)n_fold, (unsigned)s->S, (unsigned)s->nch), dim3(kThreads), lds, q,
+                           (const float*)(s->mwf ? s->fmag : s->est), s->ff * s->F, (const float*)(s->mwf ? s->fphase : s->phase), s->rf,
+                           s->Tf, s->tf, s->rt, s->S, (const float*)s->plan->win_f, (const float2*)s->plan->tw_f, N, s->plan->log2m,
                            (float)sqrt((double)N), tw_lds);
         tm.done();
         DCS_HIP(hipGetLastError());
@@ -905,6 +1003,7 @@ int stream_pull(const char* who, dcs_stream* s, const float* p_d, int64_t p_src_
         tm.done();
         DCS_HIP(hipGetLastError());
     }
+    s->mwf_rows = n_fold;
     s->Tf = Tf; s->E = E;
     s->want_pull = false;
     if (n_out) *n_out = n_pcm;

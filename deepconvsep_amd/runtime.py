@@ -614,6 +614,7 @@ class Stream(object):
     def reset(self):
         _lib.check(self.ctx._lib.dcs_stream_reset(self._h))
         self.pushed, self.ended = 0, False
+        self.last_folded = 0
         self._tiles = self._frames = self._folded = self._emitted = 0
 
     def close(self):
@@ -628,7 +629,30 @@ class Stream(object):
             pass
 
 
-class ChannelStream(Stream):
+class _StreamMwf(object):
+    """``dcs_stream_set_mwf`` / ``dcs_stream_mwf_last`` for the two-channel streams."""
+
+    def set_mwf(self, niter, forget=1.0, loading=1e-3, eps=1e-10):
+        """Arms the online multichannel Wiener filter (:class:`MwfOnline`, ``J = S``) for the pulls of this stream: before the
+        first push, or after ``reset``; ``niter = 0`` turns it off.  Two channels only.  The filtered stems replace the masked
+        ones in what ``pull`` returns; ``want_est`` still gives the unfiltered estimates.  The first frames of a signal are
+        filtered on little evidence: this is not the whole-file filter."""
+        _lib.check(self.ctx._lib.dcs_stream_set_mwf(self._h, int(niter), float(forget), float(loading), float(eps)))
+        self.mwf_iters = int(niter)
+
+    @_on_ctx_stream
+    def last_mwf(self):
+        """The filtered magnitudes and phases of the frames the last pull folded, ``[C, S, rows, F]`` each."""
+        torch = _torch()
+        rows = int(getattr(self, "last_folded", 0))
+        mag = torch.empty((self.C, self.S, rows, self.F), dtype=torch.float32, device=self.ctx.device)
+        ph = torch.empty((self.C, self.S, rows, self.F), dtype=torch.float32, device=self.ctx.device)
+        _lib.check(self.ctx._lib.dcs_stream_mwf_last(self._h, _ptr(mag) if rows else None, _ptr(ph) if rows else None,
+                                                     self.S * rows * self.F, rows * self.F, self.F))
+        return mag, ph
+
+
+class ChannelStream(_StreamMwf, Stream):
     """``dcs_stream_create_channels``: a :class:`Stream` that carries ``channels`` signal channels next to the down-mix the
     network sees -- one ring of ``p``, one fold per (frame, bin), an inverse per (channel, source).  The counts, the alternation
     and ``reset`` / ``close`` / ``bytes`` / ``max_tiles`` are the mono stream's."""
@@ -696,13 +720,13 @@ class ChannelStream(Stream):
                                                           self.S * n_fold * self.F, n_fold * self.F, self.F))
         self._emitted += got.value
         self._folded += n_fold
-        self.last_samples = got.value
+        self.last_samples, self.last_folded = got.value, n_fold
         if got.value != n_pcm:
             raise _lib.DcsError("dcs_stream_pull_channels returned %d samples, the host counts say %d" % (got.value, n_pcm))
         return (pcm, est) if want_est else pcm
 
 
-class StereoStream(Stream):
+class StereoStream(_StreamMwf, Stream):
     """``dcs_stream_create_stereo``: a :class:`Stream` for the stereo (ILD) graph -- ``channels`` rows of samples, magnitudes and
     phases and no down-mix; ``push`` returns tiles in the row layout ``[n_new, tc, C, ld]`` that
     :meth:`Network.forward_stereo_tiles` takes, ``pull`` takes ``p`` per (source, channel) and folds the stereo trainer's
@@ -778,7 +802,7 @@ class StereoStream(Stream):
                                                         self.S * n_fold * self.F, n_fold * self.F, self.F))
         self._emitted += got.value
         self._folded += n_fold
-        self.last_samples = got.value
+        self.last_samples, self.last_folded = got.value, n_fold
         if got.value != n_pcm:
             raise _lib.DcsError("dcs_stream_pull_stereo returned %d samples, the host counts say %d" % (got.value, n_pcm))
         return (pcm, est) if want_est else pcm
@@ -811,6 +835,64 @@ class ScoreStream(Stream):
         return self.ctx._lib.dcs_stream_create_score(self.plan._h, self.S, self.tc, overlap, tiler, eps_mode, scale, rise_p,
                                                      self.max_push, m.ctypes.data_as(POINTER(c_double)), int(m.shape[0]),
                                                      int(m.shape[1]), int(m.shape[2]), self._codes[0], self._codes[1], byref(h))
+
+
+class MwfOnline(object):
+    """``dcs_mwf_online``: the multichannel Wiener filter on a stream -- a causal form of :meth:`Context.mwf` whose state is
+    one Hermitian 2x2 matrix per (source, bin), whatever the length of the signal.  ``push`` filters the next frames; the
+    result does not depend on how the frames are cut into pushes.  ``forget`` in (0, 1] weighs the past down per frame,
+    ``loading`` adds that fraction of an isotropic covariance to every spatial covariance (without it the first frame's are of
+    rank one).  It is not the batch filter and is not expected to match it: the first frames of a signal are filtered on
+    little evidence."""
+
+    def __init__(self, ctx, F, J, niter, forget=1.0, loading=1e-3, eps=1e-10):
+        self.ctx, self.F, self.J, self.niter = ctx, int(F), int(J), int(niter)
+        h = c_void_p()
+        _lib.check(ctx._lib.dcs_mwf_online_create(ctx._h, self.F, self.J, self.niter, float(forget), float(loading), float(eps),
+                                                  byref(h)))
+        self._h = h
+
+    @property
+    def bytes(self):
+        return int(self.ctx._lib.dcs_mwf_online_bytes(self._h))
+
+    @property
+    def frames(self):
+        """Frames pushed since the filter was made or reset."""
+        return int(self.ctx._lib.dcs_mwf_online_frames(self._h))
+
+    @_on_ctx_stream
+    def push(self, mag, phase, src, pre_div=1.0):
+        """``mag``, ``phase`` ``[2, n, F]`` (the mixture), ``src`` ``[2, J, n, F]`` (per-channel source magnitudes, divided by
+        ``pre_div`` before use), float32 device tensors -> (magnitudes, phases) of the filtered images, both ``[2, J, n, F]``."""
+        torch = _torch()
+        if mag.dim() != 3 or src.dim() != 4 or tuple(phase.shape) != tuple(mag.shape) or int(mag.shape[0]) != 2 \
+                or tuple(src.shape) != (2, self.J, int(mag.shape[1]), self.F) or int(mag.shape[2]) != self.F:
+            raise ValueError("MwfOnline.push expects mag, phase [2, n, %d] and src [2, %d, n, %d], got %r, %r, %r"
+                             % (self.F, self.J, self.F, tuple(mag.shape), tuple(phase.shape), tuple(src.shape)))
+        if any(t.dtype != torch.float32 or t.device != self.ctx.device for t in (mag, phase, src)):
+            raise ValueError("MwfOnline.push expects float32 tensors on %s" % (self.ctx.device,))
+        mag, phase, src = mag.contiguous(), phase.contiguous(), src.contiguous()
+        J, T, F = self.J, int(mag.shape[1]), self.F
+        out_mag = torch.empty((2, J, T, F), dtype=torch.float32, device=src.device)
+        out_phase = torch.empty((2, J, T, F), dtype=torch.float32, device=src.device)
+        _lib.check(self.ctx._lib.dcs_mwf_online_push_f32(self._h, _ptr(mag), _ptr(phase), T * F, _ptr(src), J * T * F, T * F, F, T,
+                                                         float(pre_div), _ptr(out_mag), _ptr(out_phase)))
+        return out_mag, out_phase
+
+    def reset(self):
+        _lib.check(self.ctx._lib.dcs_mwf_online_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.dcs_mwf_online_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def tile(ctx, mag_t, time_context, overlap, tiler, scale=1.0):

@@ -533,22 +533,27 @@ class Separator(object):
         from .streaming import ScoreStreamSeparator
         return ScoreStreamSeparator(self, melody, max_block=max_block)
 
-    def stream_channels(self, max_block=65536):
+    def stream_channels(self, max_block=65536, mwf_iters=0, mwf_forget=1.0, mwf_loading=1e-3):
         """A :class:`deepconvsep_amd.streaming.ChannelStreamSeparator` on this separator's model and plan: the stereo stems of
-        :meth:`separate_channels` (without the Wiener filter) on a stream -- ``push(block [n, 2])`` at 44 100 Hz, finished stems
-        ``[n_i, S, 2]`` back.  ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes any other rate.
+        :meth:`separate_channels` on a stream -- ``push(block [n, 2])`` at 44 100 Hz, finished stems ``[n_i, S, 2]`` back.
+        ``mwf_iters > 0``: that many iterations per frame of the ONLINE multichannel Wiener filter (``runtime.MwfOnline``,
+        ``mwf_forget`` in (0, 1], ``mwf_loading >= 0``) -- a causal filter, not the whole-file one of
+        ``separate_channels(mwf_iters=...)`` and not expected to match it: the first frames of a signal are filtered on little
+        evidence.  ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes any other rate.
         Single-input-channel graphs only (``ValueError`` otherwise)."""
         from .streaming import ChannelStreamSeparator
-        return ChannelStreamSeparator(self, max_block=max_block)
+        return ChannelStreamSeparator(self, max_block=max_block, mwf_iters=mwf_iters, mwf_forget=mwf_forget,
+                                      mwf_loading=mwf_loading)
 
-    def stream_stereo(self, max_block=65536):
+    def stream_stereo(self, max_block=65536, mwf_iters=0, mwf_forget=1.0, mwf_loading=1e-3):
         """A :class:`deepconvsep_amd.streaming.StereoStreamSeparator` on this separator's model and plan: the stereo stems of
-        :meth:`separate_stereo` (without the Wiener filter, which needs the whole signal) on a stream -- ``push(block [n, 2])``
-        at 44 100 Hz, finished stems ``[n_i, S, 2]`` back.  ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes
-        any other rate.  The ``dsd_ild`` graph only (``ValueError`` otherwise); :meth:`stream` and :meth:`stream_channels` keep
-        refusing that graph."""
+        :meth:`separate_stereo` on a stream -- ``push(block [n, 2])`` at 44 100 Hz, finished stems ``[n_i, S, 2]`` back.
+        ``mwf_iters``, ``mwf_forget``, ``mwf_loading`` as in :meth:`stream_channels`: the online filter, not the whole-file one.
+        ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes any other rate.  The ``dsd_ild`` graph only
+        (``ValueError`` otherwise); :meth:`stream` and :meth:`stream_channels` keep refusing that graph."""
         from .streaming import StereoStreamSeparator
-        return StereoStreamSeparator(self, max_block=max_block)
+        return StereoStreamSeparator(self, max_block=max_block, mwf_iters=mwf_iters, mwf_forget=mwf_forget,
+                                     mwf_loading=mwf_loading)
 
     @_on_ctx_stream
     def channel_spectra(self, a3, want_p=False):

@@ -243,6 +243,10 @@ class ChannelStreamSeparator(object):
     """``Separator.stream_channels()``: stereo stems from a mono model on a stream -- what ``Separator.separate_channels``
     computes on a whole file (the cross-faded masks of the down-mix on each channel's own magnitudes, inverted with that
     channel's phase), block by block on ONE engine (``dcs_stream_create_channels``): one ring of ``p``, one fold.
+    ``mwf_iters > 0``: every pull sends the frames it folded through that many iterations of the ONLINE multichannel Wiener
+    filter (``runtime.MwfOnline``; ``mwf_forget``, ``mwf_loading`` its parameters) before the inverse, each (channel, source)
+    then with its own phase.  That filter is causal -- it is not ``separate_channels(mwf_iters=...)`` and does not match it: the
+    first frames of a signal are filtered on little evidence.
 
     ``push(block)`` takes the next samples ``[n, 2]`` of a 44 100 Hz signal and returns the float64 samples ``[n_i, S, 2]`` that
     became final, ``finish()`` ends the signal and returns the rest.  The down-mix the network sees is formed on the host in
@@ -253,10 +257,11 @@ class ChannelStreamSeparator(object):
     channels = 2
     rows_in = 3                      # signal rows a device block carries: L, R, down-mix
 
-    def __init__(self, separator, max_block=65536):
+    def __init__(self, separator, max_block=65536, mwf_iters=0, mwf_forget=1.0, mwf_loading=1e-3):
         separator._require_mono_graph("stream_channels")
         if int(max_block) < 1:
             raise ValueError("max_block must be at least 1 sample")
+        self._set_mwf(mwf_iters, mwf_forget, mwf_loading)
         self.sep, self.ctx = separator, separator.ctx
         self.max_block = int(max_block)
         self.counts = StreamCounts(separator.frameSize, separator.hopSize, separator.tc, separator.overlap, separator.tiler)
@@ -267,12 +272,22 @@ class ChannelStreamSeparator(object):
     def S(self):
         return self.sep.net.S
 
+    def _set_mwf(self, iters, forget, loading):
+        self.mwf = (int(iters), float(forget), float(loading))
+        if not 0 <= self.mwf[0] <= 100:
+            raise ValueError("mwf_iters %d not in 0 .. 100" % self.mwf[0])
+
+    def _arm(self, engine):
+        if self.mwf[0]:
+            engine.set_mwf(self.mwf[0], forget=self.mwf[1], loading=self.mwf[2])
+        return engine
+
     def _stream(self):
         if self._engine is None:
             from .runtime import ChannelStream
             s = self.sep
-            self._engine = ChannelStream(s.plan, s.net.S, self.channels, s.tc, s.overlap, s.tiler, s.net.arch.eps_mode,
-                                         s.scale_factor, self.max_block)
+            self._engine = self._arm(ChannelStream(s.plan, s.net.S, self.channels, s.tc, s.overlap, s.tiler, s.net.arch.eps_mode,
+                                                   s.scale_factor, self.max_block))
         return self._engine
 
     def _step(self, piece, last):
@@ -350,17 +365,19 @@ class StereoStreamSeparator(ChannelStreamSeparator):
     became final, ``finish()`` ends the signal and returns the rest; ``push_device`` / ``finish_device`` take float32 device
     tensors ``[2, n]`` and return ``[2, S, n_i]``.  Between the two halves of the stream the tiles that became ready go through
     ``net.forward_stereo_tiles``.  ``reset``, ``device_bytes`` and ``counts`` as in the other classes.  The ``dsd_ild`` graph
-    only (``ValueError`` otherwise).  There is no Wiener filter on a stream (``separate_stereo(mwf_iters=...)``): its statistics
-    run over the whole signal."""
+    only (``ValueError`` otherwise).  ``mwf_iters > 0`` arms the ONLINE multichannel Wiener filter as in
+    :class:`ChannelStreamSeparator`: causal, not ``separate_stereo(mwf_iters=...)``, whose statistics run over the whole
+    signal, and not expected to match it -- the first frames of a signal are filtered on little evidence."""
 
     rows_in = 2                      # signal rows a device block carries: no down-mix
 
-    def __init__(self, separator, max_block=65536):
+    def __init__(self, separator, max_block=65536, mwf_iters=0, mwf_forget=1.0, mwf_loading=1e-3):
         if separator.arch_name != 'dsd_ild':
             raise ValueError("stream_stereo runs the stereo (ILD) graph; '%s' takes %d input channel(s): use stream() or "
                              "stream_channels()" % (separator.arch_name, separator.net.arch.C))
         if int(max_block) < 1:
             raise ValueError("max_block must be at least 1 sample")
+        self._set_mwf(mwf_iters, mwf_forget, mwf_loading)
         self.sep, self.ctx = separator, separator.ctx
         self.max_block = int(max_block)
         # the library tiler whatever the separator's: the stereo trainer calls util.generate_overlapadd (separate_stereo)
@@ -372,8 +389,8 @@ class StereoStreamSeparator(ChannelStreamSeparator):
         if self._engine is None:
             from .runtime import StereoStream
             s = self.sep
-            self._engine = StereoStream(s.plan, s.net.S, self.channels, s.tc, s.overlap, TILER_LIBRARY, s.scale_factor,
-                                        self.max_block)
+            self._engine = self._arm(StereoStream(s.plan, s.net.S, self.channels, s.tc, s.overlap, TILER_LIBRARY, s.scale_factor,
+                                                  self.max_block))
         return self._engine
 
     def _step(self, piece, last):

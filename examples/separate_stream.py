@@ -1,8 +1,8 @@
 """Separate a 16-bit PCM wav file block by block: neither the file nor its stems are ever whole in memory.
 
-    python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536] [--stereo] [--resample]
+    python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536] [--stereo [--mwf N]] [--resample]
     python examples/separate_stream.py -a bach10_si -i mix.wav -o outdir -m model.pkl [--trainer-semantics] [--resample]
-    python examples/separate_stream.py -a dsd_ild -i stereo_mix.wav -o outdir -m model.pkl [--block 65536] [--resample]
+    python examples/separate_stream.py -a dsd_ild -i stereo_mix.wav -o outdir -m model.pkl [--block 65536] [--mwf N] [--resample]
 
 The file is read with the standard ``wave`` module ``--block`` frames at a time; each block is scaled and mixed down the way
 the architecture's separate script does it (element-wise, so block by block equals the whole file), pushed into
@@ -24,8 +24,13 @@ option).  ``--stereo`` does not apply.
 
 ``-a dsd_ild``: the stereo (ILD) DSD100 graph (``Separator.stream_stereo``), which sees both channels: a two-channel file gives
 one two-channel stem per source under the names ``examples/dsd100_2ch_ILD/separate_dsd_ild.py`` uses (``<outdir>/<source>.wav``),
-with that script's hyper-parameters.  ``--stereo`` is implied (and accepted); a mono file is refused.  No Wiener filter
-(``--mwf`` of that script): it needs the whole signal.
+with that script's hyper-parameters.  ``--stereo`` is implied (and accepted); a mono file is refused.
+
+``--mwf N`` (with ``--stereo`` or ``-a dsd_ild`` only, as in the whole-file scripts): N iterations per frame of the ONLINE
+multichannel Wiener filter between the masks and the inverse transform (``--mwf-forget X``, default 1: how much of the past
+every frame keeps; ``--mwf-loading X``, default 1e-3: the isotropic share of every spatial covariance).  It is a causal filter
+with constant memory -- not the whole-file filter of ``separate_dsd.py --stereo --mwf N`` and not expected to match it: the
+first frames of a file are filtered on little evidence.
 """
 import argparse
 import os
@@ -63,7 +68,14 @@ def main(argv=None):
     ap.add_argument("--resample", action="store_true", help="take any sample rate; the stems keep the file's rate")
     ap.add_argument("--trainer-semantics", action="store_true",
                     help="bach10_si: masks / their sum over the instruments, soft masks x the channel sum")
+    ap.add_argument("--mwf", type=int, default=0, metavar="N",
+                    help="iterations per frame of the online multichannel Wiener filter (with --stereo or -a dsd_ild)")
+    ap.add_argument("--mwf-forget", type=float, default=1.0, metavar="X", help="online filter: weight of the past per frame, (0, 1]")
+    ap.add_argument("--mwf-loading", type=float, default=1e-3, metavar="X", help="online filter: isotropic share of the covariances")
     args = ap.parse_args(argv)
+    if args.mwf and not (args.stereo or args.arch == "dsd_ild"):    # the Wiener filter works on two-channel estimates
+        ap.print_usage()
+        sys.exit(2)
     score = args.arch == "bach10_si"
     if score and args.stereo:
         raise SystemExit("--stereo does not apply to bach10_si: the score-informed graphs take one channel per instrument")
@@ -79,6 +91,7 @@ def main(argv=None):
     from deepconvsep_amd.streaming import RateStream
 
     frame, hop, window, overlap, bins = ILD_DEFAULTS if ild else _SCRIPT_DEFAULTS[args.arch]
+    mwf = dict(mwf_iters=args.mwf, mwf_forget=args.mwf_forget, mwf_loading=args.mwf_loading)
     src = wave.open(args.input, "rb")
     if src.getsampwidth() != 2 or src.getcomptype() != "NONE":
         raise SystemExit("%s is not a 16-bit PCM wav file" % args.input)
@@ -102,10 +115,10 @@ def main(argv=None):
         stream = sep.stream_scoreinformed(melody, max_block=args.block)
     elif ild:
         sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
-        stream = sep.stream_stereo(max_block=args.block)
+        stream = sep.stream_stereo(max_block=args.block, **mwf)
     else:
         sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
-        stream = sep.stream_channels(max_block=args.block) if args.stereo else sep.stream(max_block=args.block)
+        stream = sep.stream_channels(max_block=args.block, **mwf) if args.stereo else sep.stream(max_block=args.block)
     if rate != 44100:
         stream = RateStream(stream, rate)
     os.makedirs(args.outdir, exist_ok=True)

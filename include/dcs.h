@@ -466,6 +466,42 @@ DCS_API int dcs_mwf_f32(dcs_ctx* ctx, const float* mag_d, const float* phase_d, 
  * pass adds up min(ceil(n_frames / this), 32) sets of sums */
 DCS_API int dcs_mwf_frames_per_block(void);
 
+/* The same filter on a stream (csrc/mwf_online.hip): a causal form whose state per (source, bin) is one Hermitian 2x2 matrix,
+ * S_j[f], four float64 -- constant memory however long the signal is.  X and A as in dcs_mwf_f32; every bin f is independent,
+ * t is the ABSOLUTE frame since create or reset:
+ *   init:   y_j = (A[0,j] e^{i phase[0]}, A[1,j] e^{i phase[1]}),  C_j = y_j y_j^H,  v_j = tr(C_j) / 2
+ *           G_j = forget * S_j[t-1]              (zero at t = 0: the state is NOT read for frame 0)
+ *   niter times:
+ *           N_j = G_j + C_j,   n_j = Re tr(N_j) / 2
+ *           R_j = (N_j + loading n_j I) / ((1 + loading) n_j + eps)
+ *           Cx  = sum_j v_j R_j + eps I  (j increasing),   W_j = v_j R_j Cx^{-1},   y_j = W_j x
+ *           C_j = y_j y_j^H + (I - W_j) v_j R_j,   v_j = Re tr(C_j) / 2
+ *   after:  S_j[t] = G_j + C_j
+ *   out:    |y_j[c]|, angle(y_j[c]) (0 where y is 0), float32
+ * R_j is the running (forget < 1: exponentially forgetting) average of the posterior covariances of the frames so far and of
+ * THIS frame's current one, normalised to unit mean trace; `loading` adds that fraction of an isotropic covariance, without
+ * which frame 0 has a rank-1 R_j and, where every estimate is a mask times the same mixture, a Cx singular up to eps.  It is
+ * NOT the batch filter and is not expected to match it: the first frames of a signal are filtered on little evidence.
+ * niter = 0 returns src / pre_div and the mixture's phases bit for bit and keeps no state.  Phasors, 2x2 algebra and state are
+ * float64, inputs and outputs float32; v_j never leaves registers.  A push filters the absolute frames frames .. frames +
+ * n_frames - 1 and advances the count: ONE launch on the ctx stream, one lane per bin with the J sources in registers, time
+ * serial, every sum in a fixed order, no atomics -- the same bits every run and however the frames are cut into pushes.
+ * Layouts and strides are those of dcs_mwf_f32; columns F .. ld-1 of the outputs are not written.  reset sets the count to 0
+ * and touches no device memory; bytes (the state, [J][4][F] float64 rounded up to 256 bytes) depends on (F, J) alone.
+ * DCS_EINVAL for J outside 1 .. 8, niter outside 0 .. 100, F < 1, ld < F, forget outside (0, 1], loading negative or not finite,
+ * eps <= 0 or below DBL_MIN, pre_div <= 0, n_frames < 0, a stride below n_frames * ld, or a NULL pointer; n_frames == 0 does
+ * nothing. */
+typedef struct dcs_mwf_online dcs_mwf_online;
+DCS_API int dcs_mwf_online_create(dcs_ctx* ctx, int F, int J, int niter, double forget, double loading, double eps,
+                                  dcs_mwf_online** out);
+DCS_API int dcs_mwf_online_destroy(dcs_mwf_online* h);
+DCS_API int dcs_mwf_online_reset(dcs_mwf_online* h);
+DCS_API int64_t dcs_mwf_online_bytes(const dcs_mwf_online* h);  /* -1 for NULL */
+DCS_API int64_t dcs_mwf_online_frames(const dcs_mwf_online* h); /* frames pushed since create or reset; -1 for NULL */
+DCS_API int dcs_mwf_online_push_f32(dcs_mwf_online* h, const float* mag_d, const float* phase_d, int64_t ch_stride,
+                                    const float* src_d, int64_t src_ch_stride, int64_t src_stride, int64_t ld, int64_t n_frames,
+                                    float pre_div, float* out_mag_d, float* out_phase_d);
+
 /* ------------------------------------------------------------------ per-channel masks of the mono models (csrc/chanmask.hip) */
 /* Every published model but the ILD one sees a mono down-mix (separate_dsd.py:285-287, separate_ikala.py:229) and the scripts
  * write mono stems.  This applies the network's soft masks (separate_dsd.py:258-271, separate_bach10.py:251-264), cross-faded
@@ -629,6 +665,21 @@ DCS_API int dcs_stream_pull_stereo(dcs_stream* s, const float* p_d, int64_t p_sr
 DCS_API int dcs_stream_create_score(dcs_stft* plan, int S, int time_context, int overlap, int tiler, int eps_mode, float scale,
                                     const double* rise_h, int64_t max_push, const double* notes_h, int ninst, int n_notes,
                                     int width, int normalise, int mixture, dcs_stream** out);
+
+/* The multichannel Wiener filter on a channel or stereo stream of C == 2 channels: the online filter of dcs_mwf_online_* (J = S
+ * sources, its state in the stream).  Called before the first push, or after a reset; niter = 0 turns the filter off again.
+ * With it on, a pull runs the fold as before, then the filter over exactly the rows this pull folded -- X from the magnitude and
+ * phase rings, A = the fold's estimates, pre_div = 1 -- into two buffers [C][S][ff][F] of filtered magnitudes and phases, then
+ * the inverse on THOSE (a phase per (channel, source)), then the gather.  est_d of the pull still receives the unfiltered
+ * estimates; dcs_stream_mwf_last copies out the filtered rows of the last pull, mag_d / phase_d [C][S][rows, ld] (strides in
+ * elements; rows = the frames that pull folded; columns past the bins are not written).  The filter is causal and its bits do
+ * not depend on the cut, so the stream keeps its contract; it is not the batch filter of dcs_mwf_f32 and the first frames of a
+ * signal are filtered on little evidence.  dcs_stream_bytes grows by the two buffers and dcs_mwf_online_bytes -- a function of
+ * the shapes alone -- and a stream whose filter was never armed allocates, launches and computes what it did without it.
+ * DCS_EINVAL for a mono or score stream, C != 2, a stream that has samples, or values dcs_mwf_online_create refuses;
+ * dcs_stream_mwf_last: the filter off, a NULL buffer, ld below the bins or strides below the rows. */
+DCS_API int dcs_stream_set_mwf(dcs_stream* s, int niter, double forget, double loading, double eps);
+DCS_API int dcs_stream_mwf_last(dcs_stream* s, float* mag_d, float* phase_d, int64_t ch_stride, int64_t src_stride, int64_t ld);
 
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
 /* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is

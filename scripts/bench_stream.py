@@ -3,6 +3,7 @@ tile), run the tile through the network, pull the finished samples -- and of the
 left out (a fixed ``p``).  Each step ends with a stream synchronisation, as a live caller that plays the samples would.
 
     python scripts/bench_stream.py [--steps 200] [--warmup 20] [--channels 2] [--rate 48000] [--score] [--ild [--block 65536]]
+                                   [--mwf N [--block 65536]]
 
 ``--channels 2`` adds, in the same run, the stereo step on one channel engine (``Separator.stream_channels()``) and the stereo
 step composed of three mono ``runtime.Stream`` engines -- L, R and the down-mix -- that share one ``p``, which is what the mono
@@ -14,6 +15,9 @@ score as long as the run: ``Separator.stream_scoreinformed``, one launch more fo
 ``bach10`` stream's step at the same shape, and the device bytes of both.  ``--ild`` adds the step of the stereo (ILD) graph's own
 stream (``Separator.stream_stereo``: two-channel tiles, ``forward_stereo_tiles``, the per-channel fold; 7 launches + the network
 call) next to the mono DSD stream's step, both with blocks of ``--block`` samples (default: one stride), and the bytes of both.
+``--mwf N`` adds the steps of the ``dsd`` channel stream and of the ``dsd_ild`` stream with N iterations of the online Wiener
+filter per frame (one launch more per step, two when the pull's frames wrap in the rings) next to the same streams' steps without
+it, all four with blocks of ``--block`` samples, and the device bytes of the four.
 
 Prints one JSON line: the median and mean wall time per step in milliseconds, next to the block's duration in audio time."""
 import argparse
@@ -35,7 +39,8 @@ def main(argv=None):
     ap.add_argument("--rate", type=int, default=44100)
     ap.add_argument("--score", action="store_true")
     ap.add_argument("--ild", action="store_true")
-    ap.add_argument("--block", type=int, default=0, help="--ild: samples per push (default one stride)")
+    ap.add_argument("--block", type=int, default=0, help="--ild, --mwf: samples per push (default one stride)")
+    ap.add_argument("--mwf", type=int, default=0, help="iterations of the online Wiener filter on the two-channel streams")
     args = ap.parse_args(argv)
     import torch
     import deepconvsep_amd as dcs
@@ -145,6 +150,22 @@ def main(argv=None):
         extra.update({"ild_block_samples": B, "ild_step_ms_median": med(ild), "ild_step_ms_max": round(float(ild.max()), 4),
                       "ild_mono_dsd_step_ms_median": med(mono), "ild_launches_per_step": 7 + 1,
                       "ild_device_bytes": si.device_bytes, "ild_mono_dsd_device_bytes": sm.device_bytes})
+    if args.mwf:
+        B = args.block or block
+        fill = -(-tc * hop // B) + 1
+        base = 0.5 * synth_audio(8 * B, seed=4, channels=2)                                   # repeated: the values do not matter
+        a2 = ctx.to_device(np.ascontiguousarray(base.T), np.float32).repeat(1, (total + fill) // 8 + 1)
+        a3 = torch.cat([a2, 0.5 * (a2[:1] + a2[1:])])
+        sep_i = dcs.Separator("dsd_ild", synth_params("dsd_ild", tc, F, seed=7), 0.3, tc, ov, 32, F, N, hop, np.hanning,
+                              tiler='library', ctx=ctx)
+        extra.update({"mwf_iters": args.mwf, "mwf_block_samples": B, "mwf_frames_per_step": B // hop})
+        for tag, make, sig in (("channels", sep.stream_channels, a3), ("ild", sep_i.stream_stereo, a2)):
+            for name, iters in (("plain", 0), ("mwf", args.mwf)):
+                st = make(max_block=B, mwf_iters=iters)
+                t = timed(lambda i: st.push_device(sig[:, i * B:(i + 1) * B]), fill)
+                extra.update({"mwf_%s_%s_step_ms_median" % (tag, name): med(t),
+                              "mwf_%s_%s_step_ms_max" % (tag, name): round(float(t.max()), 4),
+                              "mwf_%s_%s_device_bytes" % (tag, name): st.device_bytes})
     print(json.dumps({"bench": "stream", "graph": "dsd", "bins": F, "block_samples": block,
                       "block_audio_ms": round(1e3 * block / 44100.0, 3), "steps": args.steps,
                       "step_ms_median": round(float(np.median(full)), 4), "step_ms_mean": round(float(full.mean()), 4),
