@@ -20,6 +20,8 @@ from .score_training import ScoreFeatureWindows, ScoreTrainer
 from . import augment
 from .augment import RenderedWindows, render_features
 from .score_render import ScoreInformedRenderedWindows, render_score_informed_features
+from . import align
+from .align import (align_scores, bin_classes, chroma, dtw, score_chroma, time_map, warp_times)
 
 __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "TILER_SCRIPT", "TransformFFT",
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
@@ -27,4 +29,5 @@ __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "
            "overlapadd_multi", "train_auto", "bss_eval", "bss_eval_images", "bss_eval_sources", "mwf", "MwfOnline", "Resampler", "resample", "StreamCounts", "StreamSeparator",
            "ChannelStreamSeparator", "ScoreStreamSeparator", "StereoStreamSeparator", "RateStream", "ResampleCounts", "StreamResampler", "Trainer", "FeatureWindows", "glorot_init",
            "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features",
-           "ScoreInformedRenderedWindows", "render_score_informed_features"]
+           "ScoreInformedRenderedWindows", "render_score_informed_features", "align", "align_scores", "bin_classes", "chroma", "dtw",
+           "score_chroma", "time_map", "warp_times"]

@@ -129,6 +129,10 @@ def load():
     proto("dcs_debug_d1_aux", i32, vp, i32, vp)
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
+    proto("dcs_chroma", i32, vp, vp, i64, i64, i32, vp, f32, vp)
+    proto("dcs_dtw_tile", i32)
+    proto("dcs_dtw_bytes", i64, i64, i64, i64)
+    proto("dcs_dtw", i32, vp, vp, i64, vp, i64, i64, vp, vp, vp)
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)
     proto("dcs_mwf_frames_per_block", i32)
     proto("dcs_mwf_online_create", i32, vp, i32, i32, i32, f64, f64, f64, POINTER(vp))

@@ -322,6 +322,7 @@ extern "C" int dcs_destroy(dcs_ctx* ctx) {
     ctx->gemm_ws.release();
     ctx->bss_ws.release();
     ctx->mwf_ws.release();
+    ctx->align_ws.release();
     ctx->score_ring.release();
     dcs_dev_free(ctx->ola_rise_d);
     delete ctx;

@@ -150,6 +150,7 @@ struct dcs_ctx {
     DcsUploadRing score_ring;  // note rectangles and floor values of dcs_score_masks
     DcsBuffer bss_ws;          // dcs_bss_energies / dcs_bss_lagcorr: segment sums, lag correlations, Gram matrices
     DcsBuffer mwf_ws;          // dcs_mwf_f32: v [J][T][F] float32 and the two sets of per-chunk sums
+    DcsBuffer align_ws;        // dcs_dtw: the three strips between tiles, the path from the back, the direction codes
     // which kernel the last GEMM launch took (DCS_GEMM_K_*, 0 = none yet) and {ksplit, kchunk, row blocks of 16 per workgroup, Aq used}
     // (0 where there is none): dcs_debug_gemm_last_kernel, a test aid -- one host store per launch
     int last_gemm = 0;

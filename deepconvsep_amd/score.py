@@ -88,6 +88,15 @@ def read_score(path):
     return np.asarray(on, dtype=np.float32).astype(np.float64), np.asarray(off, dtype=np.float32).astype(np.float64), names
 
 
+def write_score(path, on, off, names):
+    """The inverse of :func:`read_score`: one line ``onset,offset,name`` per note, the times as the shortest decimals that
+    give the same float32 back."""
+    with open(path, "w") as fh:
+        for a, b, name in zip(on, off, names):
+            fh.write("%s,%s,%s\n" % (np.format_float_positional(np.float32(a), unique=True, trim="0"),
+                                     np.format_float_positional(np.float32(b), unique=True, trim="0"), name))
+
+
 def _score_path(instrument, FilePath):
     p = os.path.join(FilePath, instrument)
     return p if os.path.isfile(p) or instrument.endswith(".txt") else p + ".txt"

@@ -727,6 +727,15 @@ def train_auto(arch_name, filein, outdir, model, scale_factor=0.3, time_context=
     ``stereo=True`` (single-channel graphs): a two-channel file gives two-channel stems under the same names
     (``Separator.separate_channels``: the masks of the down-mix on each channel's own spectrum), after ``mwf_iters``
     iterations of the multichannel Wiener filter when that is not 0; a mono file is separated as without it."""
+    return train_auto_scores(None, arch_name, filein, outdir, model, scale_factor, time_context, overlap, batch_size, input_size,
+                             frameSize, hopSize, window, fused, device, score_normalise, score_mixture, resample, stereo, mwf_iters)
+
+
+def train_auto_scores(score_dir, arch_name, filein, outdir, model, scale_factor=0.3, time_context=30, overlap=20, batch_size=32,
+                      input_size=513, frameSize=None, hopSize=None, window=None, fused=True, device=None, score_normalise='max',
+                      score_mixture='ch0', resample=False, stereo=False, mwf_iters=0):
+    """:func:`train_auto` with the four score files of the score-informed graph read from ``score_dir`` (None: the wav's
+    directory) -- where ``separate_bach10.py --align`` has written the aligned ones."""
     if mwf_iters and not stereo:
         raise ValueError("mwf_iters needs stereo=True: the Wiener filter works on two-channel estimates")
     d_frame, d_hop, d_win, _, _ = _SCRIPT_DEFAULTS[arch_name]
@@ -751,7 +760,7 @@ def train_auto(arch_name, filein, outdir, model, scale_factor=0.3, time_context=
             # the frames of the signal the network sees: the file's own samples, or as many as they are at 44 100 Hz
             n44 = len(audio) if sampleRate == 44100 else resampled_length(len(audio), *rate_ratio(sampleRate, TARGET_RATE))
             nframes = int(np.ceil(n44 / np.double(hopSize))) + 2     # :500
-            melody = melody_table(SI_SCORE_FILES, os.path.dirname(filein), nframes, TARGET_RATE, hopSize, frameSize,
+            melody = melody_table(SI_SCORE_FILES, os.path.dirname(filein) if score_dir is None else score_dir, nframes, TARGET_RATE, hopSize, frameSize,
                                   **SI_SCORE_PARAMS)
             pcm = sep.separate_scoreinformed(audio, melody, sample_rate=sampleRate)
         elif sampleRate != 44100:

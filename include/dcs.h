@@ -439,6 +439,38 @@ DCS_API int dcs_bss_energies(dcs_ctx* ctx, const double* ref_d, const double* es
 DCS_API int dcs_bss_lagcorr(dcs_ctx* ctx, const double* ref_d, const double* est_d, int n_ref, int n_est, int64_t n_samples,
                             int flen, double* out_d);
 
+/* ------------------------------------------------------------------ score-to-audio alignment (csrc/align.hip) */
+/* What puts a score at nominal tempo onto the recording before dcs_score_masks paints it (the reference never needed it:
+ * Bach10 ships hand-aligned scores).  Chroma of a magnitude spectrogram: mag_d [n_frames, ld] float32, cls_h [F] on the HOST,
+ * the pitch class 0 .. 11 of every bin or -1 for a bin that is not used (uploaded through the context's ring, no
+ * synchronisation); chroma_d [n_frames][12]:
+ *   c_k = sum_{f: cls[f] = k} mag[t, f],  n = sqrt(sum_k c_k^2),  row = c / n if n > floor, else twelve times 1 / sqrt(12)
+ * One wave per frame, float32 sums (lane-strided partial sums, then one butterfly over the wave); columns F .. ld-1 are never
+ * read.  DCS_EINVAL for F < 1, ld < F, n_frames < 0, a negative or NaN floor, a class outside -1 .. 11 or a NULL pointer;
+ * n_frames == 0 does nothing.  Enqueued on the ctx stream. */
+DCS_API int dcs_chroma(dcs_ctx* ctx, const float* mag_d, int64_t ld, int64_t n_frames, int F, const int8_t* cls_h, float floor,
+                       float* chroma_d);
+/* Dynamic time warping of a_d [T][12] (audio) onto s_d [U][12] (score), float32 throughout:
+ *   c[t,u] = 1 - sum_k a[t,k] s[u,k]  (twelve fused multiply-adds, then one subtraction)
+ *   D[0,0] = c[0,0];  D[t,u] = c[t,u] + best, rounded once, where best = D[t-1,u-1] (code 0), replaced by D[t-1,u] (code 1)
+ *   only if that is strictly smaller, then by D[t,u-1] (code 2) only if that is strictly smaller than the best so far;
+ *   neighbours outside the matrix are +inf.
+ * band >= 0: cell (t, u) is in the band iff |u (T-1) - t (U-1)| <= band (T-1) (int64), every other cell is +inf; band == -1:
+ * no band.  Outputs on the device: path_d [T+U-1][2] int32, rows 0 .. n-1 the cells (t, u) from (0, 0) to (T-1, U-1) in forward
+ * order (the rows behind them are not written), *n_path_d = n (int64), *cost_d = D[T-1,U-1]; when the end cell is +inf, n = 0
+ * and the cost +inf.  Tiles of dcs_dtw_tile() x dcs_dtw_tile() cells, one wave each, lane = row, columns walked skewed; ONE
+ * launch per anti-diagonal of tiles, ordered by the stream (no kernel waits for another workgroup), tiles wholly outside the
+ * band are not launched; then one launch with a single walker, a counted loop of at most T + U - 1 steps.  1 + ceil(T / tile) +
+ * ceil(U / tile) - 1 + 1 launches without a band.  Scratch -- the strips between tiles, the path from the back, 2 bits per cell
+ * of the tiles that touch the band, so about T min(U, 2 band + tile) / 4 bytes -- comes from the context's workspace;
+ * dcs_dtw_bytes reports it (-1 where dcs_dtw would refuse the shape).  DCS_EINVAL for T or U < 1, band < -1, a NULL pointer, or
+ * a band that cannot hold a path: 2 band + 1 < ceil((U-1) / max(T-1, 1)).  DCS_ESHAPE for T or U above 2^20 or scratch above
+ * 2 GiB.  A refused call writes nothing.  Enqueued on the ctx stream; nothing of size T x U leaves the device. */
+DCS_API int dcs_dtw_tile(void);
+DCS_API int64_t dcs_dtw_bytes(int64_t T, int64_t U, int64_t band);
+DCS_API int dcs_dtw(dcs_ctx* ctx, const float* a_d, int64_t T, const float* s_d, int64_t U, int64_t band, int32_t* path_d,
+                    int64_t* n_path_d, float* cost_d);
+
 /* ------------------------------------------------------------------ multichannel Wiener filter (csrc/mwf.hip) */
 /* The filter the reference's authors were transcribing behind their stereo network and never ran: util.py:633-719 mwf(spec,
  * mixture, niter=10) quotes the MATLAB of Duong / Vincent / Gribonval's EM for full-rank spatial covariances (:647-682), stops
