@@ -127,6 +127,8 @@ def load():
     proto("dcs_debug_dsd_last_kernel", i32, vp, POINTER(i32), POINTER(i64))
     proto("dcs_debug_d1_conv", i32, vp, i32, vp)
     proto("dcs_debug_d1_aux", i32, vp, i32, vp)
+    proto("dcs_debug_train_gemm", i32, vp, vp)
+    proto("dcs_debug_train_aux", i32, vp, i32, vp)
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_chroma", i32, vp, vp, i64, i64, i32, vp, f32, vp)

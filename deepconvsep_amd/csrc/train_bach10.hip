@@ -27,14 +27,23 @@ struct Bach10Sums {
 };
 constexpr int kLossSums = Bach10Sums::kOut + Bach10Sums::kDbo;
 
+}  // namespace
+
+// F6, the one launch site of this graph's conv1^T instance (train_ca.h)
+int train::bach10_deconv1(hipStream_t s, const float* g, int64_t gslot, const float* W1i, const float* bo, float* q, int B,
+                          int tc, int F, int w1) {
+    const int64_t n = (int64_t)kSrc * B * tc * F;
+    hipLaunchKernelGGL((deconv1_kernel<kK1, kC1, kS1, kSrc>), dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, s, g,
+                       gslot, W1i, bo, q, B, tc, F, w1);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+namespace {
+
 struct Bach10Trainer : CaTrainer {
     int deconv1() override {
-        const int64_t n = kSrc * RF;
-        hipLaunchKernelGGL((deconv1_kernel<kK1, kC1, kS1, kSrc>), dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads),
-                           0, ctx->stream, (const float*)(GA + Uslot), Uslot, (const float*)param(0),
-                           (const float*)param(bo()), Q, B, tc, F, w1);
-        DCS_HIP(hipGetLastError());
-        return DCS_OK;
+        return bach10_deconv1(ctx->stream, GA + Uslot, Uslot, param(0), param(bo()), Q, B, tc, F, w1);
     }
 
     int loss(const float* x, const float* tgt, double* out7_d) override {

@@ -36,6 +36,20 @@ struct SiSums {
 };
 constexpr int kLossSums = SiSums::kOut + SiSums::kDbo;
 
+}  // namespace
+
+// F6, the one launch site of this graph's conv1^T instance (train_ca.h)
+int train::bach10si_deconv1(hipStream_t s, const float* g, const float* W1i, const float* bo, float* q, int B, int tc, int F,
+                            int w1) {
+    const int64_t n = (int64_t)kSrc * B * tc * F;
+    hipLaunchKernelGGL((deconv1_channels_kernel<kK1, kC1, kS1, kCh>), dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0,
+                       s, g, W1i, bo, q, B, tc, F, w1);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+namespace {
+
 struct SiTrainer : CaTrainer {
     bool full = false;            // the 17-array layout: dead parameters held in `dead`
     int64_t ndead = 0;            // 3 (256 flat + flat) + 12
@@ -46,14 +60,7 @@ struct SiTrainer : CaTrainer {
         if (full) parts.push_back({&dead, ndead});
     }
 
-    int deconv1() override {
-        const int64_t n = kSrc * RF;
-        hipLaunchKernelGGL((deconv1_channels_kernel<kK1, kC1, kS1, kCh>), dim3((unsigned)dcs_cdiv(n, kThreads)),
-                           dim3(kThreads), 0, ctx->stream, (const float*)(GA + Uslot), (const float*)param(0),
-                           (const float*)param(bo()), Q, B, tc, F, w1);
-        DCS_HIP(hipGetLastError());
-        return DCS_OK;
-    }
+    int deconv1() override { return bach10si_deconv1(ctx->stream, GA + Uslot, param(0), param(bo()), Q, B, tc, F, w1); }
 
     int loss(const float* x, const float* tgt, double* out7_d) override {
         MaskLoss a;

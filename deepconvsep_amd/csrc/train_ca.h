@@ -145,6 +145,14 @@ __global__ __launch_bounds__(kThreads) void mask_loss_kernel(const MaskLoss a) {
     block_sums(acc, a.part);
 }
 
+// F6 of the three graph files, each the one launch site of its conv1^T instance: the trainer's deconv1() calls it, and so
+// does dcs_debug_train_aux (train_debug.hip).  g: the first source's slot, source k at + k gslot; q [B][sources][tc][F].
+int ikala_deconv1(hipStream_t s, const float* g, int64_t gslot, const float* W1i, const float* bo, float* q, int B, int tc,
+                  int F, int w1);
+int bach10_deconv1(hipStream_t s, const float* g, int64_t gslot, const float* W1i, const float* bo, float* q, int B, int tc,
+                   int F, int w1);
+int bach10si_deconv1(hipStream_t s, const float* g, const float* W1i, const float* bo, float* q, int B, int tc, int F, int w1);
+
 struct CaTrainer : dcs_trainer {
     CaDesc d;
     int w1 = 0, h2 = 0, w2 = 0, hp = 0, wp = 0, K2 = 0;

@@ -258,7 +258,8 @@ struct dcs_trainer {
 
     float* param(int i) { return state + off[i]; }
     float* grad() { return state + 4 * P4; }
-    int launch(train::Gemm g, train::Tile tile, bool ak, bool bk);
+    // grid (nullable): the grid of the launch
+    int launch(train::Gemm g, train::Tile tile, bool ak, bool bk, dim3* grid_out = nullptr);
     // the slices of a split-K GEMM with M = B rows summed in slice order, then the epilogue: C[m][n] (row-major, ld N) =
     // sum + bias[n], EPI_SAVEPRE -> X, EPI_DRELU * r'(X), EPI_RELU
     int finish(const float* part, int splits, int N, const float* bias, float* C, float* X, int epi);

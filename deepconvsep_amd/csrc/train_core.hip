@@ -443,7 +443,7 @@ void trainer_free(dcs_trainer* t) {
 
 }  // namespace
 
-int dcs_trainer::launch(Gemm g, Tile tile, bool ak, bool bk) {
+int dcs_trainer::launch(Gemm g, Tile tile, bool ak, bool bk, dim3* grid_out) {
     if (g.splits < 1) g.splits = 1;
     if (g.splits == 1) g.kchunk = g.K;
     const int bm = tile == T128x32 ? 128 : (tile == T64x64 ? 64 : 32), bn = tile == T64x64 ? 64 : 32;
@@ -452,6 +452,7 @@ int dcs_trainer::launch(Gemm g, Tile tile, bool ak, bool bk) {
     if (tile == T128x32) launch_tile<4, 1, 2, 2>(g, ak, bk, grid, s);
     else if (tile == T64x64) launch_tile<2, 2, 2, 2>(g, ak, bk, grid, s);
     else launch_tile<2, 2, 1, 1>(g, ak, bk, grid, s);
+    if (grid_out) *grid_out = grid;
     DCS_HIP(hipGetLastError());
     return DCS_OK;
 }

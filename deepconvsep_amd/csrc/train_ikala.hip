@@ -76,14 +76,23 @@ __global__ __launch_bounds__(kThreads) void ik_loss_kernel(const ILoss a) {
     block_sums(acc, a.part);
 }
 
+}  // namespace
+
+// F6, the one launch site of this graph's conv1^T instance (train_ca.h)
+int train::ikala_deconv1(hipStream_t s, const float* g, int64_t gslot, const float* W1i, const float* bo, float* q, int B,
+                         int tc, int F, int w1) {
+    const int64_t n = (int64_t)kSrc * B * tc * F;
+    hipLaunchKernelGGL((deconv1_kernel<kK1, kC1, kS1, kSrc>), dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads), 0, s, g,
+                       gslot, W1i, bo, q, B, tc, F, w1);
+    DCS_HIP(hipGetLastError());
+    return DCS_OK;
+}
+
+namespace {
+
 struct IkalaTrainer : CaTrainer {
     int deconv1() override {
-        const int64_t n = kSrc * RF;
-        hipLaunchKernelGGL((deconv1_kernel<kK1, kC1, kS1, kSrc>), dim3((unsigned)dcs_cdiv(n, kThreads)), dim3(kThreads),
-                           0, ctx->stream, (const float*)(GA + Uslot), Uslot, (const float*)param(0),
-                           (const float*)param(bo()), Q, B, tc, F, w1);
-        DCS_HIP(hipGetLastError());
-        return DCS_OK;
+        return ikala_deconv1(ctx->stream, GA + Uslot, Uslot, param(0), param(bo()), Q, B, tc, F, w1);
     }
 
     int loss(const float* x, const float* tgt, double* out7_d) override {

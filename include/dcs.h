@@ -1374,6 +1374,78 @@ typedef struct dcs_debug_d1_aux_args {
 } dcs_debug_d1_aux_args;
 DCS_API int dcs_debug_d1_aux(dcs_ctx* ctx, int which, dcs_debug_d1_aux_args* args);
 
+/* Test aids for the training GEMM and its helper kernels (csrc/train_core.h, train_core.hip, train_debug.hip;
+ * tests/test_gpu_train_kernels.py); no reference counterpart.  dcs_debug_train_gemm runs ONE dcs_trainer::launch(g, tile, ak, bk)
+ * -- one instance of train::gemm_kernel -- on the caller's buffers; no model and no trainer is needed.  The arguments carry what
+ * train::Gemm carries; the Gemm is built with gemm0, ax3 and mat, the helpers the graph files use.  An operand is a pointer, its
+ * byte count, an element offset and two axes, each (d0, d1, s0, s1, s2): index i is at (i % d0) s0 + (i / d0 % d1) s1 +
+ * (i / (d0 d1)) s2, d0 d1 clipped at 2^30.  tile: DCS_TRAIN_T128X32, _T64X64, _T32X32; ak / bk: the operand is loaded K-fastest.
+ * Before the launch the aid computes, for every operand the launch uses and every batch, the smallest and largest element the
+ * descriptor addresses over its index range (A: rows below min(M, ones_row); C and X are not used with `partial`, X only with
+ * DCS_TRAIN_EPI_SAVEPRE / _DRELU; bias, bias2 and scale may be null).  DCS_EINVAL, and nothing launched, for a null or
+ * 16-byte-misaligned pointer the launch uses, a byte count below that extent, an element below the pointer, a negative stride
+ * (the aid's extent is for non-negative strides; production's one negative stride, the flipped conv2 weights of train_ca.hip's
+ * F5 / B5, is outside it), d0 or d1 outside 1 .. 2^30, M, N or K outside 1 .. 2^30 - 1, nbatch outside 1 .. 4, splits < 1,
+ * splits > 1 without `partial` or with a kchunk that is not a positive multiple of 32, nbatch splits above 65535,
+ * DCS_TRAIN_EPI_SAVEPRE together with _DRELU, epi bits outside the three, and an unknown tile.  grid_x, grid_y, grid_z return the
+ * grid dcs_trainer::launch used.  One stream synchronisation per call. */
+#define DCS_TRAIN_T128X32 0
+#define DCS_TRAIN_T64X64 1
+#define DCS_TRAIN_T32X32 2
+#define DCS_TRAIN_EPI_RELU 1
+#define DCS_TRAIN_EPI_SAVEPRE 2
+#define DCS_TRAIN_EPI_DRELU 4
+typedef struct dcs_debug_train_mat {
+    float* p; int64_t bytes;
+    int64_t off;
+    int64_t r[5], c[5];                   /* rows and columns (A: M, K; B: K, N; C and X: M, N): d0, d1, s0, s1, s2 */
+} dcs_debug_train_mat;
+typedef struct dcs_debug_train_gemm_args {
+    int32_t M, N, K;
+    int32_t tile, ak, bk;
+    dcs_debug_train_mat A, B, C, X;
+    int32_t ones_row, ones_klim;          /* rows >= ones_row of A read 1 for k < ones_klim, else 0 */
+    int32_t nbatch, bias_cs;
+    int64_t boff[4][5];                   /* per batch: offsets of A, B, C, X, bias */
+    const float* bias; int64_t bias_bytes;
+    const float* bias2; int64_t bias2_bytes;
+    const float* scale; int64_t scale_bytes;
+    int32_t epi, splits, kchunk;
+    int32_t grid_x, grid_y, grid_z;       /* returned */
+    float* partial; int64_t partial_bytes;        /* [nbatch splits][M][N] */
+} dcs_debug_train_gemm_args;
+DCS_API int dcs_debug_train_gemm(dcs_ctx* ctx, dcs_debug_train_gemm_args* args);
+/* One launch of a helper, with the same refusals for null, misaligned or short buffers (every pointer a device pointer):
+ *   DCS_TRAIN_AUX_FINISH           dcs_trainer::finish (finish_kernel) on a trainer of B rows: in part [splits][B][N], in2 bias [N]
+ *                                  (nullable), out C [B][N], out2 X [B][N] (with DCS_TRAIN_EPI_SAVEPRE written, with _DRELU read)
+ *   DCS_TRAIN_AUX_REDUCE           dcs_trainer::reduce (reduce_kernel), two jobs: in / in2 part [splits[j]][count[j]], in3 the
+ *                                  scale, out / out2 dst: count[j] floats, and N[j] more where dup[j] (the last N[j] once more);
+ *                                  count[1] == 0: one job
+ *   DCS_TRAIN_AUX_DECONV1_IKALA    train::deconv1_kernel<30, 30, 3, 2>, the launch of train_ikala.hip
+ *   DCS_TRAIN_AUX_DECONV1_BACH10   train::deconv1_kernel<30, 30, 4, 4>, the launch of train_bach10.hip
+ *   DCS_TRAIN_AUX_DECONV1_BACH10SI train::deconv1_channels_kernel<30, 30, 4, 4>, the launch of train_bach10si.hip
+ *                                  in g [B][tc][w1][30] per source, source k at + k gslot (BACH10SI: one slot); in2 W1i [30][30]
+ *                                  (BACH10SI [4][30][30]); in3 bo per source / channel; out q [B][sources][tc][F];
+ *                                  F >= 30 and w1 == (F - 30) / S1 + 1, the graph's */
+#define DCS_TRAIN_AUX_FINISH 0
+#define DCS_TRAIN_AUX_REDUCE 1
+#define DCS_TRAIN_AUX_DECONV1_IKALA 2
+#define DCS_TRAIN_AUX_DECONV1_BACH10 3
+#define DCS_TRAIN_AUX_DECONV1_BACH10SI 4
+typedef struct dcs_debug_train_aux_args {
+    int32_t B, N, splits, epi;            /* FINISH */
+    int64_t count[2];                     /* REDUCE */
+    int32_t rsplits[2], rN[2], dup[2];
+    int32_t tc, F, w1, pad_;              /* DECONV1 (with B) */
+    int64_t gslot;
+    const float* in; int64_t in_bytes;
+    const float* in2; int64_t in2_bytes;
+    const float* in3; int64_t in3_bytes;
+    float* out; int64_t out_bytes;
+    float* out2; int64_t out2_bytes;
+} dcs_debug_train_aux_args;
+DCS_API int dcs_debug_train_aux(dcs_ctx* ctx, int which, dcs_debug_train_aux_args* args);
+
 #ifdef __cplusplus
 }
 #endif
