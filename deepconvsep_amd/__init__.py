@@ -21,7 +21,8 @@ from . import augment
 from .augment import RenderedWindows, render_features
 from .score_render import ScoreInformedRenderedWindows, render_score_informed_features
 from . import align
-from .align import (align_scores, bin_classes, chroma, dtw, score_chroma, time_map, warp_times)
+from .align import (ScoreFollower, align_scores, bin_classes, chroma, dtw, follow_scores, follow_time_map, score_chroma, time_map,
+                    warp_times)
 
 __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "TILER_SCRIPT", "TransformFFT",
            "Transforms", "transformFFT", "compute_file", "compute_inverse", "sinebell", "PredictFunction",
@@ -30,4 +31,4 @@ __all__ = ["ARCHS", "EPS_A", "EPS_B", "TIE_ALL", "TIE_FIRST", "TILER_LIBRARY", "
            "ChannelStreamSeparator", "ScoreStreamSeparator", "StereoStreamSeparator", "RateStream", "ResampleCounts", "StreamResampler", "Trainer", "FeatureWindows", "glorot_init",
            "StereoTrainer", "StereoFeatureWindows", "ScoreTrainer", "ScoreFeatureWindows", "augment", "RenderedWindows", "render_features",
            "ScoreInformedRenderedWindows", "render_score_informed_features", "align", "align_scores", "bin_classes", "chroma", "dtw",
-           "score_chroma", "time_map", "warp_times"]
+           "score_chroma", "time_map", "warp_times", "ScoreFollower", "follow_scores", "follow_time_map"]

@@ -135,6 +135,15 @@ def load():
     proto("dcs_dtw_tile", i32)
     proto("dcs_dtw_bytes", i64, i64, i64, i64)
     proto("dcs_dtw", i32, vp, vp, i64, vp, i64, i64, vp, vp, vp)
+    proto("dcs_follow_create", i32, vp, vp, i64, i32, i32, i32, f32, i64, POINTER(vp))
+    proto("dcs_follow_destroy", i32, vp)
+    proto("dcs_follow_reset", i32, vp)
+    proto("dcs_follow_bytes", i64, vp)
+    proto("dcs_follow_frames", i64, vp)
+    proto("dcs_follow_push", i32, vp, vp, i64, vp)
+    proto("dcs_follow_row", i32, vp, vp, vp, vp)
+    proto("dcs_stream_set_follow", i32, vp, vp, vp, f32)
+    proto("dcs_stream_follow_last", i32, vp, vp, i64, POINTER(i64))
     proto("dcs_mwf_f32", i32, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, f32, f64, vp, vp)
     proto("dcs_mwf_frames_per_block", i32)
     proto("dcs_mwf_online_create", i32, vp, i32, i32, i32, f64, f64, f64, POINTER(vp))

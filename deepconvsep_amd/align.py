@@ -8,6 +8,10 @@ hand-aligned scores; a MIDI or notation export does not.  This module aligns one
   path -> time map (score frame -> audio frame) -> warped onsets and offsets
 
 The two hot steps run on the GPU (csrc/align.hip); there is no CPU path for them.  The reference has no counterpart.
+
+That needs the whole recording.  :class:`ScoreFollower` (csrc/follow.hip) is the causal form with constant memory -- one DTW row
+over a window of score frames per audio frame that arrives -- which a score stream uses (``runtime.ScoreStream(follow=...)``);
+:func:`follow_scores` runs it over a file so that the two alignments can be compared.
 """
 import math
 import os
@@ -163,11 +167,148 @@ def align_scores(transform, audio, scores, band='auto', sample_rate=44100, **chr
     return aligned, path, cost
 
 
-def align_score_files(wav, score_dir, out_dir, files, frameSize=2048, hopSize=512, band='auto', resample=False, **chroma_args):
+class ScoreFollower(object):
+    """``dcs_follow``: a score follower with constant memory -- online DTW, one row over a window of ``window`` score frames per
+    audio frame (csrc/follow.hip; include/dcs.h has the recurrence).  ``S`` ``[U, 12]`` is the score's chroma
+    (:func:`score_chroma`), uploaded once.  ``max_step``: the most score frames one audio frame may advance (1 .. 4);
+    ``back``: the cells kept behind the position (None: ``window // 4``); ``penalty``: the cost of a step other than 1;
+    ``max_frames``: the most frames one launch takes (``push`` cuts longer blocks).  The result does not depend on how the
+    frames are cut into pushes.  It follows a performance forward from the score's first frame, at up to ``max_step`` times
+    nominal tempo, and never corrects a position it has given."""
+
+    def __init__(self, ctx, S, window=512, max_step=2, back=None, penalty=1.0 / 16, max_frames=4096):
+        from ctypes import byref
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        if S.ndim != 2 or S.shape[1] != 12 or S.shape[0] < 1:
+            raise ValueError("ScoreFollower expects score chroma [frames >= 1, 12], got %r" % (S.shape,))
+        window, max_step = int(window), int(max_step)
+        back = window // 4 if back is None else int(back)
+        if window % 64 or not 64 <= window <= 1024:
+            raise ValueError("window must be a multiple of 64 in 64 .. 1024, got %d" % window)
+        if not 1 <= max_step <= 4:
+            raise ValueError("max_step must be 1 .. 4, got %d" % max_step)
+        if not 0 <= back < window:
+            raise ValueError("back must be in [0, window), got %d" % back)
+        if not (math.isfinite(float(penalty)) and float(penalty) >= 0):
+            raise ValueError("penalty must be finite and not negative, got %r" % (penalty,))
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be at least 1")
+        self.ctx, self.U, self.window, self.max_step, self.back = ctx, int(S.shape[0]), window, max_step, back
+        self.penalty, self.max_frames = float(penalty), int(max_frames)
+        h = c_void_p()
+        _lib.check(ctx._lib.dcs_follow_create(ctx._h, c_void_p(S.ctypes.data), self.U, window, max_step, back, self.penalty,
+                                              self.max_frames, byref(h)))
+        self._h = h
+
+    @property
+    def device_bytes(self):
+        """device bytes the follower holds (``dcs_follow_bytes``): the score and one row, whatever has been pushed"""
+        return int(self.ctx._lib.dcs_follow_bytes(self._h))
+
+    @property
+    def frames(self):
+        """frames pushed since the follower was made or reset"""
+        return int(self.ctx._lib.dcs_follow_frames(self._h))
+
+    def push(self, chroma_t):
+        """``chroma_t`` ``[n, 12]`` float32 device tensor (:func:`chroma`'s rows) -> int32 ``[n]`` device tensor: the score frame
+        the performance has reached at each of these audio frames.  Nothing waits for the device."""
+        from .runtime import _ptr, _torch
+        torch = _torch()
+        if chroma_t.dim() != 2 or int(chroma_t.shape[1]) != 12 or chroma_t.dtype != torch.float32:
+            raise ValueError("ScoreFollower.push expects a float32 [frames, 12] tensor")
+        with self.ctx.stream_scope():
+            chroma_t = chroma_t.contiguous()
+            n = int(chroma_t.shape[0])
+            pos = torch.empty((n,), dtype=torch.int32, device=chroma_t.device)
+            for i in range(0, n, self.max_frames):
+                k = min(self.max_frames, n - i)
+                _lib.check(self.ctx._lib.dcs_follow_push(self._h, _ptr(chroma_t[i:i + k]), k, _ptr(pos[i:i + k])))
+        return pos
+
+    def row(self):
+        """``(row, w0, p)``: the window's row ``[window]`` float32 NumPy (cell ``w0 + i`` at ``i``, +inf past the score's end),
+        the window start and the position (``dcs_follow_row``; this one waits for the device)."""
+        from .runtime import _ptr, _torch
+        torch = _torch()
+        with self.ctx.stream_scope():
+            row = torch.empty((self.window,), dtype=torch.float32, device=self.ctx.device)
+            w0 = torch.empty((1,), dtype=torch.int64, device=self.ctx.device)
+            p = torch.empty((1,), dtype=torch.int32, device=self.ctx.device)
+            _lib.check(self.ctx._lib.dcs_follow_row(self._h, _ptr(row), _ptr(w0), _ptr(p)))
+            return row.cpu().numpy(), int(w0.cpu().item()), int(p.cpu().item())
+
+    def reset(self):
+        """starts another signal; the score stays"""
+        _lib.check(self.ctx._lib.dcs_follow_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.dcs_follow_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def follow_time_map(pos, U):
+    """The time map of a position track: score frame ``u`` -> the first audio frame ``t`` with ``pos[t] >= u``; past the last
+    position reached it continues at nominal tempo, ``t_last + (u - pos_last)``.  float64 ``[U]``, non-decreasing."""
+    pos = np.asarray(pos, dtype=np.int64)
+    if pos.ndim != 1 or pos.size < 1:
+        raise ValueError("follow_time_map expects a position per audio frame, at least one")
+    if (np.diff(pos) < 0).any():
+        raise ValueError("positions must not decrease")
+    u = np.arange(int(U), dtype=np.int64)
+    first = np.searchsorted(pos, u, side='left').astype(np.float64)
+    past = u > pos[-1]
+    first[past] = (pos.size - 1) + (u[past] - pos[-1])
+    return first
+
+
+FOLLOWER_ARGS = ("window", "max_step", "back", "penalty", "max_frames")
+
+
+def follow_scores(transform, audio, scores, sample_rate=44100, **args):
+    """:func:`align_scores` done causally: the same magnitudes and chroma, pushed through a :class:`ScoreFollower` in blocks
+    instead of one DTW over the whole recording, so every position depends on the audio up to its frame alone.  Returns
+    ``(aligned, pos)``: the scores with warped onsets and offsets and the int32 position per audio frame.  ``args``: the
+    follower's ``window``, ``max_step``, ``back``, ``penalty``, ``max_frames`` and the chroma arguments of ``align_scores``.
+    It exists to be compared with the offline alignment; a stream follows with
+    ``Separator.stream_scoreinformed(melody, follow_scores=...)``."""
+    plan = transform._get_plan() if hasattr(transform, "_get_plan") else transform
+    ctx = plan.ctx
+    fps = float(sample_rate) / float(plan.hop)
+    follower_args = {k: args.pop(k) for k in FOLLOWER_ARGS if k in args}
+    audio_args = {k: args.pop(k) for k in ("fmin", "fmax", "tuning_freq") if k in args}
+    floor = args.pop("floor", 1e-6)
+    a = ctx.to_device(np.asarray(audio).reshape(-1), np.float32)
+    mag, _ = plan.forward(a, phase=False)
+    if int(mag.shape[0]) < 1:
+        raise ValueError("follow_scores: %d samples of audio give no frame to follow" % int(a.numel()))
+    A = chroma(ctx, mag, bin_classes(plan.frame, sample_rate, **audio_args), floor=floor)
+    end = max([float(np.max(off)) for _, off, _ in scores if len(off)] or [0.0])
+    U = int(math.ceil(end * fps)) + 1
+    follower = ScoreFollower(ctx, score_chroma(scores, U, plan.hop, sample_rate, **args), **follower_args)
+    try:
+        pos = follower.push(A).cpu().numpy()
+    finally:
+        follower.close()
+    tmap = follow_time_map(pos, U)
+    aligned = [(warp_times(on, tmap, fps), warp_times(off, tmap, fps), list(names)) for on, off, names in scores]
+    return aligned, pos
+
+
+def align_score_files(wav, score_dir, out_dir, files, frameSize=2048, hopSize=512, band='auto', resample=False, online=False,
+                      **chroma_args):
     """The command-line step: align the score files ``files`` of ``score_dir`` to the wav file and write them, under the same
     names, into ``out_dir``.  Frames of 2048 samples every 512 by default: the features' own analysis, finer in time than the
     separation's 4096.  A file at another rate than 44 100 Hz is aligned at its own rate with ``resample`` (scores are
-    in seconds) and refused without, as the separation scripts do.  Returns ``(path, cost)``."""
+    in seconds) and refused without, as the separation scripts do.  Returns ``(path, cost)`` -- with ``online`` (the causal
+    alignment of :func:`follow_scores`; ``band`` is not used) ``(pos, None)``."""
     from .separation import read_wav, to_mono
     from .transform import transformFFT
     rate, audio = read_wav(wav)
@@ -176,7 +317,11 @@ def align_score_files(wav, score_dir, out_dir, files, frameSize=2048, hopSize=51
     audio = to_mono(audio, 'bach10_si')
     scores = [read_score(os.path.join(score_dir, f)) for f in files]
     tt = transformFFT(frameSize=frameSize, hopSize=hopSize, sampleRate=rate, precision='float32')
-    aligned, path, cost = align_scores(tt, audio, scores, band=band, sample_rate=rate, **chroma_args)
+    if online:
+        aligned, path = follow_scores(tt, audio, scores, sample_rate=rate, **chroma_args)
+        cost = None
+    else:
+        aligned, path, cost = align_scores(tt, audio, scores, band=band, sample_rate=rate, **chroma_args)
     os.makedirs(out_dir, exist_ok=True)
     for f, (on, off, names) in zip(files, aligned):
         write_score(os.path.join(out_dir, f), on, off, names)

@@ -314,8 +314,13 @@ extern "C" int dcs_chroma(dcs_ctx* ctx, const float* mag_d, int64_t ld, int64_t 
     DCS_CHECK(ctx->score_ring.begin((size_t)F, &host, &dev));
     memcpy(host, cls_h, (size_t)F);
     DCS_CHECK(ctx->score_ring.commit((size_t)F, ctx->stream));
+    return dcs_launch_chroma(ctx->stream, mag_d, ld, n_frames, F, (const int8_t*)dev, floor, chroma_d);
+}
+
+int dcs_launch_chroma(hipStream_t stream, const float* mag_d, int64_t ld, int64_t n_frames, int F, const int8_t* cls_d, float floor,
+                      float* chroma_d) {
     hipLaunchKernelGGL(chroma_kernel, dim3((unsigned)((n_frames + kChromaWaves - 1) / kChromaWaves)), dim3(kChromaWaves * 64), 0,
-                       ctx->stream, mag_d, ld, n_frames, F, (const signed char*)dev, floor, chroma_d);
+                       stream, mag_d, ld, n_frames, F, (const signed char*)cls_d, floor, chroma_d);
     DCS_HIP(hipGetLastError());
     return DCS_OK;
 }

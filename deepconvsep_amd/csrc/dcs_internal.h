@@ -320,6 +320,25 @@ int dcs_score_masks_scaled(dcs_ctx* ctx, const float* mag_d, int64_t ld, int64_t
 // the argument checks of dcs_mwf_online_create (mwf_online.hip), for dcs_stream_set_mwf to refuse the same values under its own name
 int dcs_mwf_online_check(const char* who, int F, int J, int niter, double forget, double loading, double eps);
 
+// dcs_chroma's kernel on rows that are already on the device (align.hip), for a followed score stream: cls_d [F] on the device,
+// enqueued on `stream`, no argument checks
+int dcs_launch_chroma(hipStream_t stream, const float* mag_d, int64_t ld, int64_t n_frames, int F, const int8_t* cls_d, float floor,
+                      float* chroma_d);
+
+// the score follower (follow.hip); dcs_stream_set_follow reads max_frames, frames and ctx
+struct dcs_follow {
+    dcs_ctx* ctx = nullptr;
+    int64_t U = 0, max_frames = 0;
+    int W = 0, K = 0, back = 0;
+    float lambda = 0.f;
+    int64_t frames = 0;        // pushed since create or reset
+    float* score = nullptr;    // [U][12]; the one device block: the state lies behind it
+    float* row = nullptr;      // [W]
+    int64_t* w0 = nullptr;
+    int32_t* p = nullptr;
+    int64_t bytes = 0;
+};
+
 // ---------------------------------------------------------------------------------- tiling kernels
 int dcs_launch_tile(dcs_ctx* ctx, const float* mag, int64_t ch_stride, int64_t ld, int C, int64_t T, int F,
                     int tc, int ov, int tiler, float scale, float* tiles, int64_t n);

@@ -24,6 +24,10 @@
 // instrument and the fold multiplies acc_s with the score-informed mixture formed from the two rings.  Everything else is the
 // mono stream.
 //
+// A FOLLOWED score stream (dcs_stream_set_follow) has its score at nominal tempo: a push runs dcs_chroma's kernel on its new
+// magnitude rows, sends the rows through the caller's follower (follow.hip) and paints audio frame t from score frame pos[t]
+// with a second mask kernel that looks at the whole table.  A score stream that never arms it runs what it ran before.
+//
 // A STEREO stream (dcs_stream_create_stereo) feeds the stereo (ILD) graph, which sees the C channels themselves and answers per
 // (source, channel): C rows of samples, magnitudes and phases and no down-mix, the tiles carry the channels of a frame side by
 // side (the row layout dcs_model_forward_stereo reads), the ring of p holds every (source, channel) once and the fold forms the
@@ -170,6 +174,56 @@ __global__ __launch_bounds__(kThreads) void stream_masks_kernel(const int* __res
         __syncthreads();
         for (int it = tid; it < items; it += kThreads) {
             const int* row = table + (int64_t)(r_lo + it / npairs) * W;
+            if (row[1] <= t && t < row[2]) {
+                const int k = it % npairs;
+                const int f0 = row[kRowHead + 2 * k] > c0 ? row[kRowHead + 2 * k] : c0;
+                const int f1 = row[kRowHead + 2 * k + 1] < c1 ? row[kRowHead + 2 * k + 1] : c1;
+                const unsigned bit = 1u << row[0];
+                for (int f = f0; f < f1; ++f) atomicOr(&bits[f - c0], bit);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < c1 - c0; i += kThreads) {
+            const unsigned on = bits[i];
+            float* dst = mask_ring + slot * (int64_t)F + c0 + i;
+            if (normalise == DCS_SCORE_NORM_SUM) {
+                float total = 0.f;
+                for (int j = 0; j < ninst; ++j) {
+                    const float v = ((on >> j) & 1u) ? 1.0f : 1e-18f;
+                    total = j == 0 ? v : __fadd_rn(total, v);
+                }
+                for (int j = 0; j < ninst; ++j)
+                    dst[j * rf * (int64_t)F] = __fdiv_rn(((on >> j) & 1u) ? 1.0f : 1e-18f, total);
+            } else {
+#pragma unroll
+                for (int j = 0; j < kMaxChannels; ++j)
+                    if (j < ninst) dst[j * rf * (int64_t)F] = ((on >> j) & 1u) ? vals.hi[j] : vals.lo[j];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------ push (followed score): the masks of the new frames
+// stream_masks_kernel for a stream whose score is at nominal tempo (dcs_stream_set_follow): audio frame t = n0 + blockIdx.x is
+// painted from SCORE frame pos[blockIdx.x], the position the follower gave it, into slot t mod rf.  The host does not know
+// which rows a push can meet, so the lanes walk all n_rows rows of the table (a few hundred); the rest is that kernel's.
+__global__ __launch_bounds__(kThreads) void stream_follow_masks_kernel(const int* __restrict__ table, int npairs, int n_rows,
+                                                                       const int32_t* __restrict__ pos, int64_t n0, int64_t rf,
+                                                                       int F, int ninst, int normalise, ScoreVals vals,
+                                                                       float* __restrict__ mask_ring) {
+    __shared__ unsigned bits[kMaskChunk];
+    const int tid = threadIdx.x;
+    const int64_t slot = ring_slot(n0 + blockIdx.x, rf);
+    const int t = pos[blockIdx.x];
+    const int W = kRowHead + 2 * npairs;
+    const int items = n_rows * npairs;
+    for (int c0 = 0; c0 < F; c0 += kMaskChunk) {
+        const int c1 = c0 + kMaskChunk < F ? c0 + kMaskChunk : F;
+        for (int i = tid; i < c1 - c0; i += kThreads) bits[i] = 0u;
+        __syncthreads();
+        for (int it = tid; it < items; it += kThreads) {
+            const int* row = table + (int64_t)(it / npairs) * W;
             if (row[1] <= t && t < row[2]) {
                 const int k = it % npairs;
                 const int f0 = row[kRowHead + 2 * k] > c0 ? row[kRowHead + 2 * k] : c0;
@@ -502,6 +556,16 @@ struct dcs_stream {
     dcs_mwf_online* mwf = nullptr;
     float *fmag = nullptr, *fphase = nullptr;
     int64_t mwf_bytes = 0, mwf_rows = 0;
+    // a followed score stream (dcs_stream_set_follow; null: off): the caller's follower, the class table of the chroma kernel,
+    // chroma rows and positions of one push's frames [fp], and the frames the last push followed
+    dcs_follow* follow = nullptr;
+    int8_t* follow_cls = nullptr;
+    float* follow_chroma = nullptr;
+    int32_t* follow_pos = nullptr;
+    float follow_floor = 0.f;
+    int64_t follow_bytes = 0, follow_rows = 0;
+    // a push failed (a HIP error) after the follower had taken its frames: follower and stream disagree until dcs_stream_reset
+    bool follow_stale = false;
 };
 
 namespace {
@@ -722,6 +786,9 @@ extern "C" int dcs_stream_destroy(dcs_stream* s) {
     dcs_dev_free(s->table);
     dcs_dev_free(s->fmag);
     dcs_dev_free(s->fphase);
+    dcs_dev_free(s->follow_cls);
+    dcs_dev_free(s->follow_chroma);
+    dcs_dev_free(s->follow_pos);
     dcs_mwf_online_destroy(s->mwf);
     delete s;
     return DCS_OK;
@@ -734,6 +801,9 @@ extern "C" int dcs_stream_reset(dcs_stream* s) {
     s->want_pull = s->ended = false;
     s->mwf_rows = 0;
     if (s->mwf) DCS_CHECK(dcs_mwf_online_reset(s->mwf));      // frame 0 reads no state: nothing is cleared on the device
+    s->follow_rows = 0;
+    s->follow_stale = false;
+    if (s->follow) DCS_CHECK(dcs_follow_reset(s->follow));
     return DCS_OK;
 }
 
@@ -792,6 +862,75 @@ extern "C" int dcs_stream_mwf_last(dcs_stream* s, float* mag_d, float* phase_d, 
     return DCS_OK;
 }
 
+extern "C" int dcs_stream_set_follow(dcs_stream* s, dcs_follow* f, const int8_t* cls_h, float floor) {
+    if (!s || !f || !cls_h) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: null argument");
+    if (!s->ninst) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: not a score stream (dcs_stream_create_score)");
+    if (s->P > 0 || s->want_pull || s->ended) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: the stream has samples (reset it first)");
+    if (f->frames > 0) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: the follower has taken %lld frames (reset it first)", (long long)f->frames);
+    if (f->ctx != s->ctx) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: the follower belongs to another context");
+    if (f->max_frames < s->fp)
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: the follower takes %lld frames a push, one push of this stream can complete %lld",
+                 (long long)f->max_frames, (long long)s->fp);
+    if (!(floor >= 0.f)) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: floor %g", (double)floor);
+    for (int k = 0; k < s->F; ++k)
+        if (cls_h[k] < -1 || cls_h[k] >= 12) DCS_FAIL(DCS_EINVAL, "dcs_stream_set_follow: class %d of bin %d (-1 .. 11)", (int)cls_h[k], k);
+    DCS_ON_DEVICE(s->ctx->device);
+    if (!s->follow_cls) {                                     // the first arming: the three buffers, whose sizes are the stream's own
+        struct { void** ptr; int64_t bytes; const char* name; } extra[] = {
+            {(void**)&s->follow_cls, dcs_round_up(s->F, 256), "stream.follow_cls"},
+            {(void**)&s->follow_chroma, s->fp * 12 * (int64_t)sizeof(float), "stream.follow_chroma"},
+            {(void**)&s->follow_pos, s->fp * (int64_t)sizeof(int32_t), "stream.follow_pos"},
+        };
+        hipError_t e = hipSuccess;
+        int64_t total = 0;
+        for (auto& b : extra) {
+            if (e == hipSuccess) e = dcs_dev_alloc(b.ptr, (size_t)b.bytes, b.name);
+            total += b.bytes;
+        }
+        if (e != hipSuccess) {                                // the stream is left as it was: not armed
+            for (auto& b : extra) {
+                dcs_dev_free(*b.ptr);
+                *b.ptr = nullptr;
+            }
+            dcs_set_error("dcs_stream_set_follow: %lld bytes: %s", (long long)total, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? DCS_ENOMEM : DCS_EHIP;
+        }
+        s->follow_bytes = total;
+    }
+    (void)hipStreamSynchronize(s->ctx->stream);               // no earlier launch still reads the table this call replaces
+    if (hipMemcpy(s->follow_cls, cls_h, (size_t)s->F, hipMemcpyHostToDevice) != hipSuccess) {
+        if (!s->follow) {                                     // never armed: the buffers go, the stream is left as it was
+            dcs_dev_free(s->follow_cls);
+            dcs_dev_free(s->follow_chroma);
+            dcs_dev_free(s->follow_pos);
+            s->follow_cls = nullptr;
+            s->follow_chroma = nullptr;
+            s->follow_pos = nullptr;
+            s->follow_bytes = 0;
+        }
+        DCS_FAIL(DCS_EHIP, "dcs_stream_set_follow: uploading the class table failed");
+    }
+    if (!s->follow) s->bytes += s->follow_bytes;              // counted once, when the stream is first armed
+    s->follow = f;
+    s->follow_floor = floor;
+    s->follow_rows = 0;
+    return DCS_OK;
+}
+
+extern "C" int dcs_stream_follow_last(dcs_stream* s, int32_t* pos_d, int64_t cap, int64_t* n) {
+    if (!s || !n) DCS_FAIL(DCS_EINVAL, "dcs_stream_follow_last: null argument");
+    if (!s->follow) DCS_FAIL(DCS_EINVAL, "dcs_stream_follow_last: the stream follows no score (dcs_stream_set_follow)");
+    const int64_t rows = s->follow_rows;
+    if (rows > cap || (rows > 0 && !pos_d))
+        DCS_FAIL(DCS_EINVAL, "dcs_stream_follow_last: %lld positions, room for %lld", (long long)rows, (long long)(pos_d ? cap : 0));
+    if (rows > 0) {
+        DCS_ON_DEVICE(s->ctx->device);
+        DCS_HIP(hipMemcpyAsync(pos_d, s->follow_pos, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s->ctx->stream));
+    }
+    *n = rows;
+    return DCS_OK;
+}
+
 extern "C" int64_t dcs_stream_max_tiles(const dcs_stream* s) { return s ? s->max_tiles : -1; }
 extern "C" int64_t dcs_stream_bytes(const dcs_stream* s) { return s ? s->bytes : -1; }
 
@@ -803,6 +942,8 @@ int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t ro
                 int64_t* n_frames_out) {
     if (s->want_pull) DCS_FAIL(DCS_EINVAL, "%s: the tiles of the previous push have not been pulled", who);
     if (s->ended) DCS_FAIL(DCS_EINVAL, "%s: the signal has ended (dcs_stream_reset starts another)", who);
+    if (s->follow_stale)
+        DCS_FAIL(DCS_EINVAL, "%s: an earlier push failed after the follower had taken its frames (dcs_stream_reset starts again)", who);
     if (n < 0 || n > s->max_push)
         DCS_FAIL(DCS_EINVAL, "%s: %lld samples (0 .. max_push = %lld)", who, (long long)n, (long long)s->max_push);
     if (n > 0 && !audio_d) DCS_FAIL(DCS_EINVAL, "%s: null audio", who);
@@ -840,7 +981,28 @@ int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t ro
         DCS_CHECK((launch_frames<float, float2>(s->plan, stream_frames_kernel, n_frames, s->rows - 1, s->plan->win_f,
                                                 s->plan->tw_f, (const float*)s->samples, s->cap, P, s->A, s->rf, s->mag,
                                                 s->phase, s->nch, mag_d, phase_d, ch_stride, ld)));
-    if (s->ninst && n_frames > 0) {
+    // set once the follower has taken this push's frames; a failure behind that point leaves it ahead of the stream's counts
+    struct FollowAhead {
+        dcs_stream* s;
+        bool on;
+        ~FollowAhead() { if (on) s->follow_stale = true; }
+    } ahead = {s, false};
+    if (s->follow && n_frames > 0) {
+        // chroma of the new rows of the magnitude ring (two pieces where it wraps), the follower, the masks from its positions
+        const int64_t a0 = s->A % s->rf, n1 = n_frames < s->rf - a0 ? n_frames : s->rf - a0;
+        DCS_CHECK(dcs_launch_chroma(q, s->mag + a0 * s->F, s->F, n1, s->F, s->follow_cls, s->follow_floor, s->follow_chroma));
+        if (n_frames > n1)
+            DCS_CHECK(dcs_launch_chroma(q, s->mag, s->F, n_frames - n1, s->F, s->follow_cls, s->follow_floor,
+                                        s->follow_chroma + n1 * 12));
+        DCS_CHECK(dcs_follow_push(s->follow, s->follow_chroma, n_frames, s->follow_pos));
+        ahead.on = true;
+        DcsTimer tm(s->ctx, DCS_TAG_SCORE);
+        hipLaunchKernelGGL(stream_follow_masks_kernel, dim3((unsigned)n_frames), dim3(kThreads), 0, q, (const int*)s->table,
+                           s->npairs, (int)s->row_t0.size(), (const int32_t*)s->follow_pos, s->A, s->rf, s->F, s->ninst,
+                           s->normalise, s->vals, s->masks);
+        tm.done();
+        DCS_HIP(hipGetLastError());
+    } else if (s->ninst && n_frames > 0) {
         // the candidate rows of frames [s->A, A): first frame below A (the rows are sorted by it) and, by the running maximum of
         // the end frames, no row before r_lo reaching s->A -- two binary searches, whatever the length of the score
         const int64_t a_hi = A < 2147483647LL ? A : 2147483647LL, a_lo = s->A < 2147483647LL ? s->A : 2147483647LL;
@@ -875,6 +1037,8 @@ int stream_push(const char* who, dcs_stream* s, const float* audio_d, int64_t ro
         DCS_HIP(hipGetLastError());
     }
     s->P = P; s->A = A; s->K = K;
+    ahead.on = false;
+    if (s->follow) s->follow_rows = n_frames;
     s->pending = n_tiles;
     s->want_pull = true;
     if (last) {

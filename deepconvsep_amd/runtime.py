@@ -814,10 +814,17 @@ class ScoreStream(Stream):
     ``mixture`` ``'ch0'`` | ``'sum'`` as in :meth:`Network.set_score_semantics`.  ``push`` returns tiles ``[n_new, instruments,
     tc, F]`` -- channel ``j`` is the harmonic mask of instrument ``j`` times the scaled magnitudes -- and the fold of ``pull``
     multiplies with the score-informed mixture; everything else (``pull``, ``reset``, which keeps the score, ``close``,
-    ``bytes``, ``max_tiles``, the counts) is the mono stream's."""
+    ``bytes``, ``max_tiles``, the counts) is the mono stream's.
+
+    ``follow``: an :class:`deepconvsep_amd.align.ScoreFollower` on the same context, with ``classes`` the int8 table of
+    ``align.bin_classes`` for this plan's bins (``dcs_stream_set_follow``).  ``melody`` is then the table in SCORE time
+    (``melody_table`` at nominal tempo with ``nframes`` = the follower's ``U``): a push computes the chroma of its new frames,
+    asks the follower where in the score they are and paints audio frame ``t`` from score frame ``pos[t]``;
+    :meth:`positions` returns the last push's.  The follower stays the caller's and must outlive the stream; ``reset`` resets
+    it too."""
 
     def __init__(self, plan, S, melody, time_context, overlap, tiler=TILER_LIBRARY, eps_mode=EPS_A, scale=1.0, max_push=65536,
-                 normalise='max', mixture='ch0'):
+                 normalise='max', mixture='ch0', follow=None, classes=None, floor=1e-6):
         melody = np.ascontiguousarray(melody, dtype=np.float64)
         if melody.ndim != 3:
             raise ValueError("melody must be [instruments, notes, 2*nharmonics+3]")
@@ -829,12 +836,37 @@ class ScoreStream(Stream):
         self.ninst = self.tile_channels = int(melody.shape[0])
         Stream.__init__(self, plan, S, time_context, overlap, tiler, eps_mode, scale, max_push)
         del self._melody                 # the library keeps its own converted copy
+        self.follow = None
+        if follow is not None:
+            if classes is None:
+                raise ValueError("a followed ScoreStream needs the pitch classes of its bins (align.bin_classes)")
+            cls = np.ascontiguousarray(classes, dtype=np.int8)
+            if cls.shape != (self.F,):
+                raise ValueError("classes must have one entry per bin (%d), got %r" % (self.F, cls.shape))
+            try:
+                _lib.check(self.ctx._lib.dcs_stream_set_follow(self._h, follow._h, c_void_p(cls.ctypes.data), float(floor)))
+            except Exception:
+                self.close()
+                raise
+            self.follow = follow         # kept alive as long as the stream
 
     def _create(self, overlap, tiler, eps_mode, scale, rise_p, h):
         m = self._melody
         return self.ctx._lib.dcs_stream_create_score(self.plan._h, self.S, self.tc, overlap, tiler, eps_mode, scale, rise_p,
                                                      self.max_push, m.ctypes.data_as(POINTER(c_double)), int(m.shape[0]),
                                                      int(m.shape[1]), int(m.shape[2]), self._codes[0], self._codes[1], byref(h))
+
+    @_on_ctx_stream
+    def positions(self):
+        """int32 device tensor: the score frame of every audio frame the last push completed (``dcs_stream_follow_last``)."""
+        torch = _torch()
+        if self.follow is None:
+            raise ValueError("this ScoreStream follows no score (follow=...)")
+        cap = self.counts.max_frames(self.max_push)
+        pos = torch.empty((cap,), dtype=torch.int32, device=self.ctx.device)
+        n = c_int64()
+        _lib.check(self.ctx._lib.dcs_stream_follow_last(self._h, _ptr(pos), cap, byref(n)))
+        return pos[:n.value]
 
 
 class MwfOnline(object):

@@ -523,15 +523,18 @@ class Separator(object):
         from .streaming import StreamSeparator
         return StreamSeparator(self, max_block=max_block, sample_rate=sample_rate)
 
-    def stream_scoreinformed(self, melody, max_block=65536):
+    def stream_scoreinformed(self, melody, max_block=65536, follow_scores=None, **follower_args):
         """A :class:`deepconvsep_amd.streaming.ScoreStreamSeparator` on this separator's model and plan: score-informed
         separation on a stream.  ``melody``: the note table of the whole signal (``score.melody_table`` with ``nframes`` the
         signal's frame count), read once; the harmonic masks follow ``score_normalise``, the mixture ``score_mixture``, the
         tiles this separator's ``tiler``.  ``push(block)`` takes mono 44 100 Hz samples and returns the finished stems
         ``[S, n_i]``, as :meth:`stream` does; ``deepconvsep_amd.streaming.RateStream(stream, sample_rate)`` takes any other
-        rate.  ``ValueError`` for a graph with one input channel, and when ``melody.shape[0]`` is not the graph's."""
+        rate.  ``ValueError`` for a graph with one input channel, and when ``melody.shape[0]`` is not the graph's.
+        ``follow_scores``: the score at nominal tempo (one ``(on, off, names)`` per instrument), followed on the device as the
+        audio arrives (``align.ScoreFollower``; ``follower_args`` are its arguments and the chroma's); ``melody`` is then the
+        table in score time and the stream's ``positions()`` tell how far the performance has come."""
         from .streaming import ScoreStreamSeparator
-        return ScoreStreamSeparator(self, melody, max_block=max_block)
+        return ScoreStreamSeparator(self, melody, max_block=max_block, follow_scores=follow_scores, **follower_args)
 
     def stream_channels(self, max_block=65536, mwf_iters=0, mwf_forget=1.0, mwf_loading=1e-3):
         """A :class:`deepconvsep_amd.streaming.ChannelStreamSeparator` on this separator's model and plan: the stereo stems of

@@ -7,7 +7,8 @@ by block, the samples of the same computation (``stft_norm`` -> tiler -> network
 not on the length of the signal.
 
 :class:`ScoreStreamSeparator` does it for the score-informed graphs: the score is known before the audio, so the harmonic masks
-of every frame are formed as the frame arrives (``dcs_stream_create_score``).
+of every frame are formed as the frame arrives (``dcs_stream_create_score``).  With ``follow_scores`` the score is at nominal
+tempo and the stream follows it as the audio arrives (``dcs_stream_set_follow``, ``align.ScoreFollower``).
 
 :class:`ChannelStreamSeparator` does the same for a stereo signal -- the stems of ``Separator.separate_channels`` on one engine
 -- :class:`StereoStreamSeparator` streams the one graph that is stereo by construction (``dsd_ild``: the network sees both
@@ -17,6 +18,8 @@ streaming sample-rate converters (``dcs_resample_stream``) for audio at another 
 :class:`StreamCounts` is the host arithmetic of the schedule (the table in include/dcs.h); it needs neither the library nor a
 GPU.
 """
+import math
+
 import numpy as np
 
 from .arch import TILER_LIBRARY, TILER_SCRIPT
@@ -209,9 +212,17 @@ class ScoreStreamSeparator(StreamSeparator):
     instrument, mask times scaled magnitudes, and the fold multiplies the cross-faded soft masks with the score-informed
     mixture on the unscaled magnitudes (the separator's ``score_mixture``).  The masks agree with the whole-file
     ``dcs_score_masks`` whenever no note row ends past the signal's frame count, which a table built with ``nframes`` = that
-    count guarantees."""
+    count guarantees.
 
-    def __init__(self, separator, melody, max_block=65536):
+    ``follow_scores``: the score at NOMINAL tempo, one ``(on, off, names)`` per instrument as ``score.read_score`` returns it
+    -- the case nobody can have aligned beforehand.  ``melody`` must then be the table in SCORE time, ``melody_table`` on the
+    same files with ``nframes = score_frames(follow_scores)``.  The constructor builds the score's chroma at the separator's
+    hop (``align.score_chroma``) and an ``align.ScoreFollower`` (``follower_args``: its ``window``, ``max_step``, ``back``,
+    ``penalty``; ``fmin``, ``fmax``, ``tuning_freq``, ``floor`` of the audio's chroma; ``nharmonics``, ``decay`` of the
+    score's); every push asks it where in the score its new frames are and paints their masks from there.  ``positions()``
+    returns the score frames of the audio frames the last ``push`` / ``finish`` completed."""
+
+    def __init__(self, separator, melody, max_block=65536, follow_scores=None, **follower_args):
         if separator.net.arch.C == 1:
             raise ValueError("stream_scoreinformed feeds one input channel per instrument of the score; '%s' takes one input "
                              "channel: use stream()" % separator.arch_name)
@@ -229,14 +240,99 @@ class ScoreStreamSeparator(StreamSeparator):
         self.counts = StreamCounts(separator.frameSize, separator.hopSize, separator.tc, separator.overlap, separator.tiler)
         self._engine = None              # the device state: made by the first block
         self._pushed, self._ended = 0, False
+        self._follow = None
+        if follow_scores is None:
+            if follower_args:
+                raise TypeError("unexpected arguments without follow_scores: %s" % ", ".join(sorted(follower_args)))
+            return
+        from . import align
+        known = set(align.FOLLOWER_ARGS) | {"fmin", "fmax", "tuning_freq", "floor", "nharmonics", "decay"}
+        if set(follower_args) - known:
+            raise TypeError("unexpected arguments: %s" % ", ".join(sorted(set(follower_args) - known)))
+        follow_scores = list(follow_scores)
+        if len(follow_scores) != melody.shape[0]:
+            raise ValueError("the note table has %d instruments, follow_scores %d" % (melody.shape[0], len(follow_scores)))
+        U = score_frames(follow_scores, separator.hopSize)
+        table_end = float(melody[:, :, 1].max()) if melody.shape[1] else 0.0
+        if table_end > U:
+            raise ValueError("with follow_scores the note table is in score time: its last note ends at frame %d, the score has %d "
+                             "frames (build it with nframes = score_frames(follow_scores, hopSize))" % (int(table_end), U))
+        self._score_S = align.score_chroma(follow_scores, U, separator.hopSize, 44100,
+                                           **{k: follower_args[k] for k in ("nharmonics", "decay") if k in follower_args})
+        self._classes = align.bin_classes(separator.frameSize, 44100,
+                                          **{k: follower_args[k] for k in ("fmin", "fmax", "tuning_freq") if k in follower_args})
+        self._floor = float(follower_args.get("floor", 1e-6))
+        self._follow_args = {k: follower_args[k] for k in align.FOLLOWER_ARGS if k in follower_args}
+        # one launch of the follower takes all the frames one push of the stream can complete
+        self._follow_args["max_frames"] = max(int(self._follow_args.get("max_frames", 4096)), self.counts.max_frames(self.max_block))
+        self._follow = align.ScoreFollower(self.ctx, self._score_S, **self._follow_args)
+        self._positions = []
 
     def _stream(self):
         if self._engine is None:
             from .runtime import ScoreStream
             s = self.sep
+            follow = dict(follow=self._follow, classes=self._classes, floor=self._floor) if self._follow is not None else {}
             self._engine = ScoreStream(s.plan, s.net.S, self.melody, s.tc, s.overlap, s.tiler, s.net.arch.eps_mode,
-                                       s.scale_factor, self.max_block, s.score_normalise, s.score_mixture)
+                                       s.scale_factor, self.max_block, s.score_normalise, s.score_mixture, **follow)
         return self._engine
+
+    def _step(self, piece, last):
+        pcm = StreamSeparator._step(self, piece, last)
+        if self._follow is not None:
+            self._positions.append(self._engine.positions())
+        return pcm
+
+    def push_device(self, block_t):
+        if self._follow is not None:
+            self._positions = []
+        return StreamSeparator.push_device(self, block_t)
+
+    def finish_device(self):
+        if self._follow is not None:
+            self._positions = []
+        return StreamSeparator.finish_device(self)
+
+    def reset(self):
+        StreamSeparator.reset(self)      # the engine's reset resets the follower too
+        if self._follow is not None:
+            self._positions = []
+
+    def close(self):
+        """frees the device state: the stream first, then the follower it reads (which must outlive the stream's pushes)"""
+        if getattr(self, "_engine", None) is not None:
+            self._engine.close()
+            self._engine = None
+        if getattr(self, "_follow", None) is not None:
+            self._follow.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def positions(self):
+        """int32 NumPy: the score frame of every audio frame the last ``push`` / ``finish`` completed (it waits for the device)"""
+        if self._follow is None:
+            raise ValueError("this stream follows no score (stream_scoreinformed(melody, follow_scores=...))")
+        torch = _runtime()._torch()
+        if not self._positions:
+            return np.zeros(0, dtype=np.int32)
+        with self.ctx.stream_scope():
+            return torch.cat(self._positions).cpu().numpy()
+
+    @property
+    def device_bytes(self):
+        """``dcs_stream_bytes`` plus, on a followed stream, the follower's ``dcs_follow_bytes``"""
+        return self._stream().bytes + (self._follow.device_bytes if self._follow is not None else 0)
+
+
+def score_frames(scores, hop, sample_rate=44100):
+    """frames of a score at nominal tempo, ``ceil(end * fps) + 1`` -- the ``U`` of ``align.align_scores`` and of a followed
+    stream, and the ``nframes`` its note table is built with"""
+    end = max([float(np.max(off)) for _, off, _ in scores if len(off)] or [0.0])
+    return int(math.ceil(end * float(sample_rate) / float(hop))) + 1
 
 
 class ChannelStreamSeparator(object):

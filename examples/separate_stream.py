@@ -2,6 +2,7 @@
 
     python examples/separate_stream.py -a dsd -i mix.wav -o outdir -m model.pkl [--block 65536] [--stereo [--mwf N]] [--resample]
     python examples/separate_stream.py -a bach10_si -i mix.wav -o outdir -m model.pkl [--trainer-semantics] [--resample]
+                                       [--follow [--follow-window N] [--follow-step K] [--follow-penalty X]]
     python examples/separate_stream.py -a dsd_ild -i stereo_mix.wav -o outdir -m model.pkl [--block 65536] [--mwf N] [--resample]
 
 The file is read with the standard ``wave`` module ``--block`` frames at a time; each block is scaled and mixed down the way
@@ -20,7 +21,11 @@ clarinet_b.txt, saxophone_b.txt, violin_b.txt`` are read next to the wav, as the
 is built before the first block from the frame count the wav HEADER gives (``ceil(frames / hop) + 2`` at 44 100 Hz; with
 ``--resample`` from the length the file has at 44 100 Hz).  ``--trainer-semantics``: masks divided by their sum over the
 instruments and soft masks on the channel sum, what the trainer's own models saw (``separate_bach10.py`` has the same
-option).  ``--stereo`` does not apply.
+option).  ``--stereo`` does not apply.  ``--follow``: the four score files are at the score's NOMINAL tempo, not in the
+recording's time, and the stream follows them as the audio arrives (``align.ScoreFollower``: online DTW on chroma features, one
+row over a window of ``--follow-window`` score frames per audio frame, at most ``--follow-step`` score frames per audio frame,
+``--follow-penalty`` on every step other than one): the note table is built in score time and every audio frame is painted from
+the score frame the performance has reached.  It follows forward from the score's first frame and never corrects a position.
 
 ``-a dsd_ild``: the stereo (ILD) DSD100 graph (``Separator.stream_stereo``), which sees both channels: a two-channel file gives
 one two-channel stem per source under the names ``examples/dsd100_2ch_ILD/separate_dsd_ild.py`` uses (``<outdir>/<source>.wav``),
@@ -72,6 +77,10 @@ def main(argv=None):
                     help="iterations per frame of the online multichannel Wiener filter (with --stereo or -a dsd_ild)")
     ap.add_argument("--mwf-forget", type=float, default=1.0, metavar="X", help="online filter: weight of the past per frame, (0, 1]")
     ap.add_argument("--mwf-loading", type=float, default=1e-3, metavar="X", help="online filter: isotropic share of the covariances")
+    ap.add_argument("--follow", action="store_true", help="bach10_si: the score files are at nominal tempo; follow them")
+    ap.add_argument("--follow-window", type=int, default=512, metavar="N", help="score frames in the follower's window (64 .. 1024)")
+    ap.add_argument("--follow-step", type=int, default=2, metavar="K", help="most score frames per audio frame (1 .. 4)")
+    ap.add_argument("--follow-penalty", type=float, default=1.0 / 16, metavar="X", help="cost of a step other than one")
     args = ap.parse_args(argv)
     if args.mwf and not (args.stereo or args.arch == "dsd_ild"):    # the Wiener filter works on two-channel estimates
         ap.print_usage()
@@ -81,6 +90,8 @@ def main(argv=None):
         raise SystemExit("--stereo does not apply to bach10_si: the score-informed graphs take one channel per instrument")
     if args.trainer_semantics and not score:
         raise SystemExit("--trainer-semantics applies to bach10_si only")
+    if args.follow and not score:
+        raise SystemExit("--follow applies to bach10_si only")
     ild = args.arch == "dsd_ild"
     if ild:
         args.stereo = True               # the graph is stereo by construction
@@ -111,8 +122,15 @@ def main(argv=None):
         # the frames of the signal the network sees, known from the header before any audio is read
         n44 = src.getnframes() if rate == 44100 else resampled_length(src.getnframes(), *rate_ratio(rate, TARGET_RATE))
         nframes = int(np.ceil(n44 / np.double(hop))) + 2
+        follow = {}
+        if args.follow:                  # the table in score time: its frames are the score's own, whatever the file's length
+            from deepconvsep_amd.score import read_score
+            from deepconvsep_amd.streaming import score_frames
+            scores = [read_score(os.path.join(os.path.dirname(args.input), f)) for f in SI_SCORE_FILES]
+            nframes = score_frames(scores, hop)
+            follow = dict(follow_scores=scores, window=args.follow_window, max_step=args.follow_step, penalty=args.follow_penalty)
         melody = melody_table(SI_SCORE_FILES, os.path.dirname(args.input), nframes, TARGET_RATE, hop, frame, **SI_SCORE_PARAMS)
-        stream = sep.stream_scoreinformed(melody, max_block=args.block)
+        stream = sep.stream_scoreinformed(melody, max_block=args.block, **follow)
     elif ild:
         sep = dcs.Separator(args.arch, dcs.load_model(args.model), 0.3, 30, overlap, 32, bins, frame, hop, window)
         stream = sep.stream_stereo(max_block=args.block, **mwf)

@@ -471,6 +471,45 @@ DCS_API int64_t dcs_dtw_bytes(int64_t T, int64_t U, int64_t band);
 DCS_API int dcs_dtw(dcs_ctx* ctx, const float* a_d, int64_t T, const float* s_d, int64_t U, int64_t band, int32_t* path_d,
                     int64_t* n_path_d, float* cost_d);
 
+/* ------------------------------------------------------------------ score following (csrc/follow.hip) */
+/* dcs_dtw on a stream: a score follower with constant memory.  It takes chroma rows of the audio as they arrive and returns,
+ * for each, the score frame the performance has reached.  Nothing of size T x U exists anywhere; a push allocates nothing and
+ * never waits for the device; all state is a function of (U, W, max_frames).  All arithmetic is float32 and every operation
+ * is rounded once.  State and parameters:
+ *   the score S[U][12], uploaded once at creation;  the window width W, a multiple of 64, 64 <= W <= 1024;  K, the largest
+ *   number of score frames one audio frame may advance, 1 <= K <= 4;  back, the cells kept behind the position, 0 <= back < W;
+ *   lambda, the penalty on a step other than 1, finite and >= 0;  window start w0 = 0, position p = 0, frame count t = 0;
+ *   one row D[u] over the window w0 <= u < min(U, w0 + W), every other cell +inf.
+ * For audio frame t with chroma row a:
+ *   c[u] = 1 - sum_k a[k] S[u][k] for u in the window (dcs_dtw's cost: twelve fused multiply-adds in the order k = 0 .. 11,
+ *   then one subtraction)
+ *   t == 0:  D'[0] = c[0], every other cell +inf: the follower starts at the score's first frame
+ *   t > 0:   best[u] = min(D[u-1], D[u] + lambda, D[u-k] + lambda for k = 2 .. K), cells below w0 and u - k < 0 being +inf;
+ *            D'[u] = c[u] + best[u]
+ *   m = min_u D'[u], q = the lowest u that attains it;  p = max(p, q);  D[u] = D'[u] - m (the row stays bounded on a stream
+ *   of any length);  pos[t] = p
+ *   the window moves: w0 = max(w0, max(0, min(q - back, U - W))) -- only forward, tied to q and not p, so that the minimum's
+ *   cell is always inside and m always finite; cells that enter are +inf.
+ * Every audio frame takes exactly one step, so all cells of a row have paths of equal length: no normalisation, and a row has
+ * no dependence along u.  One launch per push, one workgroup of W threads, the frames of the push in a loop counted by n; the
+ * result does not depend on how the frames are cut into pushes.
+ * dcs_follow_push: chroma_d [n][12] (dcs_chroma's rows), pos_d [n] int32, 0 <= n <= max_frames (n == 0 does nothing), enqueued
+ * on the ctx stream.  dcs_follow_reset starts another signal and keeps the score.  dcs_follow_frames is the host's count of
+ * frames pushed since create or reset.  dcs_follow_row copies the state out, device to device: row_d [W] with cell w0 + i at i,
+ * +inf past U (all +inf before the first frame), *w0_d (int64), *p_d (int32).  DCS_EINVAL for the parameter ranges above, U < 1,
+ * max_frames < 1, a NULL pointer, a lambda that is not finite, n < 0 or n > max_frames; DCS_ESHAPE for U above 2^30 or
+ * max_frames above 2^31 - 1.  A refused call writes nothing and leaves the state as it was.  Not followed: a performance that
+ * goes back, one that starts anywhere but at the score's first frame, one faster than K times nominal tempo. */
+typedef struct dcs_follow dcs_follow;
+DCS_API int dcs_follow_create(dcs_ctx* ctx, const float* s_h, int64_t U, int W, int K, int back, float lambda, int64_t max_frames,
+                              dcs_follow** out);
+DCS_API int dcs_follow_destroy(dcs_follow* f);
+DCS_API int dcs_follow_reset(dcs_follow* f);
+DCS_API int64_t dcs_follow_bytes(const dcs_follow* f);  /* -1 for NULL */
+DCS_API int64_t dcs_follow_frames(const dcs_follow* f); /* -1 for NULL */
+DCS_API int dcs_follow_push(dcs_follow* f, const float* chroma_d, int64_t n, int32_t* pos_d);
+DCS_API int dcs_follow_row(dcs_follow* f, float* row_d, int64_t* w0_d, int32_t* p_d);
+
 /* ------------------------------------------------------------------ multichannel Wiener filter (csrc/mwf.hip) */
 /* The filter the reference's authors were transcribing behind their stereo network and never ran: util.py:633-719 mwf(spec,
  * mixture, niter=10) quotes the MATLAB of Duong / Vincent / Gribonval's EM for full-rank spatial covariances (:647-682), stops
@@ -712,6 +751,25 @@ DCS_API int dcs_stream_create_score(dcs_stft* plan, int S, int time_context, int
  * dcs_stream_mwf_last: the filter off, a NULL buffer, ld below the bins or strides below the rows. */
 DCS_API int dcs_stream_set_mwf(dcs_stream* s, int niter, double forget, double loading, double eps);
 DCS_API int dcs_stream_mwf_last(dcs_stream* s, float* mag_d, float* phase_d, int64_t ch_stride, int64_t src_stride, int64_t ld);
+
+/* A FOLLOWED score stream: the score is at nominal tempo and a follower (dcs_follow_*, above) says where in it the performance
+ * is.  The note table of such a stream is in SCORE time -- melody_table at nominal tempo with nframes = U -- a position is a
+ * frame index into that table, and the stream's hop is the follower's hop.  Called on a score stream before the first push;
+ * cls_h [F] and floor are dcs_chroma's (uploaded once, here).  Armed, a push runs on the stream's queue, in this order: the
+ * frames, as before; dcs_chroma's kernel on the new magnitude rows (in two pieces where the ring wraps); the follower's push;
+ * then, instead of the mask kernel of the unfollowed stream, one that paints audio frame t from score frame pos[t] and looks at
+ * every row of the table (the host no longer knows which rows a push can meet).  Tiles, fold, inverse and gather read the mask
+ * ring as before, and a stream that was never armed allocates, launches and computes what it did without this call.
+ * dcs_stream_reset resets the follower too.  A push that fails with a HIP error after the follower has taken its frames leaves
+ * the follower ahead of the stream: every later push is refused (DCS_EINVAL) until dcs_stream_reset.  dcs_stream_bytes grows by the position and chroma buffers (a push's frames) and the
+ * class table; the follower's own bytes are dcs_follow_bytes.  The follower stays the caller's: it must outlive the stream's
+ * pushes and is not destroyed with the stream.  dcs_stream_follow_last copies the positions of the last push into pos_d [cap]
+ * (device) and stores their count in *n (host).  DCS_EINVAL: s is not a score stream; the stream or the follower has already
+ * taken frames; the follower's max_frames is below the frames one push of the stream can complete; another context's follower; a
+ * class outside -1 .. 11, a negative or NaN floor, a NULL pointer; dcs_stream_follow_last: a stream that is not armed, cap below
+ * the count, a NULL pointer. */
+DCS_API int dcs_stream_set_follow(dcs_stream* s, dcs_follow* f, const int8_t* cls_h, float floor);
+DCS_API int dcs_stream_follow_last(dcs_stream* s, int32_t* pos_d, int64_t cap, int64_t* n);
 
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip) */
 /* The reference separates 44 100 Hz files only (separate_dsd.py:283 prints "Sample rate is not 44100" for the rest); this is
