@@ -129,6 +129,9 @@ def load():
     proto("dcs_debug_d1_aux", i32, vp, i32, vp)
     proto("dcs_debug_train_gemm", i32, vp, vp)
     proto("dcs_debug_train_aux", i32, vp, i32, vp)
+    proto("dcs_debug_lat_gemm", i32, vp, vp)
+    proto("dcs_debug_lat_stft_forward_f32", i32, vp, vp, i64, i64, vp, vp, vp, i64, i64, i64)
+    proto("dcs_debug_lat_stft_inverse_f32", i32, vp, vp, i64, i64, vp, i64, i64, i64, i32, f32, vp, i64, i64, vp, i64)
     proto("dcs_bss_energies", i32, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp)
     proto("dcs_bss_lagcorr", i32, vp, vp, vp, i32, i32, i64, i32, vp)
     proto("dcs_chroma", i32, vp, vp, i64, i64, i32, vp, f32, vp)

@@ -1504,6 +1504,56 @@ typedef struct dcs_debug_train_aux_args {
 } dcs_debug_train_aux_args;
 DCS_API int dcs_debug_train_aux(dcs_ctx* ctx, int which, dcs_debug_train_aux_args* args);
 
+/* Test aids for the one-batch kernels of csrc/dsd_lat.hip (csrc/lat_debug.hip; tests/test_gpu_lat_kernels.py); no reference
+ * counterpart.  Each runs ONE launch through the launcher net.hip calls (dcs_launch_lat_gemm, dcs_launch_lat_stft,
+ * dcs_launch_lat_istft) on the caller's device buffers, after the host has computed the highest element the launch can ask of
+ * every buffer; one stream synchronisation per call.
+ *
+ * dcs_debug_lat_gemm: lat_gemm_kernel<J, NA>, J = ceil(slice_len / 16), NA = a_parts.  The fields are DcsLatGemm's (csrc/dsd_lat.h):
+ *   nz <= 1:  C[r][c] = act(a_scale * Aeff[arow(r)][0 .. K) . B[:, c] + bias[c]),  r < M, c < n_store, rows of ldc floats
+ *   nz > 1 :  part z at C + z * c_part_stride holds the sum over the slices z * waves .. z * waves + waves - 1 alone,
+ *             waves = ceil(n_slices / nz); the bias in part 0 only; no rectifier
+ *   Aeff = the sum of the a_parts arrays a_part_stride apart, rectified if relu_in; arow(r) = a_gdiv > 0 ? (r / a_gdiv) * a_gmul +
+ *   r % a_gdiv : r, rows a_row_stride apart (they may overlap); Bp in the fragment order of dcs_lat_pack_b_host.
+ * Extents: A: max_r arow(r) * a_row_stride + K + (a_parts - 1) * a_part_stride floats (and the first four floats of every part,
+ * which lanes without an operand read); Bp: n_slices * n_cb * J * 256; bias: n_cb * 16 (read past n_store); C: (nz - 1) *
+ * c_part_stride + (M - 1) * ldc + n_store.  DCS_EINVAL, and nothing launched, for a count below its extent, a pointer that is
+ * null or not 16-byte aligned, a negative stride or count (M, n_store, K, n_slices, n_cb below 1; M above 2^20), n_store above
+ * n_cb * 16 or above ldc, c_part_stride below one part while nz > 1, and everything the launcher refuses: waves outside 4 .. 16,
+ * slice_len, K, a_row_stride or a_part_stride not a multiple of 4, slice_len above 80 (J > 5), a_parts other than 1 or 4.
+ * J, NA, grid_* and block_x return the launch. */
+typedef struct dcs_debug_lat_gemm_args {
+    const float* A; int64_t n_A; int64_t a_row_stride;
+    const float* Bp; int64_t n_Bp;
+    const float* bias; int64_t n_bias;
+    float* C; int64_t n_C; int64_t ldc;
+    float a_scale;
+    int32_t M, n_store, K, slice_len, n_slices, n_cb, relu;
+    int32_t nz, a_parts, relu_in, a_gdiv;
+    int64_t c_part_stride, a_part_stride, a_gmul;
+    int32_t J, NA, grid_x, grid_y, grid_z, block_x;   /* returned */
+} dcs_debug_lat_gemm_args;
+DCS_API int dcs_debug_lat_gemm(dcs_ctx* ctx, dcs_debug_lat_gemm_args* args);
+/* lat_stft_kernel<9 | 10> (frameSize 1024 / 2048, frameSize / hop 2 or 4, else DCS_EINVAL): T = dcs_frame_count(n_samples, hop)
+ * frames of audio_d[0 .. n_samples) into rows_out >= T rows of ld >= frame / 2 + 1 values: magnitudes, angles (phase_d nullable)
+ * and unit phasors ((re, im) pairs); rows past T and the columns past frame / 2 are written as magnitude 0, angle 0, phasor
+ * (1, 0).  n_audio: floats behind audio_d (n_samples <= n_audio); n_rows_elems: elements (pairs for unit_d) behind every output,
+ * at least rows_out * ld.  audio_d, mag_d and phase_d may be aligned to 4 bytes only (an audio_d off 8 bytes takes the kernel's
+ * scalar loads), unit_d to 8. */
+DCS_API int dcs_debug_lat_stft_forward_f32(dcs_stft* plan, const float* audio_d, int64_t n_audio, int64_t n_samples, float* mag_d,
+                                           float* phase_d, float* unit_d, int64_t n_rows_elems, int64_t ld, int64_t rows_out);
+/* lat_ifft_kernel<9 | 10, 4> and lat_ola_kernel<2 | 4>: source s reads n_frames rows of ld magnitudes at mag_d + s * src_stride
+ * and the shared phasor rows at unit_d, X = (mag / pre_div) * sqrt(frame) * unit with the imaginary parts of bins 0 and frame / 2
+ * ignored; the windowed frames go to frames_d [n_src][n_frames][frame] (the caller's, so that they can be looked at), the
+ * overlap-add / sum of window^2 to audio_d [n_src][n_out]; samples no frame covers are 0.  n_mag, n_audio: floats; n_unit:
+ * pairs.  DCS_EINVAL for frames_bytes below n_src * n_frames * frame * 4, ld < frame / 2 + 1, src_stride < n_frames * ld with
+ * more than one source, n_mag < (n_src - 1) * src_stride + (n_frames - 1) * ld + frame / 2 + 1, n_unit < (n_frames - 1) * ld +
+ * frame / 2 + 1, n_audio < n_src * n_out, a count below 1, pre_div 0 or not finite, a null or misaligned pointer (mag_d, audio_d
+ * 4 bytes, unit_d, frames_d 8). */
+DCS_API int dcs_debug_lat_stft_inverse_f32(dcs_stft* plan, const float* mag_d, int64_t n_mag, int64_t src_stride, const float* unit_d,
+                                           int64_t n_unit, int64_t ld, int64_t n_frames, int n_src, float pre_div, float* audio_d,
+                                           int64_t n_audio, int64_t n_out, float* frames_d, int64_t frames_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,33 +22,55 @@ def _pack_b(B, K, n_cb, slice_len, n_slices):
     return out.reshape(n_slices, n_cb, J, 64, 4), J
 
 
-def _emu_gemm(A_flat, row_stride, M, K, Bp, J, slice_len, n_slices, n_cb):
-    """lat_gemm_kernel, lane by lane."""
-    C = np.zeros((M, n_cb * 16), dtype=np.float64)
+def _emu_gemm(A_flat, row_stride, M, K, Bp, J, slice_len, n_slices, n_cb, nz=1, a_parts=1, a_part_stride=0, relu_in=0, a_gdiv=0,
+              a_gmul=0, a_scale=1.0, touched=None):
+    """lat_gemm_kernel, lane by lane, in float64: the products and sums of the lanes' operands, before bias and rectifier.
+    nz <= 1: C [M][n_cb * 16]; nz > 1: the parts [nz][M][n_cb * 16], workgroup z owning the slices z * nw + wave.  Every load
+    of the kernel is made (a lane without an operand reads the first four floats of every part and drops them), so an index
+    outside A_flat or Bp raises; `touched` (a dict) receives the highest element asked of A and of Bp."""
+    nzz = max(nz, 1)
+    nw = (n_slices + nzz - 1) // nzz
+    C = np.zeros((nzz, M, n_cb * 16), dtype=np.float64)
+    Bflat = np.asarray(Bp).reshape(-1)
     lanes = np.arange(64)
     fi, kq = lanes & 15, lanes >> 4
-    for rb in range((M + 15) // 16):
-        rows = rb * 16 + fi
-        row_ok = rows < M
-        for cb in range(n_cb):
-            blk = np.zeros((16, 16))
-            for s in range(n_slices):
-                for j in range(J):
-                    kl = 16 * j + 4 * kq
-                    ok = row_ok & (kl < slice_len) & (s * slice_len + kl < K)
-                    for e in range(4):
-                        a = np.zeros(64)
-                        idx = np.where(ok, rows, 0) * row_stride + s * slice_len + kl + e
-                        a[ok] = A_flat[idx[ok]]
-                        b = Bp[s, cb, j, :, e].astype(np.float64)
-                        Am = np.zeros((16, 4)); Bm = np.zeros((4, 16))
-                        Am[fi, kq] = a
-                        Bm[kq, fi] = b
-                        blk += Am @ Bm
-            r0 = rb * 16
-            nr = min(16, M - r0)
-            C[r0:r0 + nr, cb * 16:(cb + 1) * 16] = blk[:nr]
-    return C
+    top_a = top_b = 0
+    for z in range(nzz):
+        for rb in range((M + 15) // 16):
+            rows = rb * 16 + fi
+            for cb in range(n_cb):
+                blk = np.zeros((16, 16))
+                for wv in range(nw):
+                    s = z * nw + wv
+                    row_ok = (rows < M) & (s < n_slices)
+                    rr = np.where(row_ok, rows, 0)
+                    arow = (rr // a_gdiv) * a_gmul + rr % a_gdiv if a_gdiv > 0 else rr
+                    a_ptr = arow * row_stride + np.where(row_ok, s, 0) * slice_len + 4 * kq
+                    b_ptr = (((s if s < n_slices else 0) * n_cb + cb) * J) * 256 + 4 * lanes
+                    for j in range(J):
+                        kl = 16 * j + 4 * kq
+                        ok = row_ok & (kl < slice_len) & (s * slice_len + kl < K)
+                        ap = np.where(ok, a_ptr + 16 * j, 0)
+                        for e in range(4):
+                            a = np.zeros(64)
+                            for p in range(a_parts):
+                                top_a = max(top_a, int((ap + p * a_part_stride + 3).max()))
+                                a = a + A_flat[ap + p * a_part_stride + e]          # unconditional, as the kernel's
+                            a = np.where(ok, a, 0.0)
+                            if a_parts > 1 and relu_in:
+                                a = np.maximum(a, 0.0)
+                            top_b = max(top_b, int((b_ptr + j * 256 + 3).max()))
+                            b = Bflat[b_ptr + j * 256 + e].astype(np.float64)
+                            Am = np.zeros((16, 4)); Bm = np.zeros((4, 16))
+                            Am[fi, kq] = a_scale * a
+                            Bm[kq, fi] = b
+                            blk += Am @ Bm
+                r0 = rb * 16
+                nr = min(16, M - r0)
+                C[z, r0:r0 + nr, cb * 16:(cb + 1) * 16] = blk[:nr]
+    if touched is not None:
+        touched.update(A=top_a, Bp=top_b)
+    return C if nz > 1 else C[0]
 
 
 @pytest.mark.parametrize("case", ["conv1_1025", "conv1_513", "conv2", "fc", "fc1x"])
